@@ -8,7 +8,13 @@ One "step" = one pass of the hot path over one synthetic particle snapshot (BASE
     -> bias forces of both CVs written for every particle (one fused pass).
 Inputs are resident in HBM before the timed region; nothing synchronises with the host inside it.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--walkers]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--walkers] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes runs or checks of its own: the
+steady-state and repeated regions, the dominant kernel's launches timed one by one (roofline), the oracle checks, the CPU
+baselines, the variants (stride 100, f64, the other trigonometry) and the config 3 / config 5 sub-records.
+--dump-outputs DIR writes what the last timed step computed (CV values, bias state, bias grid, forces of every CV) as .npy
+files; the inputs are seeded, so two builds can be compared output for output.
 
 N > 1: one rank per GPU.  Either the caller starts the ranks (`python -m torch.distributed.run --nproc-per-node N bench.py
 --gpus N ...`: WORLD_SIZE is set) or this script does: called plainly with --gpus N it starts that command ITSELF as a child
@@ -68,6 +74,12 @@ def parse(argv=None):
                          "communicator); abi: C-ABI calls from Python (N>1 fallback when the all-reduce has to go through RCCL)")
     ap.add_argument("--dtype", choices=["f32", "f64"], default="f32",
                     help="Scalar of the particle arrays (HOOMD single / double precision build); headline: f32 as in BASELINE.json")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: steady state and repeated regions, the "
+                         "dominant kernel's launches (roofline), the oracle checks, the CPU baselines, the variants and sub-records")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step as DIR/<name>.npy (float32 / float64, "
+                         "64 MB at most: per-particle arrays beyond that become a fixed, seeded sample of rows)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-steps", type=int, default=4)
     ap.add_argument("--no-sub-records", action="store_true", help="skip the config 3 / config 5 sub-records (N = 1)")
@@ -565,6 +577,64 @@ def self_check(st, stride):
             "V_rel_err": abs(st["V"] - v_ref) / max(abs(v_ref), 1e-300), "w_rel_err": abs(st["w"] - w_ref) / max(abs(w_ref), 1e-300)}
 
 
+DUMP_LIMIT_BYTES = 64 * 1024 * 1024
+DUMP_SAMPLE_SEED = 20240
+
+
+def engine_grid(lib, h):
+    """the bias grid V(s) of a grid engine (array 0), copied to the host"""
+    out = np.zeros(lib.mtd_metad_num_elements(h), dtype=np.float64)
+    _abi.check(lib.mtd_metad_get_array(h, 0, out.ctypes.data, None))
+    return out
+
+
+def host_outputs(context, integ):
+    """what a caller of the host-API step holds after its last step: the integrator's state, the bias grid and every
+    registered collective variable's force array (N x 4, the particles' scalar)"""
+    t = context.current.system.getCurrentTimeStep()
+    small = {"cv": integ.getCurrentValues(), "bias_factors": integ.getBiasFactors(),
+             "bias_V_w": [integ.getLogValue("bias", t), integ.getLogValue("weight", t)],
+             "num_gaussians": [integ.getNumGaussians()],
+             "bias_grid": engine_grid(_abi.load(), C.c_void_p(integ.getEngineHandle()))}
+    per = {}
+    for i, f in enumerate(c for c in context.current.forces if getattr(c, "grid_set", False) and c.cpp_force is not None):
+        per["forces_cv%d" % i] = f.cpp_force.getForceArray()
+    return small, per
+
+
+def abi_outputs(be, forces):
+    """the same for a C-ABI backend: its engine's state and grid, the force buffers of its CVs"""
+    st = be.state()
+    small = {"cv": st["cv"], "bias_factors": st["bias"], "bias_V_w": [st["V"], st["w"]], "num_gaussians": [st["num_gaussians"]],
+             "bias_grid": engine_grid(be.lib, be.h)}
+    return small, {"forces_cv%d" % i: f.cpu().numpy() for i, f in enumerate(forces)}
+
+
+def dump_outputs(path, small, per_particle):
+    """--dump-outputs: every array as <path>/<name>.npy in float32 (arrays of that type) or float64.  Per-particle arrays that would
+    take the files past DUMP_LIMIT_BYTES keep a fixed, seeded sample of their rows, the same rows for all of them
+    (sample_rows.npy holds the row indices)."""
+    os.makedirs(path, exist_ok=True)
+
+    def as_float(a):
+        a = np.asarray(a)
+        return np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+
+    small = {k: as_float(v) for k, v in small.items()}
+    per_particle = {k: as_float(v) for k, v in per_particle.items()}
+    budget = DUMP_LIMIT_BYTES - sum(a.nbytes for a in small.values()) - 4096 * (len(small) + len(per_particle) + 1)
+    per_bytes = sum(a.nbytes for a in per_particle.values())
+    if per_particle and per_bytes > budget:
+        n = next(iter(per_particle.values())).shape[0]
+        row_bytes = per_bytes // n
+        k = max(1, budget // (row_bytes + 8))                   # every kept row also costs its index in sample_rows
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=min(k, n), replace=False))
+        per_particle = {name: np.ascontiguousarray(a[rows]) for name, a in per_particle.items()}
+        small["sample_rows"] = rows.astype(np.float64)
+    for name, a in list(small.items()) + list(per_particle.items()):
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def measured_copy_bandwidth():
     """a measured ceiling beside the 8 TB/s of the data sheet: device-to-device copy of 512 MB (read + write counted) and a
     read-only pass (sum) over the same buffer — HIP events, best of several"""
@@ -762,8 +832,9 @@ def main_config(args):
     context.current.system.run(args.steps)
     barrier()
     elapsed = time.perf_counter() - t0
+    outputs = host_outputs(context, meta.cpp_integrator) if (args.dump_outputs and rank == 0) else None
     steady = None
-    if not args.no_variants:
+    if args.full and not args.no_variants:
         k_steady = max(500, args.steps)
         barrier()
         t1 = time.perf_counter()
@@ -819,10 +890,10 @@ def main_config(args):
         else:
             out["roofline"] = {"bound": "valu_fp64", "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s", "traffic": None, "level": "step, per GPU",
                                "pair_entries_rank0": pair_entries[0], "achieved": None, "frac": None,
-                               "note": "flops from the instruction counters: profiles/%s (single-GPU sub-record extra.config5 of the default run)" % PROFILE_ROUND}
+                               "note": "flops from the instruction counters: profiles/%s (single-GPU sub-record extra.config5 of a --full run)" % PROFILE_ROUND}
         if steady is not None:
             out["extra"] = {"steady_state": {"ms_per_step": 1e3 * steady[0] / steady[1], "steps": steady[1], "value": n_global * n_cv / (steady[0] / steady[1])}}
-        if not args.no_cpu_baseline and n_global <= 2_000_000:
+        if args.full and not args.no_cpu_baseline and n_global <= 2_000_000:
             # checker (untimed): the CV the ranks agreed on against the oracle on the WHOLE snapshot
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import mtd_ref
@@ -837,6 +908,8 @@ def main_config(args):
                 lists = util.build_nlist(pos, L[0], r_list)
                 val = mtd_ref.ql_compute_cv(pt, rbox, *lists, 1.4, 1.2, 6, 0, [0, 0, 0, 0, 1, 0, 1])[0]
                 out["cv_check"] = {"cv_oracle": [val], "rel_err": [abs(st["cv"][0] - val) / abs(val)], "tolerance": 1e-6}
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, *outputs)
         print(json.dumps(out), flush=True)
     context.current = None
     if dist is not None:
@@ -983,10 +1056,18 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     st = host.state() if host is not None else eng.state()
+    outputs = None
+    if args.dump_outputs and rank == 0:         # what the last timed step left, before anything below runs more steps
+        if isinstance(host, HostEngine):
+            outputs = host_outputs(host.context, host.meta.cpp_integrator)
+        elif isinstance(host, WalkerEngine):
+            outputs = abi_outputs(host.be, [p.force for p in host.be.parts])
+        else:
+            outputs = abi_outputs(eng.be, eng.be.forces)
     # steady state: the same loop over >= 2000 steps in the same process (a timed region has a fixed cost of ~40 us —
     # doorbell on an idle queue, completion signal — which is 2 us per step at K = 20 and nothing at K = 2000)
     steady = None
-    if not args.no_variants:
+    if args.full and not args.no_variants:
         k_steady = max(2000, args.steps)
         barrier()
         t1 = time.perf_counter()
@@ -996,7 +1077,7 @@ def main():
         st = host.state() if host is not None else eng.state()
     # the driver's call times ONE region of K steps; the same bracket ten more times shows where that one sample sits
     more_regions = None
-    if not args.no_variants and dist is None:
+    if args.full and not args.no_variants and dist is None:
         more_regions = []
         for _ in range(10):
             barrier()
@@ -1015,65 +1096,66 @@ def main():
     # empty pair (which subtracts one packet too many: low).  The rocprofv3 kernel trace of the same command is under
     # profiles/; its average is reported beside the in-process figure (roofline.rocprof_avg_launch_us) — the roofline is priced
     # with the in-process one, the larger of the two.
-    for _ in range(20):
-        eng.step()
-    n_ev = 300          # launches measured one by one (their own loops, outside the timed region: events per launch perturb the step)
     lib = _abi.load()
+    if args.full:
+        for _ in range(20):
+            eng.step()
+        n_ev = 300          # launches measured one by one (their own loops, outside the timed region: events per launch perturb the step)
 
-    def event_pair():
-        return torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        def event_pair():
+            return torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
-    alt = {}
-    if path == "fused":
-        timing = "start/stop events of each launch (hipExtLaunchKernelGGL) on the launch stream"
-        _abi.check(lib.mtd_profile_force_begin(n_ev))
+        alt = {}
+        if path == "fused":
+            timing = "start/stop events of each launch (hipExtLaunchKernelGGL) on the launch stream"
+            _abi.check(lib.mtd_profile_force_begin(n_ev))
+            for _ in range(n_ev):
+                eng.step()
+            buf = (C.c_double * n_ev)()
+            n_got = C.c_uint()
+            _abi.check(lib.mtd_profile_force_end(buf, n_ev, C.byref(n_got)))
+            direct = np.array(buf[:n_got.value])
+            e0, e1 = event_pair()
+            e0.record()
+            for _ in range(n_ev):
+                eng.step()
+            e1.record()
+            # launch A alone sends without anybody receiving: no rank may start that while a peer still polls for the last real
+            # exchange (the slots alternate between two buffers: a third send would overwrite what the peer is waiting for)
+            barrier()
+            f0, f1 = event_pair()
+            f0.record()
+            for _ in range(n_ev):
+                eng.be.cv_partials()
+            f1.record()
+            barrier()
+            step_us, a_us = e0.elapsed_time(e1) * 1e3 / n_ev, f0.elapsed_time(f1) * 1e3 / n_ev
+            alt["steps_minus_launch_A_alone_us"] = step_us - a_us
+            alt["step_us"], alt["launch_A_alone_us"] = step_us, a_us
+        else:
+            timing = "HIP events around the kernel minus the cost of an empty event pair"
+        # an event pair around the kernel, minus an empty pair (the measurement itself on the generic path)
+        eng.ev = []
         for _ in range(n_ev):
             eng.step()
-        buf = (C.c_double * n_ev)()
-        n_got = C.c_uint()
-        _abi.check(lib.mtd_profile_force_end(buf, n_ev, C.byref(n_got)))
-        direct = np.array(buf[:n_got.value])
-        e0, e1 = event_pair()
-        e0.record()
-        for _ in range(n_ev):
-            eng.step()
-        e1.record()
-        # launch A alone sends without anybody receiving: no rank may start that while a peer still polls for the last real
-        # exchange (the slots alternate between two buffers: a third send would overwrite what the peer is waiting for)
-        barrier()
-        f0, f1 = event_pair()
-        f0.record()
-        for _ in range(n_ev):
-            eng.be.cv_partials()
-        f1.record()
-        barrier()
-        step_us, a_us = e0.elapsed_time(e1) * 1e3 / n_ev, f0.elapsed_time(f1) * 1e3 / n_ev
-        alt["steps_minus_launch_A_alone_us"] = step_us - a_us
-        alt["step_us"], alt["launch_A_alone_us"] = step_us, a_us
-    else:
-        timing = "HIP events around the kernel minus the cost of an empty event pair"
-    # an event pair around the kernel, minus an empty pair (the measurement itself on the generic path)
-    eng.ev = []
-    for _ in range(n_ev):
-        eng.step()
-    empty = []
-    for _ in range(200):
-        a, b = event_pair()
-        a.record()
-        b.record()
-        empty.append((a, b))
-    torch.cuda.synchronize()
-    ev_overhead_us = float(np.median([a.elapsed_time(b) for a, b in empty]) * 1e3)
-    pair = np.array([a.elapsed_time(b) for a, b in eng.ev]) * 1e3 - ev_overhead_us
-    eng.ev = None
-    raw = direct if path == "fused" else pair
-    # a sample more than 3x the median is a stall of the queue (clock ramp, host jitter), not a kernel duration: dropped, counted
-    keep = raw <= 3.0 * np.median(raw)
-    n_stalls = int((~keep).sum())
-    force_us_mean, force_us = float(np.mean(raw[keep])), float(np.median(raw))
-    if path == "fused":
-        alt["event_pair_minus_empty_pair_us"] = float(np.mean(pair[pair <= 3.0 * np.median(pair)]))
-    alt["empty_event_pair_us"] = ev_overhead_us
+        empty = []
+        for _ in range(200):
+            a, b = event_pair()
+            a.record()
+            b.record()
+            empty.append((a, b))
+        torch.cuda.synchronize()
+        ev_overhead_us = float(np.median([a.elapsed_time(b) for a, b in empty]) * 1e3)
+        pair = np.array([a.elapsed_time(b) for a, b in eng.ev]) * 1e3 - ev_overhead_us
+        eng.ev = None
+        raw = direct if path == "fused" else pair
+        # a sample more than 3x the median is a stall of the queue (clock ramp, host jitter), not a kernel duration: dropped, counted
+        keep = raw <= 3.0 * np.median(raw)
+        n_stalls = int((~keep).sum())
+        force_us_mean, force_us = float(np.mean(raw[keep])), float(np.median(raw))
+        if path == "fused":
+            alt["event_pair_minus_empty_pair_us"] = float(np.mean(pair[pair <= 3.0 * np.median(pair)]))
+        alt["empty_event_pair_us"] = ev_overhead_us
 
     if dist is not None:
         vals = [elapsed, steady[0] if steady else 0.0]
@@ -1088,7 +1170,7 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         mailbox_timeouts = int(tt.item())
     walker_check = None
-    if walkers and host is not None:
+    if args.full and walkers and host is not None:
         s1, s2 = host.grid_checksum()
         if dist is not None:
             lo = torch.tensor([s1, s2], dtype=torch.float64, device=ctl_device())
@@ -1104,30 +1186,44 @@ def main():
         n_boxes = world if walkers else 1
         steps_per_s = args.steps / elapsed
         value = steps_per_s * n_global * n_boxes * 2
-        # dominant kernel's algorithmic bytes per launch: read Scalar4 positions + write one Scalar4
-        # force per CV (48 B/particle); the fused kernel also carries the first grid pass of the deposit
-        # (per cell: 8 B dV written, 8+8 B reweighted r/w, 4 B hist_delta read)
         scalar4 = 16 if args.dtype == "f32" else 32
-        force_bytes = n_local * (scalar4 + 2 * scalar4)
-        if path == "fused" and args.stride == 1:
-            force_bytes += 256 * 256 * 28
-        achieved = force_bytes / (force_us_mean * 1e-6) / 1e9
-        # HBM traffic of the dominant kernel from the PMC passes committed under profiles/ (FETCH_SIZE / WRITE_SIZE
-        # in separate rocprofv3 runs, gfx950 x2 correction on FETCH_SIZE); only valid for the default workload
-        # (a profiler cannot be attached from inside the run; the figure is only reported while the kernel's sources are the
-        # ones the counters were collected on — otherwise traffic is null and traffic_stale says so)
-        traffic, traffic_src, traffic_stale, rocprof_us = None, None, None, None
-        pmc = os.path.join(ROOT, "profiles", PROFILE_ROUND, "pmc_summary.json")
-        if os.path.exists(pmc) and path == "fused" and args.stride == 1 and n_local == N_PER_GPU and args.dtype == "f32" and world == 1:
-            rec = json.load(open(pmc))
-            traffic_stale = rec.get("kernel_source_sha256") != kernel_source_sha()
-            if not traffic_stale:
-                traffic = rec.get("k_fused_force", {}).get("hbm_bytes_per_launch")
-                rocprof_us = rec.get("k_fused_force", {}).get("rocprof_avg_launch_us")
-                traffic_src = "profiles/%s/pmc_summary.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command on these kernel sources)" % PROFILE_ROUND
         # step level: N (P [CV pass read] + P [force pass read] + n_cv P [force writes]) over the measured step
         step_bytes = n_local * 4 * scalar4
         step_frac = step_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS
+        roofline = {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s", "step_frac": step_frac, "step_algorithmic_bytes": step_bytes,
+                    "step_frac_definition": "N*(P + P + n_cv*P) bytes per step (SURVEY.md 8d: 64 B/particle in f32) / ms_per_step / 8 TB/s, per GPU"}
+        if args.full:
+            # dominant kernel's algorithmic bytes per launch: read Scalar4 positions + write one Scalar4
+            # force per CV (48 B/particle); the fused kernel also carries the first grid pass of the deposit
+            # (per cell: 8 B dV written, 8+8 B reweighted r/w, 4 B hist_delta read)
+            force_bytes = n_local * (scalar4 + 2 * scalar4)
+            if path == "fused" and args.stride == 1:
+                force_bytes += 256 * 256 * 28
+            achieved = force_bytes / (force_us_mean * 1e-6) / 1e9
+            # HBM traffic of the dominant kernel from the PMC passes committed under profiles/ (FETCH_SIZE / WRITE_SIZE
+            # in separate rocprofv3 runs, gfx950 x2 correction on FETCH_SIZE); only valid for the default workload
+            # (a profiler cannot be attached from inside the run; the figure is only reported while the kernel's sources are the
+            # ones the counters were collected on — otherwise traffic is null and traffic_stale says so)
+            traffic, traffic_src, traffic_stale, rocprof_us = None, None, None, None
+            pmc = os.path.join(ROOT, "profiles", PROFILE_ROUND, "pmc_summary.json")
+            if os.path.exists(pmc) and path == "fused" and args.stride == 1 and n_local == N_PER_GPU and args.dtype == "f32" and world == 1:
+                rec = json.load(open(pmc))
+                traffic_stale = rec.get("kernel_source_sha256") != kernel_source_sha()
+                if not traffic_stale:
+                    traffic = rec.get("k_fused_force", {}).get("hbm_bytes_per_launch")
+                    rocprof_us = rec.get("k_fused_force", {}).get("rocprof_avg_launch_us")
+                    traffic_src = "profiles/%s/pmc_summary.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command on these kernel sources)" % PROFILE_ROUND
+            roofline.update({"kernel": "k_fused_force" if path == "fused" else "k_lamellar_forces", "achieved": achieved,
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                             "traffic_source": traffic_src, "traffic_stale": traffic_stale,
+                             "frac_definition": "algorithmic bytes per launch / avg_launch_us (in-process start/stop events of every launch) / 8 TB/s; "
+                                                "rocprof_avg_launch_us is the kernel-trace average of the same command under profiles/ (smaller: "
+                                                "the trace excludes the dispatch's own start-up), frac_rocprof prices the roofline with it",
+                             "rocprof_avg_launch_us": rocprof_us,
+                             "frac_rocprof": (force_bytes / (rocprof_us * 1e-6) / 1e9 / HBM_PEAK_GBS) if rocprof_us else None,
+                             "algorithmic_bytes_per_launch": force_bytes, "avg_launch_us": force_us_mean, "median_launch_us": force_us,
+                             "timing": timing, "launches_timed": int(keep.sum()), "cross_checks": alt,
+                             "stalled_samples_dropped": n_stalls})
         if world == 1 and args.scaling == "weak":
             workload = "1xMI355X: 10^6 particles, 2 lamellar CVs (8 Fourier modes each), 256^2 bias grid, well-tempered"
         elif walkers:
@@ -1152,19 +1248,7 @@ def main():
                        "particles_per_gpu": n_local, "particles_global": n_global * n_boxes, "n_cv": 2, "modes_per_cv": 8, "grid": "256x256",
                        "stride": args.stride, "fast_trig": int(args.fast_trig), "fast_trig_library_default": lib_default_trig,
                        "path": path, "driver": driver, "mode": "walkers" if walkers else "sharded" if world > 1 else "single"},
-            "roofline": {"bound": "hbm", "kernel": "k_fused_force" if path == "fused" else "k_lamellar_forces", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_source": traffic_src, "traffic_stale": traffic_stale,
-                         "frac_definition": "algorithmic bytes per launch / avg_launch_us (in-process start/stop events of every launch) / 8 TB/s; "
-                                            "rocprof_avg_launch_us is the kernel-trace average of the same command under profiles/ (smaller: "
-                                            "the trace excludes the dispatch's own start-up), frac_rocprof prices the roofline with it",
-                         "rocprof_avg_launch_us": rocprof_us,
-                         "frac_rocprof": (force_bytes / (rocprof_us * 1e-6) / 1e9 / HBM_PEAK_GBS) if rocprof_us else None,
-                         "step_frac": step_frac, "step_algorithmic_bytes": step_bytes,
-                         "step_frac_definition": "N*(P + P + n_cv*P) bytes per step (SURVEY.md 8d: 64 B/particle in f32) / ms_per_step / 8 TB/s, per GPU",
-                         "algorithmic_bytes_per_launch": force_bytes, "avg_launch_us": force_us_mean, "median_launch_us": force_us,
-                         "timing": timing, "launches_timed": int(keep.sum()), "cross_checks": alt,
-                         "stalled_samples_dropped": n_stalls},
+            "roofline": roofline,
             "state": st,
         }
         if rehearsal:
@@ -1190,9 +1274,9 @@ def main():
         if more_regions:
             extra["timed_region_repeats"] = {"ms_per_step": more_regions, "steps": args.steps,
                                              "note": "ten more regions of the same K steps, same barrier + synchronise bracket, right after the steady-state run"}
-        if not args.no_cpu_baseline and st.get("num_gaussians") and args.stride == 1 and not walkers:      # any N: the grid is replicated
+        if args.full and not args.no_cpu_baseline and st.get("num_gaussians") and args.stride == 1 and not walkers:      # any N: the grid is replicated
             out["self_check"] = self_check(st, args.stride)
-        if not args.no_cpu_baseline and eng.full is not None:
+        if args.full and not args.no_cpu_baseline and eng.full is not None:
             # sharded run: the CV values the ranks agreed on against the oracle on the whole snapshot (checker, untimed).
             # On a random snapshot the sums cancel to O(sqrt(N)): the tolerance of the parity tests is 1e-6 n_wave / sqrt(N)
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -1204,7 +1288,7 @@ def main():
             out["cv_check"] = {"cv_oracle": ref_cv, "abs_err": [abs(a - b) for a, b in zip(st["cv"], ref_cv)],
                                "tolerance": 1e-6 * 8 / np.sqrt(n_global)}
         single = world == 1 and args.scaling == "weak" and not walkers and n_local == N_PER_GPU
-        if single and not args.no_variants:
+        if single and args.full and not args.no_variants:
             # the same workload with one thing changed each (SURVEY.md 8d "Metric": stride 100, the fp64 build, and the trigonometry
             # mode that is NOT the one timed above), and a measured bandwidth ceiling beside the data-sheet peak
             try:
@@ -1222,7 +1306,7 @@ def main():
                 out["roofline"]["step_frac_of_measured_copy"] = step_bytes / (ss * 1e-3) / 1e9 / mp["copy_512MB_GBs"]
             except Exception as e:                                      # never let a variant break the headline line
                 extra["variants_error"] = repr(e)
-        if not args.no_cpu_baseline and world == 1 and not walkers:
+        if args.full and not args.no_cpu_baseline and world == 1 and not walkers:
             pos, types = eng.pos_np, eng.types_np
             n_cpu = min(pos.shape[0], N_PER_GPU)                        # bounded sample (strong scaling at N = 1 holds 8 x 10^6)
             v, dt = cpu_baseline(pos[:n_cpu], types[:n_cpu], eng.L, args.cpu_steps)
@@ -1243,7 +1327,7 @@ def main():
                 out["cpu_baseline_all_cores"] = {"error": str(e)}
             finally:
                 mtd_ref.use_openmp(False)
-        if single and not args.no_sub_records:
+        if single and args.full and not args.no_sub_records:
             # the other single-GPU configurations of BASELINE.json, bounded runs (not the headline: reported beside it)
             try:
                 if host is not None and isinstance(host, HostEngine):
@@ -1254,6 +1338,8 @@ def main():
                 extra["error"] = repr(e)
         if extra:
             out["extra"] = extra
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, *outputs)
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

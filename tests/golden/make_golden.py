@@ -55,14 +55,44 @@ def sph(src):
                 polar=polar.tolist(), azimuth=azim.tolist(), values=out.reshape(n, per, 2).tolist())
 
 
+def index_grid_all(src):
+    """every index of four seeded grids of 1 to 4 dimensions (the cross-check of test_oracle_kat.py)"""
+    rng = np.random.default_rng(0)
+    cases = []
+    for dim in (1, 2, 3, 4):
+        l = rng.integers(2, 9, dim).astype(np.uint32)
+        n = int(src.refsrc_index_num_elements(dim, l.ctypes.data_as(UP)))
+        coords = []
+        for idx in range(n):
+            c = np.zeros(dim, dtype=np.uint32)
+            src.refsrc_index_coords(dim, l.ctypes.data_as(UP), idx, c.ctypes.data_as(UP))
+            assert src.refsrc_index_get(dim, l.ctypes.data_as(UP), c.ctypes.data_as(UP)) == idx
+            coords.append([int(x) for x in c])
+        cases.append(dict(lengths=[int(x) for x in l], num_elements=n, coords=coords))
+    return dict(source="IndexGrid.cc:20-58 via oracle/_ref", cases=cases)
+
+
+def sph_lmax8(src):
+    """fsph::evaluate_SPH<double>(lmax=8, full_m=true) at seeded angles (the cross-check of test_oracle_steinhardt.py)"""
+    rng = np.random.default_rng(1)
+    n, lmax = 50, 8
+    polar, azim = rng.uniform(0.01, np.pi - 0.01, n), rng.uniform(-np.pi, np.pi, n)
+    out = np.zeros(2 * (lmax + 1) ** 2 * n)
+    src.refsrc_evaluate_sph(out.ctypes.data_as(DP), lmax, polar.ctypes.data_as(DP), azim.ctypes.data_as(DP), n, 1)
+    return dict(source="spherical_harmonics.hpp:229-246 via oracle/_ref", lmax=lmax, full_m=True,
+                polar=polar.tolist(), azimuth=azim.tolist(), values=out.reshape(n, -1, 2).tolist())
+
+
 def main():
     mtd_ref.build()
     src = mtd_ref.refsrc()
     if src is None:
         raise SystemExit("needs /root/reference (oracle/_ref)")
-    json.dump(index_grid(src), open(os.path.join(HERE, "index_grid.json"), "w"))
-    json.dump(sph(src), open(os.path.join(HERE, "sph_lmax6.json"), "w"))
-    print("wrote index_grid.json, sph_lmax6.json")
+    out = {"index_grid.json": index_grid(src), "sph_lmax6.json": sph(src),
+           "index_grid_all.json": index_grid_all(src), "sph_lmax8.json": sph_lmax8(src)}
+    for name, data in out.items():
+        json.dump(data, open(os.path.join(HERE, name), "w"))
+    print("wrote " + ", ".join(out))
 
 
 if __name__ == "__main__":

@@ -27,24 +27,28 @@ def test_index_grid_golden(ref):
 
 
 def test_index_grid_against_reference_source(ref):
-    """live cross-check with oracle/_ref (only where /root/reference exists, i.e. not on the GPU box)"""
-    src = ref.refsrc()
-    if src is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this box)")
+    """every index of four seeded grids of 1 to 4 dimensions as the reference's IndexGrid.cc maps them: the committed fixture
+    (tests/golden/make_golden.py), and where oracle/_ref is built the live library as well"""
     import ctypes as C
-    rng = np.random.default_rng(0)
-    for dim in (1, 2, 3, 4):
-        lengths = rng.integers(2, 9, dim).astype(np.uint32)
-        n = int(np.prod(lengths))
-        assert src.refsrc_index_num_elements(dim, lengths.ctypes.data_as(C.POINTER(C.c_uint))) == n
-        for idx in range(n):
-            c = np.zeros(dim, dtype=np.uint32)
-            src.refsrc_index_coords(dim, lengths.ctypes.data_as(C.POINTER(C.c_uint)), idx,
-                                    c.ctypes.data_as(C.POINTER(C.c_uint)))
-            assert list(ref.index_coords(lengths, idx)) == list(c)
+    data = json.load(open(os.path.join(GOLDEN, "index_grid_all.json")))
+    src = ref.refsrc()
+    for case in data["cases"]:
+        lengths = np.array(case["lengths"], dtype=np.uint32)
+        dim, n = len(lengths), int(np.prod(lengths))
+        assert case["num_elements"] == n and len(case["coords"]) == n
+        if src is not None:
+            assert src.refsrc_index_num_elements(dim, lengths.ctypes.data_as(C.POINTER(C.c_uint))) == n
+        for idx, want in enumerate(case["coords"]):
+            c = np.array(want, dtype=np.uint32)
+            assert list(ref.index_coords(lengths, idx)) == want
             assert ref.index_get(lengths, c) == idx
-            assert src.refsrc_index_get(dim, lengths.ctypes.data_as(C.POINTER(C.c_uint)),
-                                        c.ctypes.data_as(C.POINTER(C.c_uint))) == idx
+            if src is not None:
+                live = np.zeros(dim, dtype=np.uint32)
+                src.refsrc_index_coords(dim, lengths.ctypes.data_as(C.POINTER(C.c_uint)), idx,
+                                        live.ctypes.data_as(C.POINTER(C.c_uint)))
+                assert list(live) == want
+                assert src.refsrc_index_get(dim, lengths.ctypes.data_as(C.POINTER(C.c_uint)),
+                                            c.ctypes.data_as(C.POINTER(C.c_uint))) == idx
 
 
 def test_first_cv_fastest(ref):

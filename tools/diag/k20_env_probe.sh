@@ -6,7 +6,7 @@ mkdir -p gpurun_out/r4
 R=${1:-8}
 for round in $(seq 1 $R); do
   for v in "" "ROC_ACTIVE_WAIT_TIMEOUT=1000" "ROC_CPU_WAIT_FOR_SIGNAL=0"; do
-    out=$(env $v timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-sub-records --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | tail -1 | python -c "
+    out=$(env $v timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-sub-records --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 r=d['extra']['timed_region_repeats']['ms_per_step']

@@ -23,10 +23,10 @@ if [[ " $WHAT " == *" bench "* ]]; then
   # counters of the headline kernels first: the bench lines below read profiles/$ROUND/pmc_summary.json and report `traffic` only
   # while its hash of the kernel sources matches
   for c in FETCH_SIZE WRITE_SIZE; do
-    pmc_pass $c $c -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-sub-records --no-variants --driver abi
+    pmc_pass $c $c -- python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-sub-records --no-variants --driver abi
   done
   rm -rf $O/kt
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o bench -- python3 bench.py --no-cpu-baseline --no-sub-records --no-variants > $O/bench_under_rocprof.log 2>&1
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o bench -- python3 bench.py --full --no-cpu-baseline --no-sub-records --no-variants > $O/bench_under_rocprof.log 2>&1
   grep '^{"metric"' $O/bench_under_rocprof.log | tail -1 > $O/bench_default_under_rocprof.json
   cp "$(find $O/kt -name '*kernel_stats.csv' | head -1)" $O/bench_default_kernel_stats.csv
   cp "$(find $O/kt -name '*agent_info.csv' | head -1)" $O/agent_info.csv; rm -rf $O/kt
@@ -57,23 +57,23 @@ if [[ " $WHAT " == *" mesh "* || " $WHAT " == *" ql "* ]]; then
 fi
 if [[ " $WHAT " == *" bench "* ]]; then
   # the lines themselves LAST: they read the counter summaries written above (profiles/$ROUND/ of this copy of the tree)
-  timeout -k 10 600 python3 bench.py > $O/bench_default.log 2>&1 && tail -1 $O/bench_default.log > $O/bench_default.json
-  timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 > $O/bench_k20.log 2>&1 && tail -1 $O/bench_k20.log > $O/bench_driver_call_k20.json
+  timeout -k 10 600 python3 bench.py --full > $O/bench_default.log 2>&1 && tail -1 $O/bench_default.log > $O/bench_default.json
+  timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 > $O/bench_k20.log 2>&1 && tail -1 $O/bench_k20.log > $O/bench_driver_call_k20.json
 fi
 if [[ " $WHAT " == *" sharded "* ]]; then
   # the particle-sharded code path with one rank (mailbox to itself) and with two ranks sharing this GPU (rehearsal: software path only)
-  MTD_BENCH_FORCE_DIST=1 timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-sub-records --no-variants > $O/mailbox_1rank.log 2>&1; grep '^{"metric"' $O/mailbox_1rank.log | tail -1 > $O/bench_mailbox_1rank.json
-  MTD_XGMI_MAILBOX=0 MTD_BENCH_FORCE_DIST=1 timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-sub-records --no-variants > $O/rccl_1rank.log 2>&1; grep '^{"metric"' $O/rccl_1rank.log | tail -1 > $O/bench_rccl_1rank.json
-  timeout -k 10 400 python3 bench.py --gpus 2 --particles 500000 > $O/rehearsal2.log 2>&1; grep '^{"metric"' $O/rehearsal2.log | tail -1 > $O/bench_rehearsal_2ranks_weak.json
-  timeout -k 10 400 python3 bench.py --gpus 2 --scaling strong --particles 1000000 > $O/rehearsal2s.log 2>&1; grep '^{"metric"' $O/rehearsal2s.log | tail -1 > $O/bench_rehearsal_2ranks_strong.json
-  timeout -k 10 400 python3 bench.py --gpus 2 --walkers --particles 500000 --steps 500 --warmup 50 > $O/rehearsal2w.log 2>&1; grep '^{"metric"' $O/rehearsal2w.log | tail -1 > $O/bench_rehearsal_2walkers.json
+  MTD_BENCH_FORCE_DIST=1 timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-sub-records --no-variants > $O/mailbox_1rank.log 2>&1; grep '^{"metric"' $O/mailbox_1rank.log | tail -1 > $O/bench_mailbox_1rank.json
+  MTD_XGMI_MAILBOX=0 MTD_BENCH_FORCE_DIST=1 timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-sub-records --no-variants > $O/rccl_1rank.log 2>&1; grep '^{"metric"' $O/rccl_1rank.log | tail -1 > $O/bench_rccl_1rank.json
+  timeout -k 10 400 python3 bench.py --full --gpus 2 --particles 500000 > $O/rehearsal2.log 2>&1; grep '^{"metric"' $O/rehearsal2.log | tail -1 > $O/bench_rehearsal_2ranks_weak.json
+  timeout -k 10 400 python3 bench.py --full --gpus 2 --scaling strong --particles 1000000 > $O/rehearsal2s.log 2>&1; grep '^{"metric"' $O/rehearsal2s.log | tail -1 > $O/bench_rehearsal_2ranks_strong.json
+  timeout -k 10 400 python3 bench.py --full --gpus 2 --walkers --particles 500000 --steps 500 --warmup 50 > $O/rehearsal2w.log 2>&1; grep '^{"metric"' $O/rehearsal2w.log | tail -1 > $O/bench_rehearsal_2walkers.json
   # configs 3 and 5 domain decomposed inside the C++ host classes (two processes on this GPU: the code path is real, the numbers mean nothing)
-  timeout -k 10 400 python3 bench.py --config 3 --gpus 2 --particles 500000 --steps 200 --warmup 20 > $O/rehearsal_c3r.log 2>&1; grep '^{"metric"' $O/rehearsal_c3r.log | tail -1 > $O/bench_rehearsal_config3_replicated.json
-  timeout -k 10 400 python3 bench.py --config 3 --gpus 2 --particles 500000 --steps 200 --warmup 20 --mesh slab > $O/rehearsal_c3s.log 2>&1; grep '^{"metric"' $O/rehearsal_c3s.log | tail -1 > $O/bench_rehearsal_config3_slab.json
-  timeout -k 10 400 python3 bench.py --config 5 --gpus 2 --steps 200 --warmup 20 > $O/rehearsal_c5.log 2>&1; grep '^{"metric"' $O/rehearsal_c5.log | tail -1 > $O/bench_rehearsal_config5.json
+  timeout -k 10 400 python3 bench.py --full --config 3 --gpus 2 --particles 500000 --steps 200 --warmup 20 > $O/rehearsal_c3r.log 2>&1; grep '^{"metric"' $O/rehearsal_c3r.log | tail -1 > $O/bench_rehearsal_config3_replicated.json
+  timeout -k 10 400 python3 bench.py --full --config 3 --gpus 2 --particles 500000 --steps 200 --warmup 20 --mesh slab > $O/rehearsal_c3s.log 2>&1; grep '^{"metric"' $O/rehearsal_c3s.log | tail -1 > $O/bench_rehearsal_config3_slab.json
+  timeout -k 10 400 python3 bench.py --full --config 5 --gpus 2 --steps 200 --warmup 20 > $O/rehearsal_c5.log 2>&1; grep '^{"metric"' $O/rehearsal_c5.log | tail -1 > $O/bench_rehearsal_config5.json
   # the same entry at N = 1 (the single-GPU lines of configs 3 and 5 through bench.py --config)
-  timeout -k 10 400 python3 bench.py --config 3 > $O/config3_n1.log 2>&1; grep '^{"metric"' $O/config3_n1.log | tail -1 > $O/bench_config3_n1.json
-  timeout -k 10 400 python3 bench.py --config 5 > $O/config5_n1.log 2>&1; grep '^{"metric"' $O/config5_n1.log | tail -1 > $O/bench_config5_n1.json
+  timeout -k 10 400 python3 bench.py --full --config 3 > $O/config3_n1.log 2>&1; grep '^{"metric"' $O/config3_n1.log | tail -1 > $O/bench_config3_n1.json
+  timeout -k 10 400 python3 bench.py --full --config 5 > $O/config5_n1.log 2>&1; grep '^{"metric"' $O/config5_n1.log | tail -1 > $O/bench_config5_n1.json
 fi
 set +x
 ls -la $O
