@@ -72,7 +72,7 @@ constexpr int FF_UNROLL = 2;
 
 // COMM (particle-sharded step): the last CV block to finish adds up this rank's block partial sums (fixed order) and
 // stores the NCV totals into every rank's mailbox over xGMI (comm_device.hpp); launch B polls its local mailbox.
-template<typename S4, int NCV, bool FAST, bool COMM, int U = FCV_UNROLL>
+template<typename S4, int NCV, bool FAST, bool COMM, bool ORTHO, int U = FCV_UNROLL>
 __global__ __launch_bounds__(FCV_THREADS) void k_fused_cv(const LamKArgs a, const S4 *__restrict__ postype, const unsigned int N,
                                                           double *partials, const MetadCfg c,
                                                           const unsigned int n_apply_blocks, const CommK ck)
@@ -110,8 +110,8 @@ __global__ __launch_bounds__(FCV_THREADS) void k_fused_cv(const LamKArgs a, cons
     float acc[NCV];
 #pragma unroll
     for (int i = 0; i < NCV; ++i) acc[i] = 0.0f;
-    lam_cv_accumulate<S4, NCV, FAST, U>(a, postype, N, block_id * FCV_THREADS + threadIdx.x, n_blocks * FCV_THREADS,
-                                        s_coeff, s_mt, first, acc);
+    lam_cv_accumulate<S4, NCV, FAST, U, ORTHO>(a, postype, N, block_id * FCV_THREADS + threadIdx.x, n_blocks * FCV_THREADS,
+                                               s_coeff, s_mt, first, acc);
     MTD_STAMP(5, block_id == 0 && threadIdx.x == 0);
     lam_cv_block_reduce<NCV>(acc, s_wave, partials, block_id);
     MTD_STAMP(6, block_id == 0 && threadIdx.x == 0);
@@ -157,7 +157,8 @@ template<> struct ff_groups<float4, 1, false> { static constexpr int value = 2; 
 template<> struct ff_groups<double4, 1, true> { static constexpr int value = 2; };
 template<> struct ff_groups<double4, 1, false> { static constexpr int value = 2; };
 
-template<typename S4, int NCV, bool FAST, int GROUPS, bool COMM>
+// ORTHO: the B of `a` is diagonal (LamKArgs::ortho)
+template<typename S4, int NCV, bool FAST, int GROUPS, bool COMM, bool ORTHO>
 __global__ __launch_bounds__(FF_THREADS, 4) void k_fused_force(const LamKArgs a, const S4 *__restrict__ postype, const ForcePtrs out,
                                                             const unsigned int N, const double two_over_n, const MetadCfg c,
                                                             const int deposit, const unsigned int n_grid_blocks, const CommK ck)
@@ -261,8 +262,8 @@ __global__ __launch_bounds__(FF_THREADS, 4) void k_fused_force(const LamKArgs a,
         {
         RawGroup<S4, FF_U> raw1;
         if (GROUPS > 1) lam_force_request<S4, FF_U>(postype, N, first1, stride, raw1);     // in flight while group 0 is summed
-        lam_force_unscaled_from<S4, NCV, FAST, FF_U>(a, N, first, stride, s_mt, raw0, R);
-        if (GROUPS > 1) lam_force_unscaled_from<S4, NCV, FAST, FF_U>(a, N, first1, stride, s_mt, raw1, R1);
+        lam_force_unscaled_from<S4, NCV, FAST, FF_U, ORTHO>(a, N, first, stride, s_mt, raw0, R);
+        if (GROUPS > 1) lam_force_unscaled_from<S4, NCV, FAST, FF_U, ORTHO>(a, N, first1, stride, s_mt, raw1, R1);
         MTD_STAMP(27, blockIdx.x == n_grid_blocks && threadIdx.x == 64);
         }
     lds_barrier();                 // publishes s_chain / s_wcoef (LDS only: nothing that went to global memory is read back)
@@ -494,20 +495,25 @@ unsigned int resident_capacity(const void *kernel, int threads)
     return cap;
     }
 
-template<typename S4, bool FAST> const void *fused_cv_comm_kernel_of(unsigned int n_cv)
+template<typename S4, bool FAST, bool ORTHO> const void *fused_cv_comm_kernel_of(unsigned int n_cv)
     {
-    return n_cv == 1 ? (const void *)k_fused_cv<S4, 1, FAST, true>
-                     : (n_cv == 2 ? (const void *)k_fused_cv<S4, 2, FAST, true> : (const void *)k_fused_cv<S4, 3, FAST, true>);
+    return n_cv == 1 ? (const void *)k_fused_cv<S4, 1, FAST, true, ORTHO>
+                     : (n_cv == 2 ? (const void *)k_fused_cv<S4, 2, FAST, true, ORTHO> : (const void *)k_fused_cv<S4, 3, FAST, true, ORTHO>);
     }
 
 // the instantiation a sharded CV pass launches (mtd_fused_cv_pass asks for its residency before it takes an exchange number)
-const void *fused_cv_comm_kernel(int dtype, unsigned int n_cv, bool fast)
+template<bool ORTHO> const void *fused_cv_comm_kernel_o(int dtype, unsigned int n_cv, bool fast)
     {
-    if (dtype == MTD_F32) return fast ? fused_cv_comm_kernel_of<float4, true>(n_cv) : fused_cv_comm_kernel_of<float4, false>(n_cv);
-    return fast ? fused_cv_comm_kernel_of<double4, true>(n_cv) : fused_cv_comm_kernel_of<double4, false>(n_cv);
+    if (dtype == MTD_F32)
+        return fast ? fused_cv_comm_kernel_of<float4, true, ORTHO>(n_cv) : fused_cv_comm_kernel_of<float4, false, ORTHO>(n_cv);
+    return fast ? fused_cv_comm_kernel_of<double4, true, ORTHO>(n_cv) : fused_cv_comm_kernel_of<double4, false, ORTHO>(n_cv);
+    }
+const void *fused_cv_comm_kernel(int dtype, unsigned int n_cv, bool fast, bool ortho)
+    {
+    return ortho ? fused_cv_comm_kernel_o<true>(dtype, n_cv, fast) : fused_cv_comm_kernel_o<false>(dtype, n_cv, fast);
     }
 
-template<typename S4, bool FAST>
+template<typename S4, bool FAST, bool ORTHO>
 int launch_fused_cv(const LamKArgs &k_in, unsigned int N, const void *d_postype, double *d_partials, unsigned int cv_blocks,
                     const MetadCfg &cfg, unsigned int n_apply, const CommK *ck, hipStream_t s)
     {
@@ -516,12 +522,12 @@ int launch_fused_cv(const LamKArgs &k_in, unsigned int N, const void *d_postype,
     const LamKArgs k = dense_cv_args(k_in);                          // (the kernel stages its tables with flat loads)
     if (ck)
         {
-        if (grid > resident_capacity(fused_cv_comm_kernel_of<S4, FAST>(k.n_cv), FCV_THREADS)) return MTD_ERR_UNSUPPORTED;
+        if (grid > resident_capacity(fused_cv_comm_kernel_of<S4, FAST, ORTHO>(k.n_cv), FCV_THREADS)) return MTD_ERR_UNSUPPORTED;
         switch (k.n_cv)
             {
-            case 1: k_fused_cv<S4, 1, FAST, true><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, *ck); break;
-            case 2: k_fused_cv<S4, 2, FAST, true><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, *ck); break;
-            case 3: k_fused_cv<S4, 3, FAST, true><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, *ck); break;
+            case 1: k_fused_cv<S4, 1, FAST, true, ORTHO><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, *ck); break;
+            case 2: k_fused_cv<S4, 2, FAST, true, ORTHO><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, *ck); break;
+            case 3: k_fused_cv<S4, 3, FAST, true, ORTHO><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, *ck); break;
             default: return MTD_ERR_UNSUPPORTED;
             }
         MTD_LAUNCH_CHECK();
@@ -531,12 +537,12 @@ int launch_fused_cv(const LamKArgs &k_in, unsigned int N, const void *d_postype,
     std::memset(&none, 0, sizeof(none));
     switch (k.n_cv)
         {
-        case 1: k_fused_cv<S4, 1, FAST, false><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, none); break;
-        case 2: k_fused_cv<S4, 2, FAST, false><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, none); break;
-        case 3: k_fused_cv<S4, 3, FAST, false><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, none); break;
-        case 4: k_fused_cv<S4, 4, FAST, false><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, none); break;
-        case 5: k_fused_cv<S4, 5, FAST, false><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, none); break;
-        case 6: k_fused_cv<S4, 6, FAST, false><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, none); break;
+        case 1: k_fused_cv<S4, 1, FAST, false, ORTHO><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, none); break;
+        case 2: k_fused_cv<S4, 2, FAST, false, ORTHO><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, none); break;
+        case 3: k_fused_cv<S4, 3, FAST, false, ORTHO><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, none); break;
+        case 4: k_fused_cv<S4, 4, FAST, false, ORTHO><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, none); break;
+        case 5: k_fused_cv<S4, 5, FAST, false, ORTHO><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, none); break;
+        case 6: k_fused_cv<S4, 6, FAST, false, ORTHO><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, none); break;
         default: return MTD_ERR_UNSUPPORTED;
         }
     MTD_LAUNCH_CHECK();
@@ -571,18 +577,20 @@ int mtd_fused_cv_pass(mtd_metad *m, const mtd_lamellar_set *set, unsigned int n_
         if (set->n_cv > (unsigned int)CHAIN_MAX_CV || set->n_cv != m->cfg.n_cv) return MTD_ERR_UNSUPPORTED;
         // every refusal comes BEFORE the exchange number advances: a call that sends nothing must not consume a number
         // (the peers would wait for an exchange that never happens)
-        const void *kern = fused_cv_comm_kernel(dtype, set->n_cv, fast);
+        const void *kern = fused_cv_comm_kernel(dtype, set->n_cv, fast, k.ortho != 0);
         if (blocks + n_apply > resident_capacity(kern, FCV_THREADS)) return MTD_ERR_UNSUPPORTED;
         rc = comm_next(m->comm, ckv);                           // this launch sends exchange seq, launch B receives it
         if (rc) return rc;
         ck = &ckv;
         }
+#define MTD_LAUNCH_FCV(S4, FASTV) \
+        (k.ortho ? launch_fused_cv<S4, FASTV, true>(k, n_particles, d_postype, d_partials, blocks, m->cfg, n_apply, ck, s) \
+                 : launch_fused_cv<S4, FASTV, false>(k, n_particles, d_postype, d_partials, blocks, m->cfg, n_apply, ck, s))
     if (dtype == MTD_F32)
-        rc = fast ? launch_fused_cv<float4, true>(k, n_particles, d_postype, d_partials, blocks, m->cfg, n_apply, ck, s)
-                  : launch_fused_cv<float4, false>(k, n_particles, d_postype, d_partials, blocks, m->cfg, n_apply, ck, s);
+        rc = fast ? MTD_LAUNCH_FCV(float4, true) : MTD_LAUNCH_FCV(float4, false);
     else
-        rc = fast ? launch_fused_cv<double4, true>(k, n_particles, d_postype, d_partials, blocks, m->cfg, n_apply, ck, s)
-                  : launch_fused_cv<double4, false>(k, n_particles, d_postype, d_partials, blocks, m->cfg, n_apply, ck, s);
+        rc = fast ? MTD_LAUNCH_FCV(double4, true) : MTD_LAUNCH_FCV(double4, false);
+#undef MTD_LAUNCH_FCV
     if (rc) return rc;
     m->pending_apply = 0;
     return MTD_SUCCESS;
@@ -659,8 +667,11 @@ int mtd_fused_force_pass_slots(mtd_metad *m, const mtd_lamellar_set *set, const 
              unsigned int fblocks = (n_particles + per_block - 1) / per_block; \
              if (fblocks == 0 && n_grid == 0) fblocks = 1;               /* still one block to publish the scalars */ \
              grid = n_grid + fblocks; \
-             if (m->comm) MTD_LAUNCH_FF_K((k_fused_force<S4, NCV, FASTV, ff_groups<S4, NCV, FASTV>::value, true>)); \
-             else MTD_LAUNCH_FF_K((k_fused_force<S4, NCV, FASTV, ff_groups<S4, NCV, FASTV>::value, false>)); } while (0)
+             constexpr int G = ff_groups<S4, NCV, FASTV>::value; \
+             if (m->comm) { if (k.ortho) MTD_LAUNCH_FF_K((k_fused_force<S4, NCV, FASTV, G, true, true>)); \
+                            else MTD_LAUNCH_FF_K((k_fused_force<S4, NCV, FASTV, G, true, false>)); } \
+             else { if (k.ortho) MTD_LAUNCH_FF_K((k_fused_force<S4, NCV, FASTV, G, false, true>)); \
+                    else MTD_LAUNCH_FF_K((k_fused_force<S4, NCV, FASTV, G, false, false>)); } } while (0)
 #define MTD_LAUNCH_FF_NCV(S4, FASTV) \
         switch (set->n_cv) { case 1: MTD_LAUNCH_FF(S4, 1, FASTV); break; case 2: MTD_LAUNCH_FF(S4, 2, FASTV); break; default: MTD_LAUNCH_FF(S4, 3, FASTV); break; }
         if (dtype == MTD_F32)
@@ -771,9 +782,9 @@ int fused_grid_step(mtd_metad *m, unsigned int timestep, hipStream_t s)
     std::memset(&ck, 0, sizeof(ck));
     switch (m->cfg.n_cv)
         {
-        case 1: k_fused_force<float4, 1, true, 1, false><<<grid, FF_THREADS, 0, s>>>(k, nullptr, out, 0, 0.0, m->cfg, dep, n_grid, ck); break;
-        case 2: k_fused_force<float4, 2, true, 1, false><<<grid, FF_THREADS, 0, s>>>(k, nullptr, out, 0, 0.0, m->cfg, dep, n_grid, ck); break;
-        default: k_fused_force<float4, 3, true, 1, false><<<grid, FF_THREADS, 0, s>>>(k, nullptr, out, 0, 0.0, m->cfg, dep, n_grid, ck); break;
+        case 1: k_fused_force<float4, 1, true, 1, false, false><<<grid, FF_THREADS, 0, s>>>(k, nullptr, out, 0, 0.0, m->cfg, dep, n_grid, ck); break;
+        case 2: k_fused_force<float4, 2, true, 1, false, false><<<grid, FF_THREADS, 0, s>>>(k, nullptr, out, 0, 0.0, m->cfg, dep, n_grid, ck); break;
+        default: k_fused_force<float4, 3, true, 1, false, false><<<grid, FF_THREADS, 0, s>>>(k, nullptr, out, 0, 0.0, m->cfg, dep, n_grid, ck); break;
         }
     MTD_LAUNCH_CHECK();
     m->pending_apply = dep;

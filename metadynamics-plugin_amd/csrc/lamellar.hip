@@ -255,6 +255,9 @@ int fill_kargs(LamKArgs &k, const mtd_lamellar_set *set, const mtd_box *box)
 
     std::memset(&k, 0, sizeof(k));
     reciprocal_rows(*box, k.B);
+    // a box without tilt has a diagonal reciprocal matrix (its off-diagonal entries come out as exact zeros)
+    k.ortho = (k.B[0][1] == 0.0 && k.B[0][2] == 0.0 && k.B[1][0] == 0.0 && k.B[1][2] == 0.0 && k.B[2][0] == 0.0 && k.B[2][1] == 0.0)
+                  ? 1u : 0u;
     k.n_cv = set->n_cv;
     k.n_modes = set->n_modes;
     k.n_types = set->n_types;

@@ -21,7 +21,7 @@ struct LamKArgs
     unsigned int trig;                        // mtd_lamellar_set::trig_mode (host side only: selects the instantiation, lam_fast_trig)
     unsigned int first[MTD_MAX_CV + 1];
     unsigned char slot[MTD_MAX_CV];           // CV c of the set is collective variable slot[c] of the bias grid (fused force pass)
-    unsigned int _pad2;
+    unsigned int ortho;                       // 1: B is diagonal (orthorhombic box) — host side only: selects the ORTHO instantiations
     float4 h[MTD_MAX_MODES];                  // Miller indices (h, k, l, fold): fold = 1 when the mode 2(h,k,l) of the same CV is
                                               // folded into this one by the CV pass, else 0
     unsigned char corder[MTD_MAX_MODES];      // CV pass: the modes of CV c it visits are corder[first[c] .. first[c] + nact[c])
@@ -61,6 +61,21 @@ __device__ __forceinline__ void project(const LamKArgs &a, const Particle &p, fl
     g0 = (float)(a.B[0][0] * p.x + a.B[0][1] * p.y + a.B[0][2] * p.z);
     g1 = (float)(a.B[1][0] * p.x + a.B[1][1] * p.y + a.B[1][2] * p.z);
     g2 = (float)(a.B[2][0] * p.x + a.B[2][1] * p.y + a.B[2][2] * p.z);
+    }
+
+// ORTHO (the host saw B diagonal, LamKArgs::ortho): 3 fp64 products instead of 9 products / fmas.  The off-diagonal terms of the
+// general form are exact zeros, so for finite positions both give the same bits.
+template<bool ORTHO>
+__device__ __forceinline__ void project_o(const LamKArgs &a, const Particle &p, float &g0, float &g1, float &g2)
+    {
+    if constexpr (ORTHO)
+        {
+        g0 = (float)(a.B[0][0] * p.x);
+        g1 = (float)(a.B[1][1] * p.y);
+        g2 = (float)(a.B[2][2] * p.z);
+        }
+    else
+        project(a, p, g0, g1, g2);
     }
 
 // s_coeff[MTD_MAX_CV * MTD_MAX_TYPES] <- per-type mode coefficients (call from all threads, then sync)
@@ -177,7 +192,7 @@ __device__ __forceinline__ void lam_load_group_nc(const S4 *__restrict__ postype
 // group is requested before the current one is summed, so only the very first memory round trip of the launch is exposed
 // (measured: 2.6 us per exposed round trip, more than summing a group)
 // one group's terms: acc[c] += sum over the U particles of `cur` (at base, base + n_threads, ...) of a_c(type_j) sum_k cos(q_k . r_j)
-template<typename S4, int NCV, bool FAST, int U>
+template<typename S4, int NCV, bool FAST, int U, bool ORTHO = false>
 __device__ __forceinline__ void lam_cv_group(const LamKArgs &a, const unsigned int N, const unsigned int base, const unsigned int n_threads,
                                              const float *s_coeff, const ModeTables &mt, const RawGroup<S4, U> &cur, float (&acc)[NCV])
     {
@@ -192,7 +207,7 @@ __device__ __forceinline__ void lam_cv_group(const LamKArgs &a, const unsigned i
         ok[u] = base + u * n_threads < N;
         const Particle p = scalar4_traits<S4>::unpack(cur.v[u]);
         float x0, x1, x2;
-        project(a, p, x0, x1, x2);
+        project_o<ORTHO>(a, p, x0, x1, x2);
         g0[u / 2][u % 2] = x0;
         g1[u / 2][u % 2] = x1;
         g2[u / 2][u % 2] = x2;
@@ -236,7 +251,7 @@ __device__ __forceinline__ void lam_cv_group(const LamKArgs &a, const unsigned i
         }
     }
 
-template<typename S4, int NCV, bool FAST, int U>
+template<typename S4, int NCV, bool FAST, int U, bool ORTHO = false>
 __device__ __forceinline__ void lam_cv_accumulate(const LamKArgs &a, const S4 *__restrict__ postype, const unsigned int N,
                                                   const unsigned int tid, const unsigned int n_threads,
                                                   const float *s_coeff, const ModeTables &mt, RawGroup<S4, U> cur,
@@ -250,7 +265,7 @@ __device__ __forceinline__ void lam_cv_accumulate(const LamKArgs &a, const S4 *_
         // group — the next group's round trip was paid in full before the first cosine (gfx950 ISA), not overlapped
         RawGroup<S4, U> nxt;
         lam_load_group_nc<S4, U>(postype, N, next < N ? next : N - 1, n_threads, nxt);
-        lam_cv_group<S4, NCV, FAST, U>(a, N, base, n_threads, s_coeff, mt, cur, acc);
+        lam_cv_group<S4, NCV, FAST, U, ORTHO>(a, N, base, n_threads, s_coeff, mt, cur, acc);
         cur = nxt;
         }
     }
@@ -350,7 +365,7 @@ template<int NCV, int U> struct ForceRegs
 template<typename S4, int U>
 __device__ __forceinline__ void lam_force_request(const S4 *__restrict__ postype, const unsigned int N, const unsigned int first,
                                                   const unsigned int stride, RawGroup<S4, U> &raw);
-template<typename S4, int NCV, bool FAST, int U>
+template<typename S4, int NCV, bool FAST, int U, bool ORTHO = false>
 __device__ __forceinline__ void lam_force_unscaled_from(const LamKArgs &a, const unsigned int N, const unsigned int first,
                                                         const unsigned int stride, const ModeTables &mt, const RawGroup<S4, U> &raw,
                                                         ForceRegs<NCV, U> &R);
@@ -383,7 +398,7 @@ __device__ __forceinline__ void lam_force_request(const S4 *__restrict__ postype
         }
     }
 
-template<typename S4, int NCV, bool FAST, int U>
+template<typename S4, int NCV, bool FAST, int U, bool ORTHO>
 __device__ __forceinline__ void lam_force_unscaled_from(const LamKArgs &a, const unsigned int N, const unsigned int first,
                                                         const unsigned int stride, const ModeTables &mt, const RawGroup<S4, U> &raw,
                                                         ForceRegs<NCV, U> &R)
@@ -398,7 +413,7 @@ __device__ __forceinline__ void lam_force_unscaled_from(const LamKArgs &a, const
         R.ok[u] = i < N;
         const Particle p = scalar4_traits<S4>::unpack(raw.v[u]);
         float x0, x1, x2;
-        project(a, p, x0, x1, x2);
+        project_o<ORTHO>(a, p, x0, x1, x2);
         g0[u / 2][u % 2] = x0;
         g1[u / 2][u % 2] = x1;
         g2[u / 2][u % 2] = x2;
