@@ -568,6 +568,51 @@ int mtd_ql_forces(unsigned int n_particles, const void *d_postype, void *d_force
                   const double *d_scratch, const double *d_bias, double bias_host, mtd_stream_t stream);
 
 /* ================================================================================================
+ * Neighbour list of the stand-alone path (cell list, built on the device)
+ * no reference counterpart: HOOMD's md::NeighborList is HOOMD core.  Produces the three arrays SteinhardtQl.cc:80-85 reads, in
+ * HOOMD's layout: the neighbours of particle i are d_nlist[d_head_list[i] .. d_head_list[i] + d_n_neigh[i]).
+ * ============================================================================================== */
+
+typedef struct mtd_nlist mtd_nlist;
+
+/* A handle owns its device buffers and grows them geometrically.  _create touches no device (buffers come with the first build);
+ * it returns hipErrorOutOfMemory (as a positive status) when the host allocation of the handle fails. */
+int mtd_nlist_create(mtd_nlist **out);
+int mtd_nlist_destroy(mtd_nlist *h);
+
+/* All pairs with |minimum_image(r_i - r_j)|^2 <= r_list^2, tested in fp64 (MTD_F32 positions are widened first) under HOOMD's
+ * BoxDim::minImage of `box`, for the n_local particles at the front of d_postype; the n_ghost particles behind them are partners
+ * only and own no row (entries may index them, as n_local, n_local + 1, ...).
+ *   half_nlist = 0: full list, (i, j) listed <=> (j, i) listed for local i, j;  != 0: every pair once, in the row of its smaller
+ *                   index (MTD_ERR_UNSUPPORTED together with ghosts: SteinhardtQl refuses that combination)
+ *   type >= 0:      only pairs whose two particles are both of that type (cv.steinhardt.get_rcut, cv.py:603-622); -1: all pairs
+ * Cells per direction: floor(d_k / r_list), d_k = distance between the k-th pair of faces of the box (tilt included), at least 1.
+ * In a box that is large against the particle number the count is capped at cbrt(2 N) per direction (not below 3, not above 1024),
+ * so that a dilute system does not pay for millions of empty cells: fewer, larger cells give the same list.
+ * r_list <= d_k / 2 is required in every periodic direction (then no cell is visited twice and the image is unique), else
+ * MTD_ERR_INVALID_ARGUMENT; directions with box->periodic[k] == 0 take no image and do not wrap.  Arguments (null handle,
+ * r_list <= 0, unknown dtype, r_list against the box) are checked before the device is touched.
+ * The result does not depend on the arrival order of any atomic: two builds of the same input give the same bits, whatever the
+ * handle built before.  Rows are ordered by cell, inside a cell by particle index.
+ * Synchronises the stream ONCE (the entry count sizes d_nlist); the fill itself is only stream-ordered.  The returned device
+ * pointers belong to the handle and stay valid until its next build or its destruction; *n_entries (host) = sum of d_n_neigh. */
+int mtd_nlist_build(mtd_nlist *h, unsigned int n_local, unsigned int n_ghost, const void *d_postype, int dtype,
+                    const mtd_box *box, double r_list, int half_nlist, int type, const unsigned int **d_head_list,
+                    const unsigned int **d_n_neigh, const unsigned int **d_nlist, size_t *n_entries, mtd_stream_t stream);
+
+/* HOOMD's displacement check: *needs_rebuild (host) = 1 when some particle of the last build (locals and ghosts, the same N and
+ * order) has moved by more than r_buff / 2 since then, under minimum image (a particle that was wrapped into the box has not
+ * moved by L); also 1, without any device work, when the box or the dtype differ from the last build's or nothing was built yet.
+ * A caller whose particle number changed builds anew (the check has the last build's N).  One launch and one stream
+ * synchronisation. */
+int mtd_nlist_check(mtd_nlist *h, const void *d_postype, int dtype, const mtd_box *box, double r_buff, int *needs_rebuild,
+                    mtd_stream_t stream);
+
+/* cells per direction of the handle's last build, the cap of mtd_nlist_build applied (host, no device work);
+ * MTD_ERR_INVALID_ARGUMENT before the first build */
+int mtd_nlist_cells(const mtd_nlist *h, unsigned int dim[3]);
+
+/* ================================================================================================
  * WellTemperedEnsemble (potential energy as CV)
  * replaces WellTemperedEnsemble.cuh:3-19 (gpu_scale_netforce, gpu_reduce_potential_energy)
  * ============================================================================================== */

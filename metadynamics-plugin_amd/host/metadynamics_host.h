@@ -282,8 +282,9 @@ class SteinhardtQl : public CollectiveVariable
         double getCurrentValue(unsigned int timestep) override;        // SteinhardtQl.h:44-48
         void enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot) override;
         bool enqueueValueAndBias(unsigned int timestep, mtd_metad *engine) override;
-        //! this build: the steps of this variable can be replayed from a captured graph (no half-list scratch from a pool, no list rebuild pending)
-        bool graphSafe() { return lists().mode != 1; }
+        //! this build: the steps of this variable can be replayed from a captured graph (no half-list scratch from a pool, no list rebuild
+        //! pending; a device-built list reads its rebuild flag on the host every check, which a replayed graph would skip)
+        bool graphSafe() { return !m_nlist->isDeviceBuild() && lists().mode != 1; }
         void computeBiasForces(unsigned int timestep) override;        // SteinhardtQl.cc:203-339
         std::vector<std::string> getProvidedLogQuantities() override;  // SteinhardtQl.h:34-42
         double getLogValue(const std::string &quantity, unsigned int timestep) override;   // :49-67

@@ -41,20 +41,29 @@ class DeviceBuffer
     public:
         DeviceBuffer() : m_ptr(nullptr), m_bytes(0) {}
         explicit DeviceBuffer(size_t bytes) : m_ptr(nullptr), m_bytes(0) { resize(bytes); }
-        ~DeviceBuffer() { if (m_ptr) (void)hipFree(m_ptr); }
+        ~DeviceBuffer() { if (m_ptr && m_owned) (void)hipFree(m_ptr); }
         DeviceBuffer(const DeviceBuffer &) = delete;
         DeviceBuffer &operator=(const DeviceBuffer &) = delete;
         void resize(size_t bytes)
             {
-            if (bytes == m_bytes) return;
-            if (m_ptr) hip_check(hipFree(m_ptr), "hipFree");
+            if (bytes == m_bytes && m_owned) return;
+            if (m_ptr && m_owned) hip_check(hipFree(m_ptr), "hipFree");
             m_ptr = nullptr;
             m_bytes = bytes;
+            m_owned = true;
             if (bytes)
                 {
                 hip_check(hipMalloc(&m_ptr, bytes), "hipMalloc");
                 hip_check(hipMemset(m_ptr, 0, bytes), "hipMemset");
                 }
+            }
+        //! a view of device memory somebody else owns (the arrays of a mtd_nlist handle): never freed here
+        void borrow(const void *ptr, size_t bytes)
+            {
+            if (m_ptr && m_owned) hip_check(hipFree(m_ptr), "hipFree");
+            m_ptr = const_cast<void *>(ptr);
+            m_bytes = bytes;
+            m_owned = false;
             }
         void upload(const void *host, size_t bytes) { hip_check(hipMemcpy(m_ptr, host, bytes, hipMemcpyHostToDevice), "hipMemcpy H2D"); }
         void download(void *host, size_t bytes) const { hip_check(hipMemcpy(host, m_ptr, bytes, hipMemcpyDeviceToHost), "hipMemcpy D2H"); }
@@ -64,6 +73,7 @@ class DeviceBuffer
     private:
         void *m_ptr;
         size_t m_bytes;
+        bool m_owned = true;
     };
 
 //! BoxDim (orthorhombic + triclinic), HOOMD conventions: a1=(Lx,0,0), a2=(xy Ly,Ly,0), a3=(xz Lz,yz Lz,Lz)
@@ -408,7 +418,8 @@ class PrescribedForceCompute : public ForceCompute
     };
 
 //! The part of HOOMD's md::NeighborList the plugin reads (SteinhardtQl.cc:80-85): head list, neighbour counts, flat list.
-//! Building the list is HOOMD core; in the stand-alone system the arrays are supplied from outside (setLists).
+//! Building the list is HOOMD core; in the stand-alone system the arrays are either supplied from outside (setLists) or built
+//! on the device from the current positions (setDeviceBuild: mtd_nlist_*, a cell list with HOOMD's r_buff displacement check).
 class NeighborList
     {
     public:
@@ -417,18 +428,28 @@ class NeighborList
             half,
             full
             };
-        explicit NeighborList(std::shared_ptr<SystemDefinition> sysdef) : m_N(sysdef->getParticleData()->getN()), m_mode(full), m_last(0), m_has(false) {}
-        void setStorageMode(storageMode m) { m_mode = m; }
+        explicit NeighborList(std::shared_ptr<SystemDefinition> sysdef)
+            : m_sysdef(sysdef), m_N(sysdef->getParticleData()->getN()), m_mode(full), m_last(0), m_has(false) {}
+        ~NeighborList() { if (m_handle) (void)mtd_nlist_destroy(m_handle); }
+        NeighborList(const NeighborList &) = delete;
+        NeighborList &operator=(const NeighborList &) = delete;
+        void setStorageMode(storageMode m)
+            {
+            if (m != m_mode) m_force_rebuild = true;
+            m_mode = m;
+            }
         storageMode getStorageMode() const { return m_mode; }
         void setLists(const unsigned int *head, const unsigned int *n_neigh, size_t n, const unsigned int *nlist, size_t n_list)
             {
             if (n != m_N) throw std::runtime_error("NeighborList::setLists: head_list / n_neigh must have N entries");
+            m_device_build = false;          // a list handed in replaces the device build
             m_head.resize(sizeof(unsigned int) * n);
             m_nneigh.resize(sizeof(unsigned int) * n);
             m_nlist.resize(sizeof(unsigned int) * (n_list ? n_list : 1));
             if (n) m_head.upload(head, sizeof(unsigned int) * n);
             if (n) m_nneigh.upload(n_neigh, sizeof(unsigned int) * n);
             if (n_list) m_nlist.upload(nlist, sizeof(unsigned int) * n_list);
+            m_nlist_entries = n_list;
             m_has = true;
             m_version++;
             // a full list of HOOMD is symmetric by construction ((i, j) listed <=> (j, i) listed) and, on one rank, indexes
@@ -444,21 +465,110 @@ class NeighborList
                     m_symmetric = back;
                     }
             }
+        //! Build the list on the device from now on: r_list = r_cut + r_buff; compute() rebuilds on its first call, then checks
+        //! every check_period steps whether a particle has moved by more than r_buff / 2 since the last build and rebuilds when
+        //! one has (HOOMD's rule).  The check runs on the time steps that are multiples of check_period (HOOMD counts from its last
+        //! build instead: here a list built at step 9 with period 10 is checked again at step 10).  A changed box, particle number
+        //! or storage mode rebuilds at the next compute() whatever the period.  type >= 0: only pairs of that type
+        //! (cv.steinhardt.get_rcut); -1: all pairs.
+        void setDeviceBuild(double r_cut, double r_buff, unsigned int check_period, int type)
+            {
+            if (!(r_cut > 0.0) || !(r_buff >= 0.0)) throw std::runtime_error("NeighborList::setDeviceBuild: r_cut > 0 and r_buff >= 0 are required");
+            m_r_cut = r_cut;
+            m_r_buff = r_buff;
+            m_check_period = check_period ? check_period : 1;
+            m_type = type;
+            m_device_build = true;
+            m_force_rebuild = true;
+            }
+        bool isDeviceBuild() const { return m_device_build; }
+        //! the next compute() rebuilds whatever the displacement check would say
+        void forceRebuild() { m_force_rebuild = true; }
+        //! device builds so far (the first one included)
+        unsigned int getNumRebuilds() const { return m_num_rebuilds; }
+        size_t getNumEntries() const { return m_nlist_entries; }
         //! full list, (i, j) listed <=> (j, i) listed, no ghost particles
         bool isSymmetricFull() const { return m_mode == full && m_has && m_symmetric; }
-        //! HOOMD rebuilds the list here when particles moved too far; the stand-in only checks that one was supplied
+        //! HOOMD rebuilds the list here when particles moved too far.  With a device build so does the stand-in (one launch and
+        //! one stream synchronisation every check_period steps); otherwise it only checks that a list was supplied
         void compute(unsigned int timestep)
             {
+            if (m_device_build)
+                {
+                computeDevice(timestep);
+                return;
+                }
             if (!m_has) throw std::runtime_error("NeighborList: no neighbour list supplied (nlist.set_lists)");
             m_last = timestep;
             }
-        //! counts the lists handed in (HOOMD: a rebuild of the list): consumers that derive something from a list redo it then
+        //! counts the lists handed in or built (HOOMD: a rebuild of the list): consumers that derive something from a list redo it then
         unsigned int getVersion() const { return m_version; }
         DeviceBuffer &getHeadList() { return m_head; }
         DeviceBuffer &getNNeighArray() { return m_nneigh; }
         DeviceBuffer &getNListArray() { return m_nlist; }
 
     private:
+        void computeDevice(unsigned int timestep)
+            {
+            auto pdata = m_sysdef->getParticleData();
+            hipStream_t s = m_sysdef->getExecConf()->getStream();
+            const unsigned int n_local = pdata->getN(), n_ghost = pdata->getNGhosts();
+            const mtd_box box = pdata->getGlobalBox().toMtd();
+            if (!m_handle) mtd_check(mtd_nlist_create(&m_handle), "mtd_nlist_create");
+            // what is compared on the host at EVERY call, whatever check_period says: a list built for another particle number,
+            // storage mode (setStorageMode sets m_force_rebuild) or box is never used
+            bool rebuild = m_force_rebuild || !m_has || n_local != m_built_local || n_ghost != m_built_ghost || !sameBox(box, m_built_box);
+            if (!rebuild)
+                {
+                // One displacement check per TIME STEP (the CV pass and the force pass of a step call compute() twice), not per
+                // change of the positions: positions set again at the SAME time step are not looked at before the step number
+                // advances (SteinhardtQl caches its value per time step in the same way) — forceRebuild() / nlist_cell.update()
+                // is the way to a list of such positions.
+                if (m_checked_once && timestep == m_last) return;
+                if (timestep % m_check_period == 0)
+                    {
+                    int needs = 0;
+                    mtd_check(mtd_nlist_check(m_handle, pdata->positionsPtr(), pdata->getDtype(), &box, m_r_buff, &needs, s), "mtd_nlist_check");
+                    rebuild = needs != 0;
+                    }
+                }
+            m_last = timestep;
+            m_checked_once = true;
+            if (!rebuild) return;
+            // the build regrows the handle's buffers before it can fail: from here until it has succeeded there is no list,
+            // and a caller that catches the exception and goes on gets a fresh build, not the arrays of the old one
+            m_has = false;
+            m_force_rebuild = true;
+            m_head.borrow(nullptr, 0);
+            m_nneigh.borrow(nullptr, 0);
+            m_nlist.borrow(nullptr, 0);
+            const unsigned int *head = nullptr, *nneigh = nullptr, *list = nullptr;
+            size_t entries = 0;
+            mtd_check(mtd_nlist_build(m_handle, n_local, n_ghost, pdata->positionsPtr(), pdata->getDtype(), &box, m_r_cut + m_r_buff,
+                                      m_mode == half ? 1 : 0, m_type, &head, &nneigh, &list, &entries, s),
+                      "mtd_nlist_build");
+            m_built_box = box;
+            m_head.borrow(head, sizeof(unsigned int) * n_local);
+            m_nneigh.borrow(nneigh, sizeof(unsigned int) * n_local);
+            m_nlist.borrow(list, sizeof(unsigned int) * entries);
+            m_nlist_entries = entries;
+            m_built_local = n_local;
+            m_built_ghost = n_ghost;
+            m_has = true;
+            m_force_rebuild = false;
+            m_symmetric = m_mode == full && n_ghost == 0;     // by construction: every pair is found from both of its ends
+            m_version++;
+            m_num_rebuilds++;
+            }
+
+        static bool sameBox(const mtd_box &a, const mtd_box &b)
+            {
+            for (int k = 0; k < 3; ++k)
+                if (a.L[k] != b.L[k] || a.lo[k] != b.lo[k] || (a.periodic[k] != 0) != (b.periodic[k] != 0)) return false;
+            return a.xy == b.xy && a.xz == b.xz && a.yz == b.yz;
+            }
+
+        std::shared_ptr<SystemDefinition> m_sysdef;
         unsigned int m_N;
         storageMode m_mode;
         unsigned int m_last;
@@ -466,6 +576,15 @@ class NeighborList
         bool m_symmetric = false;
         unsigned int m_version = 0;
         DeviceBuffer m_head, m_nneigh, m_nlist;
+        // device build
+        mtd_nlist *m_handle = nullptr;
+        bool m_device_build = false, m_force_rebuild = false, m_checked_once = false;
+        double m_r_cut = 0.0, m_r_buff = 0.0;
+        unsigned int m_check_period = 1;
+        int m_type = -1;
+        unsigned int m_built_local = 0, m_built_ghost = 0, m_num_rebuilds = 0;
+        mtd_box m_built_box = {};
+        size_t m_nlist_entries = 0;
     };
 
 } // namespace mtdhost

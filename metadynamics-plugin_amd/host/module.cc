@@ -100,6 +100,16 @@ PYBIND11_MODULE(_metadynamics, m)
     m.def("make_int3", [](int x, int y, int z) { return make_int3(x, y, z); });
     py::bind_vector<std::vector<int3>>(m, "std_vector_int3");          // module.cc:25
     m.def("pack_postype", &pack_postype);
+    // unsigned ints read back from a raw device address (the arrays a mtd_nlist handle returns), for tests and tools
+    m.def("download_uints", [](size_t ptr, size_t count) {
+        py::array_t<unsigned int> out((ssize_t)count);
+        if (count)
+            {
+            if (!ptr) throw std::runtime_error("download_uints: null device pointer");
+            hip_check(hipMemcpy(out.mutable_data(), (const void *)ptr, sizeof(unsigned int) * count, hipMemcpyDeviceToHost), "hipMemcpy D2H");
+            }
+        return out;
+    });
     // the text formats of the grid dump and the hills log as host-only functions (grid_file.h): reachable without a GPU
     m.def("parse_grid_file", [](const std::string &path, size_t n_cv, size_t len)
         {
@@ -268,6 +278,24 @@ PYBIND11_MODULE(_metadynamics, m)
                             py::array_t<unsigned int, py::array::c_style | py::array::forcecast> list) {
             if (head.size() != nneigh.size()) throw std::runtime_error("setLists: head_list and n_neigh differ in length");
             n.setLists(head.data(), nneigh.data(), (size_t)head.size(), list.data(), (size_t)list.size());
+        })
+        .def("setDeviceBuild", &NeighborList::setDeviceBuild, py::arg("r_cut"), py::arg("r_buff"), py::arg("check_period") = 1, py::arg("type") = -1)
+        .def("isDeviceBuild", &NeighborList::isDeviceBuild)
+        .def("forceRebuild", &NeighborList::forceRebuild)
+        .def("getNumRebuilds", &NeighborList::getNumRebuilds)
+        .def("getNumEntries", &NeighborList::getNumEntries)
+        .def("getVersion", &NeighborList::getVersion)
+        .def("isSymmetricFull", &NeighborList::isSymmetricFull)
+        .def("getLists", [](NeighborList &n) {
+            // (head_list, n_neigh, nlist) copied back to the host: for tests and for people who want to look
+            auto get = [](const DeviceBuffer &b, size_t count) {
+                py::array_t<unsigned int> out((ssize_t)count);
+                if (count) b.download(out.mutable_data(), sizeof(unsigned int) * count);
+                return out;
+            };
+            const size_t rows = n.getHeadList().bytes() / sizeof(unsigned int);
+            const size_t entries = n.getNumEntries();
+            return py::make_tuple(get(n.getHeadList(), rows), get(n.getNNeighArray(), rows), get(n.getNListArray(), entries));
         });
     py::enum_<NeighborList::storageMode>(nlist, "storageMode").value("half", NeighborList::half).value("full", NeighborList::full).export_values();
 

@@ -204,6 +204,8 @@ class steinhardt(_collective_variable):
             raise RuntimeError("Error creating collective variable.")     # cv.py:591-593
         self.cpp_force = _metadynamics.SteinhardtQl(context.current.system_definition, float(r_cut), float(r_on), int(lmax),
                                                     nlist.cpp_nlist, type_list.index(type), [float(q) for q in Ql_ref], suffix)
+        if getattr(nlist, "device", False):
+            nlist._attach(type_list.index(type))      # a device-built list only needs the pairs of this CV's type (get_rcut)
 
     def get_rcut(self):
         """cv.py:603-617: the cut-off this CV asks of the neighbour list, by type pair — only (type, type) interacts.
@@ -213,19 +215,43 @@ class steinhardt(_collective_variable):
 
 
 class nlist_cell(object):
-    """Stand-in for ``hoomd.md.nlist.cell``: HOOMD's NeighborList is not part of the plugin.  The list is built on the host
-    with a periodic KD-tree (cubic boxes) whenever ``update`` is called and handed to the device in HOOMD's layout."""
+    """Stand-in for ``hoomd.md.nlist.cell``: HOOMD's NeighborList is not part of the plugin.
 
-    def __init__(self, r_cut):
+    ``device=False`` (default): the list is built on the host with a periodic KD-tree (cubic boxes) whenever ``update`` is called
+    and handed to the device in HOOMD's layout; without a call of ``update`` or ``set_lists`` a run raises.
+    ``device=True``: the list is built on the GPU (cell list, any box of ``mtd_box``, ghosts, half or full storage) with
+    ``r_list = r_cut + r_buff``, first when a run needs it and again whenever a particle has moved by more than ``r_buff / 2``
+    since the last build, which is checked every ``check_period`` steps.  ``update`` then forces a rebuild and copies the arrays back."""
+
+    def __init__(self, r_cut, r_buff=0.4, check_period=1, device=False):
         self.r_cut = float(r_cut)
+        self.r_buff = float(r_buff)
+        self.check_period = int(check_period)
+        self.device = bool(device)
+        self._type, self._types = -1, set()
         self.cpp_nlist = _metadynamics.NeighborList(context.current.system_definition)
+        if self.device:
+            if self.check_period < 1:
+                raise RuntimeError("nlist_cell: check_period must be at least 1")
+            self.cpp_nlist.setDeviceBuild(self.r_cut, self.r_buff, self.check_period, self._type)
+
+    def _attach(self, type_id):
+        """a cv.steinhardt uses this list: build only the pairs of its type; two CVs of different types need all pairs"""
+        self._types.add(int(type_id))
+        self._type = int(type_id) if len(self._types) == 1 else -1
+        self.cpp_nlist.setDeviceBuild(self.r_cut, self.r_buff, self.check_period, self._type)
 
     def set_lists(self, head_list, n_neigh, nlist):
         """hand over a list in HOOMD's layout: neighbours of i are nlist[head_list[i] : head_list[i] + n_neigh[i]]"""
         self.cpp_nlist.setLists(head_list, n_neigh, nlist)
 
     def update(self):
-        """rebuild from the current positions (cubic boxes; host-side periodic KD-tree)"""
+        """rebuild from the current positions: on the device when ``device=True``, else cubic boxes with a host-side periodic
+        KD-tree; returns (head_list, n_neigh, nlist) as host arrays"""
+        if self.device:
+            self.cpp_nlist.forceRebuild()
+            self.cpp_nlist.compute(context.current.system.getCurrentTimeStep())
+            return self.cpp_nlist.getLists()
         import numpy as np
         from scipy.spatial import cKDTree
         pdata = context.current.system_definition.getParticleData()
