@@ -568,6 +568,44 @@ int mtd_ql_forces(unsigned int n_particles, const void *d_postype, void *d_force
                   const double *d_scratch, const double *d_bias, double bias_host, mtd_stream_t stream);
 
 /* ================================================================================================
+ * Local Steinhardt bond order (cv.steinhardt_local) — no reference counterpart.  The harmonics summed over one particle's own
+ * neighbours, turned into a rotational invariant PER PARTICLE, then averaged; conventions of mtd_ql_accumulate in every respect
+ * (smoothing f of SteinhardtQl.cc:36-48, Condon-Shortley phase, d = minImage(r_i - r_j)).  For a particle i of `type`, over the
+ * entries j of row i with type(j) == type and r_ij^2 <= r_cut^2:
+ *     n_i      = sum_j f(r_ij)
+ *     A_lm(i)  = sum_j f(r_ij) Y_lm(d_ij / r_ij)                        l = 0..lmax
+ *     q_l^2(i) = 4 pi / (2l + 1) sum_{m = -l..l} |A_lm(i)|^2 / n_i^2     (0 when n_i == 0)
+ *     c_i      = sum_l Ql_ref[l] q_l^2(i)                               (0 for particles of another type)
+ *     s        = (1 / N_global) sum_i c_i
+ *     F_k      = -bias ds/dr_k                                          (w component 0)
+ * Not square-rooted, divided by N_global: the conventions of the global variable, with the square taken per particle.
+ * Preconditions: the list is FULL and symmetric for same-type pairs within r_cut ((i, j) listed <=> (j, i) listed: what HOOMD and
+ * mtd_nlist_build produce — the force pass gathers both roles of a particle from its own row), holds no duplicate and indexes no
+ * ghost particle; entries j >= n_particles and self entries are skipped.  Known limits: a pair exactly on the z axis gives NaN in
+ * the force, as in mtd_ql_forces; c_i jumps from 0 to the one-neighbour value when a first neighbour enters an empty shell.
+ * Arguments are checked before a device is touched: MTD_ERR_INVALID_ARGUMENT for null pointers, r_cut <= 0, r_on < 0,
+ * r_on >= r_cut, n_global == 0, an unknown dtype or a d_scratch that is not 16-byte aligned; MTD_ERR_UNSUPPORTED for lmax > 12.
+ * ============================================================================================== */
+
+/* device doubles the two calls share: block sums, n_i, c_i and the per-particle table of weights the force pass gathers */
+size_t mtd_ql_local_scratch_doubles(unsigned int n_particles, unsigned int lmax);
+
+/* First pass.  Ql_ref: host double[lmax+1].  On return *d_partials points at *n_partials block sums of c_i (consume with
+ * mtd_metad_set_cv_source(engine, slot, *d_partials, *n_partials, 1, 0, 1.0 / N_global, 0.0) or mtd_reduce_partials), *d_c at
+ * c_i[n_particles] and *d_n at n_i[n_particles] (d_c, d_n may be NULL), all inside d_scratch.  Sums follow the order of the list. */
+int mtd_ql_local_accumulate(unsigned int n_particles, const void *d_postype, int dtype, const mtd_box *box, const unsigned int *d_head_list,
+                            const unsigned int *d_n_neigh, const unsigned int *d_nlist, double rcut, double ron, unsigned int lmax,
+                            unsigned int type, const double *Ql_ref, unsigned int n_global, double *d_scratch, const double **d_partials,
+                            unsigned int *n_partials, const double **d_c, const double **d_n, mtd_stream_t stream);
+
+/* Second pass, with the table the last mtd_ql_local_accumulate (same arguments) left in d_scratch: writes d_force[0..n_particles),
+ * zero for particles of another type; bias = *d_bias when d_bias != NULL, else bias_host.  No atomics: bitwise reproducible. */
+int mtd_ql_local_forces(unsigned int n_particles, const void *d_postype, void *d_force, int dtype, const mtd_box *box,
+                        const unsigned int *d_head_list, const unsigned int *d_n_neigh, const unsigned int *d_nlist, double rcut, double ron,
+                        unsigned int lmax, unsigned int type, const double *Ql_ref, unsigned int n_global, const double *d_scratch,
+                        const double *d_bias, double bias_host, mtd_stream_t stream);
+
+/* ================================================================================================
  * Neighbour list of the stand-alone path (cell list, built on the device)
  * no reference counterpart: HOOMD's md::NeighborList is HOOMD core.  Produces the three arrays SteinhardtQl.cc:80-85 reads, in
  * HOOMD's layout: the neighbours of particle i are d_nlist[d_head_list[i] .. d_head_list[i] + d_n_neigh[i]).

@@ -739,6 +739,111 @@ double SteinhardtQl::getLogValue(const std::string &quantity, unsigned int times
     }
 
 // ------------------------------------------------------------------------------------------------
+// SteinhardtLocal
+// ------------------------------------------------------------------------------------------------
+
+SteinhardtLocal::SteinhardtLocal(std::shared_ptr<SystemDefinition> sysdef, double rcut, double ron, unsigned int lmax,
+                                 std::shared_ptr<NeighborList> nlist, unsigned int type, const std::vector<double> &Ql_ref,
+                                 const std::string &log_suffix)
+    : CollectiveVariable(sysdef, "steinhardt_local" + log_suffix), m_rcut(rcut), m_ron(ron), m_lmax(lmax), m_nlist(nlist), m_type(type),
+      m_Ql_ref(Ql_ref), m_cv_last_updated(0), m_have_computed(false), m_d_partials(nullptr), m_d_c(nullptr), m_d_n(nullptr), m_n_partials(0)
+    {
+    if (Ql_ref.size() != lmax + 1) throw std::runtime_error("Error setting up local Steinhardt CV");
+    if (lmax > 12) throw std::runtime_error("cv.steinhardt_local: lmax <= 12 in this build");
+    if (!nlist) throw std::runtime_error("cv.steinhardt_local: a neighbour list is required");
+    if (!(rcut > 0.0) || !(ron >= 0.0) || !(ron < rcut)) throw std::runtime_error("cv.steinhardt_local: 0 <= r_on < r_cut is required");
+    m_scratch.resize(sizeof(double) * mtd_ql_local_scratch_doubles(m_pdata->getN(), lmax));
+    m_sum.resize(sizeof(double));
+    }
+
+void SteinhardtLocal::computeCV(unsigned int timestep)
+    {
+    ProfRange prof_range("CV");
+    if (m_cv_last_updated == timestep && m_have_computed) return;
+    // the force pass gathers a neighbour's table row: both roles of a particle must be in its own row, and the row of a ghost
+    // would have to be exchanged between the ranks
+    if (m_nlist->getStorageMode() == NeighborList::half)
+        throw std::runtime_error("cv.steinhardt_local: a full neighbour list is required (the force pass gathers both roles of a "
+                                 "particle from its own row)");
+    if (distributed())
+        throw std::runtime_error("cv.steinhardt_local: domain-decomposed runs are not supported (the table row of a ghost "
+                                 "neighbour would have to be exchanged)");
+    m_nlist->compute(timestep);                                      // a device-built list rebuilds here when particles have moved
+    const mtd_box box = m_pdata->getBox().toMtd();
+    mtd_check(mtd_ql_local_accumulate(m_pdata->getN(), m_pdata->positionsPtr(), m_pdata->getDtype(), &box,
+                                      (const unsigned int *)m_nlist->getHeadList().data(), (const unsigned int *)m_nlist->getNNeighArray().data(),
+                                      (const unsigned int *)m_nlist->getNListArray().data(), m_rcut, m_ron, m_lmax, m_type, m_Ql_ref.data(),
+                                      m_pdata->getNGlobal(), (double *)m_scratch.data(), &m_d_partials, &m_n_partials, &m_d_c, &m_d_n,
+                                      m_exec_conf->getStream()),
+              "mtd_ql_local_accumulate");
+    m_have_computed = true;
+    m_cv_last_updated = timestep;
+    }
+
+void SteinhardtLocal::enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot)
+    {
+    computeCV(timestep);
+    mtd_check(mtd_metad_set_cv_source(engine, slot, m_d_partials, m_n_partials, 1, 0, 1.0 / (double)m_pdata->getNGlobal(), 0.0),
+              "mtd_metad_set_cv_source");
+    }
+
+double SteinhardtLocal::getCurrentValue(unsigned int timestep)
+    {
+    computeCV(timestep);
+    mtd_check(mtd_reduce_partials(m_d_partials, m_n_partials, 1, 1, 1.0 / (double)m_pdata->getNGlobal(), 0.0, (double *)m_sum.data(),
+                                  m_exec_conf->getStream()),
+              "mtd_reduce_partials");
+    m_exec_conf->sync();
+    double value = 0.0;
+    hip_check(hipMemcpy(&value, m_sum.data(), sizeof(double), hipMemcpyDeviceToHost), "cv read-back");
+    return value;
+    }
+
+void SteinhardtLocal::computeBiasForces(unsigned int timestep)
+    {
+    ProfRange prof_range("Force");
+    if (!m_have_computed || m_cv_last_updated != timestep) computeCV(timestep);      // the table of THIS step's positions
+    m_nlist->compute(timestep);
+    const mtd_box box = m_pdata->getBox().toMtd();
+    mtd_check(mtd_ql_local_forces(m_pdata->getN(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &box,
+                                  (const unsigned int *)m_nlist->getHeadList().data(), (const unsigned int *)m_nlist->getNNeighArray().data(),
+                                  (const unsigned int *)m_nlist->getNListArray().data(), m_rcut, m_ron, m_lmax, m_type, m_Ql_ref.data(),
+                                  m_pdata->getNGlobal(), (const double *)m_scratch.data(), m_bias_device, m_bias, m_exec_conf->getStream()),
+              "mtd_ql_local_forces");
+    }
+
+std::vector<double> SteinhardtLocal::getLocalValues(unsigned int timestep)
+    {
+    computeCV(timestep);
+    m_exec_conf->sync();
+    std::vector<double> out(m_pdata->getN());
+    if (!out.empty()) hip_check(hipMemcpy(out.data(), m_d_c, sizeof(double) * out.size(), hipMemcpyDeviceToHost), "c_i read-back");
+    return out;
+    }
+
+std::vector<double> SteinhardtLocal::getCoordination(unsigned int timestep)
+    {
+    computeCV(timestep);
+    m_exec_conf->sync();
+    std::vector<double> out(m_pdata->getN());
+    if (!out.empty()) hip_check(hipMemcpy(out.data(), m_d_n, sizeof(double) * out.size(), hipMemcpyDeviceToHost), "n_i read-back");
+    return out;
+    }
+
+std::vector<std::string> SteinhardtLocal::getProvidedLogQuantities()
+    {
+    auto list = CollectiveVariable::getProvidedLogQuantities();
+    list.push_back("cv_" + m_cv_name);
+    return list;
+    }
+
+double SteinhardtLocal::getLogValue(const std::string &quantity, unsigned int timestep)
+    {
+    if (quantity == "cv_" + m_cv_name) return getCurrentValue(timestep);
+    return CollectiveVariable::getLogValue(quantity, timestep);
+    }
+
+// ------------------------------------------------------------------------------------------------
 // AspectRatio, Density
 // ------------------------------------------------------------------------------------------------
 

@@ -315,6 +315,37 @@ class SteinhardtQl : public CollectiveVariable
         bool m_sym_ok;
     };
 
+//! Local Steinhardt bond order (no reference counterpart; include/mtd_abi.h "Local Steinhardt bond order"): the harmonics summed
+//! over one particle's own neighbours, squared per particle, averaged over the particles: s = (1/N_global) sum_i sum_l Ql_ref[l] q_l^2(i)
+class SteinhardtLocal : public CollectiveVariable
+    {
+    public:
+        SteinhardtLocal(std::shared_ptr<SystemDefinition> sysdef, double rcut, double ron, unsigned int lmax,
+                        std::shared_ptr<NeighborList> nlist, unsigned int type, const std::vector<double> &Ql_ref,
+                        const std::string &log_suffix = "");
+        double getCurrentValue(unsigned int timestep) override;
+        //! device-resident: the block sums of c_i become the engine's source of this variable, no host synchronisation
+        void enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot) override;
+        void computeBiasForces(unsigned int timestep) override;
+        std::vector<std::string> getProvidedLogQuantities() override;
+        double getLogValue(const std::string &quantity, unsigned int timestep) override;
+        std::vector<double> getLocalValues(unsigned int timestep);     //!< c_i of every local particle (0 for other types)
+        std::vector<double> getCoordination(unsigned int timestep);    //!< n_i = sum_j f(r_ij)
+
+    private:
+        void computeCV(unsigned int timestep);
+        double m_rcut, m_ron;
+        unsigned int m_lmax;
+        std::shared_ptr<NeighborList> m_nlist;
+        unsigned int m_type;
+        std::vector<double> m_Ql_ref;
+        unsigned int m_cv_last_updated;
+        bool m_have_computed;
+        DeviceBuffer m_scratch, m_sum;
+        const double *m_d_partials, *m_d_c, *m_d_n;
+        unsigned int m_n_partials;
+    };
+
 //! AspectRatio.h / AspectRatio.cc:5-130 — box-shape CV, external virial only
 class AspectRatio : public CollectiveVariable
     {

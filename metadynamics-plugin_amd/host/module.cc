@@ -322,6 +322,19 @@ PYBIND11_MODULE(_metadynamics, m)
         .def(py::init<std::shared_ptr<SystemDefinition>, double, double, unsigned int, std::shared_ptr<NeighborList>, unsigned int,
                       const std::vector<double> &, const std::string &>());
 
+    // no reference counterpart: the local (per-particle) Steinhardt variable
+    py::class_<SteinhardtLocal, CollectiveVariable, std::shared_ptr<SteinhardtLocal>>(m, "SteinhardtLocal")
+        .def(py::init<std::shared_ptr<SystemDefinition>, double, double, unsigned int, std::shared_ptr<NeighborList>, unsigned int,
+                      const std::vector<double> &, const std::string &>())
+        .def("getLocalValues", [](SteinhardtLocal &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getLocalValues(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        })
+        .def("getCoordination", [](SteinhardtLocal &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getCoordination(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        });
+
     py::class_<WellTemperedEnsemble, CollectiveVariable, std::shared_ptr<WellTemperedEnsemble>>(m, "WellTemperedEnsemble")
         .def(py::init<std::shared_ptr<SystemDefinition>, const std::string &>());
 

@@ -214,6 +214,43 @@ class steinhardt(_collective_variable):
         return {(a, b): (self.r_cut if a == b == self.type else -1.0) for i, a in enumerate(names) for b in names[i:]}
 
 
+class steinhardt_local(_collective_variable):
+    """this build (no reference counterpart): the LOCAL Steinhardt order parameter.  The harmonics are summed over one particle's own
+    neighbours, turned into the rotational invariant per particle and averaged:
+    CV = (1 / N) sum_i sum_l Ql_ref[l] * q_l^2(i),  q_l^2(i) = 4 pi / (2l + 1) sum_m |sum_j f(r_ij) Y_lm(r_ij)|^2 / (sum_j f(r_ij))^2
+    over particles of one type within r_cut (smoothing and conventions of cv.steinhardt; not square-rooted).  Needs a full list."""
+
+    def __init__(self, r_cut, r_on, lmax, Ql_ref, nlist, type, name=None, sigma=1.0):
+        suffix = ""
+        if name is not None:
+            suffix = "_" + name
+        _collective_variable.__init__(self, sigma, name)
+        self.type = type
+        self.nlist = nlist
+        self.r_cut = r_cut
+        self.nlist.cpp_nlist.setStorageMode(_metadynamics.NeighborList.storageMode.full)
+        type_list = context.current.type_names
+        if type not in type_list:
+            raise RuntimeError("Error creating collective variable.")
+        self.cpp_force = _metadynamics.SteinhardtLocal(context.current.system_definition, float(r_cut), float(r_on), int(lmax),
+                                                       nlist.cpp_nlist, type_list.index(type), [float(q) for q in Ql_ref], suffix)
+        if getattr(nlist, "device", False):
+            nlist._attach(type_list.index(type))      # a device-built list only needs the pairs of this CV's type
+
+    def get_rcut(self):
+        """the cut-off this CV asks of the neighbour list, by type pair — only (type, type) interacts"""
+        names = context.current.type_names
+        return {(a, b): (self.r_cut if a == b == self.type else -1.0) for i, a in enumerate(names) for b in names[i:]}
+
+    def get_local(self):
+        """c_i = sum_l Ql_ref[l] q_l^2(i) of every particle at the current time step (0 for particles of another type)"""
+        return self.cpp_force.getLocalValues(context.current.system.getCurrentTimeStep())
+
+    def get_coordination(self):
+        """n_i = sum_j f(r_ij): the smoothed number of neighbours of every particle at the current time step"""
+        return self.cpp_force.getCoordination(context.current.system.getCurrentTimeStep())
+
+
 class nlist_cell(object):
     """Stand-in for ``hoomd.md.nlist.cell``: HOOMD's NeighborList is not part of the plugin.
 

@@ -1,0 +1,54 @@
+#!/usr/bin/env python3
+"""Developer tool: the config 5 snapshot of tools/bench_ql.py (256 000-particle noisy fcc crystal, lmax 6, degrees 4 and 6,
+r_cut 1.4, 512-point grid) with cv.steinhardt_local instead of the global variable; prints us/step.
+usage: tools/bench_ql_local.py [steps] [f32|f64] [--device-nlist]   (--device-nlist: cv.nlist_cell(device=True), r_buff 0.4)
+Run under rocprofv3 --kernel-trace --stats for the per-kernel table."""
+import os, sys, time
+root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(root, "metadynamics-plugin_amd"), os.path.join(root, "tests")]
+import numpy as np, torch
+import util
+from metadynamics import context, cv, integrate
+args = [a for a in sys.argv[1:] if not a.startswith("--")]
+device_nlist = "--device-nlist" in sys.argv[1:]
+steps = int(args[0]) if len(args) > 0 else 100
+dtype = np.float32 if (len(args) > 1 and args[1] == "f32") else np.float64
+pos, L = util.fcc_lattice(40)
+pos = pos + np.random.default_rng(777).normal(0, 0.05, pos.shape)
+N = len(pos)
+
+
+def build(lo, hi, sigma):
+    context.initialize(pos, np.zeros(N, dtype=np.int32), ["A"], L, dtype=dtype)
+    meta = integrate.mode_metadynamics(dt=0.005, stride=1, mode="well_tempered", W=1.0, deltaT=7.0, T=1.0)
+    nl = cv.nlist_cell(r_cut=1.4, device=device_nlist)
+    entries = None if device_nlist else len(nl.update()[2])
+    st = cv.steinhardt_local(r_cut=1.4, r_on=1.2, lmax=6, Ql_ref=[0, 0, 0, 0, 1, 0, 1], nlist=nl, type="A", sigma=sigma)
+    st.set_grid(lo, hi, 512)
+    return meta, st, nl, entries
+
+
+# grid [0, 2 s] x 512, sigma 1 % of the range — one untimed evaluation supplies s
+t0 = time.perf_counter()
+meta, st, nl, entries = build(0.0, 1.0, 1.0)
+context.run(1)
+s0 = st.cpp_force.getCurrentValue(1)
+print("N = %d, set up in %.1f s, neighbour list %s" % (N, time.perf_counter() - t0, "built on the device" if device_nlist else "built on the host"))
+context.current = None
+meta, st, nl, entries = build(0.0, 2.0 * s0, 0.02 * s0)
+context.run(1)
+entries = nl.cpp_nlist.getNumEntries() if entries is None else entries
+print("steinhardt_local cv =", s0, "grid", (0.0, 2.0 * s0), "list entries per particle %.1f" % (entries / N))
+context.run(5)
+torch.cuda.synchronize()
+t0 = time.perf_counter()
+context.current.system.run(steps)
+torch.cuda.synchronize()
+dt = time.perf_counter() - t0
+t_now = context.current.system.getCurrentTimeStep()
+c = st.get_local()
+print("on grid: %s, hills %d, bias factors %s, V = %g, mean c_i %.6f, mean n_i %.3f"
+      % (0.0 <= st.cpp_force.getCurrentValue(t_now) < 2.0 * s0, meta.cpp_integrator.getNumGaussians(), list(meta.cpp_integrator.getBiasFactors()),
+         meta.cpp_integrator.getLogValue("bias", t_now), c.mean(), st.get_coordination().mean()))
+print("config 5 local (%s%s): %.1f us/step  (%.3e particle-CV-evals/s, %.3e list entries/s incl. CV + force pass)"
+      % (np.dtype(dtype).name, ", device list" if device_nlist else "", 1e6 * dt / steps, N * steps / dt, 2 * entries * steps / dt))
