@@ -179,7 +179,12 @@ void uncached_release(void *p)
         if (b.p == p) b.in_use = false;
     }
 
-unsigned long long env_timeout_ticks()
+} // namespace
+
+namespace mtd
+{
+
+unsigned long long comm_timeout_ticks()
     {
     const char *e = std::getenv("MTD_COMM_TIMEOUT_MS");
     double ms = 5000.0;
@@ -187,11 +192,6 @@ unsigned long long env_timeout_ticks()
     if (!(ms > 0.0)) ms = 5000.0;
     return (unsigned long long)(ms * 1.0e5);            // wall_clock64: 100 MHz
     }
-
-} // namespace
-
-namespace mtd
-{
 
 int comm_next(mtd_comm *c, CommK &k)
     {
@@ -228,7 +228,7 @@ int mtd_comm_create(mtd_comm **out, unsigned int rank, unsigned int world, unsig
     c->k.rank = rank;
     c->k.world = world;
     c->k.words_per_rank = 2 * max_doubles;
-    c->k.timeout_ticks = env_timeout_ticks();
+    c->k.timeout_ticks = comm_timeout_ticks();
     c->max_doubles = max_doubles;
     c->bytes = sizeof(unsigned long long) * 2 * world * c->k.words_per_rank;
     // uncached device memory: peers' stores and this GPU's polling loads must not sit in a non-coherent L2

@@ -37,4 +37,6 @@ int comm_next(mtd_comm *c, CommK &k);
 int comm_current(const mtd_comm *c, CommK &k);
 // a wait of this communicator has expired (sticky): every entry point that would use it returns MTD_ERR_COMM_TIMEOUT
 inline bool comm_failed(const mtd_comm *c) { return c && c->h_err && *c->h_err != 0; }
+// the bound of every in-kernel wait in wall_clock64 ticks: MTD_COMM_TIMEOUT_MS, 5 s by default (comm.hip)
+unsigned long long comm_timeout_ticks();
 }

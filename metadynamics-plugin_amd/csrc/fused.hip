@@ -29,10 +29,14 @@
 // dependency on the first pass: it is deferred into the next launch A (or mtd_metad_get_state /
 // get_array, which flush it), so the grid arrays are "one apply behind" between B and the next A.
 // Forces never wait for it: dV/ds_c only needs grid_old + dV on <= (2 n_cv + 1) 2^n_cv cells.
+//
+// The pieces of launch B that other kernels carry too — the LDS copy of the chain's result, the first grid pass, the publishing
+// wave — are in metad_device.hpp (chain_share, grid_first_pass_*, publish_step); k_fused_force calls them and only adds its time
+// stamps between them.  The launches pick their instantiation through the dispatchers of lamellar_host.hpp.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
-// Diagnostic build only (-DMTD_STAMPS, tools/stamps.sh): s_memrealtime (100 MHz) stamps of one grid block and
+// Diagnostic build only (-DMTD_STAMPS, tools/build_stamps.sh, tools/stamps.py): s_memrealtime (100 MHz) stamps of one grid block and
 // one particle block per kernel, written to a buffer of their own; the product build has no stamps.
 #ifdef MTD_STAMPS
 __device__ unsigned long long g_stamps[64];
@@ -102,7 +106,7 @@ __global__ __launch_bounds__(FCV_THREADS) void k_fused_cv(const LamKArgs a, cons
     // contract: unconditional loads, see lam_load_group_nc; nothing of it is used, the loop below does not run)
     const S4 *src = N ? postype : (const S4 *)partials;
     lam_load_group_nc<S4, U>(src, N ? N : 1u, block_id * FCV_THREADS + threadIdx.x, n_blocks * FCV_THREADS, first);
-    // (the tables: one unconditional load per thread behind the particles' — `a` is the dense form, launch_fused_cv)
+    // (the tables: one unconditional load per thread behind the particles' — `a` is the dense form, mtd_fused_cv_pass)
     const CvTableRegs tab = stage_cv_tables_request(a);
     stage_cv_tables_store(tab, s_coeff, s_mt);
     __syncthreads();
@@ -243,13 +247,7 @@ __global__ __launch_bounds__(FF_THREADS, 4) void k_fused_force(const LamKArgs a,
             r = chain_wave(c, deposit != 0, true, &ck, nullptr, false, &pre.patch, pre.patch_ok != 0);
         MTD_STAMP(17, blockIdx.x == 0 && threadIdx.x == 0);
         MTD_STAMP(26, blockIdx.x == n_grid_blocks && threadIdx.x == 0);
-        if (lane == 0)
-            {
-            s_chain.cv[0] = r.cv[0]; s_chain.cv[1] = r.cv[1]; s_chain.cv[2] = r.cv[2];
-            s_chain.bias[0] = r.bias[0]; s_chain.bias[1] = r.bias[1]; s_chain.bias[2] = r.bias[2];
-            s_chain.scal = r.scal; s_chain.V = r.V; s_chain.w = r.w;
-            s_chain.bin = r.bin; s_chain.on_grid = r.on_grid; s_chain.oob = r.oob; s_chain.failed = r.failed;
-            }
+        if (lane == 0) chain_share(s_chain, r);
         if (!grid_block && lane < NCV * MTD_MAX_TYPES)
             {
             const unsigned int cv = lane / MTD_MAX_TYPES;
@@ -272,47 +270,10 @@ __global__ __launch_bounds__(FF_THREADS, 4) void k_fused_force(const LamKArgs a,
 
     if (grid_block)
         {
-        // ---- first grid pass of a deposit step: updateGrid (:1002-1047), updateHistogram (:1092-1119),
-        //      updateSigmaGrid (:1122-1155), first loop of updateReweightedEstimator (:1070-1075)
-        const unsigned int g = blockIdx.x * FF_THREADS + threadIdx.x;
-        double s1 = 0.0, s2 = 0.0;
-        if (g < c.len && !s_chain.failed)
-            {
-            const double dV = (c.W * s_chain.scal) * exp(-gauss_exponent3(c, g, s_chain.cv[0], s_chain.cv[1], s_chain.cv[2]));
-            c.grid_delta[g] = dV;
-            unsigned int hd = c.hist_delta[g];
-            if (s_chain.on_grid && g == s_chain.bin)
-                {
-                hd += 1;
-                c.hist_delta[g] = hd;
-                c.sigma_grid_delta[g] += c.det_sigma;
-                c.hist_gauss_delta[g] += 1;
-                }
-            const double Rw = c.rew[g] + (double)hd;
-            c.rew[g] = Rw;
-            s1 = Rw * dV;
-            s2 = Rw;
-            }
+        // ---- first grid pass of a deposit step (metad_device.hpp), in its two halves with a time stamp between them
+        const double2 sums = grid_first_pass_cells_256(c, s_chain, blockIdx.x);
         MTD_STAMP(19, blockIdx.x == 0 && threadIdx.x == 0);
-        s1 = wave_sum(s1);
-        s2 = wave_sum(s2);
-        if (lane == 0)
-            {
-            s_red[2 * wave] = s1;
-            s_red[2 * wave + 1] = s2;
-            }
-        __syncthreads();
-        if (threadIdx.x == 0)
-            {
-            double t1 = 0.0, t2 = 0.0;
-            for (int w = 0; w < FF_THREADS / MTD_WAVE; ++w)
-                {
-                t1 += s_red[2 * w];
-                t2 += s_red[2 * w + 1];
-                }
-            c.gpart[2 * blockIdx.x] = t1;
-            c.gpart[2 * blockIdx.x + 1] = t2;
-            }
+        grid_first_pass_sums_256(c, blockIdx.x, sums, s_red);
         MTD_STAMP(20, blockIdx.x == 0 && threadIdx.x == 0);
         }
     else if (wave != 0 && N)
@@ -324,40 +285,7 @@ __global__ __launch_bounds__(FF_THREADS, 4) void k_fused_force(const LamKArgs a,
 
     // one block publishes the step's scalars for the host (lazy read-back) and, on non-deposit steps,
     // owns the histogram increment (:366) and the weight read-out (the weight grid is final then)
-    if (blockIdx.x == 0 && wave == 0)
-        {
-        double w_now = 1.0;
-        if (!deposit) w_now = chain_wave(c, false, false, COMM ? &ck : nullptr).w;     // w(s) from the (final) weight grid
-        if (lane < (int)c.n_cv)
-            {
-            const double s_l = lane == 0 ? s_chain.cv[0] : (lane == 1 ? s_chain.cv[1] : s_chain.cv[2]);
-            c.st->cv[lane] = s_l;
-            c.st->bias[lane] = lane == 0 ? s_chain.bias[0] : (lane == 1 ? s_chain.bias[1] : s_chain.bias[2]);
-            // where the grid patch of the next step should sit (apply_cells fills it at this origin): the cell of s, minus 2
-            const double dl = lane == 0 ? c.delta[0] : (lane == 1 ? c.delta[1] : c.delta[2]);
-            const double ml = lane == 0 ? c.cv_min[0] : (lane == 1 ? c.cv_min[1] : c.cv_min[2]);
-            const double ll = (double)(lane == 0 ? c.lengths[0] : (lane == 1 ? c.lengths[1] : c.lengths[2]));
-            double q = (s_l - ml) / dl;
-            if (!(q > 0.0)) q = 0.0;                                   // (NaN too)
-            if (q > ll) q = ll;
-            c.st->guess_org[lane] = (int)q - 2;
-            }
-        if (lane == 0)
-            {
-            c.st->V = s_chain.V;
-            c.st->failed = (unsigned int)s_chain.failed;                 // the deferred pass of a poisoned deposit is skipped (0 without a mailbox)
-            c.st->bin = s_chain.bin;
-            c.st->on_grid = (unsigned int)s_chain.on_grid;
-            if (deposit)
-                c.st->scal = s_chain.scal;
-            else
-                {
-                c.st->w = s_chain.failed ? s_chain.V : w_now;            // (V is NaN then)
-                if (s_chain.on_grid) c.hist_delta[s_chain.bin] += 1;
-                }
-            if (s_chain.oob) c.st->n_oob += (deposit && c.mode == MTD_MODE_WELL_TEMPERED) ? 2 : 1;
-            }
-        }
+    if (blockIdx.x == 0 && wave == 0) publish_step(c, s_chain, deposit, nullptr, COMM ? &ck : nullptr);
     }
 
 // General form (any n_cv the grid engine supports): block-cooperative prologue, then the force pass.
@@ -467,11 +395,34 @@ bool force_profile_next(hipEvent_t &start, hipEvent_t &stop)
     return true;
     }
 
-// Blocks of `kernel` the device holds at one time (occupancy x compute units), cached per kernel.  A launch in which a
-// block WAITS for other blocks of the same launch (the collector of the sharded CV pass) is only issued when the whole grid
-// is resident at once: then the wait is one memory round trip after the slowest block, never a wait for blocks that have not
-// started.  (With a single waiting block a larger grid could not deadlock either — every other block runs to completion
-// unconditionally and frees its slot — but its wait would span whole generations of blocks; refused rather than slow.)
+// The instantiation of k_fused_cv a pass launches: f(kernel, type_tag<S4>).  The sharded pass (mailbox attached) exists for the
+// chain's n_cv <= 3 only.  One expression chooses the kernel whose residency is asked for and the kernel that is launched.
+// n_cv: 1 .. MAXCV, with a mailbox 1 .. CHAIN_MAX_CV (fill_kargs refuses 0, mtd_fused_cv_pass the counts above).
+template<typename F> int with_fused_cv_kernel(int dtype, bool fast, bool ortho, bool comm, unsigned int n_cv, F &&f)
+    {
+    return dispatch_s4_fast(dtype, fast, [&](auto s4, auto fast_c)
+        {
+        using S4 = typename decltype(s4)::type;
+        constexpr bool FAST = decltype(fast_c)::value;
+        return dispatch_bool(ortho, [&](auto ortho_c)
+            {
+            constexpr bool ORTHO = decltype(ortho_c)::value;
+            if (comm)
+                return dispatch_count<CHAIN_MAX_CV>(n_cv, [&](auto n) { return f(k_fused_cv<S4, decltype(n)::value, FAST, true, ORTHO>, s4); });
+            return dispatch_count<MAXCV>(n_cv, [&](auto n) { return f(k_fused_cv<S4, decltype(n)::value, FAST, false, ORTHO>, s4); });
+            });
+        });
+    }
+
+} // namespace
+
+namespace mtd
+{
+// A launch in which a block WAITS for other blocks of the same launch (the collector of the sharded CV pass, every block of the
+// one-launch step) is only issued when the whole grid is resident at once: then the wait is one memory round trip after the
+// slowest block, never a wait for blocks that have not started.  (With a single waiting block a larger grid could not deadlock
+// either — every other block runs to completion unconditionally and frees its slot — but its wait would span whole generations
+// of blocks; refused rather than slow.)
 unsigned int resident_capacity(const void *kernel, int threads)
     {
     static std::mutex mu;
@@ -494,62 +445,7 @@ unsigned int resident_capacity(const void *kernel, int threads)
     cache[std::make_pair(dev, kernel)] = cap;
     return cap;
     }
-
-template<typename S4, bool FAST, bool ORTHO> const void *fused_cv_comm_kernel_of(unsigned int n_cv)
-    {
-    return n_cv == 1 ? (const void *)k_fused_cv<S4, 1, FAST, true, ORTHO>
-                     : (n_cv == 2 ? (const void *)k_fused_cv<S4, 2, FAST, true, ORTHO> : (const void *)k_fused_cv<S4, 3, FAST, true, ORTHO>);
-    }
-
-// the instantiation a sharded CV pass launches (mtd_fused_cv_pass asks for its residency before it takes an exchange number)
-template<bool ORTHO> const void *fused_cv_comm_kernel_o(int dtype, unsigned int n_cv, bool fast)
-    {
-    if (dtype == MTD_F32)
-        return fast ? fused_cv_comm_kernel_of<float4, true, ORTHO>(n_cv) : fused_cv_comm_kernel_of<float4, false, ORTHO>(n_cv);
-    return fast ? fused_cv_comm_kernel_of<double4, true, ORTHO>(n_cv) : fused_cv_comm_kernel_of<double4, false, ORTHO>(n_cv);
-    }
-const void *fused_cv_comm_kernel(int dtype, unsigned int n_cv, bool fast, bool ortho)
-    {
-    return ortho ? fused_cv_comm_kernel_o<true>(dtype, n_cv, fast) : fused_cv_comm_kernel_o<false>(dtype, n_cv, fast);
-    }
-
-template<typename S4, bool FAST, bool ORTHO>
-int launch_fused_cv(const LamKArgs &k_in, unsigned int N, const void *d_postype, double *d_partials, unsigned int cv_blocks,
-                    const MetadCfg &cfg, unsigned int n_apply, const CommK *ck, hipStream_t s)
-    {
-    const S4 *p = (const S4 *)d_postype;
-    const unsigned int grid = cv_blocks + n_apply;
-    const LamKArgs k = dense_cv_args(k_in);                          // (the kernel stages its tables with flat loads)
-    if (ck)
-        {
-        if (grid > resident_capacity(fused_cv_comm_kernel_of<S4, FAST, ORTHO>(k.n_cv), FCV_THREADS)) return MTD_ERR_UNSUPPORTED;
-        switch (k.n_cv)
-            {
-            case 1: k_fused_cv<S4, 1, FAST, true, ORTHO><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, *ck); break;
-            case 2: k_fused_cv<S4, 2, FAST, true, ORTHO><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, *ck); break;
-            case 3: k_fused_cv<S4, 3, FAST, true, ORTHO><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, *ck); break;
-            default: return MTD_ERR_UNSUPPORTED;
-            }
-        MTD_LAUNCH_CHECK();
-        return MTD_SUCCESS;
-        }
-    CommK none;
-    std::memset(&none, 0, sizeof(none));
-    switch (k.n_cv)
-        {
-        case 1: k_fused_cv<S4, 1, FAST, false, ORTHO><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, none); break;
-        case 2: k_fused_cv<S4, 2, FAST, false, ORTHO><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, none); break;
-        case 3: k_fused_cv<S4, 3, FAST, false, ORTHO><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, none); break;
-        case 4: k_fused_cv<S4, 4, FAST, false, ORTHO><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, none); break;
-        case 5: k_fused_cv<S4, 5, FAST, false, ORTHO><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, none); break;
-        case 6: k_fused_cv<S4, 6, FAST, false, ORTHO><<<grid, FCV_THREADS, 0, s>>>(k, p, N, d_partials, cfg, n_apply, none); break;
-        default: return MTD_ERR_UNSUPPORTED;
-        }
-    MTD_LAUNCH_CHECK();
-    return MTD_SUCCESS;
-    }
-
-} // namespace
+} // namespace mtd
 
 extern "C" {
 
@@ -570,27 +466,26 @@ int mtd_fused_cv_pass(mtd_metad *m, const mtd_lamellar_set *set, unsigned int n_
     *n_partials = blocks;
     const unsigned int n_apply = m->pending_apply ? (m->cfg.len + FCV_THREADS - 1) / FCV_THREADS : 0;
     const bool fast = lam_fast_trig(k) != 0;
-    CommK ckv;
-    const CommK *ck = nullptr;
-    if (m->comm)
+    if (m->comm && (set->n_cv > (unsigned int)CHAIN_MAX_CV || set->n_cv != m->cfg.n_cv)) return MTD_ERR_UNSUPPORTED;
+    const LamKArgs kd = dense_cv_args(k);                           // (the kernel stages its tables with flat loads)
+    rc = with_fused_cv_kernel(dtype, fast, k.ortho != 0, m->comm != nullptr, set->n_cv, [&](auto kernel, auto s4) -> int
         {
-        if (set->n_cv > (unsigned int)CHAIN_MAX_CV || set->n_cv != m->cfg.n_cv) return MTD_ERR_UNSUPPORTED;
-        // every refusal comes BEFORE the exchange number advances: a call that sends nothing must not consume a number
-        // (the peers would wait for an exchange that never happens)
-        const void *kern = fused_cv_comm_kernel(dtype, set->n_cv, fast, k.ortho != 0);
-        if (blocks + n_apply > resident_capacity(kern, FCV_THREADS)) return MTD_ERR_UNSUPPORTED;
-        rc = comm_next(m->comm, ckv);                           // this launch sends exchange seq, launch B receives it
-        if (rc) return rc;
-        ck = &ckv;
-        }
-#define MTD_LAUNCH_FCV(S4, FASTV) \
-        (k.ortho ? launch_fused_cv<S4, FASTV, true>(k, n_particles, d_postype, d_partials, blocks, m->cfg, n_apply, ck, s) \
-                 : launch_fused_cv<S4, FASTV, false>(k, n_particles, d_postype, d_partials, blocks, m->cfg, n_apply, ck, s))
-    if (dtype == MTD_F32)
-        rc = fast ? MTD_LAUNCH_FCV(float4, true) : MTD_LAUNCH_FCV(float4, false);
-    else
-        rc = fast ? MTD_LAUNCH_FCV(double4, true) : MTD_LAUNCH_FCV(double4, false);
-#undef MTD_LAUNCH_FCV
+        using S4 = typename decltype(s4)::type;
+        const unsigned int grid = blocks + n_apply;
+        CommK ck;
+        std::memset(&ck, 0, sizeof(ck));
+        if (m->comm)
+            {
+            // every refusal comes BEFORE the exchange number advances: a call that sends nothing must not consume a number
+            // (the peers would wait for an exchange that never happens)
+            if (grid > resident_capacity((const void *)kernel, FCV_THREADS)) return MTD_ERR_UNSUPPORTED;
+            const int rcn = comm_next(m->comm, ck);                 // this launch sends exchange seq, launch B receives it
+            if (rcn) return rcn;
+            }
+        kernel<<<grid, FCV_THREADS, 0, s>>>(kd, (const S4 *)d_postype, n_particles, d_partials, m->cfg, n_apply, ck);
+        MTD_LAUNCH_CHECK();
+        return MTD_SUCCESS;
+        });
     if (rc) return rc;
     m->pending_apply = 0;
     return MTD_SUCCESS;
@@ -636,7 +531,7 @@ int mtd_fused_force_pass_slots(mtd_metad *m, const mtd_lamellar_set *set, const 
         if (!d_force[c] && n_particles) return MTD_ERR_INVALID_ARGUMENT;
         out.f[c] = d_force[c];
         }
-    const int dep = (m->add_bias && (timestep % m->stride == 0)) ? 1 : 0;   // .cc:368
+    const int dep = deposit_due(m, timestep);
     const unsigned int n_grid = dep ? m->cfg.n_gblocks : 0;
     const double two_over_n = 2.0 / (double)n_global;
     const bool fast = lam_fast_trig(k) != 0;
@@ -651,60 +546,50 @@ int mtd_fused_force_pass_slots(mtd_metad *m, const mtd_lamellar_set *set, const 
         }
     if (m->cfg.n_cv <= (unsigned int)CHAIN_MAX_CV && !force_general)
         {
-        // (the force blocks of the launch: every streaming thread takes ff_groups<S4, NCV, FASTV>::value groups of FF_U particles — the
-        // count is formed where the instantiation is chosen, so that the two cannot disagree)
-        unsigned int grid = 0;
         // measurement aid (mtd_profile_force_begin): the launch records its own begin and end through the start / stop events of
         // hipExtLaunchKernelGGL — the dispatch's time stamps, what a kernel trace reports for it
         hipEvent_t ev_start = nullptr, ev_stop = nullptr;
         const bool timed = force_profile_next(ev_start, ev_stop);
-#define MTD_LAUNCH_FF_K(KERNEL) \
-        do { if (timed) hipExtLaunchKernelGGL(KERNEL, dim3(grid), dim3(FF_THREADS), 0, s, ev_start, ev_stop, 0, k, (const S4T *)d_postype, out, n_particles, two_over_n, m->cfg, dep, n_grid, ck); \
-             else KERNEL<<<grid, FF_THREADS, 0, s>>>(k, (const S4T *)d_postype, out, n_particles, two_over_n, m->cfg, dep, n_grid, ck); } while (0)
-#define MTD_LAUNCH_FF(S4, NCV, FASTV) \
-        do { typedef S4 S4T; \
-             const unsigned int per_block = FF_STREAM_THREADS * FF_U * ff_groups<S4, NCV, FASTV>::value; \
-             unsigned int fblocks = (n_particles + per_block - 1) / per_block; \
-             if (fblocks == 0 && n_grid == 0) fblocks = 1;               /* still one block to publish the scalars */ \
-             grid = n_grid + fblocks; \
-             constexpr int G = ff_groups<S4, NCV, FASTV>::value; \
-             if (m->comm) { if (k.ortho) MTD_LAUNCH_FF_K((k_fused_force<S4, NCV, FASTV, G, true, true>)); \
-                            else MTD_LAUNCH_FF_K((k_fused_force<S4, NCV, FASTV, G, true, false>)); } \
-             else { if (k.ortho) MTD_LAUNCH_FF_K((k_fused_force<S4, NCV, FASTV, G, false, true>)); \
-                    else MTD_LAUNCH_FF_K((k_fused_force<S4, NCV, FASTV, G, false, false>)); } } while (0)
-#define MTD_LAUNCH_FF_NCV(S4, FASTV) \
-        switch (set->n_cv) { case 1: MTD_LAUNCH_FF(S4, 1, FASTV); break; case 2: MTD_LAUNCH_FF(S4, 2, FASTV); break; default: MTD_LAUNCH_FF(S4, 3, FASTV); break; }
-        if (dtype == MTD_F32)
+        dispatch_s4_fast(dtype, fast, [&](auto s4, auto fast_c)
             {
-            if (fast) { MTD_LAUNCH_FF_NCV(float4, true) } else { MTD_LAUNCH_FF_NCV(float4, false) }
-            }
-        else
-            {
-            if (fast) { MTD_LAUNCH_FF_NCV(double4, true) } else { MTD_LAUNCH_FF_NCV(double4, false) }
-            }
-#undef MTD_LAUNCH_FF_NCV
-#undef MTD_LAUNCH_FF
-#undef MTD_LAUNCH_FF_K
+            using S4 = typename decltype(s4)::type;
+            constexpr bool FAST = decltype(fast_c)::value;
+            // (1 <= set->n_cv: fill_kargs; set->n_cv <= cfg.n_cv <= CHAIN_MAX_CV: checked above)
+            dispatch_count<CHAIN_MAX_CV>(set->n_cv, [&](auto n)
+                {
+                // (the force blocks of the launch: every streaming thread takes ff_groups<S4, NCV, FAST>::value groups of FF_U
+                // particles — the count is formed where the instantiation is chosen, so that the two cannot disagree)
+                constexpr int NCV = decltype(n)::value, G = ff_groups<S4, NCV, FAST>::value;
+                const unsigned int per_block = FF_STREAM_THREADS * FF_U * G;
+                unsigned int fblocks = (n_particles + per_block - 1) / per_block;
+                if (fblocks == 0 && n_grid == 0) fblocks = 1;               // still one block to publish the scalars
+                const unsigned int grid = n_grid + fblocks;
+                dispatch_bool(m->comm != nullptr, [&](auto comm_c)
+                    {
+                    dispatch_bool(k.ortho != 0, [&](auto ortho_c)
+                        {
+                        const auto kernel = k_fused_force<S4, NCV, FAST, G, decltype(comm_c)::value, decltype(ortho_c)::value>;
+                        if (timed)
+                            hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(FF_THREADS), 0, s, ev_start, ev_stop, 0, k, (const S4 *)d_postype, out,
+                                                  n_particles, two_over_n, m->cfg, dep, n_grid, ck);
+                        else
+                            kernel<<<grid, FF_THREADS, 0, s>>>(k, (const S4 *)d_postype, out, n_particles, two_over_n, m->cfg, dep, n_grid, ck);
+                        });
+                    });
+                });
+            });
         }
     else
         {
         unsigned int fblocks = lam_force_blocks(n_particles);
         if (n_particles == 0) fblocks = n_grid ? 0 : 1;
         const unsigned int grid = n_grid + fblocks;
-        if (dtype == MTD_F32)
+        dispatch_s4_fast(dtype, fast, [&](auto s4, auto fast_c)
             {
-            if (fast)
-                k_fused_force_general<float4, true><<<grid, FF_THREADS, 0, s>>>(k, (const float4 *)d_postype, out, n_particles, two_over_n, m->cfg, dep, n_grid);
-            else
-                k_fused_force_general<float4, false><<<grid, FF_THREADS, 0, s>>>(k, (const float4 *)d_postype, out, n_particles, two_over_n, m->cfg, dep, n_grid);
-            }
-        else
-            {
-            if (fast)
-                k_fused_force_general<double4, true><<<grid, FF_THREADS, 0, s>>>(k, (const double4 *)d_postype, out, n_particles, two_over_n, m->cfg, dep, n_grid);
-            else
-                k_fused_force_general<double4, false><<<grid, FF_THREADS, 0, s>>>(k, (const double4 *)d_postype, out, n_particles, two_over_n, m->cfg, dep, n_grid);
-            }
+            using S4 = typename decltype(s4)::type;
+            k_fused_force_general<S4, decltype(fast_c)::value><<<grid, FF_THREADS, 0, s>>>(k, (const S4 *)d_postype, out, n_particles, two_over_n,
+                                                                                        m->cfg, dep, n_grid);
+            });
         }
     MTD_LAUNCH_CHECK();
     m->pending_apply = dep;
@@ -775,7 +660,7 @@ int fused_grid_step(mtd_metad *m, unsigned int timestep, hipStream_t s)
     k.n_cv = m->cfg.n_cv;
     ForcePtrs out;
     for (unsigned int c = 0; c < MTD_MAX_CV; ++c) out.f[c] = nullptr;
-    const int dep = (m->add_bias && (timestep % m->stride == 0)) ? 1 : 0;
+    const int dep = deposit_due(m, timestep);
     const unsigned int n_grid = dep ? m->cfg.n_gblocks : 0;
     const unsigned int grid = n_grid ? n_grid : 1;                  // still one block to publish the scalars
     CommK ck;

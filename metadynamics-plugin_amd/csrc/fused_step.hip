@@ -32,6 +32,10 @@
 // A launch whose blocks wait for each other is only issued when the whole grid is resident at once (occupancy x compute
 // units, checked per launch); otherwise, and for anything outside its envelope (more than 4096 particles per compute unit,
 // more than 3 collective variables, a slot map, MTD_FUSED_STEP=0), mtd_fused_step runs the two-launch form.
+//
+// Shared with the other carriers of the grid engine's launch (metad_device.hpp): the LDS copy of the chain's result (chain_share)
+// and the per-cell body of the first grid pass (grid_first_pass_cell).  The block sums over a strided slice and the publishing tail
+// (closed-form w, <dV>, the Gaussian count, no patch origin) are this kernel's own.
 #include <hip/hip_runtime.h>
 
 // Diagnostic build only (-DMTD_STAMPS, tools/build_stamps.sh): s_memrealtime (100 MHz) stamps of block 0 and of the last
@@ -64,9 +68,6 @@ extern "C" int mtd_debug_read_step_stamps(unsigned long long *host)
 
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <utility>
-#include <mutex>
 
 namespace
 {
@@ -380,13 +381,7 @@ __global__ __launch_bounds__(FS_THREADS, 1) void k_fused_step(const LamKArgs a, 
         c_wt = r.c_wt; c_wold = r.c_wold; c_dV = r.c_dV;
         MTD_STAMP(5, blockIdx.x == 0 && threadIdx.x == 0); MTD_STAMP(21, blockIdx.x == gridDim.x - 1 && threadIdx.x == 0);
         if (lane == 0) MTD_BSTAMP(3);
-        if (lane == 0)
-            {
-            s_chain.cv[0] = r.cv[0]; s_chain.cv[1] = r.cv[1]; s_chain.cv[2] = r.cv[2];
-            s_chain.bias[0] = r.bias[0]; s_chain.bias[1] = r.bias[1]; s_chain.bias[2] = r.bias[2];
-            s_chain.scal = r.scal; s_chain.V = r.V; s_chain.w = r.w;
-            s_chain.bin = r.bin; s_chain.on_grid = r.on_grid; s_chain.oob = r.oob; s_chain.failed = r.failed;
-            }
+        if (lane == 0) chain_share(s_chain, r);
         for (unsigned int i = lane; i < NCV * MTD_MAX_TYPES; i += MTD_WAVE)
             {
             const unsigned int cv = i / MTD_MAX_TYPES;
@@ -442,25 +437,13 @@ __global__ __launch_bounds__(FS_THREADS, 1) void k_fused_step(const LamKArgs a, 
     bool grid_expired = false;
     if (dep)
         {
-        // first grid pass on this block's slice: updateGrid (:1002-1047), updateHistogram (:1092-1119), updateSigmaGrid
-        // (:1122-1155), first loop of updateReweightedEstimator (:1070-1075)
+        // first grid pass on this block's slice (metad_device.hpp: grid_first_pass_cell)
         double s1 = 0.0, s2 = 0.0;
         for (unsigned int g = cell0 + threadIdx.x; g < cell1; g += FS_THREADS)
             {
-            const double dV = (c.W * s_chain.scal) * exp(-gauss_exponent3(c, g, s_chain.cv[0], s_chain.cv[1], s_chain.cv[2]));
-            c.grid_delta[g] = dV;
-            unsigned int hd = c.hist_delta[g];
-            if (s_chain.on_grid && g == s_chain.bin)
-                {
-                hd += 1;
-                c.hist_delta[g] = hd;
-                c.sigma_grid_delta[g] += c.det_sigma;
-                c.hist_gauss_delta[g] += 1;
-                }
-            const double Rw = c.rew[g] + (double)hd;
-            c.rew[g] = Rw;
-            s1 += Rw * dV;
-            s2 += Rw;
+            const double2 t = grid_first_pass_cell(c, s_chain, g);
+            s1 += t.x;
+            s2 += t.y;
             }
         s1 = wave_sum(s1);
         s2 = wave_sum(s2);
@@ -568,39 +551,6 @@ __global__ __launch_bounds__(FS_THREADS, 1) void k_fused_step(const LamKArgs a, 
         }
     }
 
-// blocks of `kernel` the device holds at one time (see fused.hip: resident_capacity)
-unsigned int step_capacity(const void *kernel)
-    {
-    static std::mutex mu;
-    static std::map<std::pair<int, const void *>, unsigned int> cache;      // per device
-    int per_cu = 0, dev = 0, n_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess)
-        {
-        (void)hipGetLastError();
-        return 0;
-        }
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = cache.find(std::make_pair(dev, kernel));
-    if (it != cache.end()) return it->second;
-    unsigned int cap = 0;
-    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, FS_THREADS, 0) == hipSuccess)
-        cap = (unsigned int)per_cu * (unsigned int)n_cu;
-    else
-        (void)hipGetLastError();
-    cache[std::make_pair(dev, kernel)] = cap;
-    return cap;
-    }
-
-unsigned long long step_timeout_ticks()
-    {
-    const char *e = std::getenv("MTD_COMM_TIMEOUT_MS");
-    double ms = 5000.0;
-    if (e && *e) ms = std::atof(e);
-    if (!(ms > 0.0)) ms = 5000.0;
-    return (unsigned long long)(ms * 1.0e5);            // wall_clock64: 100 MHz
-    }
-
 int step_buffers(mtd_metad *m)
     {
     if (m->d_ll) return MTD_SUCCESS;
@@ -633,15 +583,20 @@ int step_buffers(mtd_metad *m)
     return MTD_SUCCESS;
     }
 
-template<typename S4, bool FAST>
-const void *step_kernel(unsigned int n_cv, bool comm)
+// The instantiation of k_fused_step a step launches: f(kernel, type_tag<S4>).  One expression chooses the kernel whose residency
+// is asked for and the kernel that is launched.  n_cv: 1 .. CHAIN_MAX_CV (fill_kargs refuses 0; mtd_fused_step takes the
+// two-launch form for more).
+template<typename F> auto with_step_kernel(int dtype, bool fast, unsigned int n_cv, bool comm, F &&f)
     {
-    switch (n_cv)
+    return dispatch_s4_fast(dtype, fast, [&](auto s4, auto fast_c)
         {
-        case 1: return comm ? (const void *)k_fused_step<S4, 1, FAST, true> : (const void *)k_fused_step<S4, 1, FAST, false>;
-        case 2: return comm ? (const void *)k_fused_step<S4, 2, FAST, true> : (const void *)k_fused_step<S4, 2, FAST, false>;
-        default: return comm ? (const void *)k_fused_step<S4, 3, FAST, true> : (const void *)k_fused_step<S4, 3, FAST, false>;
-        }
+        using S4 = typename decltype(s4)::type;
+        constexpr bool FAST = decltype(fast_c)::value;
+        return dispatch_count<CHAIN_MAX_CV>(n_cv, [&](auto n)
+            {
+            return dispatch_bool(comm, [&](auto comm_c) { return f(k_fused_step<S4, decltype(n)::value, FAST, decltype(comm_c)::value>, s4); });
+            });
+        });
     }
 
 } // namespace
@@ -686,18 +641,16 @@ int mtd_fused_step(mtd_metad *m, const mtd_lamellar_set *set, unsigned int n_par
     unsigned int nb = (n_particles + FS_CHUNK - 1) / FS_CHUNK;
     if (nb < 1) nb = 1;
     bool one_launch = !off && set->n_cv <= (unsigned int)CHAIN_MAX_CV && nb <= FS_MAX_BLOCKS;
-    const void *kern = nullptr;
+    // the step's instantiation, named once: asked for its residency here, launched below
+    const auto with_kernel = [&](auto &&f) { return with_step_kernel(dtype, fast, set->n_cv, comm, f); };
     if (one_launch)
         {
         // enough blocks for the grid passes too (a block's slice of the bias grid: a few cells per thread at most)
         const unsigned int nb_grid = (m->cfg.len + 4 * FS_THREADS - 1) / (4 * FS_THREADS);
         if (nb < nb_grid) nb = nb_grid > FS_MAX_BLOCKS ? FS_MAX_BLOCKS : nb_grid;
-        // spread the particles evenly over the blocks (not 4096 each with a short last one)
-        if (dtype == MTD_F32)
-            kern = fast ? step_kernel<float4, true>(set->n_cv, comm) : step_kernel<float4, false>(set->n_cv, comm);
-        else
-            kern = fast ? step_kernel<double4, true>(set->n_cv, comm) : step_kernel<double4, false>(set->n_cv, comm);
-        if (nb > step_capacity(kern)) one_launch = false;          // blocks wait for each other: the whole grid must be resident
+        // blocks wait for each other: the whole grid must be resident
+        const unsigned int cap = with_kernel([](auto kernel, auto) { return resident_capacity((const void *)kernel, FS_THREADS); });
+        if (nb > cap) one_launch = false;
         }
     if (!one_launch)
         {
@@ -734,7 +687,7 @@ int mtd_fused_step(mtd_metad *m, const mtd_lamellar_set *set, unsigned int n_par
     lk.seq = m->step_seq;
     lk.err = m->d_step_err;
     lk.err_host = m->d_step_err_host;
-    lk.timeout_ticks = step_timeout_ticks();
+    lk.timeout_ticks = comm_timeout_ticks();
     lk.world = 1;
 
     MetadCfg cfg = m->cfg;
@@ -747,28 +700,20 @@ int mtd_fused_step(mtd_metad *m, const mtd_lamellar_set *set, unsigned int n_par
         }
     ForcePtrs out;
     for (unsigned int c = 0; c < MTD_MAX_CV; ++c) out.f[c] = c < set->n_cv ? d_force[c] : nullptr;
-    const int dep = (m->add_bias && (timestep % m->stride == 0)) ? 1 : 0;   // .cc:368
+    const int dep = deposit_due(m, timestep);
     const double two_over_n = 2.0 / (double)n_global;
+    // spread the particles evenly over the blocks (not 4096 each with a short last one)
     unsigned int chunk = (n_particles + nb - 1) / nb;
     chunk = (chunk + MTD_WAVE - 1) / MTD_WAVE * MTD_WAVE;                 // whole waves of consecutive particles
     if (chunk > FS_CHUNK) chunk = FS_CHUNK;
     if (chunk == 0) chunk = MTD_WAVE;
     const unsigned int cells_per_block = (cfg.len + nb - 1) / nb;
 
-#define MTD_LAUNCH_FS(S4, NCV, FASTV, COMMV) \
-    k_fused_step<S4, NCV, FASTV, COMMV><<<nb, FS_THREADS, 0, s>>>(k, (const S4 *)d_postype, out, n_particles, chunk, two_over_n, cfg, dep, cells_per_block, lk, ck)
-#define MTD_LAUNCH_FS_NCV(S4, FASTV, COMMV) \
-    switch (set->n_cv) { case 1: MTD_LAUNCH_FS(S4, 1, FASTV, COMMV); break; case 2: MTD_LAUNCH_FS(S4, 2, FASTV, COMMV); break; default: MTD_LAUNCH_FS(S4, 3, FASTV, COMMV); break; }
-#define MTD_LAUNCH_FS_ALL(S4) \
-    do { if (fast) { if (comm) { MTD_LAUNCH_FS_NCV(S4, true, true) } else { MTD_LAUNCH_FS_NCV(S4, true, false) } } \
-         else { if (comm) { MTD_LAUNCH_FS_NCV(S4, false, true) } else { MTD_LAUNCH_FS_NCV(S4, false, false) } } } while (0)
-    if (dtype == MTD_F32)
-        MTD_LAUNCH_FS_ALL(float4);
-    else
-        MTD_LAUNCH_FS_ALL(double4);
-#undef MTD_LAUNCH_FS_ALL
-#undef MTD_LAUNCH_FS_NCV
-#undef MTD_LAUNCH_FS
+    with_kernel([&](auto kernel, auto s4)
+        {
+        using S4 = typename decltype(s4)::type;
+        kernel<<<nb, FS_THREADS, 0, s>>>(k, (const S4 *)d_postype, out, n_particles, chunk, two_over_n, cfg, dep, cells_per_block, lk, ck);
+        });
     MTD_LAUNCH_CHECK();
     m->pending_apply = 0;
     m->w_stale = 0;                                             // (w(s) comes out of the launch in closed form)

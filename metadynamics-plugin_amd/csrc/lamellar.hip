@@ -210,34 +210,6 @@ unsigned int force_blocks(unsigned int N)
     return b;
     }
 
-template<typename S4, bool FAST>
-int launch_cv(const LamKArgs &k, unsigned int N, const void *d_postype, double *d_partials, unsigned int blocks, hipStream_t s)
-    {
-    const S4 *p = (const S4 *)d_postype;
-    if (k.n_cv == 1)
-        k_lamellar_cv_partials<S4, 1, FAST><<<blocks, CV_THREADS, 0, s>>>(k, p, N, d_partials);
-    else if (k.n_cv == 2)
-        k_lamellar_cv_partials<S4, 2, FAST><<<blocks, CV_THREADS, 0, s>>>(k, p, N, d_partials);
-    else if (k.n_cv <= 4)
-        {
-        // partial rows are n_cv wide only when NCV == n_cv: pad by instantiating exact widths
-        if (k.n_cv == 3)
-            k_lamellar_cv_partials<S4, 3, FAST><<<blocks, CV_THREADS, 0, s>>>(k, p, N, d_partials);
-        else
-            k_lamellar_cv_partials<S4, 4, FAST><<<blocks, CV_THREADS, 0, s>>>(k, p, N, d_partials);
-        }
-    else if (k.n_cv == 5)
-        k_lamellar_cv_partials<S4, 5, FAST><<<blocks, CV_THREADS, 0, s>>>(k, p, N, d_partials);
-    else if (k.n_cv == 6)
-        k_lamellar_cv_partials<S4, 6, FAST><<<blocks, CV_THREADS, 0, s>>>(k, p, N, d_partials);
-    else if (k.n_cv == 7)
-        k_lamellar_cv_partials<S4, 7, FAST><<<blocks, CV_THREADS, 0, s>>>(k, p, N, d_partials);
-    else
-        k_lamellar_cv_partials<S4, 8, FAST><<<blocks, CV_THREADS, 0, s>>>(k, p, N, d_partials);
-    MTD_LAUNCH_CHECK();
-    return MTD_SUCCESS;
-    }
-
 } // namespace
 
 namespace mtd
@@ -356,11 +328,18 @@ int mtd_lamellar_cv_partials(const mtd_lamellar_set *set, unsigned int n_particl
     hipStream_t s = (hipStream_t)stream;
     const unsigned int blocks = cv_blocks(n_particles);
     *n_partials = blocks;
-    if (dtype == MTD_F32)
-        return lam_fast_trig(k) ? launch_cv<float4, true>(k, n_particles, d_postype, d_partials, blocks, s)
-                           : launch_cv<float4, false>(k, n_particles, d_postype, d_partials, blocks, s);
-    return lam_fast_trig(k) ? launch_cv<double4, true>(k, n_particles, d_postype, d_partials, blocks, s)
-                       : launch_cv<double4, false>(k, n_particles, d_postype, d_partials, blocks, s);
+    dispatch_s4_fast(dtype, lam_fast_trig(k) != 0, [&](auto s4, auto fast_c)
+        {
+        using S4 = typename decltype(s4)::type;
+        // (partial rows are n_cv wide only when NCV == n_cv: exact widths are instantiated; 1 <= n_cv <= MTD_MAX_CV: fill_kargs)
+        dispatch_count<MTD_MAX_CV>(k.n_cv, [&](auto n)
+            {
+            k_lamellar_cv_partials<S4, decltype(n)::value, decltype(fast_c)::value><<<blocks, CV_THREADS, 0, s>>>(k, (const S4 *)d_postype,
+                                                                                                              n_particles, d_partials);
+            });
+        });
+    MTD_LAUNCH_CHECK();
+    return MTD_SUCCESS;
     }
 
 int mtd_reduce_partials(const double *d_partials, unsigned int n_partials, unsigned int stride,
@@ -395,20 +374,11 @@ int mtd_calculate_fourier_modes(unsigned int n_wave, const int *lattice_vectors,
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const unsigned int blocks = cv_blocks(n_particles);
-    if (dtype == MTD_F32)
+    dispatch_s4_fast(dtype, lam_fast_trig(k) != 0, [&](auto s4, auto fast_c)
         {
-        if (lam_fast_trig(k))
-            k_lamellar_mode_partials<float4, true><<<blocks, CV_THREADS, 0, s>>>(k, (const float4 *)d_postype, n_particles, d_scratch);
-        else
-            k_lamellar_mode_partials<float4, false><<<blocks, CV_THREADS, 0, s>>>(k, (const float4 *)d_postype, n_particles, d_scratch);
-        }
-    else
-        {
-        if (lam_fast_trig(k))
-            k_lamellar_mode_partials<double4, true><<<blocks, CV_THREADS, 0, s>>>(k, (const double4 *)d_postype, n_particles, d_scratch);
-        else
-            k_lamellar_mode_partials<double4, false><<<blocks, CV_THREADS, 0, s>>>(k, (const double4 *)d_postype, n_particles, d_scratch);
-        }
+        using S4 = typename decltype(s4)::type;
+        k_lamellar_mode_partials<S4, decltype(fast_c)::value><<<blocks, CV_THREADS, 0, s>>>(k, (const S4 *)d_postype, n_particles, d_scratch);
+        });
     MTD_LAUNCH_CHECK();
     return mtd_reduce_partials(d_scratch, blocks, 2 * n_wave, 2 * n_wave, 1.0, 0.0, d_fourier_modes, stream);
     }
@@ -433,20 +403,12 @@ static int lamellar_forces_impl(const mtd_lamellar_set *set, unsigned int n_part
     hipStream_t s = (hipStream_t)stream;
     const unsigned int blocks = force_blocks(n_particles);
     const double two_over_n = 2.0 / (double)n_global;
-    if (dtype == MTD_F32)
+    dispatch_s4_fast(dtype, lam_fast_trig(k) != 0, [&](auto s4, auto fast_c)
         {
-        if (lam_fast_trig(k))
-            k_lamellar_forces<float4, true><<<blocks, FORCE_THREADS, 0, s>>>(k, (const float4 *)d_postype, out, n_particles, d_bias, bias_host, two_over_n);
-        else
-            k_lamellar_forces<float4, false><<<blocks, FORCE_THREADS, 0, s>>>(k, (const float4 *)d_postype, out, n_particles, d_bias, bias_host, two_over_n);
-        }
-    else
-        {
-        if (lam_fast_trig(k))
-            k_lamellar_forces<double4, true><<<blocks, FORCE_THREADS, 0, s>>>(k, (const double4 *)d_postype, out, n_particles, d_bias, bias_host, two_over_n);
-        else
-            k_lamellar_forces<double4, false><<<blocks, FORCE_THREADS, 0, s>>>(k, (const double4 *)d_postype, out, n_particles, d_bias, bias_host, two_over_n);
-        }
+        using S4 = typename decltype(s4)::type;
+        k_lamellar_forces<S4, decltype(fast_c)::value><<<blocks, FORCE_THREADS, 0, s>>>(k, (const S4 *)d_postype, out, n_particles, d_bias, bias_host,
+                                                                                     two_over_n);
+        });
     MTD_LAUNCH_CHECK();
     return MTD_SUCCESS;
     }

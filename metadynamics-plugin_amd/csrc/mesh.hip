@@ -4489,7 +4489,7 @@ int mtd_mesh_forces_update_bias(mtd_mesh *mesh, mtd_metad *m, unsigned int mesh_
         if (!d_force_lamellar[cv]) return MTD_ERR_INVALID_ARGUMENT;
         k.slot[cv] = (unsigned char)slots[cv];
         }
-    const int dep = (m->add_bias && (timestep % m->stride == 0)) ? 1 : 0;   // .cc:368
+    const int dep = deposit_due(m, timestep);   // .cc:368
     const unsigned int n_grid = dep ? m->cfg.n_gblocks : 0;
     const unsigned int blocks = 8 * ((mesh->tg.n_tiles + 7) / 8);
     if (n_grid > blocks) return MTD_ERR_UNSUPPORTED;

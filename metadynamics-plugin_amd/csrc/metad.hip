@@ -581,7 +581,7 @@ int mtd_metad_update_phase_a(mtd_metad *m, unsigned int timestep, int *deposited
     if (!m || !deposited) return MTD_ERR_INVALID_ARGUMENT;
     { int frc = mtd::metad_flush(m, (hipStream_t)stream); if (frc) return frc; }
     hipStream_t s = (hipStream_t)stream;
-    const int dep = (m->add_bias && (timestep % m->stride == 0)) ? 1 : 0;   // .cc:368
+    const int dep = deposit_due(m, timestep);   // .cc:368
     k_prepare<<<1, GRID_THREADS, 0, s>>>(m->cfg, dep);
     MTD_LAUNCH_CHECK();
     if (dep)
@@ -683,7 +683,7 @@ int mtd_metad_update_bias(mtd_metad *m, unsigned int timestep, mtd_stream_t stre
     if (m->cfg.n_cv <= 3 && !four_launches) return mtd::fused_grid_step(m, timestep, (hipStream_t)stream);
     { int frc = mtd::metad_flush(m, (hipStream_t)stream); if (frc) return frc; }
     hipStream_t s = (hipStream_t)stream;
-    const int dep = (m->add_bias && (timestep % m->stride == 0)) ? 1 : 0;
+    const int dep = deposit_due(m, timestep);
     k_prepare<<<1, GRID_THREADS, 0, s>>>(m->cfg, dep);
     MTD_LAUNCH_CHECK();
     if (dep)

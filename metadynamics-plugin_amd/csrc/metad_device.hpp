@@ -1,5 +1,5 @@
 // metad_device.hpp — device structures and functions of the bias-grid engine, shared by the generic
-// kernels (metad.hip) and the fused bias-step kernels (fused.hip).
+// kernels (metad.hip) and every kernel that carries the fused bias step (fused.hip, fused_step.hip, mesh.hip, steinhardt.hip).
 //
 // Reference arithmetic: IntegratorMetaDynamics.cc:663-736 (interpolateGrid), :738-776
 // (biasPotentialDerivative), :1002-1047 (updateGrid), :1092-1155 (histogram bins), IndexGrid.cc:20-58.
@@ -347,7 +347,7 @@ __device__ __forceinline__ void apply_cells(const MetadCfg &c, const unsigned in
             {
             // the patch around the last CV values follows the grid (MetadState::patch_v)
             unsigned int rest = g;
-            int slot = 0, mul = 1;
+            int slot = 0;
             bool in = true;
             for (int i = (int)c.n_cv - 1; i >= 0; --i)
                 {
@@ -357,7 +357,6 @@ __device__ __forceinline__ void apply_cells(const MetadCfg &c, const unsigned in
                 in = in && o >= 0 && o < 6;
                 slot += o * (i == 0 ? 1 : (i == 1 ? 6 : 36));
                 }
-            (void)mul;
             if (in) c.st->patch_v[slot] = g_new;
             }
         // the histogram and width increments are zero everywhere but at the few cells the CV visited since the last pass: only
@@ -875,10 +874,13 @@ __device__ __forceinline__ double gauss_exponent3(const MetadCfg &c, unsigned in
     return gauss_exp;
     }
 
-// ---- pieces of the bias-grid engine's launch for kernels of OTHER files that carry it (mesh.hip: k_tile_forces_chain) -----------
-// The same statements as k_fused_force's grid blocks and its publishing wave (fused.hip, which keeps its own copy with the diagnostic
-// time stamps in it): the same sums in the same order, so the grid arrays come out the same whichever launch carried the pass
-// (k_tile_forces_chain in mesh.hip, k_ql_finalize_chain in steinhardt.hip).
+// ---- pieces of the bias-grid engine's launch, shared by every kernel that carries it -------------------------------------------
+// k_fused_force (fused.hip), k_fused_step (fused_step.hip), k_tile_forces_chain (mesh.hip) and k_ql_finalize_chain (steinhardt.hip)
+// all run these statements, so the grid arrays come out the same whichever launch carried the pass.  None of them holds a
+// diagnostic time stamp: a caller that wants one (k_fused_force, slots 19 / 20) calls the two halves of grid_first_pass_256 and
+// stamps in between, into its own file's buffer.  The n-dimensional forms of the first pass (k_fused_force_general in fused.hip,
+// k_reweight1 in metad.hip: gauss_exponent over a runtime dimension count, block_sum instead of the wave sums below) add up in a
+// different order and keep their own statements.
 
 // what the chain's wave returns, as the block shares it (lane 0 of the chain's wave writes, a barrier publishes)
 __device__ __forceinline__ void chain_share(ChainResult &s_chain, const ChainResult &r)
@@ -889,35 +891,44 @@ __device__ __forceinline__ void chain_share(ChainResult &s_chain, const ChainRes
     s_chain.bin = r.bin; s_chain.on_grid = r.on_grid; s_chain.oob = r.oob; s_chain.failed = r.failed;
     }
 
-// First grid pass of a deposit step (updateGrid :1002-1047, updateHistogram :1092-1119, updateSigmaGrid :1122-1155, first loop of
-// updateReweightedEstimator :1070-1075) for the 256 cells of grid block `vb`, by threads 0 .. 255 of the calling block.  EVERY
-// thread of the block calls it (one __syncthreads inside); s_red: 8 doubles.
-__device__ __forceinline__ void grid_first_pass_256(const MetadCfg &c, const ChainResult &s_chain, const unsigned int vb, double *s_red)
+// First grid pass of a deposit step at ONE cell g < c.len (updateGrid :1002-1047, updateHistogram :1092-1119, updateSigmaGrid
+// :1122-1155, first loop of updateReweightedEstimator :1070-1075): Gaussian increment, histogram / sigma-grid bin, R += hist_delta.
+// Returns the cell's summands (R dV, R) of <dV>; the caller adds them up in its own order.
+__device__ __forceinline__ double2 grid_first_pass_cell(const MetadCfg &c, const ChainResult &s_chain, const unsigned int g)
     {
-    const unsigned int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const double dV = (c.W * s_chain.scal) * exp(-gauss_exponent3(c, g, s_chain.cv[0], s_chain.cv[1], s_chain.cv[2]));
+    c.grid_delta[g] = dV;
+    unsigned int hd = c.hist_delta[g];
+    if (s_chain.on_grid && g == s_chain.bin)
+        {
+        hd += 1;
+        c.hist_delta[g] = hd;
+        c.sigma_grid_delta[g] += c.det_sigma;
+        c.hist_gauss_delta[g] += 1;
+        }
+    const double Rw = c.rew[g] + (double)hd;
+    c.rew[g] = Rw;
+    return make_double2(Rw * dV, Rw);
+    }
+
+// The first grid pass for the 256 cells of grid block `vb`, by threads 0 .. 255 of the calling block, in two halves.  EVERY thread
+// of the block calls both (one __syncthreads in the second); s_red: 8 doubles.
+// 1. the cells: this thread's summands (zeros beyond the grid, in threads >= 256 and on a poisoned step)
+__device__ __forceinline__ double2 grid_first_pass_cells_256(const MetadCfg &c, const ChainResult &s_chain, const unsigned int vb)
+    {
     const bool mine = threadIdx.x < 256;
     const unsigned int g = vb * 256 + threadIdx.x;
-    double s1 = 0.0, s2 = 0.0;
-    if (mine && g < c.len && !s_chain.failed)
-        {
-        const double dV = (c.W * s_chain.scal) * exp(-gauss_exponent3(c, g, s_chain.cv[0], s_chain.cv[1], s_chain.cv[2]));
-        c.grid_delta[g] = dV;
-        unsigned int hd = c.hist_delta[g];
-        if (s_chain.on_grid && g == s_chain.bin)
-            {
-            hd += 1;
-            c.hist_delta[g] = hd;
-            c.sigma_grid_delta[g] += c.det_sigma;
-            c.hist_gauss_delta[g] += 1;
-            }
-        const double Rw = c.rew[g] + (double)hd;
-        c.rew[g] = Rw;
-        s1 = Rw * dV;
-        s2 = Rw;
-        }
-    s1 = wave_sum(s1);
-    s2 = wave_sum(s2);
-    if (mine && lane == 0)
+    double2 s = make_double2(0.0, 0.0);
+    if (mine && g < c.len && !s_chain.failed) s = grid_first_pass_cell(c, s_chain, g);
+    return s;
+    }
+
+// 2. the block sums: wave sums, then the four waves in order, into gpart[2 vb], gpart[2 vb + 1]
+__device__ __forceinline__ void grid_first_pass_sums_256(const MetadCfg &c, const unsigned int vb, const double2 s, double *s_red)
+    {
+    const unsigned int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const double s1 = wave_sum(s.x), s2 = wave_sum(s.y);
+    if (threadIdx.x < 256 && lane == 0)
         {
         s_red[2 * wave] = s1;
         s_red[2 * wave + 1] = s2;
@@ -936,14 +947,21 @@ __device__ __forceinline__ void grid_first_pass_256(const MetadCfg &c, const Cha
         }
     }
 
+__device__ __forceinline__ void grid_first_pass_256(const MetadCfg &c, const ChainResult &s_chain, const unsigned int vb, double *s_red)
+    {
+    grid_first_pass_sums_256(c, vb, grid_first_pass_cells_256(c, s_chain, vb), s_red);
+    }
+
 // One wave of one block publishes the step's scalars for the host (lazy read-back) and, on non-deposit steps, owns the histogram
 // increment (:366) and the weight read-out (the weight grid is final then).  Called by a FULL wave (chain_wave inside).
 // given: the CV values handed to the chain in registers / LDS (k_ql_finalize_chain) instead of registered partial sums
-__device__ __forceinline__ void publish_step(const MetadCfg &c, const ChainResult &s_chain, const int deposit, const double *given = nullptr)
+// rx: the mailbox the CV sums came out of (sharded step, k_fused_force<..., COMM>)
+__device__ __forceinline__ void publish_step(const MetadCfg &c, const ChainResult &s_chain, const int deposit, const double *given = nullptr,
+                                             const CommK *rx = nullptr)
     {
     const int lane = threadIdx.x & 63;
     double w_now = 1.0;
-    if (!deposit) w_now = chain_wave(c, false, false, nullptr, given).w;    // w(s) from the (final) weight grid
+    if (!deposit) w_now = chain_wave(c, false, false, rx, given).w;         // w(s) from the (final) weight grid
     if (lane < (int)c.n_cv)
         {
         const double s_l = lane == 0 ? s_chain.cv[0] : (lane == 1 ? s_chain.cv[1] : s_chain.cv[2]);
@@ -961,7 +979,7 @@ __device__ __forceinline__ void publish_step(const MetadCfg &c, const ChainResul
     if (lane == 0)
         {
         c.st->V = s_chain.V;
-        c.st->failed = (unsigned int)s_chain.failed;
+        c.st->failed = (unsigned int)s_chain.failed;                 // the deferred pass of a poisoned deposit is skipped (0 without a mailbox)
         c.st->bin = s_chain.bin;
         c.st->on_grid = (unsigned int)s_chain.on_grid;
         if (deposit)

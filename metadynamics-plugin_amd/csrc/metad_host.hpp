@@ -34,6 +34,11 @@ struct mtd_metad
 
 namespace mtd
 {
+// does this step deposit a hill? (IntegratorMetaDynamics.cc:368)
+inline int deposit_due(const mtd_metad *m, unsigned int timestep) { return (m->add_bias && (timestep % m->stride == 0)) ? 1 : 0; }
+// Blocks of `kernel` the current device holds at one time (occupancy x compute units; 0 if the query fails), cached per device
+// and kernel (fused.hip).  A launch whose blocks wait for each other is only issued when its whole grid is resident at once.
+unsigned int resident_capacity(const void *kernel, int threads);
 // run the deferred k_apply if one is pending (called by every entry point that reads or updates the grid)
 int metad_flush(mtd_metad *m, hipStream_t s);
 // fused.hip: deferred apply + one launch for the whole update (n_cv <= 3), MTD_ERR_UNSUPPORTED otherwise

@@ -636,8 +636,8 @@ __global__ __launch_bounds__(256) void k_ql_finalize_carrier(const QlArgs<LMAX> 
 // hands the value to the engine's scalar chain in registers (chain_wave's `given`: no trip through memory), and goes on with
 // the first grid pass of a deposit (updateGrid :1002-1047, updateHistogram :1092-1119, updateSigmaGrid :1122-1155, first loop of
 // updateReweightedEstimator :1070-1075); block 0 writes the tables the force pass reads and publishes the step's scalars.  The
-// grid-pass and publishing code (metad_device.hpp: grid_first_pass_256, publish_step) is the twin of k_fused_force's (fused.hip): tests
-// hold the two against each other bit for bit
+// grid-pass and publishing code (metad_device.hpp: grid_first_pass_256, publish_step) is the code k_fused_force runs (fused.hip); a test
+// holds the merged launch against the separate launches bit for bit
 // (tests/test_gpu_steinhardt.py::test_ql_merged_launch_matches_separate_launches).  The engine's DEFERRED pass of the previous
 // deposit cannot ride here (this launch's chain reads the grid it writes): it travels in the force pass of its own step
 // (k_ql_forces<..., CARRY>), which follows the deposit's launch directly.
@@ -970,6 +970,8 @@ void launch_finalize(const QlArgs<LMAX> &a, const double *d_qprime, double *d_ql
 
 // blocks of `kernel` that are resident at once on the current device (both pair passes launch exactly that many, or fewer if the
 // system is small: every block then walks its chunks in a pipeline); cached per (kernel, device)
+// (not mtd::resident_capacity: a failed query there means "refuse the launch" (0); here each factor falls back on its own — one
+// block per compute unit, 256 compute units — and the pass runs all the same)
 template<typename Kernel> unsigned int ql_resident_blocks(Kernel kernel)
     {
     static std::mutex mtx;
@@ -1556,7 +1558,7 @@ int mtd_ql_finalize_update_bias(mtd_metad *m, int half_nlist, unsigned int lmax,
     if (rc) return rc;
     rc = mtd::metad_flush(m, s);                                        // (nothing to do when the force pass carried the deferred pass)
     if (rc) return rc;
-    const int dep = (m->add_bias && (timestep % m->stride == 0)) ? 1 : 0;      // IntegratorMetaDynamics.cc:368
+    const int dep = deposit_due(m, timestep);      // IntegratorMetaDynamics.cc:368
     const unsigned int n_grid = dep ? m->cfg.n_gblocks : 0;
     if (lmax <= 4)
         rc = finalize_chain_impl<4>(m, half_nlist, lmax, Ql_ref, n_global, qprime, qlm, ql, value, dep, n_grid, s);

@@ -312,8 +312,8 @@ def test_deferred_grid_pass_rides_in_the_finalize_launch(abi, ref):
 def test_ql_merged_launch_matches_separate_launches(abi, ref, dtype, stride, mode, off_grid):
     """mtd_ql_finalize_update_bias (finalize step + scalar chain + first grid pass in ONE launch, the engine's deferred pass riding
     in the force pass) against mtd_ql_accumulate + mtd_metad_update_bias + mtd_ql_forces on a moving snapshot: every grid array,
-    V, w, dV/ds, the hill count and the forces the same BITS (the grid-pass code of k_ql_finalize_chain is the twin of
-    k_fused_force's), deposit and non-deposit steps, a value that leaves the grid; and the separate path against the oracle"""
+    V, w, dV/ds, the hill count and the forces the same BITS (k_ql_finalize_chain and k_fused_force run the same grid-pass
+    code, metad_device.hpp), deposit and non-deposit steps, a value that leaves the grid; and the separate path against the oracle"""
     from test_gpu_metad import GpuMetad
     lib = abi.load()
     pos0, L = noisy_fcc(5, seed=3)
