@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Developer tool (GPU box): randomised check of the bias-grid engine (mtd_metad_update_bias: the fused grid step for <= 3
-variables, the four-launch sequence above that) against the oracle: 1-5 variables, random grids / widths / temperatures,
-stride, standard and well-tempered, trajectories that wander on and off the grid and sit exactly on nodes and edges,
-reset_histogram, add_hills toggles.  usage: fuzz_grid.py [seconds] [seed]"""
+variables, the four-launch sequence above that — or everywhere with MTD_METAD_FOUR_LAUNCHES=1 in the environment) against the
+oracle: 1-6 variables (6: the most the engine holds), random grids / widths / temperatures — 2 ... 13 points per axis above two
+variables, fewer where the grid would otherwise reach 50 000 cells (8 per axis with five variables, 6 with six) —, stride, standard
+and well-tempered, trajectories that wander on and off the grid and sit exactly on nodes and edges, add_hills toggles.
+usage: fuzz_grid.py [seconds] [seed]"""
 import os, sys, time
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(root, "metadynamics-plugin_amd"), os.path.join(root, "tests"), os.path.join(root, "oracle")]
@@ -20,8 +22,9 @@ while time.time() - t0 < budget:
     if time.time() - t_print > 30.0:
         t_print = time.time()
         print("fuzz_grid: %d cases, %d steps so far" % (it, steps_total), flush=True)
-    n_cv = int(rng.choice([1, 1, 2, 2, 3, 4, 5]))
-    pts = [int(x) for x in rng.integers(2, 14 if n_cv > 2 else 60, n_cv)]
+    n_cv = int(rng.choice([1, 1, 2, 2, 3, 4, 5, 6]))
+    most = min(13, int(49999.0 ** (1.0 / n_cv))) if n_cv > 2 else 59             # points per axis: the grid stays below 50 000 cells
+    pts = [int(x) for x in rng.integers(2, most + 1, n_cv)]
     lo = [float(x) for x in rng.uniform(-3.0, 1.0, n_cv)]
     hi = [l + float(x) for l, x in zip(lo, rng.uniform(0.5, 4.0, n_cv))]
     kw = dict(sigma=[float(x) for x in rng.uniform(0.03, 0.8, n_cv)], cv_min=lo, cv_max=hi, num_points=pts,
