@@ -585,7 +585,37 @@ int mtd_ql_forces(unsigned int n_particles, const void *d_postype, void *d_force
  * the force, as in mtd_ql_forces; c_i jumps from 0 to the one-neighbour value when a first neighbour enters an empty shell.
  * Arguments are checked before a device is touched: MTD_ERR_INVALID_ARGUMENT for null pointers, r_cut <= 0, r_on < 0,
  * r_on >= r_cut, n_global == 0, an unknown dtype or a d_scratch that is not 16-byte aligned; MTD_ERR_UNSUPPORTED for lmax > 12.
+ *
+ * Options (mtd_ql_local_options, the *_opt entry points) turn the mean of c_i into what nucleation is biased with.  With
+ * q_lm(i) = A_lm(i) / n_i (0 when n_i == 0):
+ *     average:  qbar_lm(i) = [ q_lm(i) + sum_j f(r_ij) q_lm(j) ] / (1 + n_i)      (Lechner and Dellago, J. Chem. Phys. 129, 114707,
+ *                                                                                 with the smoothing as weight; else qbar = q)
+ *     c_i      = sum_l Ql_ref[l] 4 pi / (2l + 1) sum_m |qbar_lm(i)|^2             (what *d_c holds)
+ *     switch:   h(c) = x^p / (1 + x^p),  x = max(c, 0) / c0,  c0 > 0, p >= 1      (else h(c) = c)
+ *     gate:     g(n) = 3 t^2 - 2 t^3,  t = clip((n - n_lo) / (n_hi - n_lo), 0, 1), 0 <= n_lo < n_hi     (else g = 1)
+ *     v_i      = g(n_i) h(c_i)   (0 for other types; what *d_v holds)             s = (1 / N_global) sum_i v_i
+ * With a switch s is the smooth NUMBER FRACTION of solid-like particles; the gate removes the jump of c_i when a first neighbour
+ * enters an empty shell.  With all three off (or opt == NULL) this is the variable above, bit for bit.  Gradient: with
+ * g_l = Ql_ref[l] 4 pi / (2l + 1),
+ *     B_lm(i) = g(n_i) h'(c_i) 2 g_l conj(qbar_lm(i)) / (1 + n_i)       (divided by 1 without the average)
+ *     C_lm(k) = B_lm(k) + sum_{i in row k} f_ik B_lm(i)                 (C = B without the average)
+ *     a_k     = g'(n_k) h(c_k) - Re sum_lm C_lm(k) q_lm(k) / n_k - [average] Re sum_lm B_lm(k) qbar_lm(k)
+ *     G_kj    = Re sum_lm (C_lm(k) / n_k) grad(f Y_lm)(d_kj) + ( a_k + [average] Re sum_lm B_lm(k) q_lm(j) ) grad f(d_kj)
+ *     N_global ds/dr_k = sum_j G_kj - sum_j G_jk
+ * The averaged variable reaches second neighbours: it needs the same full, symmetric list, two more gather passes inside
+ * mtd_ql_local_accumulate_opt and one double per list entry in the scratch.
  * ============================================================================================== */
+
+/* all-zero = the plain variable.  c0, p are read when switch_on != 0; n_lo, n_hi when gate_on != 0 */
+typedef struct
+    {
+    int average;
+    int switch_on;
+    double c0;
+    unsigned int p;
+    int gate_on;
+    double n_lo, n_hi;
+    } mtd_ql_local_options;
 
 /* device doubles the two calls share: block sums, n_i, c_i and the per-particle table of weights the force pass gathers */
 size_t mtd_ql_local_scratch_doubles(unsigned int n_particles, unsigned int lmax);
@@ -604,6 +634,24 @@ int mtd_ql_local_forces(unsigned int n_particles, const void *d_postype, void *d
                         const unsigned int *d_head_list, const unsigned int *d_n_neigh, const unsigned int *d_nlist, double rcut, double ron,
                         unsigned int lmax, unsigned int type, const double *Ql_ref, unsigned int n_global, const double *d_scratch,
                         const double *d_bias, double bias_host, mtd_stream_t stream);
+
+/* The same three with options; opt == NULL or an all-zero struct is the plain variable, bit for bit (the three above forward here).
+ * n_list_entries: the length of d_nlist (the largest d_head_list[i] + d_n_neigh[i]) — with `average` the scratch keeps one double per
+ * list entry, and the two calls cannot see the size of either array: size the scratch again whenever the list grows.
+ * *d_partials: block sums of v_i (consumed as above); *d_c: c_i, averaged when `average` is set; *d_v (may be NULL): v_i.
+ * The same opt goes to both passes.  MTD_ERR_INVALID_ARGUMENT, before a device is touched, for a switch with c0 <= 0 or p == 0
+ * and for a gate without 0 <= n_lo < n_hi.  A scratch that is too small for the list is NOT detected (no size is passed): with `average`
+ * the pass would write beyond it. */
+size_t mtd_ql_local_scratch_doubles_opt(unsigned int n_particles, unsigned int lmax, size_t n_list_entries, const mtd_ql_local_options *opt);
+int mtd_ql_local_accumulate_opt(unsigned int n_particles, const void *d_postype, int dtype, const mtd_box *box, const unsigned int *d_head_list,
+                                const unsigned int *d_n_neigh, const unsigned int *d_nlist, double rcut, double ron, unsigned int lmax,
+                                unsigned int type, const double *Ql_ref, unsigned int n_global, double *d_scratch, const double **d_partials,
+                                unsigned int *n_partials, const double **d_c, const double **d_n, mtd_stream_t stream,
+                                const mtd_ql_local_options *opt, const double **d_v);
+int mtd_ql_local_forces_opt(unsigned int n_particles, const void *d_postype, void *d_force, int dtype, const mtd_box *box,
+                            const unsigned int *d_head_list, const unsigned int *d_n_neigh, const unsigned int *d_nlist, double rcut, double ron,
+                            unsigned int lmax, unsigned int type, const double *Ql_ref, unsigned int n_global, const double *d_scratch,
+                            const double *d_bias, double bias_host, mtd_stream_t stream, const mtd_ql_local_options *opt);
 
 /* ================================================================================================
  * Neighbour list of the stand-alone path (cell list, built on the device)

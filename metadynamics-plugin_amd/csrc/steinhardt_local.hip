@@ -46,6 +46,16 @@
 //   k_qll_forces     the same with R(k) and R(j) read per lane and (l, m) straight from memory: rows longer than 256 bytes (more
 //                    than 16 complex slots) whose tiles would not fit
 // Double precision throughout.
+//
+// Options (mtd_ql_local_options; definition and gradient in include/mtd_abi.h): per-particle transforms of the quantities above.
+//   switch, gate     v_i = g(n_i) h(c_i) in place of c_i.  Still two launches: the epilogue of k_qll_accumulate<QLL_TRANSFORM> forms c_i
+//                    first, scales the row with g h'(c_i), adds g'(n_i) h(c_i) to its (0, 0) slot and sums v_i; the force kernels are
+//                    the plain ones.  The plain instantiations sit behind template switches and keep their instruction streams.
+//   average          qbar_lm(i) = [q_lm(i) + sum_j f_ij q_lm(j)] / (1 + n_i): the value of i depends on its neighbours' rows and its
+//                    gradient on its second neighbours.  Four launches: k_qll_accumulate<QLL_AVERAGE> (n_i, the rows q(i)),
+//                    k_qll_average (gathers q(j): qbar, c_i, v_i, the rows B(i)), k_qll_backprop (gathers B(j) and q(j): the table row
+//                    C(k) / n_k with a_k folded in, and one double E_kj per list entry), then the force pass, which streams E beside
+//                    the list and adds it to the (0, 0) weight of the pair.  See the block above k_qll_average.
 #include "mtd_device.hpp"
 #include "steinhardt_device.hpp"
 
@@ -80,14 +90,71 @@ __device__ __forceinline__ double quad_sum(double v)
     return v;
     }
 
+// value of lane u of the quad in all four of its lanes
+template<int U> __device__ __forceinline__ double quad_bcast(const double v) { return dpp_move<U * 0x55>(v); }
+template<int U> __device__ __forceinline__ unsigned int quad_bcast(const unsigned int v)
+    {
+    return (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, U * 0x55, 0xf, 0xf, false);
+    }
+
+// ---- the per-particle transforms of the options: v_i = g(n_i) h(c_i) ------------------------------------------------------------
+struct QllOpt
+    {
+    int sw, gate;
+    unsigned int p;
+    double inv_c0, n_lo, inv_dn;                           // 1 / c0, n_lo, 1 / (n_hi - n_lo)
+    };
+
+enum { QLL_PLAIN = 0, QLL_TRANSFORM = 1, QLL_AVERAGE = 2 };
+
+// h = x^p / (1 + x^p), x = max(c, 0) / c0 (h = c without a switch); g = 3 t^2 - 2 t^3, t = clip((n - n_lo) / (n_hi - n_lo), 0, 1)
+// (g = 1 without a gate); and their derivatives.  x^(p - 1) by squaring: p is uniform, the loop is a scalar one.
+__device__ __forceinline__ void qll_transform(const QllOpt &o, const double c, const double n, double &h, double &dh, double &g, double &dg)
+    {
+    h = c;
+    dh = 1.0;
+    if (o.sw)
+        {
+        const double x = fmax(c, 0.0) * o.inv_c0;
+        double xp1 = 1.0, b = x;
+        for (unsigned int k = o.p - 1; k != 0; k >>= 1)
+            {
+            if (k & 1u) xp1 *= b;
+            b *= b;
+            }
+        const double xp = xp1 * x, den = 1.0 / (1.0 + xp);
+        h = xp * den;
+        dh = c >= 0.0 ? (double)o.p * xp1 * (den * den) * o.inv_c0 : 0.0;
+        if (!(xp < HUGE_VAL))                                // x^p beyond the range of a double: the limit, not inf * 0
+            {
+            h = 1.0;
+            dh = 0.0;
+            }
+        }
+    g = 1.0;
+    dg = 0.0;
+    if (o.gate)
+        {
+        const double t = fmin(fmax((n - o.n_lo) * o.inv_dn, 0.0), 1.0);
+        g = t * t * (3.0 - 2.0 * t);
+        dg = 6.0 * t * (1.0 - t) * o.inv_dn;
+        }
+    }
+
 // ---- pass 1: n_i, A_lm(i) -> c_i, table row, block sums of c_i ------------------------------------------------------------
-template<typename S4, int LMAX>
-__global__ __launch_bounds__(QLL_THREADS) void k_qll_accumulate(const QlArgs<LMAX> a, const QllLayout lay, const S4 *__restrict__ postype,
+// MODE  QLL_PLAIN      the variable without options, as described above
+//       QLL_TRANSFORM  switch and/or gate, no average: c_i is formed before the row is scaled; the row is g h'(c_i) times the plain one
+//                      with g'(n_i) h(c_i) added to its (0, 0) slot, v_i = g h is written and block-summed in place of c_i
+//       QLL_AVERAGE    writes n_i and the monic row S_lm(i) / n_i (q_lm = nrm(l, m) times it) for the two gather passes below, and
+//                      (block 0) the weight of every slot, wtab[off[l] + m] = Ql_ref[l] 4 pi / (2l + 1) (m > 0 ? 2 : 1) nrm(l, m)^2
+template<typename S4, int LMAX, int MODE>
+__global__ __launch_bounds__(QLL_THREADS) void k_qll_accumulate(const QlArgs<LMAX> a, const QllLayout lay, const QllOpt o, const S4 *__restrict__ postype,
                                                                 const unsigned int *__restrict__ head_list,
                                                                 const unsigned int *__restrict__ n_neigh,
                                                                 const unsigned int *__restrict__ nlist, double *__restrict__ n_out,
-                                                                double *__restrict__ c_out, double *__restrict__ rows,
-                                                                double *__restrict__ partials, const double *__restrict__ tab)
+                                                                double *__restrict__ c_out, double *__restrict__ v_out, double *__restrict__ rows,
+                                                                double *__restrict__ wtab, double *__restrict__ partials,
+                                                                const double *__restrict__ tab)
     {
     typedef QlTab<LMAX> T;
     __shared__ double s_c[QLL_PPB];
@@ -183,77 +250,169 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_accumulate(const QlArgs<LMA
         const bool write = q == 0 && i < a.N;
         double *__restrict__ row = rows + (size_t)(i < a.N ? i : 0) * lay.row_doubles;
         double c = 0.0, r00 = 0.0;
-#pragma unroll
-        for (int l = 0; l <= LMAX; ++l)
+        if constexpr (MODE == QLL_PLAIN)
             {
 #pragma unroll
-            for (int m = 0; m <= l; ++m)
+            for (int l = 0; l <= LMAX; ++l)
                 {
-                S[m][l].re = quad_sum(S[m][l].re);
-                if (m > 0) S[m][l].im = quad_sum(S[m][l].im);
-                }
-            if (lay.act & (1u << l))
-                {
-                const double gl = a.ql_ref[l] * (4.0 * M_PI / (2 * l + 1)) * inv_n2;
-                double sq = 0.0;
 #pragma unroll
                 for (int m = 0; m <= l; ++m)
                     {
-                    const double nr = tab[T::nrm(l, m)];
-                    const double w = (m > 0 ? 2.0 : 1.0) * (nr * nr);
-                    sq += w * (S[m][l].re * S[m][l].re + S[m][l].im * S[m][l].im);
-                    const double rr = 2.0 * gl * w;
-                    if (l == 0)
-                        r00 = rr * S[m][l].re;
-                    else if (write)
-                        {
-                        row[2 * (lay.off[l] + m)] = rr * S[m][l].re;
-                        row[2 * (lay.off[l] + m) + 1] = -(rr * S[m][l].im);
-                        }
+                    S[m][l].re = quad_sum(S[m][l].re);
+                    if (m > 0) S[m][l].im = quad_sum(S[m][l].im);
                     }
-                c += gl * sq;
+                if (lay.act & (1u << l))
+                    {
+                    const double gl = a.ql_ref[l] * (4.0 * M_PI / (2 * l + 1)) * inv_n2;
+                    double sq = 0.0;
+#pragma unroll
+                    for (int m = 0; m <= l; ++m)
+                        {
+                        const double nr = tab[T::nrm(l, m)];
+                        const double w = (m > 0 ? 2.0 : 1.0) * (nr * nr);
+                        sq += w * (S[m][l].re * S[m][l].re + S[m][l].im * S[m][l].im);
+                        const double rr = 2.0 * gl * w;
+                        if (l == 0)
+                            r00 = rr * S[m][l].re;
+                        else if (write)
+                            {
+                            row[2 * (lay.off[l] + m)] = rr * S[m][l].re;
+                            row[2 * (lay.off[l] + m) + 1] = -(rr * S[m][l].im);
+                            }
+                        }
+                    c += gl * sq;
+                    }
+                }
+            if (write)
+                {
+                row[0] = r00 - 2.0 * c * inv_n;
+                row[1] = 0.0;
+                n_out[i] = nsum;
+                c_out[i] = c;
                 }
             }
-        if (write)
+        else if constexpr (MODE == QLL_TRANSFORM)
             {
-            row[0] = r00 - 2.0 * c * inv_n;
-            row[1] = 0.0;
-            n_out[i] = nsum;
-            c_out[i] = c;
+            // c_i first: the row is scaled with g(n_i) h'(c_i)
+#pragma unroll
+            for (int l = 0; l <= LMAX; ++l)
+                if (lay.act & (1u << l))
+                    {
+                    const double gl = a.ql_ref[l] * (4.0 * M_PI / (2 * l + 1)) * inv_n2;
+                    double sq = 0.0;
+#pragma unroll
+                    for (int m = 0; m <= l; ++m)
+                        {
+                        S[m][l].re = quad_sum(S[m][l].re);
+                        if (m > 0) S[m][l].im = quad_sum(S[m][l].im);
+                        const double nr = tab[T::nrm(l, m)];
+                        sq += ((m > 0 ? 2.0 : 1.0) * (nr * nr)) * (S[m][l].re * S[m][l].re + S[m][l].im * S[m][l].im);
+                        }
+                    c += gl * sq;
+                    }
+            double h, dh, g, dg;
+            qll_transform(o, c, nsum, h, dh, g, dg);
+            const double gh = g * dh;
+#pragma unroll
+            for (int l = 0; l <= LMAX; ++l)
+                if (lay.act & (1u << l))
+                    {
+                    const double gl = a.ql_ref[l] * (4.0 * M_PI / (2 * l + 1)) * inv_n2;
+#pragma unroll
+                    for (int m = 0; m <= l; ++m)
+                        {
+                        const double nr = tab[T::nrm(l, m)];
+                        const double rr = gh * (2.0 * gl * ((m > 0 ? 2.0 : 1.0) * (nr * nr)));
+                        if (l == 0)
+                            r00 = rr * S[m][l].re;
+                        else if (write)
+                            {
+                            row[2 * (lay.off[l] + m)] = rr * S[m][l].re;
+                            row[2 * (lay.off[l] + m) + 1] = -(rr * S[m][l].im);
+                            }
+                        }
+                    }
+            if (write)
+                {
+                row[0] = r00 - gh * (2.0 * c * inv_n) + dg * h;
+                row[1] = 0.0;
+                n_out[i] = nsum;
+                c_out[i] = c;
+                v_out[i] = g * h;
+                }
+            c = g * h;                                                              // what the blocks sum
             }
-        // the chunk's sum of c_i: wave 0, fixed order
-        __syncthreads();
-        if (q == 0) s_c[p] = i < a.N ? c : 0.0;
-        __syncthreads();
-        if (tid < MTD_WAVE) block_c += wave_sum(s_c[tid]);
+        else
+            {
+            if (write)
+                {
+                row[0] = 0.0;
+                row[1] = 0.0;
+                n_out[i] = nsum;
+                }
+#pragma unroll
+            for (int l = 0; l <= LMAX; ++l)
+                if (lay.act & (1u << l))
+                    {
+#pragma unroll
+                    for (int m = 0; m <= l; ++m)
+                        {
+                        S[m][l].re = quad_sum(S[m][l].re);
+                        if (m > 0) S[m][l].im = quad_sum(S[m][l].im);
+                        if (write)
+                            {
+                            row[2 * (lay.off[l] + m)] = S[m][l].re * inv_n;
+                            row[2 * (lay.off[l] + m) + 1] = m > 0 ? S[m][l].im * inv_n : 0.0;
+                            }
+                        if (chunk == 0 && tid == 0)
+                            {
+                            const double nr = tab[T::nrm(l, m)];
+                            wtab[lay.off[l] + m] = a.ql_ref[l] * (4.0 * M_PI / (2 * l + 1)) * ((m > 0 ? 2.0 : 1.0) * (nr * nr));
+                            }
+                        }
+                    }
+            if (chunk == 0 && tid == 0 && !(lay.act & 1u)) wtab[0] = 0.0;
+            }
+        if constexpr (MODE != QLL_AVERAGE)
+            {
+            // the chunk's sum of c_i (v_i with a switch or a gate): wave 0, fixed order
+            __syncthreads();
+            if (q == 0) s_c[p] = i < a.N ? c : 0.0;
+            __syncthreads();
+            if (tid < MTD_WAVE) block_c += wave_sum(s_c[tid]);
+            }
         }
+    if constexpr (MODE == QLL_AVERAGE) return;                                      // k_qll_average sums the v_i
     if (tid == 0) partials[blockIdx.x] = block_c;
     }
 
 // ---- pass 2: forces, gathered --------------------------------------------------------------------------------------------
-struct QllPairWeights
+// AVG: the pair's own scalar E_kj (k_qll_backprop) joins the (0, 0) weight, the coefficient of grad f
+template<bool AVG> struct QllPairWeights
     {
     const double *__restrict__ rk;
     const double *__restrict__ rj;
     const QllLayout &lay;
+    double e;
     __device__ __forceinline__ cplx operator()(const int l, const int m, const int) const
         {
         const unsigned int s = 2 * (lay.off[l] + m);
         const double2 wk = *reinterpret_cast<const double2 *>(rk + s), wj = *reinterpret_cast<const double2 *>(rj + s);
         if (l & 1) return {wk.x - wj.x, wk.y - wj.y};
+        if (AVG && l == 0) return {wk.x + wj.x + e, wk.y + wj.y};
         return {wk.x + wj.x, wk.y + wj.y};
         }
     };
 
 template<int LMAX> constexpr int qll_force_waves() { return LMAX <= 4 ? 3 : (LMAX <= 6 ? 2 : 1); }
 
-template<typename S4, int LMAX>
+template<typename S4, int LMAX, bool AVG>
 __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_forces(const QlArgs<LMAX> a, const QllLayout lay, const S4 *__restrict__ postype,
                                                             const unsigned int *__restrict__ head_list,
                                                             const unsigned int *__restrict__ n_neigh,
                                                             const unsigned int *__restrict__ nlist, const double *__restrict__ rows,
                                                             S4 *__restrict__ force, const double *__restrict__ d_bias, const double bias_host,
-                                                            const double *__restrict__ tab)
+                                                            const double *__restrict__ tab, const double *__restrict__ epair)
     {
     typedef typename scalar4_traits<S4>::scalar scalar;
     const unsigned int tid = threadIdx.x, p = tid / QLL_G, q = tid % QLL_G;
@@ -281,6 +440,8 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
         unsigned int j1 = e + QLL_G < cnt ? nlist[start + e + QLL_G] : QLL_NONE;
         S4 pos0 = qll_zero<S4>();
         if (j0 < a.N) pos0 = postype[j0];
+        double e0 = 0.0;                                     // E of the entry in hand; the next one travels with the next position
+        if (AVG && e < cnt) e0 = epair[start + e];
 #pragma unroll 1
         for (; e < cnt; e += QLL_G)
             {
@@ -290,6 +451,8 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
             const unsigned int j2 = e + 2 * QLL_G < cnt ? nlist[start + e + 2 * QLL_G] : QLL_NONE;
             S4 pos1 = qll_zero<S4>();
             if (j1 < a.N) pos1 = postype[j1];
+            double e1 = 0.0;
+            if (AVG && e + QLL_G < cnt) e1 = epair[start + e + QLL_G];
             if (j0 < a.N && j0 != k)
                 {
                 const Particle pj = scalar4_traits<S4>::unpack(pos0);
@@ -299,7 +462,7 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
                 if ((unsigned int)pj.type == a.type && rsq <= a.rcutsq)
                     {
                     double fpx, fpy, fpz;
-                    ql_pair_force<LMAX>(a, tab_k, QllPairWeights{rk, rows + (size_t)j0 * lay.row_doubles, lay}, act, dx, dy, dz, rsq, fpx, fpy, fpz);
+                    ql_pair_force<LMAX>(a, tab_k, QllPairWeights<AVG>{rk, rows + (size_t)j0 * lay.row_doubles, lay, e0}, act, dx, dy, dz, rsq, fpx, fpy, fpz);
                     Fx += fpx;
                     Fy += fpy;
                     Fz += fpz;
@@ -308,6 +471,7 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
             j0 = j1;
             j1 = j2;
             pos0 = pos1;
+            if (AVG) e0 = e1;
             }
         Fx = quad_sum(Fx);
         Fy = quad_sum(Fy);
@@ -334,27 +498,30 @@ __device__ __forceinline__ void qll_wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
 
-struct QllTileWeights
+template<bool AVG> struct QllTileWeights
     {
     const double2 *tk;                                     // LDS: the row of this lane's particle
     const double2 *tj;                                     // LDS: the row of this lane's neighbour
     const QllLayout &lay;
+    double e;
     __device__ __forceinline__ cplx operator()(const int l, const int m, const int) const
         {
         const unsigned int s = lay.off[l] + m;
         const double2 wk = tk[s], wj = tj[s];
         if (l & 1) return {wk.x - wj.x, wk.y - wj.y};
+        if (AVG && l == 0) return {wk.x + wj.x + e, wk.y + wj.y};
         return {wk.x + wj.x, wk.y + wj.y};
         }
     };
 
-template<typename S4, int LMAX>
+template<typename S4, int LMAX, bool AVG>
 __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_forces_tile(const QlArgs<LMAX> a, const QllLayout lay, const S4 *__restrict__ postype,
                                                             const unsigned int *__restrict__ head_list,
                                                             const unsigned int *__restrict__ n_neigh,
                                                             const unsigned int *__restrict__ nlist, const double *__restrict__ rows,
                                                             S4 *__restrict__ force, const double *__restrict__ d_bias, const double bias_host,
-                                                            const double *__restrict__ tab, const unsigned int ts /* tile row stride, 16-byte units */)
+                                                            const double *__restrict__ tab, const unsigned int ts /* tile row stride, 16-byte units */,
+                                                            const double *__restrict__ epair)
     {
     typedef typename scalar4_traits<S4>::scalar scalar;
     extern __shared__ double2 s_tiles[];
@@ -398,6 +565,8 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
         unsigned int j1 = e + QLL_G < cnt ? nlist[start + e + QLL_G] : QLL_NONE;
         S4 pos0 = qll_zero<S4>();
         if (j0 < a.N) pos0 = postype[j0];
+        double e0 = 0.0;                                     // E of the entry in hand; the next one travels with the next position
+        if (AVG && e < cnt) e0 = epair[start + e];
 #pragma unroll 1
         while (__ballot(e < cnt) != 0ull)
             {
@@ -407,6 +576,8 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
             const unsigned int j2 = e + 2 * QLL_G < cnt ? nlist[start + e + 2 * QLL_G] : QLL_NONE;
             S4 pos1 = qll_zero<S4>();
             if (j1 < a.N) pos1 = postype[j1];
+            double e1 = 0.0;
+            if (AVG && e + QLL_G < cnt) e1 = epair[start + e + QLL_G];
             const Particle pj = scalar4_traits<S4>::unpack(pos0);
             double dx = pk.x - pj.x, dy = pk.y - pj.y, dz = pk.z - pj.z;
             min_image(a, dx, dy, dz);
@@ -442,7 +613,7 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
                 if (visit)
                     {
                     double fpx, fpy, fpz;
-                    ql_pair_force<LMAX>(a, tab_k, QllTileWeights{tile_k + (lane / QLL_G) * ts, tile_j + lane * ts, lay}, act, dx, dy, dz, rsq, fpx, fpy, fpz);
+                    ql_pair_force<LMAX>(a, tab_k, QllTileWeights<AVG>{tile_k + (lane / QLL_G) * ts, tile_j + lane * ts, lay, e0}, act, dx, dy, dz, rsq, fpx, fpy, fpz);
                     Fx += fpx;
                     Fy += fpy;
                     Fz += fpz;
@@ -452,6 +623,7 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
             j0 = j1;
             j1 = j2;
             pos0 = pos1;
+            if (AVG) e0 = e1;
             e += QLL_G;
             }
         Fx = quad_sum(Fx);
@@ -462,22 +634,287 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
         }
     }
 
-template<typename S4, int LMAX>
+// ---- the averaged variable: two gather passes between pass 1 and the force pass ---------------------------------------------------
+// Rows here are the MONIC ones of pass 1, qm_c(i) = S_lm(i) / n_i per slot c = off[l] + m (q_lm = nrm(l, m) qm), and the slot weights
+// w_c = Ql_ref[l] 4 pi / (2l + 1) (m > 0 ? 2 : 1) nrm(l, m)^2 carry everything that depends on (l, m):
+//   k_qll_average   qbar_c(i) = [qm_c(i) + sum_j f_ij qm_c(j)] / (1 + n_i),  c_i = sum_c w_c |qbar_c(i)|^2,  v_i = g(n_i) h(c_i),
+//                   Bm_c(i) = g h'(c_i) 2 w_c conj(qbar_c(i)) / (1 + n_i)    (sum_c Re Bm_c qm_c = Re sum_lm B_lm q_lm of the header),
+//                   a0_i = g'(n_i) h(c_i) - g h' 2 c_i / (1 + n_i),  block sums of v_i
+//   k_qll_backprop  Cm_c(k) = Bm_c(k) + sum_i f_ik Bm_c(i);  the table row of the force pass R_c(k) = Cm_c(k) / n_k with
+//                   a_k = a0_k - sum_c Re Cm_c(k) qm_c(k) / n_k added to slot 0;  per list entry E_kj = sum_c Re[Bm_c(k) qm_c(j) + Bm_c(j) qm_c(k)]
+// Gather pattern: a quad still owns one central particle and its lanes still take entries q, q + 4, ... of the row for
+// the pair geometry (same look-ahead), but the ROWS are split by slot: lane q holds slots q, q + 4, ... of its particle.  Each of the
+// quad's four entries is handed round with a DPP quad broadcast (index and f), and the four lanes read 64 consecutive bytes of that
+// neighbour's row: sixteen rows per wave instruction, whole 64-byte segments, no LDS, and the sums stay in registers in list order.
+// Rows longer than QLL_GV x 64 bytes are taken in windows of QLL_GV x 4 slots, the list walked once per window.  Entries that do not
+// count (beyond r_cut, other type, self, j >= N) read the particle's own row with f = 0: the loads need no branch.
+constexpr unsigned int QLL_GV = 4;                                  // 16-byte slots per lane and window: one window up to 256-byte rows
+
+template<typename S4>
+__global__ __launch_bounds__(QLL_THREADS) void k_qll_average(const QlArgs<12> a, const QllOpt o, const unsigned int rs16, const S4 *__restrict__ postype,
+                                                             const unsigned int *__restrict__ head_list, const unsigned int *__restrict__ n_neigh,
+                                                             const unsigned int *__restrict__ nlist, const double *__restrict__ n_in,
+                                                             const double2 *__restrict__ qrows, const double *__restrict__ wtab,
+                                                             double2 *brows, double *__restrict__ c_out, double *__restrict__ v_out,
+                                                             double *__restrict__ a0_out, double *__restrict__ partials, const double *__restrict__ tab)
+    {
+    __shared__ double s_c[QLL_PPB];
+    const unsigned int tid = threadIdx.x, p = tid / QLL_G, q = tid % QLL_G;
+    const unsigned int n_chunks = (a.N + QLL_PPB - 1) / QLL_PPB;
+    double block_v = 0.0;
+    for (unsigned int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
+        {
+        const unsigned int i = chunk * QLL_PPB + p;
+        const unsigned int ii = i < a.N ? i : 0;
+        Particle pi = {0.0, 0.0, 0.0, -1};
+        unsigned int start = 0, cnt = 0;
+        double ni = 0.0;
+        if (i < a.N)
+            {
+            pi = scalar4_traits<S4>::load(postype, i);
+            ni = n_in[i];
+            if ((unsigned int)pi.type == a.type)
+                {
+                start = head_list[i];
+                cnt = n_neigh[i];
+                }
+            }
+        const double inv_1n = 1.0 / (1.0 + ni);
+        double csum = 0.0;
+        for (unsigned int w0 = 0; w0 < rs16; w0 += QLL_G * QLL_GV)
+            {
+            unsigned int cs[QLL_GV];                                                 // this lane's slots, clamped into the row
+            double2 acc[QLL_GV];
+#pragma unroll
+            for (unsigned int v = 0; v < QLL_GV; ++v)
+                {
+                const unsigned int c = w0 + QLL_G * v + q;
+                cs[v] = c < rs16 ? c : rs16 - 1;
+                acc[v] = qrows[(size_t)ii * rs16 + cs[v]];
+                }
+            unsigned int e = q;
+            unsigned int j0 = e < cnt ? nlist[start + e] : QLL_NONE;
+            unsigned int j1 = e + QLL_G < cnt ? nlist[start + e + QLL_G] : QLL_NONE;
+            S4 pos0 = qll_zero<S4>();
+            if (j0 < a.N) pos0 = postype[j0];
+#pragma unroll 1
+            for (unsigned int eb = 0; eb < cnt; eb += QLL_G, e += QLL_G)            // cnt is the quad's: its four lanes stay together
+                {
+                unsigned int tab_shift = 0;
+                asm volatile("" : "+s"(tab_shift));                 // a zero the compiler cannot see through: the table loads stay in the loop
+                const double *__restrict__ tab_k = tab + tab_shift;
+                const unsigned int j2 = e + 2 * QLL_G < cnt ? nlist[start + e + 2 * QLL_G] : QLL_NONE;
+                S4 pos1 = qll_zero<S4>();
+                if (j1 < a.N) pos1 = postype[j1];
+                double f = 0.0;
+                unsigned int jv = ii;
+                if (j0 < a.N && j0 != i)
+                    {
+                    const Particle pj = scalar4_traits<S4>::unpack(pos0);
+                    double dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
+                    min_image(a, dx, dy, dz);
+                    const double rsq = dx * dx + dy * dy + dz * dz;
+                    if ((unsigned int)pj.type == a.type && rsq <= a.rcutsq)
+                        {
+                        double fprime_divr;
+                        smoothing_tab<12>(a, tab_k, rsq, rsqrt(rsq), f, fprime_divr);
+                        jv = j0;
+                        }
+                    }
+                const unsigned int ju[QLL_G] = {quad_bcast<0>(jv), quad_bcast<1>(jv), quad_bcast<2>(jv), quad_bcast<3>(jv)};
+                const double fu[QLL_G] = {quad_bcast<0>(f), quad_bcast<1>(f), quad_bcast<2>(f), quad_bcast<3>(f)};
+#pragma unroll
+                for (unsigned int u = 0; u < QLL_G; ++u)
+#pragma unroll
+                    for (unsigned int v = 0; v < QLL_GV; ++v)
+                        {
+                        const double2 r = qrows[(size_t)ju[u] * rs16 + cs[v]];
+                        acc[v].x += fu[u] * r.x;
+                        acc[v].y += fu[u] * r.y;
+                        }
+                j0 = j1;
+                j1 = j2;
+                pos0 = pos1;
+                }
+            // this window of qbar: its share of c_i, and 2 w conj(qbar) / (1 + n) parked in the B row until h'(c_i) is known
+#pragma unroll
+            for (unsigned int v = 0; v < QLL_GV; ++v)
+                {
+                const unsigned int c = w0 + QLL_G * v + q;
+                if (c < rs16)
+                    {
+                    const double w = wtab[c];
+                    const double qx = acc[v].x * inv_1n, qy = acc[v].y * inv_1n;
+                    csum += w * (qx * qx + qy * qy);
+                    if (i < a.N) brows[(size_t)i * rs16 + c] = make_double2(2.0 * w * inv_1n * qx, -(2.0 * w * inv_1n * qy));
+                    }
+                }
+            }
+        const double c = quad_sum(csum);
+        double h, dh, g, dg;
+        qll_transform(o, c, ni, h, dh, g, dg);
+        const double gh = g * dh;
+        for (unsigned int cc = q; cc < rs16; cc += QLL_G)                           // the lane scales what it wrote itself
+            if (i < a.N)
+                {
+                const double2 b = brows[(size_t)i * rs16 + cc];
+                brows[(size_t)i * rs16 + cc] = make_double2(gh * b.x, gh * b.y);
+                }
+        if (q == 0 && i < a.N)
+            {
+            c_out[i] = c;
+            v_out[i] = g * h;
+            a0_out[i] = dg * h - gh * (2.0 * c * inv_1n);
+            }
+        // the chunk's sum of v_i: wave 0, fixed order
+        __syncthreads();
+        if (q == 0) s_c[p] = i < a.N ? g * h : 0.0;
+        __syncthreads();
+        if (tid < MTD_WAVE) block_v += wave_sum(s_c[tid]);
+        }
+    if (tid == 0) partials[blockIdx.x] = block_v;
+    }
+
+template<typename S4>
+__global__ __launch_bounds__(QLL_THREADS) void k_qll_backprop(const QlArgs<12> a, const unsigned int rs16, const S4 *__restrict__ postype,
+                                                              const unsigned int *__restrict__ head_list, const unsigned int *__restrict__ n_neigh,
+                                                              const unsigned int *__restrict__ nlist, const double *__restrict__ n_in,
+                                                              const double *__restrict__ a0_in, const double2 *__restrict__ qrows,
+                                                              const double2 *__restrict__ brows, double2 *__restrict__ rows, double *epair,
+                                                              const double *__restrict__ tab)
+    {
+    const unsigned int tid = threadIdx.x, p = tid / QLL_G, q = tid % QLL_G;
+    const unsigned int n_chunks = (a.N + QLL_PPB - 1) / QLL_PPB;
+    for (unsigned int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
+        {
+        const unsigned int k = chunk * QLL_PPB + p;
+        const unsigned int kk = k < a.N ? k : 0;
+        Particle pk = {0.0, 0.0, 0.0, -1};
+        unsigned int start = 0, cnt = 0;
+        double nk = 0.0, a0 = 0.0;
+        if (k < a.N)
+            {
+            pk = scalar4_traits<S4>::load(postype, k);
+            nk = n_in[k];
+            a0 = a0_in[k];
+            if ((unsigned int)pk.type == a.type)
+                {
+                start = head_list[k];
+                cnt = n_neigh[k];
+                }
+            }
+        const double inv_n = nk > 0.0 ? 1.0 / nk : 0.0;
+        double cq = 0.0, r00 = 0.0;
+        for (unsigned int w0 = 0; w0 < rs16; w0 += QLL_G * QLL_GV)
+            {
+            unsigned int cs[QLL_GV];
+            double2 acc[QLL_GV], bk[QLL_GV], qk[QLL_GV];
+#pragma unroll
+            for (unsigned int v = 0; v < QLL_GV; ++v)
+                {
+                const unsigned int c = w0 + QLL_G * v + q;
+                cs[v] = c < rs16 ? c : rs16 - 1;
+                bk[v] = brows[(size_t)kk * rs16 + cs[v]];
+                qk[v] = qrows[(size_t)kk * rs16 + cs[v]];
+                if (c >= rs16) bk[v] = qk[v] = make_double2(0.0, 0.0);              // a slot past the row adds nothing to E
+                acc[v] = bk[v];
+                }
+            unsigned int e = q;
+            unsigned int j0 = e < cnt ? nlist[start + e] : QLL_NONE;
+            unsigned int j1 = e + QLL_G < cnt ? nlist[start + e + QLL_G] : QLL_NONE;
+            S4 pos0 = qll_zero<S4>();
+            if (j0 < a.N) pos0 = postype[j0];
+#pragma unroll 1
+            for (unsigned int eb = 0; eb < cnt; eb += QLL_G, e += QLL_G)
+                {
+                unsigned int tab_shift = 0;
+                asm volatile("" : "+s"(tab_shift));                 // a zero the compiler cannot see through: the table loads stay in the loop
+                const double *__restrict__ tab_k = tab + tab_shift;
+                const unsigned int j2 = e + 2 * QLL_G < cnt ? nlist[start + e + 2 * QLL_G] : QLL_NONE;
+                S4 pos1 = qll_zero<S4>();
+                if (j1 < a.N) pos1 = postype[j1];
+                double f = 0.0;
+                unsigned int jv = kk;
+                bool visit = false;
+                if (j0 < a.N && j0 != k)
+                    {
+                    const Particle pj = scalar4_traits<S4>::unpack(pos0);
+                    double dx = pk.x - pj.x, dy = pk.y - pj.y, dz = pk.z - pj.z;
+                    min_image(a, dx, dy, dz);
+                    const double rsq = dx * dx + dy * dy + dz * dz;
+                    if ((unsigned int)pj.type == a.type && rsq <= a.rcutsq)
+                        {
+                        double fprime_divr;
+                        smoothing_tab<12>(a, tab_k, rsq, rsqrt(rsq), f, fprime_divr);
+                        jv = j0;
+                        visit = true;
+                        }
+                    }
+                const unsigned int ju[QLL_G] = {quad_bcast<0>(jv), quad_bcast<1>(jv), quad_bcast<2>(jv), quad_bcast<3>(jv)};
+                const double fu[QLL_G] = {quad_bcast<0>(f), quad_bcast<1>(f), quad_bcast<2>(f), quad_bcast<3>(f)};
+                double mine = 0.0;
+#pragma unroll
+                for (unsigned int u = 0; u < QLL_G; ++u)
+                    {
+                    double ee = 0.0;
+#pragma unroll
+                    for (unsigned int v = 0; v < QLL_GV; ++v)
+                        {
+                        const double2 bj = brows[(size_t)ju[u] * rs16 + cs[v]], qj = qrows[(size_t)ju[u] * rs16 + cs[v]];
+                        acc[v].x += fu[u] * bj.x;
+                        acc[v].y += fu[u] * bj.y;
+                        ee += (bk[v].x * qj.x - bk[v].y * qj.y) + (bj.x * qk[v].x - bj.y * qk[v].y);
+                        }
+                    ee = quad_sum(ee);
+                    if (q == u) mine = ee;
+                    }
+                if (e < cnt)
+                    {
+                    double val = visit ? mine : 0.0;
+                    if (w0 > 0) val += epair[start + e];                             // the lane adds to what it wrote in the last window
+                    epair[start + e] = val;
+                    }
+                j0 = j1;
+                j1 = j2;
+                pos0 = pos1;
+                }
+            // Cm of this window: its share of sum Re Cm qm, and the row of the force pass
+#pragma unroll
+            for (unsigned int v = 0; v < QLL_GV; ++v)
+                {
+                const unsigned int c = w0 + QLL_G * v + q;
+                if (c < rs16)
+                    {
+                    cq += acc[v].x * qk[v].x - acc[v].y * qk[v].y;
+                    if (c == 0)
+                        r00 = acc[v].x * inv_n;
+                    else if (k < a.N)
+                        rows[(size_t)k * rs16 + c] = make_double2(acc[v].x * inv_n, acc[v].y * inv_n);
+                    }
+                }
+            }
+        cq = quad_sum(cq);
+        if (q == 0 && k < a.N) rows[(size_t)k * rs16] = make_double2(r00 + (a0 - cq * inv_n), 0.0);
+        }
+    }
+
+template<typename S4, int LMAX, bool AVG>
 int qll_launch_forces(const QlArgs<LMAX> &a, const QllLayout &lay, const unsigned int blocks, const S4 *postype, const unsigned int *d_head,
                       const unsigned int *d_nneigh, const unsigned int *d_nlist, const double *rows, S4 *force, const double *d_bias,
-                      const double bias_host, const double *tab, hipStream_t s)
+                      const double bias_host, const double *tab, const double *epair, hipStream_t s)
     {
     const unsigned int rs16 = lay.row_doubles / 2;
     if (rs16 <= QLL_TILE_MAX16)
         {
         const unsigned int ts = rs16 | 1u;                  // odd: rows of a tile start in different banks
         const size_t bytes = (size_t)QLL_TILE_ROWS * ts * sizeof(double2);
-        MTD_HIP_TRY(hipFuncSetAttribute((const void *)k_qll_forces_tile<S4, LMAX>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        MTD_HIP_TRY(hipFuncSetAttribute((const void *)k_qll_forces_tile<S4, LMAX, AVG>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int)((size_t)QLL_TILE_ROWS * (QLL_TILE_MAX16 | 1u) * sizeof(double2))));
-        k_qll_forces_tile<S4, LMAX><<<blocks, QLL_THREADS, bytes, s>>>(a, lay, postype, d_head, d_nneigh, d_nlist, rows, force, d_bias, bias_host, tab, ts);
+        k_qll_forces_tile<S4, LMAX, AVG><<<blocks, QLL_THREADS, bytes, s>>>(a, lay, postype, d_head, d_nneigh, d_nlist, rows, force, d_bias, bias_host, tab, ts,
+                                                                            epair);
         }
     else
-        k_qll_forces<S4, LMAX><<<blocks, QLL_THREADS, 0, s>>>(a, lay, postype, d_head, d_nneigh, d_nlist, rows, force, d_bias, bias_host, tab);
+        k_qll_forces<S4, LMAX, AVG><<<blocks, QLL_THREADS, 0, s>>>(a, lay, postype, d_head, d_nneigh, d_nlist, rows, force, d_bias, bias_host, tab, epair);
     MTD_LAUNCH_CHECK();
     return MTD_SUCCESS;
     }
@@ -501,18 +938,54 @@ QllLayout qll_layout(const unsigned int lmax, const double *ql_ref)
     }
 
 // scratch: block sums [QLL_MAX_BLOCKS] | n_i [N] | c_i [N] (+ one double when N is odd) | rows [N][<= (lmax + 1)(lmax + 2)]
+// with a switch or a gate, behind these:  (one double when the above is an odd number) v_i [N] (+ one when N is odd)
+// with the average, behind those:         a0_i [N] (+ one) | slot weights [(lmax + 1)(lmax + 2) / 2] (+ one when odd)
+//                                         | monic rows [N][..] | B rows [N][..] | E [list entries]
 struct QllScratch
     {
-    double *partials, *n, *c, *rows;
+    double *partials, *n, *c, *rows, *v, *a0, *wtab, *qrows, *brows, *epair;
     };
 
-QllScratch qll_scratch(double *scratch, const unsigned int N)
+struct QllSizes
     {
+    size_t base, pad, v, a0, wtab, rows, total;
+    };
+
+int qll_mode(const mtd_ql_local_options *opt)
+    {
+    if (!opt) return QLL_PLAIN;
+    if (opt->average) return QLL_AVERAGE;
+    return opt->switch_on || opt->gate_on ? QLL_TRANSFORM : QLL_PLAIN;
+    }
+
+QllSizes qll_sizes(const size_t n, const unsigned int lmax, const size_t n_list_entries, const int mode)
+    {
+    QllSizes z;
+    z.rows = n * (size_t)(lmax + 1) * (lmax + 2);
+    z.base = (size_t)QLL_MAX_BLOCKS + 2 * n + (n & 1u) + z.rows;
+    z.pad = mode == QLL_PLAIN ? 0 : z.base & 1u;                // what the options add starts on a 16-byte boundary
+    z.v = mode == QLL_PLAIN ? 0 : n + (n & 1u);
+    z.a0 = mode == QLL_AVERAGE ? n + (n & 1u) : 0;
+    const size_t slots = (size_t)(lmax + 1) * (lmax + 2) / 2;
+    z.wtab = mode == QLL_AVERAGE ? slots + (slots & 1u) : 0;
+    z.total = z.base + z.pad + z.v + z.a0 + z.wtab + (mode == QLL_AVERAGE ? 2 * z.rows + n_list_entries : 0);
+    return z;
+    }
+
+QllScratch qll_scratch(double *scratch, const unsigned int N, const unsigned int lmax, const int mode)
+    {
+    const QllSizes z = qll_sizes(N, lmax, 0, mode);
     QllScratch s;
     s.partials = scratch;
     s.n = scratch + QLL_MAX_BLOCKS;
     s.c = s.n + N;
     s.rows = s.c + N + (N & 1u);
+    s.v = mode == QLL_PLAIN ? s.c : scratch + z.base + z.pad;
+    s.a0 = scratch + z.base + z.pad + z.v;
+    s.wtab = s.a0 + z.a0;
+    s.qrows = s.wtab + z.wtab;
+    s.brows = s.qrows + z.rows;
+    s.epair = s.brows + z.rows;
     return s;
     }
 
@@ -523,25 +996,69 @@ unsigned int qll_blocks(const unsigned int N)
     return b > QLL_MAX_BLOCKS ? QLL_MAX_BLOCKS : b;
     }
 
+QllOpt qll_opt(const mtd_ql_local_options *opt)
+    {
+    QllOpt o;
+    std::memset(&o, 0, sizeof(o));
+    if (!opt) return o;
+    o.sw = opt->switch_on != 0;
+    o.gate = opt->gate_on != 0;
+    o.p = o.sw ? opt->p : 1;
+    o.inv_c0 = o.sw ? 1.0 / opt->c0 : 0.0;
+    o.n_lo = o.gate ? opt->n_lo : 0.0;
+    o.inv_dn = o.gate ? 1.0 / (opt->n_hi - opt->n_lo) : 0.0;
+    return o;
+    }
+
+template<typename S4, int LMAX>
+int qll_accumulate_typed(const QlArgs<LMAX> &a, const QlArgs<12> &a12, const QllLayout &lay, const QllOpt &o, const int mode, const unsigned int blocks,
+                         const S4 *postype, const unsigned int *d_head, const unsigned int *d_nneigh, const unsigned int *d_nlist,
+                         const QllScratch &sc, const double *tab, hipStream_t s)
+    {
+    if (mode == QLL_PLAIN)
+        k_qll_accumulate<S4, LMAX, QLL_PLAIN><<<blocks, QLL_THREADS, 0, s>>>(a, lay, o, postype, d_head, d_nneigh, d_nlist, sc.n, sc.c, sc.v, sc.rows, sc.wtab,
+                                                                              sc.partials, tab);
+    else if (mode == QLL_TRANSFORM)
+        k_qll_accumulate<S4, LMAX, QLL_TRANSFORM><<<blocks, QLL_THREADS, 0, s>>>(a, lay, o, postype, d_head, d_nneigh, d_nlist, sc.n, sc.c, sc.v, sc.rows,
+                                                                                  sc.wtab, sc.partials, tab);
+    else
+        {
+        const unsigned int rs16 = lay.row_doubles / 2;
+        k_qll_accumulate<S4, LMAX, QLL_AVERAGE><<<blocks, QLL_THREADS, 0, s>>>(a, lay, o, postype, d_head, d_nneigh, d_nlist, sc.n, sc.c, sc.v, sc.qrows,
+                                                                                sc.wtab, sc.partials, tab);
+        MTD_LAUNCH_CHECK();
+        k_qll_average<S4><<<blocks, QLL_THREADS, 0, s>>>(a12, o, rs16, postype, d_head, d_nneigh, d_nlist, sc.n, (const double2 *)sc.qrows, sc.wtab,
+                                                          (double2 *)sc.brows, sc.c, sc.v, sc.a0, sc.partials, tab);
+        MTD_LAUNCH_CHECK();
+        k_qll_backprop<S4><<<blocks, QLL_THREADS, 0, s>>>(a12, rs16, postype, d_head, d_nneigh, d_nlist, sc.n, sc.a0, (const double2 *)sc.qrows,
+                                                           (const double2 *)sc.brows, (double2 *)sc.rows, sc.epair, tab);
+        }
+    MTD_LAUNCH_CHECK();
+    return MTD_SUCCESS;
+    }
+
 template<int LMAX>
 int qll_accumulate_impl(unsigned int N, const void *d_postype, int dtype, const mtd_box *box, const unsigned int *d_head, const unsigned int *d_nneigh,
                         const unsigned int *d_nlist, double rcut, double ron, unsigned int lmax, unsigned int type, const double *ql_ref,
-                        unsigned int n_global, const QllScratch &sc, unsigned int *n_partials, hipStream_t s)
+                        unsigned int n_global, const QllScratch &sc, const mtd_ql_local_options *opt, unsigned int *n_partials, hipStream_t s)
     {
     QlArgs<LMAX> a;
     int rc = fill_args<LMAX>(a, N, box, rcut, ron, lmax, type, ql_ref, n_global, 0);
     if (rc) return rc;
-    const double *tab = ql_device_table<LMAX>(s, rc);
+    QlArgs<12> a12;                                              // the gather passes need the box and the window only: one instantiation
+    rc = fill_args<12>(a12, N, box, rcut, ron, lmax, type, ql_ref, n_global, 0);
+    if (rc) return rc;
+    const double *tab = ql_device_table<LMAX>(s, rc);            // (the smoothing coefficients sit at the same place for every LMAX)
     if (rc) return rc;
     const QllLayout lay = qll_layout(lmax, ql_ref);
     const unsigned int blocks = qll_blocks(N);
+    const QllOpt o = qll_opt(opt);
+    const int mode = qll_mode(opt);
     if (dtype == MTD_F32)
-        k_qll_accumulate<float4, LMAX><<<blocks, QLL_THREADS, 0, s>>>(a, lay, (const float4 *)d_postype, d_head, d_nneigh, d_nlist, sc.n, sc.c, sc.rows,
-                                                                        sc.partials, tab);
+        rc = qll_accumulate_typed<float4, LMAX>(a, a12, lay, o, mode, blocks, (const float4 *)d_postype, d_head, d_nneigh, d_nlist, sc, tab, s);
     else
-        k_qll_accumulate<double4, LMAX><<<blocks, QLL_THREADS, 0, s>>>(a, lay, (const double4 *)d_postype, d_head, d_nneigh, d_nlist, sc.n, sc.c, sc.rows,
-                                                                         sc.partials, tab);
-    MTD_LAUNCH_CHECK();
+        rc = qll_accumulate_typed<double4, LMAX>(a, a12, lay, o, mode, blocks, (const double4 *)d_postype, d_head, d_nneigh, d_nlist, sc, tab, s);
+    if (rc) return rc;
     *n_partials = blocks;
     return MTD_SUCCESS;
     }
@@ -549,7 +1066,8 @@ int qll_accumulate_impl(unsigned int N, const void *d_postype, int dtype, const 
 template<int LMAX>
 int qll_forces_impl(unsigned int N, const void *d_postype, void *d_force, int dtype, const mtd_box *box, const unsigned int *d_head,
                     const unsigned int *d_nneigh, const unsigned int *d_nlist, double rcut, double ron, unsigned int lmax, unsigned int type,
-                    const double *ql_ref, unsigned int n_global, const QllScratch &sc, const double *d_bias, double bias_host, hipStream_t s)
+                    const double *ql_ref, unsigned int n_global, const QllScratch &sc, const bool avg, const double *d_bias, double bias_host,
+                    hipStream_t s)
     {
     QlArgs<LMAX> a;
     int rc = fill_args<LMAX>(a, N, box, rcut, ron, lmax, type, ql_ref, n_global, 0);
@@ -559,10 +1077,18 @@ int qll_forces_impl(unsigned int N, const void *d_postype, void *d_force, int dt
     const QllLayout lay = qll_layout(lmax, ql_ref);
     const unsigned int blocks = qll_blocks(N);
     if (dtype == MTD_F32)
-        return qll_launch_forces<float4, LMAX>(a, lay, blocks, (const float4 *)d_postype, d_head, d_nneigh, d_nlist, sc.rows, (float4 *)d_force, d_bias,
-                                               bias_host, tab, s);
-    return qll_launch_forces<double4, LMAX>(a, lay, blocks, (const double4 *)d_postype, d_head, d_nneigh, d_nlist, sc.rows, (double4 *)d_force, d_bias,
-                                            bias_host, tab, s);
+        {
+        if (avg)
+            return qll_launch_forces<float4, LMAX, true>(a, lay, blocks, (const float4 *)d_postype, d_head, d_nneigh, d_nlist, sc.rows, (float4 *)d_force,
+                                                         d_bias, bias_host, tab, sc.epair, s);
+        return qll_launch_forces<float4, LMAX, false>(a, lay, blocks, (const float4 *)d_postype, d_head, d_nneigh, d_nlist, sc.rows, (float4 *)d_force, d_bias,
+                                                      bias_host, tab, nullptr, s);
+        }
+    if (avg)
+        return qll_launch_forces<double4, LMAX, true>(a, lay, blocks, (const double4 *)d_postype, d_head, d_nneigh, d_nlist, sc.rows, (double4 *)d_force,
+                                                      d_bias, bias_host, tab, sc.epair, s);
+    return qll_launch_forces<double4, LMAX, false>(a, lay, blocks, (const double4 *)d_postype, d_head, d_nneigh, d_nlist, sc.rows, (double4 *)d_force, d_bias,
+                                                   bias_host, tab, nullptr, s);
     }
 
 // what both entry points refuse before a device is touched
@@ -579,14 +1105,30 @@ int qll_validate(unsigned int n_particles, const void *d_postype, int dtype, con
     return MTD_SUCCESS;
     }
 
+// the options: a switch needs c0 > 0 and p >= 1, a gate 0 <= n_lo < n_hi (NaN fails every comparison).
+// NOT checked, deliberately: a scratch sized for fewer list entries than the list holds.  Neither pass is told the size of the scratch
+// or the length of d_nlist (the entry points keep the argument lists of the plain ones), so it cannot be known here; the caller sizes the
+// scratch with mtd_ql_local_scratch_doubles_opt(N, lmax, length of d_nlist, opt), as SteinhardtLocal::computeCV does at every step.
+int qll_validate_options(const mtd_ql_local_options *opt)
+    {
+    if (!opt) return MTD_SUCCESS;
+    if (opt->switch_on && (!(opt->c0 > 0.0) || !std::isfinite(opt->c0) || opt->p == 0)) return MTD_ERR_INVALID_ARGUMENT;
+    if (opt->gate_on && (!(opt->n_lo >= 0.0) || !(opt->n_lo < opt->n_hi) || !std::isfinite(opt->n_hi))) return MTD_ERR_INVALID_ARGUMENT;
+    return MTD_SUCCESS;
+    }
+
 } // namespace
 
 extern "C" {
 
 size_t mtd_ql_local_scratch_doubles(unsigned int n_particles, unsigned int lmax)
     {
-    const size_t n = n_particles;
-    return (size_t)QLL_MAX_BLOCKS + 2 * n + (n & 1u) + n * (size_t)(lmax + 1) * (lmax + 2);
+    return mtd_ql_local_scratch_doubles_opt(n_particles, lmax, 0, nullptr);
+    }
+
+size_t mtd_ql_local_scratch_doubles_opt(unsigned int n_particles, unsigned int lmax, size_t n_list_entries, const mtd_ql_local_options *opt)
+    {
+    return qll_sizes(n_particles, lmax, n_list_entries, qll_mode(opt)).total;
     }
 
 int mtd_ql_local_accumulate(unsigned int n_particles, const void *d_postype, int dtype, const mtd_box *box, const unsigned int *d_head_list,
@@ -594,14 +1136,26 @@ int mtd_ql_local_accumulate(unsigned int n_particles, const void *d_postype, int
                             unsigned int type, const double *Ql_ref, unsigned int n_global, double *d_scratch, const double **d_partials,
                             unsigned int *n_partials, const double **d_c, const double **d_n, mtd_stream_t stream)
     {
+    return mtd_ql_local_accumulate_opt(n_particles, d_postype, dtype, box, d_head_list, d_n_neigh, d_nlist, rcut, ron, lmax, type, Ql_ref, n_global,
+                                       d_scratch, d_partials, n_partials, d_c, d_n, stream, nullptr, nullptr);
+    }
+
+int mtd_ql_local_accumulate_opt(unsigned int n_particles, const void *d_postype, int dtype, const mtd_box *box, const unsigned int *d_head_list,
+                                const unsigned int *d_n_neigh, const unsigned int *d_nlist, double rcut, double ron, unsigned int lmax,
+                                unsigned int type, const double *Ql_ref, unsigned int n_global, double *d_scratch, const double **d_partials,
+                                unsigned int *n_partials, const double **d_c, const double **d_n, mtd_stream_t stream,
+                                const mtd_ql_local_options *opt, const double **d_v)
+    {
     if (!d_partials || !n_partials) return MTD_ERR_INVALID_ARGUMENT;
     int rc = qll_validate(n_particles, d_postype, dtype, box, d_head_list, d_n_neigh, rcut, ron, lmax, Ql_ref, n_global, d_scratch);
     if (rc) return rc;
-    const QllScratch sc = qll_scratch(d_scratch, n_particles);
+    rc = qll_validate_options(opt);
+    if (rc) return rc;
+    const QllScratch sc = qll_scratch(d_scratch, n_particles, lmax, qll_mode(opt));
     hipStream_t s = (hipStream_t)stream;
     unsigned int n = 0;
 #define MTD_QLL_ACC(LM) qll_accumulate_impl<LM>(n_particles, d_postype, dtype, box, d_head_list, d_n_neigh, d_nlist, rcut, ron, lmax, type, Ql_ref, \
-                                                n_global, sc, &n, s)
+                                                n_global, sc, opt, &n, s)
     if (lmax <= 4)
         rc = MTD_QLL_ACC(4);
     else if (lmax <= 6)
@@ -616,6 +1170,7 @@ int mtd_ql_local_accumulate(unsigned int n_particles, const void *d_postype, int
     *n_partials = n;
     if (d_c) *d_c = sc.c;
     if (d_n) *d_n = sc.n;
+    if (d_v) *d_v = sc.v;
     return MTD_SUCCESS;
     }
 
@@ -624,14 +1179,27 @@ int mtd_ql_local_forces(unsigned int n_particles, const void *d_postype, void *d
                         unsigned int lmax, unsigned int type, const double *Ql_ref, unsigned int n_global, const double *d_scratch,
                         const double *d_bias, double bias_host, mtd_stream_t stream)
     {
+    return mtd_ql_local_forces_opt(n_particles, d_postype, d_force, dtype, box, d_head_list, d_n_neigh, d_nlist, rcut, ron, lmax, type, Ql_ref, n_global,
+                                   d_scratch, d_bias, bias_host, stream, nullptr);
+    }
+
+int mtd_ql_local_forces_opt(unsigned int n_particles, const void *d_postype, void *d_force, int dtype, const mtd_box *box,
+                            const unsigned int *d_head_list, const unsigned int *d_n_neigh, const unsigned int *d_nlist, double rcut, double ron,
+                            unsigned int lmax, unsigned int type, const double *Ql_ref, unsigned int n_global, const double *d_scratch,
+                            const double *d_bias, double bias_host, mtd_stream_t stream, const mtd_ql_local_options *opt)
+    {
     int rc = qll_validate(n_particles, d_postype, dtype, box, d_head_list, d_n_neigh, rcut, ron, lmax, Ql_ref, n_global, d_scratch);
+    if (rc) return rc;
+    rc = qll_validate_options(opt);
     if (rc) return rc;
     if (n_particles && !d_force) return MTD_ERR_INVALID_ARGUMENT;
     if (n_particles == 0) return MTD_SUCCESS;
-    const QllScratch sc = qll_scratch(const_cast<double *>(d_scratch), n_particles);
+    const int mode = qll_mode(opt);
+    const QllScratch sc = qll_scratch(const_cast<double *>(d_scratch), n_particles, lmax, mode);
+    const bool avg = mode == QLL_AVERAGE;
     hipStream_t s = (hipStream_t)stream;
 #define MTD_QLL_F(LM) qll_forces_impl<LM>(n_particles, d_postype, d_force, dtype, box, d_head_list, d_n_neigh, d_nlist, rcut, ron, lmax, type, Ql_ref, \
-                                          n_global, sc, d_bias, bias_host, s)
+                                          n_global, sc, avg, d_bias, bias_host, s)
     if (lmax <= 4) return MTD_QLL_F(4);
     if (lmax <= 6) return MTD_QLL_F(6);
     if (lmax <= 8) return MTD_QLL_F(8);

@@ -746,7 +746,8 @@ SteinhardtLocal::SteinhardtLocal(std::shared_ptr<SystemDefinition> sysdef, doubl
                                  std::shared_ptr<NeighborList> nlist, unsigned int type, const std::vector<double> &Ql_ref,
                                  const std::string &log_suffix)
     : CollectiveVariable(sysdef, "steinhardt_local" + log_suffix), m_rcut(rcut), m_ron(ron), m_lmax(lmax), m_nlist(nlist), m_type(type),
-      m_Ql_ref(Ql_ref), m_cv_last_updated(0), m_have_computed(false), m_d_partials(nullptr), m_d_c(nullptr), m_d_n(nullptr), m_n_partials(0)
+      m_Ql_ref(Ql_ref), m_cv_last_updated(0), m_have_computed(false), m_d_partials(nullptr), m_d_c(nullptr), m_d_n(nullptr), m_d_v(nullptr),
+      m_n_partials(0), m_opt()
     {
     if (Ql_ref.size() != lmax + 1) throw std::runtime_error("Error setting up local Steinhardt CV");
     if (lmax > 12) throw std::runtime_error("cv.steinhardt_local: lmax <= 12 in this build");
@@ -770,14 +771,62 @@ void SteinhardtLocal::computeCV(unsigned int timestep)
                                  "neighbour would have to be exchanged)");
     m_nlist->compute(timestep);                                      // a device-built list rebuilds here when particles have moved
     const mtd_box box = m_pdata->getBox().toMtd();
-    mtd_check(mtd_ql_local_accumulate(m_pdata->getN(), m_pdata->positionsPtr(), m_pdata->getDtype(), &box,
-                                      (const unsigned int *)m_nlist->getHeadList().data(), (const unsigned int *)m_nlist->getNNeighArray().data(),
-                                      (const unsigned int *)m_nlist->getNListArray().data(), m_rcut, m_ron, m_lmax, m_type, m_Ql_ref.data(),
-                                      m_pdata->getNGlobal(), (double *)m_scratch.data(), &m_d_partials, &m_n_partials, &m_d_c, &m_d_n,
-                                      m_exec_conf->getStream()),
-              "mtd_ql_local_accumulate");
+    // the averaged variable keeps one double per list entry: the scratch grows with the list and with the options (never shrinks)
+    const size_t need = sizeof(double) * mtd_ql_local_scratch_doubles_opt(m_pdata->getN(), m_lmax,
+                                                                          m_nlist->getNListArray().bytes() / sizeof(unsigned int), &m_opt);
+    if (need > m_scratch.bytes()) m_scratch.resize(need);
+    mtd_check(mtd_ql_local_accumulate_opt(m_pdata->getN(), m_pdata->positionsPtr(), m_pdata->getDtype(), &box,
+                                          (const unsigned int *)m_nlist->getHeadList().data(), (const unsigned int *)m_nlist->getNNeighArray().data(),
+                                          (const unsigned int *)m_nlist->getNListArray().data(), m_rcut, m_ron, m_lmax, m_type, m_Ql_ref.data(),
+                                          m_pdata->getNGlobal(), (double *)m_scratch.data(), &m_d_partials, &m_n_partials, &m_d_c, &m_d_n,
+                                          m_exec_conf->getStream(), &m_opt, &m_d_v),
+              "mtd_ql_local_accumulate_opt");
     m_have_computed = true;
     m_cv_last_updated = timestep;
+    }
+
+void SteinhardtLocal::optionsChanged()
+    {
+    m_have_computed = false;                                         // the table in the scratch belongs to the old options
+    }
+
+void SteinhardtLocal::setAverage(bool on)
+    {
+    m_opt.average = on ? 1 : 0;
+    optionsChanged();
+    }
+
+void SteinhardtLocal::setSwitch(double c0, unsigned int p)
+    {
+    if (!(c0 > 0.0) || !std::isfinite(c0) || p == 0) throw std::runtime_error("cv.steinhardt_local: a switch needs c0 > 0 and an integer p >= 1");
+    m_opt.switch_on = 1;
+    m_opt.c0 = c0;
+    m_opt.p = p;
+    optionsChanged();
+    }
+
+void SteinhardtLocal::clearSwitch()
+    {
+    m_opt.switch_on = 0;
+    m_opt.c0 = 0.0;
+    m_opt.p = 0;
+    optionsChanged();
+    }
+
+void SteinhardtLocal::setGate(double n_lo, double n_hi)
+    {
+    if (!(n_lo >= 0.0) || !(n_lo < n_hi) || !std::isfinite(n_hi)) throw std::runtime_error("cv.steinhardt_local: a gate needs 0 <= n_lo < n_hi");
+    m_opt.gate_on = 1;
+    m_opt.n_lo = n_lo;
+    m_opt.n_hi = n_hi;
+    optionsChanged();
+    }
+
+void SteinhardtLocal::clearGate()
+    {
+    m_opt.gate_on = 0;
+    m_opt.n_lo = m_opt.n_hi = 0.0;
+    optionsChanged();
     }
 
 void SteinhardtLocal::enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot)
@@ -805,11 +854,21 @@ void SteinhardtLocal::computeBiasForces(unsigned int timestep)
     if (!m_have_computed || m_cv_last_updated != timestep) computeCV(timestep);      // the table of THIS step's positions
     m_nlist->compute(timestep);
     const mtd_box box = m_pdata->getBox().toMtd();
-    mtd_check(mtd_ql_local_forces(m_pdata->getN(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &box,
-                                  (const unsigned int *)m_nlist->getHeadList().data(), (const unsigned int *)m_nlist->getNNeighArray().data(),
-                                  (const unsigned int *)m_nlist->getNListArray().data(), m_rcut, m_ron, m_lmax, m_type, m_Ql_ref.data(),
-                                  m_pdata->getNGlobal(), (const double *)m_scratch.data(), m_bias_device, m_bias, m_exec_conf->getStream()),
-              "mtd_ql_local_forces");
+    mtd_check(mtd_ql_local_forces_opt(m_pdata->getN(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &box,
+                                      (const unsigned int *)m_nlist->getHeadList().data(), (const unsigned int *)m_nlist->getNNeighArray().data(),
+                                      (const unsigned int *)m_nlist->getNListArray().data(), m_rcut, m_ron, m_lmax, m_type, m_Ql_ref.data(),
+                                      m_pdata->getNGlobal(), (const double *)m_scratch.data(), m_bias_device, m_bias, m_exec_conf->getStream(),
+                                      &m_opt),
+              "mtd_ql_local_forces_opt");
+    }
+
+std::vector<double> SteinhardtLocal::getSwitchedValues(unsigned int timestep)
+    {
+    computeCV(timestep);
+    m_exec_conf->sync();
+    std::vector<double> out(m_pdata->getN());
+    if (!out.empty()) hip_check(hipMemcpy(out.data(), m_d_v, sizeof(double) * out.size(), hipMemcpyDeviceToHost), "v_i read-back");
+    return out;
     }
 
 std::vector<double> SteinhardtLocal::getLocalValues(unsigned int timestep)

@@ -331,9 +331,17 @@ class SteinhardtLocal : public CollectiveVariable
         double getLogValue(const std::string &quantity, unsigned int timestep) override;
         std::vector<double> getLocalValues(unsigned int timestep);     //!< c_i of every local particle (0 for other types)
         std::vector<double> getCoordination(unsigned int timestep);    //!< n_i = sum_j f(r_ij)
+        //! the options of mtd_ql_local_options; every change invalidates the cached step
+        void setAverage(bool on);                                      //!< neighbour-averaged qbar_lm(i) in place of q_lm(i)
+        void setSwitch(double c0, unsigned int p);                     //!< h(c) = x^p / (1 + x^p), x = max(c, 0) / c0
+        void clearSwitch();
+        void setGate(double n_lo, double n_hi);                        //!< g(n) = smoothstep from n_lo to n_hi
+        void clearGate();
+        std::vector<double> getSwitchedValues(unsigned int timestep);  //!< v_i = g(n_i) h(c_i) (c_i without options)
 
     private:
         void computeCV(unsigned int timestep);
+        void optionsChanged();
         double m_rcut, m_ron;
         unsigned int m_lmax;
         std::shared_ptr<NeighborList> m_nlist;
@@ -342,8 +350,9 @@ class SteinhardtLocal : public CollectiveVariable
         unsigned int m_cv_last_updated;
         bool m_have_computed;
         DeviceBuffer m_scratch, m_sum;
-        const double *m_d_partials, *m_d_c, *m_d_n;
+        const double *m_d_partials, *m_d_c, *m_d_n, *m_d_v;
         unsigned int m_n_partials;
+        mtd_ql_local_options m_opt;
     };
 
 //! AspectRatio.h / AspectRatio.cc:5-130 — box-shape CV, external virial only

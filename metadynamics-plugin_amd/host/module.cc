@@ -333,7 +333,16 @@ PYBIND11_MODULE(_metadynamics, m)
         .def("getCoordination", [](SteinhardtLocal &cv, unsigned int timestep) {
             const std::vector<double> v = cv.getCoordination(timestep);
             return py::array_t<double>((ssize_t)v.size(), v.data());
-        });
+        })
+        .def("getSwitchedValues", [](SteinhardtLocal &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getSwitchedValues(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        })
+        .def("setAverage", &SteinhardtLocal::setAverage)
+        .def("setSwitch", &SteinhardtLocal::setSwitch)
+        .def("clearSwitch", &SteinhardtLocal::clearSwitch)
+        .def("setGate", &SteinhardtLocal::setGate)
+        .def("clearGate", &SteinhardtLocal::clearGate);
 
     py::class_<WellTemperedEnsemble, CollectiveVariable, std::shared_ptr<WellTemperedEnsemble>>(m, "WellTemperedEnsemble")
         .def(py::init<std::shared_ptr<SystemDefinition>, const std::string &>());

@@ -84,6 +84,23 @@ class LamellarSet(C.Structure):
         return s
 
 
+class QlLocalOptions(C.Structure):
+    """mtd_ql_local_options: all-zero is the plain variable; c0, p count with switch_on, n_lo, n_hi with gate_on"""
+    _fields_ = [("average", C.c_int), ("switch_on", C.c_int), ("c0", C.c_double), ("p", C.c_uint), ("gate_on", C.c_int),
+                ("n_lo", C.c_double), ("n_hi", C.c_double)]
+
+    @classmethod
+    def make(cls, average=False, switch=None, gate=None):
+        """switch: (c0, p) or None; gate: (n_lo, n_hi) or None"""
+        o = cls()
+        o.average = int(bool(average))
+        if switch is not None:
+            o.switch_on, o.c0, o.p = 1, float(switch[0]), int(switch[1])
+        if gate is not None:
+            o.gate_on, o.n_lo, o.n_hi = 1, float(gate[0]), float(gate[1])
+        return o
+
+
 _vp = C.c_void_p
 _dp = C.POINTER(C.c_double)
 _up = C.POINTER(C.c_uint)
@@ -206,6 +223,12 @@ _SIGNATURES = {
                                            _dp, C.c_uint, _vp, C.POINTER(_vp), _up, C.POINTER(_vp), C.POINTER(_vp), _vp]),
     "mtd_ql_local_forces": (C.c_int, [C.c_uint, _vp, _vp, C.c_int, C.POINTER(Box), _vp, _vp, _vp, C.c_double, C.c_double, C.c_uint, C.c_uint,
                                        _dp, C.c_uint, _vp, _vp, C.c_double, _vp]),
+    "mtd_ql_local_scratch_doubles_opt": (C.c_size_t, [C.c_uint, C.c_uint, C.c_size_t, C.POINTER(QlLocalOptions)]),
+    "mtd_ql_local_accumulate_opt": (C.c_int, [C.c_uint, _vp, C.c_int, C.POINTER(Box), _vp, _vp, _vp, C.c_double, C.c_double, C.c_uint, C.c_uint,
+                                               _dp, C.c_uint, _vp, C.POINTER(_vp), _up, C.POINTER(_vp), C.POINTER(_vp), _vp,
+                                               C.POINTER(QlLocalOptions), C.POINTER(_vp)]),
+    "mtd_ql_local_forces_opt": (C.c_int, [C.c_uint, _vp, _vp, C.c_int, C.POINTER(Box), _vp, _vp, _vp, C.c_double, C.c_double, C.c_uint, C.c_uint,
+                                           _dp, C.c_uint, _vp, _vp, C.c_double, _vp, C.POINTER(QlLocalOptions)]),
     "mtd_nlist_create": (C.c_int, [C.POINTER(_vp)]),
     "mtd_nlist_destroy": (C.c_int, [_vp]),
     "mtd_nlist_build": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp, C.c_int, C.POINTER(Box), C.c_double, C.c_int, C.c_int,

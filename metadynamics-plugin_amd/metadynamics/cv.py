@@ -214,11 +214,34 @@ class steinhardt(_collective_variable):
         return {(a, b): (self.r_cut if a == b == self.type else -1.0) for i, a in enumerate(names) for b in names[i:]}
 
 
-class steinhardt_local(_collective_variable):
+class _local_options(type):
+    """``cv.steinhardt_local(..., average=False, switch=None, gate=None)``: the three options are keyword arguments of the CALL.  They
+    are taken off here and applied to the finished object, so that ``__init__`` keeps the argument list of the variable without options,
+    which tests/test_ql_local_abi.py pins.  The price: ``inspect.signature(cv.steinhardt_local)`` and ``help()`` do not show the three
+    options, and subclasses inherit this metaclass.  Once that test may change, move the three keywords into ``__init__`` (ending with a
+    call of ``set_options``) and delete this class."""
+
+    def __call__(cls, *args, average=False, switch=None, gate=None, **kwargs):
+        obj = super().__call__(*args, **kwargs)
+        try:
+            obj.set_options(average=average, switch=switch, gate=gate)
+        except RuntimeError:
+            context.current.forces.remove(obj)                       # refused: the run must not find a half-made variable
+            raise
+        return obj
+
+
+class steinhardt_local(_collective_variable, metaclass=_local_options):
     """this build (no reference counterpart): the LOCAL Steinhardt order parameter.  The harmonics are summed over one particle's own
     neighbours, turned into the rotational invariant per particle and averaged:
     CV = (1 / N) sum_i sum_l Ql_ref[l] * q_l^2(i),  q_l^2(i) = 4 pi / (2l + 1) sum_m |sum_j f(r_ij) Y_lm(r_ij)|^2 / (sum_j f(r_ij))^2
-    over particles of one type within r_cut (smoothing and conventions of cv.steinhardt; not square-rooted).  Needs a full list."""
+    over particles of one type within r_cut (smoothing and conventions of cv.steinhardt; not square-rooted).  Needs a full list.
+
+    Options (keyword arguments of the call, include/mtd_abi.h "Local Steinhardt bond order"):
+    ``average=True``: the Lechner-Dellago neighbour average, qbar_lm(i) = [q_lm(i) + sum_j f_ij q_lm(j)] / (1 + n_i), before the invariant;
+    ``switch=dict(c0=..., p=...)``: h(c) = x^p / (1 + x^p), x = max(c, 0) / c0 per particle — CV * N is then the smooth number of solid-like
+    particles; ``gate=dict(n_lo=..., n_hi=...)``: a smoothstep in the coordination n_i that takes under-coordinated particles out.
+    CV = (1 / N) sum_i g(n_i) h(c_i)."""
 
     def __init__(self, r_cut, r_on, lmax, Ql_ref, nlist, type, name=None, sigma=1.0):
         suffix = ""
@@ -249,6 +272,31 @@ class steinhardt_local(_collective_variable):
     def get_coordination(self):
         """n_i = sum_j f(r_ij): the smoothed number of neighbours of every particle at the current time step"""
         return self.cpp_force.getCoordination(context.current.system.getCurrentTimeStep())
+
+    def get_switched(self):
+        """v_i = g(n_i) h(c_i) of every particle at the current time step: what the CV averages (c_i itself without options)"""
+        return self.cpp_force.getSwitchedValues(context.current.system.getCurrentTimeStep())
+
+    def set_options(self, average=False, switch=None, gate=None):
+        """set all three options (the defaults switch them off); takes effect with the next step"""
+        try:
+            sw = None if switch is None else (float(switch["c0"]), int(switch["p"]))
+            gt = None if gate is None else (float(gate["n_lo"]), float(gate["n_hi"]))
+            if sw is not None and (set(switch.keys()) != {"c0", "p"} or int(switch["p"]) != switch["p"] or not sw[0] > 0.0 or sw[1] < 1):
+                raise ValueError
+            if gt is not None and (set(gate.keys()) != {"n_lo", "n_hi"} or not 0.0 <= gt[0] < gt[1]):
+                raise ValueError
+            if sw is None:
+                self.cpp_force.clearSwitch()
+            else:
+                self.cpp_force.setSwitch(*sw)
+            if gt is None:
+                self.cpp_force.clearGate()
+            else:
+                self.cpp_force.setGate(*gt)
+            self.cpp_force.setAverage(bool(average))
+        except (TypeError, KeyError, ValueError, AttributeError, RuntimeError):
+            raise RuntimeError("Error creating collective variable.")
 
 
 class nlist_cell(object):

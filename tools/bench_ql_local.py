@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Developer tool: the config 5 snapshot of tools/bench_ql.py (256 000-particle noisy fcc crystal, lmax 6, degrees 4 and 6,
 r_cut 1.4, 512-point grid) with cv.steinhardt_local instead of the global variable; prints us/step.
-usage: tools/bench_ql_local.py [steps] [f32|f64] [--device-nlist]   (--device-nlist: cv.nlist_cell(device=True), r_buff 0.4)
+usage: tools/bench_ql_local.py [steps] [f32|f64] [--device-nlist] [--average] [--switch c0,p] [--gate lo,hi]
+(--device-nlist: cv.nlist_cell(device=True), r_buff 0.4; the other three: the options of cv.steinhardt_local, e.g. --average --switch 0.12,3)
 Run under rocprofv3 --kernel-trace --stats for the per-kernel table."""
 import os, sys, time
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -9,8 +10,17 @@ sys.path[:0] = [os.path.join(root, "metadynamics-plugin_amd"), os.path.join(root
 import numpy as np, torch
 import util
 from metadynamics import context, cv, integrate
-args = [a for a in sys.argv[1:] if not a.startswith("--")]
-device_nlist = "--device-nlist" in sys.argv[1:]
+argv = sys.argv[1:]
+options = {}
+for flag, keys, kinds in (("--switch", ("c0", "p"), (float, int)), ("--gate", ("n_lo", "n_hi"), (float, float))):
+    if flag in argv:
+        k = argv.index(flag)
+        options[flag[2:]] = {key: kind(v) for key, kind, v in zip(keys, kinds, argv[k + 1].split(","))}
+        del argv[k:k + 2]
+if "--average" in argv:
+    options["average"] = True
+args = [a for a in argv if not a.startswith("--")]
+device_nlist = "--device-nlist" in argv
 steps = int(args[0]) if len(args) > 0 else 100
 dtype = np.float32 if (len(args) > 1 and args[1] == "f32") else np.float64
 pos, L = util.fcc_lattice(40)
@@ -23,7 +33,7 @@ def build(lo, hi, sigma):
     meta = integrate.mode_metadynamics(dt=0.005, stride=1, mode="well_tempered", W=1.0, deltaT=7.0, T=1.0)
     nl = cv.nlist_cell(r_cut=1.4, device=device_nlist)
     entries = None if device_nlist else len(nl.update()[2])
-    st = cv.steinhardt_local(r_cut=1.4, r_on=1.2, lmax=6, Ql_ref=[0, 0, 0, 0, 1, 0, 1], nlist=nl, type="A", sigma=sigma)
+    st = cv.steinhardt_local(r_cut=1.4, r_on=1.2, lmax=6, Ql_ref=[0, 0, 0, 0, 1, 0, 1], nlist=nl, type="A", sigma=sigma, **options)
     st.set_grid(lo, hi, 512)
     return meta, st, nl, entries
 
@@ -50,5 +60,7 @@ c = st.get_local()
 print("on grid: %s, hills %d, bias factors %s, V = %g, mean c_i %.6f, mean n_i %.3f"
       % (0.0 <= st.cpp_force.getCurrentValue(t_now) < 2.0 * s0, meta.cpp_integrator.getNumGaussians(), list(meta.cpp_integrator.getBiasFactors()),
          meta.cpp_integrator.getLogValue("bias", t_now), c.mean(), st.get_coordination().mean()))
+if options:
+    print("options %s: mean v_i %.6f" % (options, st.get_switched().mean()))
 print("config 5 local (%s%s): %.1f us/step  (%.3e particle-CV-evals/s, %.3e list entries/s incl. CV + force pass)"
       % (np.dtype(dtype).name, ", device list" if device_nlist else "", 1e6 * dt / steps, N * steps / dt, 2 * entries * steps / dt))

@@ -1,0 +1,71 @@
+#!/usr/bin/env python3
+"""Developer tool (no GPU needed): do the PLAIN kernels of steinhardt_local.hip have the instruction streams of another revision's?
+Compiles csrc/steinhardt_local.hip of <git revision> and of this tree to gfx950 assembly with the Makefile's flags and compares, kernel
+by kernel, the 24 kernels of the revision with the plain instantiations of this tree (k_qll_accumulate<.., QLL_PLAIN>,
+k_qll_forces<.., false>, k_qll_forces_tile<.., false>): instruction count, identical text, identical opcode sequence.
+usage: tools/ql_local_isa_cmp.py <git revision>        (profiles/r8/qll_isa_cmp.txt: the parent commit)"""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+FLAGS = "--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -ffp-contract=fast -S --cuda-device-only".split()
+
+
+def assembly(tree, out):
+    csrc = os.path.join(tree, "metadynamics-plugin_amd", "csrc")
+    subprocess.check_call([HIPCC] + FLAGS + ["-I" + os.path.join(tree, "include"), "-I" + csrc, os.path.join(csrc, "steinhardt_local.hip"), "-o", out])
+
+
+def kernels(path):
+    """{demangled short name: [instruction lines]} of the k_qll_* kernels of an assembly file"""
+    out, cur, name = {}, None, None
+    for line in open(path):
+        m = re.match(r"^(_Z\w+):", line)
+        if m and "k_qll" in m.group(1):
+            name, cur = m.group(1), []
+            continue
+        if cur is None:
+            continue
+        t = line.strip()
+        if t.startswith(".Lfunc_end"):
+            out[name] = cur
+            cur = None
+        elif t and not t.startswith(".") and not t.startswith(";"):
+            cur.append(re.sub(r"\s*;.*", "", t))
+    names = list(out)
+    dem = subprocess.run(["c++filt"] + names, capture_output=True, text=True, check=True).stdout.strip().split("\n")
+    short = [re.sub(r"\(anonymous namespace\)::|void |HIP_vector_type<|, 4u>", "", re.sub(r"\(mtd::.*", "", d)) for d in dem]
+    return dict(zip(short, out.values()))
+
+
+def main(rev):
+    with tempfile.TemporaryDirectory() as tmp:
+        old_tree = os.path.join(tmp, "old")
+        os.mkdir(old_tree)
+        tar = subprocess.run(["git", "-C", root, "archive", rev, "metadynamics-plugin_amd/csrc", "include"], capture_output=True, check=True).stdout
+        subprocess.run(["tar", "-x", "-C", old_tree], input=tar, check=True)
+        assembly(old_tree, os.path.join(tmp, "old.s"))
+        assembly(root, os.path.join(tmp, "new.s"))
+        old, new = kernels(os.path.join(tmp, "old.s")), kernels(os.path.join(tmp, "new.s"))
+    same = True
+    ops = lambda body: [x.split()[0] for x in body]
+    for k, body in sorted(old.items()):
+        k2 = k if k in new else k[:-1] + (", 0>" if "accumulate" in k else ", false>")          # the plain instantiation of this tree
+        b2 = new.get(k2)
+        if b2 is None:
+            print("%-40s has no counterpart %s" % (k, k2))
+            same = False
+            continue
+        same = same and ops(body) == ops(b2)
+        print("%-40s %5d vs %5d instructions; identical text: %s; identical opcode sequence: %s" % (k, len(body), len(b2), body == b2, ops(body) == ops(b2)))
+    return 0 if same else 1
+
+
+if __name__ == "__main__":
+    if len(sys.argv) != 2:
+        sys.exit(__doc__)
+    sys.exit(main(sys.argv[1]))
