@@ -34,6 +34,7 @@
 #include "mtd_device.hpp"
 #include "steinhardt_device.hpp"
 #include "metad_host.hpp"
+#include "dispatch.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -1423,27 +1424,14 @@ int mtd_debug_sph_harmonics(unsigned int lmax, unsigned int n, const double *h_s
     if (e == hipSuccess)
         {
         const unsigned int blocks = (n + 63) / 64;
-        int rc = MTD_SUCCESS;
-        if (lmax <= 4)
+        const int rc = dispatch_lmax(lmax, [&](auto lm)
             {
-            const double *tab = ql_device_table<4>(nullptr, rc);
-            if (!rc) k_debug_sph<4><<<blocks, 64>>>(n, lmax, d_sep, d_out, tab);
-            }
-        else if (lmax <= 6)
-            {
-            const double *tab = ql_device_table<6>(nullptr, rc);
-            if (!rc) k_debug_sph<6><<<blocks, 64>>>(n, lmax, d_sep, d_out, tab);
-            }
-        else if (lmax <= 8)
-            {
-            const double *tab = ql_device_table<8>(nullptr, rc);
-            if (!rc) k_debug_sph<8><<<blocks, 64>>>(n, lmax, d_sep, d_out, tab);
-            }
-        else
-            {
-            const double *tab = ql_device_table<12>(nullptr, rc);
-            if (!rc) k_debug_sph<12><<<blocks, 64>>>(n, lmax, d_sep, d_out, tab);
-            }
+            constexpr int LMAX = decltype(lm)::value;
+            int err = MTD_SUCCESS;
+            const double *tab = ql_device_table<LMAX>(nullptr, err);
+            if (!err) k_debug_sph<LMAX><<<blocks, 64>>>(n, lmax, d_sep, d_out, tab);
+            return err;
+            });
         e = rc ? (hipError_t)rc : hipGetLastError();
         }
     if (e == hipSuccess) e = hipMemcpy(h_out, d_out, n_out * sizeof(double), hipMemcpyDeviceToHost);
@@ -1485,18 +1473,11 @@ static int ql_dispatch(unsigned int n_particles, const void *d_postype, int dtyp
     ql_layout(d_scratch, lmax, &partials, &qprime, &qlm, &ql, &value);
     unsigned int n_partials = 0;
     hipStream_t s = (hipStream_t)stream;
-    int rc;
-#define MTD_QL_ACC(LM) accumulate_impl<LM>(n_particles, d_postype, dtype, box, d_head_list, d_n_neigh, d_nlist, half_nlist, rcut, ron, lmax, \
-                                           type, Ql_ref, n_global, partials, &n_partials, qprime, qlm, ql, value, accumulate, finalize, s)
-    if (lmax <= 4)
-        rc = MTD_QL_ACC(4);
-    else if (lmax <= 6)
-        rc = MTD_QL_ACC(6);
-    else if (lmax <= 8)
-        rc = MTD_QL_ACC(8);
-    else
-        rc = MTD_QL_ACC(12);
-#undef MTD_QL_ACC
+    const int rc = dispatch_lmax(lmax, [&](auto lm)
+        {
+        return accumulate_impl<decltype(lm)::value>(n_particles, d_postype, dtype, box, d_head_list, d_n_neigh, d_nlist, half_nlist, rcut, ron, lmax, type,
+                                                    Ql_ref, n_global, partials, &n_partials, qprime, qlm, ql, value, accumulate, finalize, s);
+        });
     if (rc) return rc;
     if (d_value) *d_value = value;
     if (d_Ql) *d_Ql = ql;
@@ -1560,14 +1541,8 @@ int mtd_ql_finalize_update_bias(mtd_metad *m, int half_nlist, unsigned int lmax,
     if (rc) return rc;
     const int dep = deposit_due(m, timestep);      // IntegratorMetaDynamics.cc:368
     const unsigned int n_grid = dep ? m->cfg.n_gblocks : 0;
-    if (lmax <= 4)
-        rc = finalize_chain_impl<4>(m, half_nlist, lmax, Ql_ref, n_global, qprime, qlm, ql, value, dep, n_grid, s);
-    else if (lmax <= 6)
-        rc = finalize_chain_impl<6>(m, half_nlist, lmax, Ql_ref, n_global, qprime, qlm, ql, value, dep, n_grid, s);
-    else if (lmax <= 8)
-        rc = finalize_chain_impl<8>(m, half_nlist, lmax, Ql_ref, n_global, qprime, qlm, ql, value, dep, n_grid, s);
-    else
-        rc = finalize_chain_impl<12>(m, half_nlist, lmax, Ql_ref, n_global, qprime, qlm, ql, value, dep, n_grid, s);
+    rc = dispatch_lmax(lmax, [&](auto lm)
+        { return finalize_chain_impl<decltype(lm)::value>(m, half_nlist, lmax, Ql_ref, n_global, qprime, qlm, ql, value, dep, n_grid, s); });
     if (rc) return rc;
     m->pending_apply = dep;
     m->w_stale = dep;
@@ -1590,13 +1565,11 @@ int mtd_ql_forces(unsigned int n_particles, const void *d_postype, void *d_force
     double *partials, *qprime, *qlm, *ql, *value;
     ql_layout((double *)d_scratch, lmax, &partials, &qprime, &qlm, &ql, &value);
     hipStream_t s = (hipStream_t)stream;
-#define MTD_QL_F(LM) forces_impl<LM>(n_particles, d_postype, d_force, dtype, box, d_head_list, d_n_neigh, d_nlist, half_nlist, rcut, ron, lmax, \
-                                     type, Ql_ref, n_global, qlm, d_bias, bias_host, s)
-    if (lmax <= 4) return MTD_QL_F(4);
-    if (lmax <= 6) return MTD_QL_F(6);
-    if (lmax <= 8) return MTD_QL_F(8);
-    return MTD_QL_F(12);
-#undef MTD_QL_F
+    return dispatch_lmax(lmax, [&](auto lm)
+        {
+        return forces_impl<decltype(lm)::value>(n_particles, d_postype, d_force, dtype, box, d_head_list, d_n_neigh, d_nlist, half_nlist, rcut, ron, lmax, type,
+                                                Ql_ref, n_global, qlm, d_bias, bias_host, s);
+        });
     }
 
 } // extern "C"

@@ -34,6 +34,10 @@
 //                    per-particle sums stay in registers: no LDS atomics.  The quad's sums are added with two DPP quad_perm moves
 //                    ((q0 + q1) + (q2 + q3), the same bits in all four lanes)
 //   memory trips     list entry two iterations ahead, neighbour position one iteration ahead of the arithmetic
+//   one walk         the centre of a quad (QllCentre / qll_centre) and the zero that keeps the table loads in the loop
+//                    (qll_loop_table) are written once for all five kernels; the look-ahead and the pair test once (QllWalker) for
+//                    average and backprop (loop condition per quad).  accumulate, forces (per lane) and forces_tile (per wave) keep
+//                    them written out: see the note above QllWalker
 //   k_qll_accumulate monic sums S_lm = sum f p_m,l-m(cos theta) h^m (QlTab, as k_ql_accumulate) for every (l, m >= 0) of the compiled
 //                    LMAX; then per particle n_i, c_i and the table row
 //                        R_lm(i) = nrm(l, m)^2 (m > 0 ? 2 : 1) g_l(i) conj(S_lm(i))        degrees in use only, m >= 0
@@ -45,7 +49,7 @@
 //                    into an LDS tile of its own, R(k) of its 16 particles once per chunk; times bias / N_global at the end
 //   k_qll_forces     the same with R(k) and R(j) read per lane and (l, m) straight from memory: rows longer than 256 bytes (more
 //                    than 16 complex slots) whose tiles would not fit
-// Double precision throughout.
+// Double precision throughout.  Host side: the compiled LMAX, the array type, AVG and the mode of pass 1 are chosen through dispatch.hpp.
 //
 // Options (mtd_ql_local_options; definition and gradient in include/mtd_abi.h): per-particle transforms of the quantities above.
 //   switch, gate     v_i = g(n_i) h(c_i) in place of c_i.  Still two launches: the epilogue of k_qll_accumulate<QLL_TRANSFORM> forms c_i
@@ -58,6 +62,7 @@
 //                    the list and adds it to the (0, 0) weight of the pair.  See the block above k_qll_average.
 #include "mtd_device.hpp"
 #include "steinhardt_device.hpp"
+#include "dispatch.hpp"
 
 namespace
 {
@@ -95,6 +100,107 @@ template<int U> __device__ __forceinline__ double quad_bcast(const double v) { r
 template<int U> __device__ __forceinline__ unsigned int quad_bcast(const unsigned int v)
     {
     return (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, U * 0x55, 0xf, 0xf, false);
+    }
+
+// ---- the walk over a row: a quad's central particle (all five kernels) and its lane's share of the row ----------------------------
+// the central particle of a quad: particle i of the chunk, its row of the list (empty for i >= N and for a particle of another type)
+struct QllCentre
+    {
+    unsigned int i;
+    Particle p;
+    unsigned int start, cnt;
+    __device__ __forceinline__ unsigned int row(const unsigned int N) const { return i < N ? i : 0; }   // a table row that is safe to address
+    };
+
+template<typename S4, int LMAX>
+__device__ __forceinline__ QllCentre qll_centre(const QlArgs<LMAX> &a, const S4 *postype, const unsigned int *head_list, const unsigned int *n_neigh,
+                                                const unsigned int i)
+    {
+    Particle p = {0.0, 0.0, 0.0, -1};
+    unsigned int start = 0, cnt = 0;
+    if (i < a.N)
+        {
+        p = scalar4_traits<S4>::load(postype, i);
+        if ((unsigned int)p.type == a.type)
+            {
+            start = head_list[i];
+            cnt = n_neigh[i];
+            }
+        }
+    return {i, p, start, cnt};
+    }
+
+// Lane q of the quad takes entries q, q + 4, ... of the row.  The walker owns the look-ahead: the list entry is asked for two
+// iterations, the neighbour's position one iteration ahead of the arithmetic on (j0, pos0).  A loop is
+//     w.begin(..); while (its own condition on w.e) { w.ahead(..); w.pair(.., what to do with the pair); w.step(); }
+// Used by k_qll_average and k_qll_backprop.  k_qll_accumulate, k_qll_forces and k_qll_forces_tile keep the same walk written out:
+// through the walker their bits or their speed did not stay the parent's (profiles/r10/README.md).  A change to the look-ahead, the
+// list format or the skip rule is made here AND in those three loops.  The walker holds the look-ahead only; what it reads from is
+// handed to begin and ahead.
+template<typename S4> struct QllWalker
+    {
+    unsigned int e, j0, j1, j2;                            // the entry in hand and its index; the indices one and two entries on
+    S4 pos0, pos1;                                         // the positions of j0 and j1
+
+    static __device__ __forceinline__ unsigned int entry(const unsigned int *nlist, const QllCentre &c, const unsigned int k)
+        {
+        return k < c.cnt ? nlist[c.start + k] : QLL_NONE;
+        }
+    static __device__ __forceinline__ S4 position(const unsigned int N, const S4 *postype, const unsigned int j)
+        {
+        S4 pos = qll_zero<S4>();
+        if (j < N) pos = postype[j];
+        return pos;
+        }
+    __device__ __forceinline__ void begin(const unsigned int N, const S4 *postype, const unsigned int *nlist, const QllCentre &c, const unsigned int q)
+        {
+        e = q;
+        j0 = entry(nlist, c, e);
+        j1 = entry(nlist, c, e + QLL_G);
+        pos0 = position(N, postype, j0);
+        }
+    __device__ __forceinline__ void ahead(const unsigned int N, const S4 *postype, const unsigned int *nlist, const QllCentre &c)
+        {
+        j2 = entry(nlist, c, e + 2 * QLL_G);
+        pos1 = position(N, postype, j1);
+        }
+    __device__ __forceinline__ void step()
+        {
+        j0 = j1;
+        j1 = j2;
+        pos0 = pos1;
+        e += QLL_G;
+        }
+    // The pair test, in two halves.  listed: the entry in hand is a neighbour at all — an index >= N (a ghost, or QLL_NONE past the end
+    // of the row) and the particle itself are skipped.  near: d = minImage(r_c - r_j0), and whether j0 has the type and lies within the
+    // cut-off.  pair: calls f(dx, dy, dz, rsq) for an entry that passes both, the geometry formed for listed entries only.  The pair's
+    // arithmetic is handed in, not a flag handed out: d then lives where the hand-written loops declared it.
+    __device__ __forceinline__ bool listed(const unsigned int N, const QllCentre &c) const { return j0 < N && j0 != c.i; }
+    template<int LMAX>
+    __device__ __forceinline__ bool near(const QlArgs<LMAX> &a, const QllCentre &c, double &dx, double &dy, double &dz, double &rsq) const
+        {
+        const Particle pj = scalar4_traits<S4>::unpack(pos0);
+        dx = c.p.x - pj.x, dy = c.p.y - pj.y, dz = c.p.z - pj.z;
+        min_image(a, dx, dy, dz);
+        rsq = dx * dx + dy * dy + dz * dz;
+        return (unsigned int)pj.type == a.type && rsq <= a.rcutsq;
+        }
+    template<int LMAX, typename F> __device__ __forceinline__ void pair(const QlArgs<LMAX> &a, const QllCentre &c, F &&f) const
+        {
+        if (listed(a.N, c))
+            {
+            double dx, dy, dz, rsq;
+            if (near(a, c, dx, dy, dz, rsq)) f(dx, dy, dz, rsq);
+            }
+        }
+    };
+
+// the table with a zero added that the compiler cannot see through: called inside a loop, it keeps the table loads in the loop
+__device__ __forceinline__ const double *qll_loop_table(const double *tab)
+    {
+    unsigned int tab_shift = 0;
+    asm volatile("" : "+s"(tab_shift));
+    return tab + tab_shift;
     }
 
 // ---- the per-particle transforms of the options: v_i = g(n_i) h(c_i) ------------------------------------------------------------
@@ -163,18 +269,9 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_accumulate(const QlArgs<LMA
     double block_c = 0.0;
     for (unsigned int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
         {
-        const unsigned int i = chunk * QLL_PPB + p;
-        Particle pi = {0.0, 0.0, 0.0, -1};
-        unsigned int start = 0, cnt = 0;
-        if (i < a.N)
-            {
-            pi = scalar4_traits<S4>::load(postype, i);
-            if ((unsigned int)pi.type == a.type)
-                {
-                start = head_list[i];
-                cnt = n_neigh[i];
-                }
-            }
+        const QllCentre ci = qll_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
+        const unsigned int i = ci.i, start = ci.start, cnt = ci.cnt;
+        const Particle pi = ci.p;
         cplx S[LMAX + 1][LMAX + 1];                                                // [m][l], l >= m
 #pragma unroll
         for (int m = 0; m <= LMAX; ++m)
@@ -189,9 +286,7 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_accumulate(const QlArgs<LMA
 #pragma unroll 1
         for (; e < cnt; e += QLL_G)
             {
-            unsigned int tab_shift = 0;
-            asm volatile("" : "+s"(tab_shift));                 // a zero the compiler cannot see through: the table loads stay in the loop
-            const double *__restrict__ tab_k = tab + tab_shift;
+            const double *__restrict__ tab_k = qll_loop_table(tab);
             const unsigned int j2 = e + 2 * QLL_G < cnt ? nlist[start + e + 2 * QLL_G] : QLL_NONE;
             S4 pos1 = qll_zero<S4>();
             if (j1 < a.N) pos1 = postype[j1];
@@ -248,7 +343,7 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_accumulate(const QlArgs<LMA
         const double inv_n = nsum > 0.0 ? 1.0 / nsum : 0.0;
         const double inv_n2 = inv_n * inv_n;
         const bool write = q == 0 && i < a.N;
-        double *__restrict__ row = rows + (size_t)(i < a.N ? i : 0) * lay.row_doubles;
+        double *__restrict__ row = rows + (size_t)ci.row(a.N) * lay.row_doubles;
         double c = 0.0, r00 = 0.0;
         if constexpr (MODE == QLL_PLAIN)
             {
@@ -387,17 +482,21 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_accumulate(const QlArgs<LMA
     }
 
 // ---- pass 2: forces, gathered --------------------------------------------------------------------------------------------
-// AVG: the pair's own scalar E_kj (k_qll_backprop) joins the (0, 0) weight, the coefficient of grad f
-template<bool AVG> struct QllPairWeights
+// The weight q_lm = R_lm(k) + (-1)^l R_lm(j) ql_pair_force contracts, from the two table rows: ROW is const double * (memory, a slot
+// read as one double2) or const double2 * (the LDS tiles).  AVG: the pair's own scalar E_kj (k_qll_backprop) joins the (0, 0) weight,
+// the coefficient of grad f
+__device__ __forceinline__ double2 qll_slot(const double *row, const unsigned int s) { return *reinterpret_cast<const double2 *>(row + 2 * s); }
+__device__ __forceinline__ double2 qll_slot(const double2 *row, const unsigned int s) { return row[s]; }
+
+template<bool AVG, typename ROW> struct QllWeights
     {
-    const double *__restrict__ rk;
-    const double *__restrict__ rj;
+    ROW rk, rj;                                            // the rows of this lane's particle and of its neighbour
     const QllLayout &lay;
     double e;
     __device__ __forceinline__ cplx operator()(const int l, const int m, const int) const
         {
-        const unsigned int s = 2 * (lay.off[l] + m);
-        const double2 wk = *reinterpret_cast<const double2 *>(rk + s), wj = *reinterpret_cast<const double2 *>(rj + s);
+        const unsigned int s = lay.off[l] + m;
+        const double2 wk = qll_slot(rk, s), wj = qll_slot(rj, s);
         if (l & 1) return {wk.x - wj.x, wk.y - wj.y};
         if (AVG && l == 0) return {wk.x + wj.x + e, wk.y + wj.y};
         return {wk.x + wj.x, wk.y + wj.y};
@@ -421,19 +520,10 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
     const unsigned int act = __builtin_amdgcn_readfirstlane(lay.act | 1u);         // slot (0, 0) carries the -2 (c_k/n_k + c_j/n_j) grad f term
     for (unsigned int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
         {
-        const unsigned int k = chunk * QLL_PPB + p;
-        Particle pk = {0.0, 0.0, 0.0, -1};
-        unsigned int start = 0, cnt = 0;
-        if (k < a.N)
-            {
-            pk = scalar4_traits<S4>::load(postype, k);
-            if ((unsigned int)pk.type == a.type)
-                {
-                start = head_list[k];
-                cnt = n_neigh[k];
-                }
-            }
-        const double *__restrict__ rk = rows + (size_t)(k < a.N ? k : 0) * lay.row_doubles;
+        const QllCentre ck = qll_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
+        const unsigned int k = ck.i, start = ck.start, cnt = ck.cnt;
+        const Particle pk = ck.p;
+        const double *__restrict__ rk = rows + (size_t)ck.row(a.N) * lay.row_doubles;
         double Fx = 0.0, Fy = 0.0, Fz = 0.0;
         unsigned int e = q;
         unsigned int j0 = e < cnt ? nlist[start + e] : QLL_NONE;
@@ -445,9 +535,7 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
 #pragma unroll 1
         for (; e < cnt; e += QLL_G)
             {
-            unsigned int tab_shift = 0;
-            asm volatile("" : "+s"(tab_shift));                 // a zero the compiler cannot see through: the table loads stay in the loop
-            const double *__restrict__ tab_k = tab + tab_shift;
+            const double *__restrict__ tab_k = qll_loop_table(tab);
             const unsigned int j2 = e + 2 * QLL_G < cnt ? nlist[start + e + 2 * QLL_G] : QLL_NONE;
             S4 pos1 = qll_zero<S4>();
             if (j1 < a.N) pos1 = postype[j1];
@@ -462,7 +550,7 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
                 if ((unsigned int)pj.type == a.type && rsq <= a.rcutsq)
                     {
                     double fpx, fpy, fpz;
-                    ql_pair_force<LMAX>(a, tab_k, QllPairWeights<AVG>{rk, rows + (size_t)j0 * lay.row_doubles, lay, e0}, act, dx, dy, dz, rsq, fpx, fpy, fpz);
+                    ql_pair_force<LMAX>(a, tab_k, QllWeights<AVG, const double *>{rk, rows + (size_t)j0 * lay.row_doubles, lay, e0}, act, dx, dy, dz, rsq, fpx, fpy, fpz);
                     Fx += fpx;
                     Fy += fpy;
                     Fz += fpz;
@@ -498,22 +586,6 @@ __device__ __forceinline__ void qll_wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
 
-template<bool AVG> struct QllTileWeights
-    {
-    const double2 *tk;                                     // LDS: the row of this lane's particle
-    const double2 *tj;                                     // LDS: the row of this lane's neighbour
-    const QllLayout &lay;
-    double e;
-    __device__ __forceinline__ cplx operator()(const int l, const int m, const int) const
-        {
-        const unsigned int s = lay.off[l] + m;
-        const double2 wk = tk[s], wj = tj[s];
-        if (l & 1) return {wk.x - wj.x, wk.y - wj.y};
-        if (AVG && l == 0) return {wk.x + wj.x + e, wk.y + wj.y};
-        return {wk.x + wj.x, wk.y + wj.y};
-        }
-    };
-
 template<typename S4, int LMAX, bool AVG>
 __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_forces_tile(const QlArgs<LMAX> a, const QllLayout lay, const S4 *__restrict__ postype,
                                                             const unsigned int *__restrict__ head_list,
@@ -537,18 +609,9 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
     const unsigned int act = __builtin_amdgcn_readfirstlane(lay.act | 1u);
     for (unsigned int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
         {
-        const unsigned int k = chunk * QLL_PPB + p;
-        Particle pk = {0.0, 0.0, 0.0, -1};
-        unsigned int start = 0, cnt = 0;
-        if (k < a.N)
-            {
-            pk = scalar4_traits<S4>::load(postype, k);
-            if ((unsigned int)pk.type == a.type)
-                {
-                start = head_list[k];
-                cnt = n_neigh[k];
-                }
-            }
+        const QllCentre ck = qll_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
+        const unsigned int k = ck.i, start = ck.start, cnt = ck.cnt;
+        const Particle pk = ck.p;
         qll_wave_sync();                                    // the last chunk's reads of the tiles are done
         if (cnt > 0)
             {
@@ -570,9 +633,7 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
 #pragma unroll 1
         while (__ballot(e < cnt) != 0ull)
             {
-            unsigned int tab_shift = 0;
-            asm volatile("" : "+s"(tab_shift));                 // a zero the compiler cannot see through: the table loads stay in the loop
-            const double *__restrict__ tab_k = tab + tab_shift;
+            const double *__restrict__ tab_k = qll_loop_table(tab);
             const unsigned int j2 = e + 2 * QLL_G < cnt ? nlist[start + e + 2 * QLL_G] : QLL_NONE;
             S4 pos1 = qll_zero<S4>();
             if (j1 < a.N) pos1 = postype[j1];
@@ -613,7 +674,7 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
                 if (visit)
                     {
                     double fpx, fpy, fpz;
-                    ql_pair_force<LMAX>(a, tab_k, QllTileWeights<AVG>{tile_k + (lane / QLL_G) * ts, tile_j + lane * ts, lay, e0}, act, dx, dy, dz, rsq, fpx, fpy, fpz);
+                    ql_pair_force<LMAX>(a, tab_k, QllWeights<AVG, const double2 *>{tile_k + (lane / QLL_G) * ts, tile_j + lane * ts, lay, e0}, act, dx, dy, dz, rsq, fpx, fpy, fpz);
                     Fx += fpx;
                     Fy += fpy;
                     Fz += fpz;
@@ -664,21 +725,9 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_average(const QlArgs<12> a,
     double block_v = 0.0;
     for (unsigned int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
         {
-        const unsigned int i = chunk * QLL_PPB + p;
-        const unsigned int ii = i < a.N ? i : 0;
-        Particle pi = {0.0, 0.0, 0.0, -1};
-        unsigned int start = 0, cnt = 0;
-        double ni = 0.0;
-        if (i < a.N)
-            {
-            pi = scalar4_traits<S4>::load(postype, i);
-            ni = n_in[i];
-            if ((unsigned int)pi.type == a.type)
-                {
-                start = head_list[i];
-                cnt = n_neigh[i];
-                }
-            }
+        const QllCentre ci = qll_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
+        const unsigned int i = ci.i, ii = ci.row(a.N);
+        const double ni = i < a.N ? n_in[i] : 0.0;
         const double inv_1n = 1.0 / (1.0 + ni);
         double csum = 0.0;
         for (unsigned int w0 = 0; w0 < rs16; w0 += QLL_G * QLL_GV)
@@ -692,35 +741,21 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_average(const QlArgs<12> a,
                 cs[v] = c < rs16 ? c : rs16 - 1;
                 acc[v] = qrows[(size_t)ii * rs16 + cs[v]];
                 }
-            unsigned int e = q;
-            unsigned int j0 = e < cnt ? nlist[start + e] : QLL_NONE;
-            unsigned int j1 = e + QLL_G < cnt ? nlist[start + e + QLL_G] : QLL_NONE;
-            S4 pos0 = qll_zero<S4>();
-            if (j0 < a.N) pos0 = postype[j0];
+            QllWalker<S4> w;
+            w.begin(a.N, postype, nlist, ci, q);
 #pragma unroll 1
-            for (unsigned int eb = 0; eb < cnt; eb += QLL_G, e += QLL_G)            // cnt is the quad's: its four lanes stay together
+            for (unsigned int eb = 0; eb < ci.cnt; eb += QLL_G, w.step())           // cnt is the quad's: its four lanes stay together
                 {
-                unsigned int tab_shift = 0;
-                asm volatile("" : "+s"(tab_shift));                 // a zero the compiler cannot see through: the table loads stay in the loop
-                const double *__restrict__ tab_k = tab + tab_shift;
-                const unsigned int j2 = e + 2 * QLL_G < cnt ? nlist[start + e + 2 * QLL_G] : QLL_NONE;
-                S4 pos1 = qll_zero<S4>();
-                if (j1 < a.N) pos1 = postype[j1];
+                const double *__restrict__ tab_k = qll_loop_table(tab);
+                w.ahead(a.N, postype, nlist, ci);
                 double f = 0.0;
                 unsigned int jv = ii;
-                if (j0 < a.N && j0 != i)
+                w.pair(a, ci, [&](double, double, double, const double rsq)
                     {
-                    const Particle pj = scalar4_traits<S4>::unpack(pos0);
-                    double dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
-                    min_image(a, dx, dy, dz);
-                    const double rsq = dx * dx + dy * dy + dz * dz;
-                    if ((unsigned int)pj.type == a.type && rsq <= a.rcutsq)
-                        {
-                        double fprime_divr;
-                        smoothing_tab<12>(a, tab_k, rsq, rsqrt(rsq), f, fprime_divr);
-                        jv = j0;
-                        }
-                    }
+                    double fprime_divr;
+                    smoothing_tab<12>(a, tab_k, rsq, rsqrt(rsq), f, fprime_divr);
+                    jv = w.j0;
+                    });
                 const unsigned int ju[QLL_G] = {quad_bcast<0>(jv), quad_bcast<1>(jv), quad_bcast<2>(jv), quad_bcast<3>(jv)};
                 const double fu[QLL_G] = {quad_bcast<0>(f), quad_bcast<1>(f), quad_bcast<2>(f), quad_bcast<3>(f)};
 #pragma unroll
@@ -732,9 +767,6 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_average(const QlArgs<12> a,
                         acc[v].x += fu[u] * r.x;
                         acc[v].y += fu[u] * r.y;
                         }
-                j0 = j1;
-                j1 = j2;
-                pos0 = pos1;
                 }
             // this window of qbar: its share of c_i, and 2 w conj(qbar) / (1 + n) parked in the B row until h'(c_i) is known
 #pragma unroll
@@ -787,22 +819,9 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_backprop(const QlArgs<12> a
     const unsigned int n_chunks = (a.N + QLL_PPB - 1) / QLL_PPB;
     for (unsigned int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
         {
-        const unsigned int k = chunk * QLL_PPB + p;
-        const unsigned int kk = k < a.N ? k : 0;
-        Particle pk = {0.0, 0.0, 0.0, -1};
-        unsigned int start = 0, cnt = 0;
-        double nk = 0.0, a0 = 0.0;
-        if (k < a.N)
-            {
-            pk = scalar4_traits<S4>::load(postype, k);
-            nk = n_in[k];
-            a0 = a0_in[k];
-            if ((unsigned int)pk.type == a.type)
-                {
-                start = head_list[k];
-                cnt = n_neigh[k];
-                }
-            }
+        const QllCentre ck = qll_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
+        const unsigned int k = ck.i, kk = ck.row(a.N);
+        const double nk = k < a.N ? n_in[k] : 0.0, a0 = k < a.N ? a0_in[k] : 0.0;
         const double inv_n = nk > 0.0 ? 1.0 / nk : 0.0;
         double cq = 0.0, r00 = 0.0;
         for (unsigned int w0 = 0; w0 < rs16; w0 += QLL_G * QLL_GV)
@@ -819,37 +838,23 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_backprop(const QlArgs<12> a
                 if (c >= rs16) bk[v] = qk[v] = make_double2(0.0, 0.0);              // a slot past the row adds nothing to E
                 acc[v] = bk[v];
                 }
-            unsigned int e = q;
-            unsigned int j0 = e < cnt ? nlist[start + e] : QLL_NONE;
-            unsigned int j1 = e + QLL_G < cnt ? nlist[start + e + QLL_G] : QLL_NONE;
-            S4 pos0 = qll_zero<S4>();
-            if (j0 < a.N) pos0 = postype[j0];
+            QllWalker<S4> w;
+            w.begin(a.N, postype, nlist, ck, q);
 #pragma unroll 1
-            for (unsigned int eb = 0; eb < cnt; eb += QLL_G, e += QLL_G)
+            for (unsigned int eb = 0; eb < ck.cnt; eb += QLL_G, w.step())
                 {
-                unsigned int tab_shift = 0;
-                asm volatile("" : "+s"(tab_shift));                 // a zero the compiler cannot see through: the table loads stay in the loop
-                const double *__restrict__ tab_k = tab + tab_shift;
-                const unsigned int j2 = e + 2 * QLL_G < cnt ? nlist[start + e + 2 * QLL_G] : QLL_NONE;
-                S4 pos1 = qll_zero<S4>();
-                if (j1 < a.N) pos1 = postype[j1];
+                const double *__restrict__ tab_k = qll_loop_table(tab);
+                w.ahead(a.N, postype, nlist, ck);
                 double f = 0.0;
                 unsigned int jv = kk;
                 bool visit = false;
-                if (j0 < a.N && j0 != k)
+                w.pair(a, ck, [&](double, double, double, const double rsq)
                     {
-                    const Particle pj = scalar4_traits<S4>::unpack(pos0);
-                    double dx = pk.x - pj.x, dy = pk.y - pj.y, dz = pk.z - pj.z;
-                    min_image(a, dx, dy, dz);
-                    const double rsq = dx * dx + dy * dy + dz * dz;
-                    if ((unsigned int)pj.type == a.type && rsq <= a.rcutsq)
-                        {
-                        double fprime_divr;
-                        smoothing_tab<12>(a, tab_k, rsq, rsqrt(rsq), f, fprime_divr);
-                        jv = j0;
-                        visit = true;
-                        }
-                    }
+                    double fprime_divr;
+                    smoothing_tab<12>(a, tab_k, rsq, rsqrt(rsq), f, fprime_divr);
+                    jv = w.j0;
+                    visit = true;
+                    });
                 const unsigned int ju[QLL_G] = {quad_bcast<0>(jv), quad_bcast<1>(jv), quad_bcast<2>(jv), quad_bcast<3>(jv)};
                 const double fu[QLL_G] = {quad_bcast<0>(f), quad_bcast<1>(f), quad_bcast<2>(f), quad_bcast<3>(f)};
                 double mine = 0.0;
@@ -868,15 +873,12 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_backprop(const QlArgs<12> a
                     ee = quad_sum(ee);
                     if (q == u) mine = ee;
                     }
-                if (e < cnt)
+                if (w.e < ck.cnt)
                     {
                     double val = visit ? mine : 0.0;
-                    if (w0 > 0) val += epair[start + e];                             // the lane adds to what it wrote in the last window
-                    epair[start + e] = val;
+                    if (w0 > 0) val += epair[ck.start + w.e];                        // the lane adds to what it wrote in the last window
+                    epair[ck.start + w.e] = val;
                     }
-                j0 = j1;
-                j1 = j2;
-                pos0 = pos1;
                 }
             // Cm of this window: its share of sum Re Cm qm, and the row of the force pass
 #pragma unroll
@@ -896,27 +898,6 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_backprop(const QlArgs<12> a
         cq = quad_sum(cq);
         if (q == 0 && k < a.N) rows[(size_t)k * rs16] = make_double2(r00 + (a0 - cq * inv_n), 0.0);
         }
-    }
-
-template<typename S4, int LMAX, bool AVG>
-int qll_launch_forces(const QlArgs<LMAX> &a, const QllLayout &lay, const unsigned int blocks, const S4 *postype, const unsigned int *d_head,
-                      const unsigned int *d_nneigh, const unsigned int *d_nlist, const double *rows, S4 *force, const double *d_bias,
-                      const double bias_host, const double *tab, const double *epair, hipStream_t s)
-    {
-    const unsigned int rs16 = lay.row_doubles / 2;
-    if (rs16 <= QLL_TILE_MAX16)
-        {
-        const unsigned int ts = rs16 | 1u;                  // odd: rows of a tile start in different banks
-        const size_t bytes = (size_t)QLL_TILE_ROWS * ts * sizeof(double2);
-        MTD_HIP_TRY(hipFuncSetAttribute((const void *)k_qll_forces_tile<S4, LMAX, AVG>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)((size_t)QLL_TILE_ROWS * (QLL_TILE_MAX16 | 1u) * sizeof(double2))));
-        k_qll_forces_tile<S4, LMAX, AVG><<<blocks, QLL_THREADS, bytes, s>>>(a, lay, postype, d_head, d_nneigh, d_nlist, rows, force, d_bias, bias_host, tab, ts,
-                                                                            epair);
-        }
-    else
-        k_qll_forces<S4, LMAX, AVG><<<blocks, QLL_THREADS, 0, s>>>(a, lay, postype, d_head, d_nneigh, d_nlist, rows, force, d_bias, bias_host, tab, epair);
-    MTD_LAUNCH_CHECK();
-    return MTD_SUCCESS;
     }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
@@ -1011,34 +992,7 @@ QllOpt qll_opt(const mtd_ql_local_options *opt)
     }
 
 template<typename S4, int LMAX>
-int qll_accumulate_typed(const QlArgs<LMAX> &a, const QlArgs<12> &a12, const QllLayout &lay, const QllOpt &o, const int mode, const unsigned int blocks,
-                         const S4 *postype, const unsigned int *d_head, const unsigned int *d_nneigh, const unsigned int *d_nlist,
-                         const QllScratch &sc, const double *tab, hipStream_t s)
-    {
-    if (mode == QLL_PLAIN)
-        k_qll_accumulate<S4, LMAX, QLL_PLAIN><<<blocks, QLL_THREADS, 0, s>>>(a, lay, o, postype, d_head, d_nneigh, d_nlist, sc.n, sc.c, sc.v, sc.rows, sc.wtab,
-                                                                              sc.partials, tab);
-    else if (mode == QLL_TRANSFORM)
-        k_qll_accumulate<S4, LMAX, QLL_TRANSFORM><<<blocks, QLL_THREADS, 0, s>>>(a, lay, o, postype, d_head, d_nneigh, d_nlist, sc.n, sc.c, sc.v, sc.rows,
-                                                                                  sc.wtab, sc.partials, tab);
-    else
-        {
-        const unsigned int rs16 = lay.row_doubles / 2;
-        k_qll_accumulate<S4, LMAX, QLL_AVERAGE><<<blocks, QLL_THREADS, 0, s>>>(a, lay, o, postype, d_head, d_nneigh, d_nlist, sc.n, sc.c, sc.v, sc.qrows,
-                                                                                sc.wtab, sc.partials, tab);
-        MTD_LAUNCH_CHECK();
-        k_qll_average<S4><<<blocks, QLL_THREADS, 0, s>>>(a12, o, rs16, postype, d_head, d_nneigh, d_nlist, sc.n, (const double2 *)sc.qrows, sc.wtab,
-                                                          (double2 *)sc.brows, sc.c, sc.v, sc.a0, sc.partials, tab);
-        MTD_LAUNCH_CHECK();
-        k_qll_backprop<S4><<<blocks, QLL_THREADS, 0, s>>>(a12, rs16, postype, d_head, d_nneigh, d_nlist, sc.n, sc.a0, (const double2 *)sc.qrows,
-                                                           (const double2 *)sc.brows, (double2 *)sc.rows, sc.epair, tab);
-        }
-    MTD_LAUNCH_CHECK();
-    return MTD_SUCCESS;
-    }
-
-template<int LMAX>
-int qll_accumulate_impl(unsigned int N, const void *d_postype, int dtype, const mtd_box *box, const unsigned int *d_head, const unsigned int *d_nneigh,
+int qll_accumulate_impl(unsigned int N, const void *d_postype, const mtd_box *box, const unsigned int *d_head, const unsigned int *d_nneigh,
                         const unsigned int *d_nlist, double rcut, double ron, unsigned int lmax, unsigned int type, const double *ql_ref,
                         unsigned int n_global, const QllScratch &sc, const mtd_ql_local_options *opt, unsigned int *n_partials, hipStream_t s)
     {
@@ -1054,20 +1008,34 @@ int qll_accumulate_impl(unsigned int N, const void *d_postype, int dtype, const 
     const unsigned int blocks = qll_blocks(N);
     const QllOpt o = qll_opt(opt);
     const int mode = qll_mode(opt);
-    if (dtype == MTD_F32)
-        rc = qll_accumulate_typed<float4, LMAX>(a, a12, lay, o, mode, blocks, (const float4 *)d_postype, d_head, d_nneigh, d_nlist, sc, tab, s);
-    else
-        rc = qll_accumulate_typed<double4, LMAX>(a, a12, lay, o, mode, blocks, (const double4 *)d_postype, d_head, d_nneigh, d_nlist, sc, tab, s);
-    if (rc) return rc;
+    const S4 *postype = (const S4 *)d_postype;
+    static_assert(QLL_PLAIN == 0 && QLL_TRANSFORM == 1 && QLL_AVERAGE == 2, "the mode is dispatched as the count mode + 1 of 3");
+    dispatch_count<3>(mode + 1, [&](auto m1)
+        {
+        constexpr int MODE = decltype(m1)::value - 1;
+        k_qll_accumulate<S4, LMAX, MODE><<<blocks, QLL_THREADS, 0, s>>>(a, lay, o, postype, d_head, d_nneigh, d_nlist, sc.n, sc.c, sc.v,
+                                                                         MODE == QLL_AVERAGE ? sc.qrows : sc.rows, sc.wtab, sc.partials, tab);
+        });
+    MTD_LAUNCH_CHECK();
+    if (mode == QLL_AVERAGE)
+        {
+        const unsigned int rs16 = lay.row_doubles / 2;
+        k_qll_average<S4><<<blocks, QLL_THREADS, 0, s>>>(a12, o, rs16, postype, d_head, d_nneigh, d_nlist, sc.n, (const double2 *)sc.qrows, sc.wtab,
+                                                          (double2 *)sc.brows, sc.c, sc.v, sc.a0, sc.partials, tab);
+        MTD_LAUNCH_CHECK();
+        k_qll_backprop<S4><<<blocks, QLL_THREADS, 0, s>>>(a12, rs16, postype, d_head, d_nneigh, d_nlist, sc.n, sc.a0, (const double2 *)sc.qrows,
+                                                           (const double2 *)sc.brows, (double2 *)sc.rows, sc.epair, tab);
+        MTD_LAUNCH_CHECK();
+        }
     *n_partials = blocks;
     return MTD_SUCCESS;
     }
 
-template<int LMAX>
-int qll_forces_impl(unsigned int N, const void *d_postype, void *d_force, int dtype, const mtd_box *box, const unsigned int *d_head,
+// the force pass: through LDS tiles while a table row fits one, else straight from memory
+template<typename S4, int LMAX, bool AVG>
+int qll_forces_impl(unsigned int N, const void *d_postype, void *d_force, const mtd_box *box, const unsigned int *d_head,
                     const unsigned int *d_nneigh, const unsigned int *d_nlist, double rcut, double ron, unsigned int lmax, unsigned int type,
-                    const double *ql_ref, unsigned int n_global, const QllScratch &sc, const bool avg, const double *d_bias, double bias_host,
-                    hipStream_t s)
+                    const double *ql_ref, unsigned int n_global, const QllScratch &sc, const double *d_bias, double bias_host, hipStream_t s)
     {
     QlArgs<LMAX> a;
     int rc = fill_args<LMAX>(a, N, box, rcut, ron, lmax, type, ql_ref, n_global, 0);
@@ -1076,19 +1044,24 @@ int qll_forces_impl(unsigned int N, const void *d_postype, void *d_force, int dt
     if (rc) return rc;
     const QllLayout lay = qll_layout(lmax, ql_ref);
     const unsigned int blocks = qll_blocks(N);
-    if (dtype == MTD_F32)
+    const S4 *postype = (const S4 *)d_postype;
+    S4 *force = (S4 *)d_force;
+    const double *epair = AVG ? sc.epair : nullptr;
+    const unsigned int rs16 = lay.row_doubles / 2;
+    if (rs16 <= QLL_TILE_MAX16)
         {
-        if (avg)
-            return qll_launch_forces<float4, LMAX, true>(a, lay, blocks, (const float4 *)d_postype, d_head, d_nneigh, d_nlist, sc.rows, (float4 *)d_force,
-                                                         d_bias, bias_host, tab, sc.epair, s);
-        return qll_launch_forces<float4, LMAX, false>(a, lay, blocks, (const float4 *)d_postype, d_head, d_nneigh, d_nlist, sc.rows, (float4 *)d_force, d_bias,
-                                                      bias_host, tab, nullptr, s);
+        const unsigned int ts = rs16 | 1u;                  // odd: rows of a tile start in different banks
+        const size_t bytes = (size_t)QLL_TILE_ROWS * ts * sizeof(double2);
+        MTD_HIP_TRY(hipFuncSetAttribute((const void *)k_qll_forces_tile<S4, LMAX, AVG>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)((size_t)QLL_TILE_ROWS * (QLL_TILE_MAX16 | 1u) * sizeof(double2))));
+        k_qll_forces_tile<S4, LMAX, AVG><<<blocks, QLL_THREADS, bytes, s>>>(a, lay, postype, d_head, d_nneigh, d_nlist, sc.rows, force, d_bias, bias_host,
+                                                                            tab, ts, epair);
         }
-    if (avg)
-        return qll_launch_forces<double4, LMAX, true>(a, lay, blocks, (const double4 *)d_postype, d_head, d_nneigh, d_nlist, sc.rows, (double4 *)d_force,
-                                                      d_bias, bias_host, tab, sc.epair, s);
-    return qll_launch_forces<double4, LMAX, false>(a, lay, blocks, (const double4 *)d_postype, d_head, d_nneigh, d_nlist, sc.rows, (double4 *)d_force, d_bias,
-                                                   bias_host, tab, nullptr, s);
+    else
+        k_qll_forces<S4, LMAX, AVG><<<blocks, QLL_THREADS, 0, s>>>(a, lay, postype, d_head, d_nneigh, d_nlist, sc.rows, force, d_bias, bias_host, tab,
+                                                                   epair);
+    MTD_LAUNCH_CHECK();
+    return MTD_SUCCESS;
     }
 
 // what both entry points refuse before a device is touched
@@ -1154,17 +1127,14 @@ int mtd_ql_local_accumulate_opt(unsigned int n_particles, const void *d_postype,
     const QllScratch sc = qll_scratch(d_scratch, n_particles, lmax, qll_mode(opt));
     hipStream_t s = (hipStream_t)stream;
     unsigned int n = 0;
-#define MTD_QLL_ACC(LM) qll_accumulate_impl<LM>(n_particles, d_postype, dtype, box, d_head_list, d_n_neigh, d_nlist, rcut, ron, lmax, type, Ql_ref, \
-                                                n_global, sc, opt, &n, s)
-    if (lmax <= 4)
-        rc = MTD_QLL_ACC(4);
-    else if (lmax <= 6)
-        rc = MTD_QLL_ACC(6);
-    else if (lmax <= 8)
-        rc = MTD_QLL_ACC(8);
-    else
-        rc = MTD_QLL_ACC(12);
-#undef MTD_QLL_ACC
+    rc = dispatch_lmax(lmax, [&](auto lm)
+        {
+        return dispatch_s4(dtype, [&](auto t)
+            {
+            return qll_accumulate_impl<typename decltype(t)::type, decltype(lm)::value>(n_particles, d_postype, box, d_head_list, d_n_neigh, d_nlist, rcut,
+                                                                                        ron, lmax, type, Ql_ref, n_global, sc, opt, &n, s);
+            });
+        });
     if (rc) return rc;
     *d_partials = sc.partials;
     *n_partials = n;
@@ -1196,15 +1166,18 @@ int mtd_ql_local_forces_opt(unsigned int n_particles, const void *d_postype, voi
     if (n_particles == 0) return MTD_SUCCESS;
     const int mode = qll_mode(opt);
     const QllScratch sc = qll_scratch(const_cast<double *>(d_scratch), n_particles, lmax, mode);
-    const bool avg = mode == QLL_AVERAGE;
     hipStream_t s = (hipStream_t)stream;
-#define MTD_QLL_F(LM) qll_forces_impl<LM>(n_particles, d_postype, d_force, dtype, box, d_head_list, d_n_neigh, d_nlist, rcut, ron, lmax, type, Ql_ref, \
-                                          n_global, sc, avg, d_bias, bias_host, s)
-    if (lmax <= 4) return MTD_QLL_F(4);
-    if (lmax <= 6) return MTD_QLL_F(6);
-    if (lmax <= 8) return MTD_QLL_F(8);
-    return MTD_QLL_F(12);
-#undef MTD_QLL_F
+    return dispatch_lmax(lmax, [&](auto lm)
+        {
+        return dispatch_s4(dtype, [&](auto t)
+            {
+            return dispatch_bool(mode == QLL_AVERAGE, [&](auto avg)
+                {
+                return qll_forces_impl<typename decltype(t)::type, decltype(lm)::value, decltype(avg)::value>(
+                    n_particles, d_postype, d_force, box, d_head_list, d_n_neigh, d_nlist, rcut, ron, lmax, type, Ql_ref, n_global, sc, d_bias, bias_host, s);
+                });
+            });
+        });
     }
 
 } // extern "C"

@@ -421,3 +421,65 @@ def test_harmonic_umbrella_adds_to_the_bias_factor(api, ref):
     assert abs(kappa * (val - cv0)) > 0.1 * abs(total)
     assert np.abs(F[:, :3] - F_ref).max() <= 1e-7 * np.abs(F_ref).max()
     assert st.cpp_force.getUmbrellaPotential(t) == pytest.approx(0.5 * kappa * (val - cv0) ** 2, rel=1e-9)
+
+
+# ---- rows of every length 0 .. 13, and entries the passes must skip -------------------------------------------------------------
+
+_clusters = {}
+
+
+def cluster_case(dtype):
+    """14 clusters of 1, 2, ..., 14 particles (N = 105: one full chunk of 64 and a partial one) far apart in a box of L = 40: every member
+    of cluster m has m - 1 neighbours, all inside r_cut = 1.4, so the rows have every length 0 .. 13 — each boundary of e < cnt,
+    e + 4 < cnt and e + 8 < cnt of the two-deep look-ahead, for each of the four lanes of a quad.  Returns the system, its list (A), the
+    list with one self entry and two entries >= N added to every row (B), and the restatement's answer for list A per option set."""
+    key = np.dtype(dtype).name
+    if key not in _clusters:
+        rng = np.random.default_rng(2024)
+        L, pos = 40.0, []
+        centres = 8.0 * (np.array([[x, y, z] for x in range(5) for y in range(5) for z in range(5)], dtype=np.float64) - 2.0)
+        for m in range(1, 15):
+            members = []
+            while len(members) < m:
+                x = rng.uniform(-0.45, 0.45, 3)
+                if all(np.linalg.norm(x - y) >= 0.3 for y in members):
+                    members.append(x)
+            pos += [centres[m - 1] + x for x in members]
+        pos = np.array(pos).astype(dtype).astype(np.float64)
+        N = len(pos)
+        types = np.zeros(N, dtype=np.int32)
+        head, nn, lst = (np.asarray(x).astype(np.int64) for x in util.build_nlist(pos, L, 1.55))
+        sizes = np.repeat(np.arange(1, 15), np.arange(1, 15))
+        assert N == 105 and np.array_equal(nn, sizes - 1)
+        rows = []
+        for i in range(N):
+            row = list(lst[head[i]:head[i] + nn[i]])
+            assert all(np.linalg.norm(pos[i] - pos[j]) < 1.4 for j in row)
+            pad = [i, N, N + 7]
+            pad = pad[i % 3:] + pad[:i % 3]                                 # which of the three goes to the front, the middle, the end
+            mid = len(row) // 2
+            rows.append([pad[0]] + row[:mid] + [pad[1]] + row[mid:] + [pad[2]])
+        nn_b = np.array([len(r) for r in rows], dtype=np.uint32)
+        head_b = np.zeros(N, dtype=np.uint32)
+        head_b[1:] = np.cumsum(nn_b)[:-1]
+        padded = (head_b, nn_b, np.concatenate(rows).astype(np.uint32))
+        nl = (head.astype(np.uint32), nn.astype(np.uint32), lst.astype(np.uint32))
+        ref = {c: avg_ref.compute(pos, types, L, nl, 1.4, 1.2, 6, 0, QL_46, **SKIP_COMBOS[c]) for c in SKIP_COMBOS}
+        _clusters[key] = (pos, L, types, nl, padded, ref)
+    return _clusters[key]
+
+
+SKIP_COMBOS = {"plain": {}, "average": COMBOS["average"], "average+switch+gate": COMBOS["average+switch+gate"]}
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("combo", sorted(SKIP_COMBOS))
+def test_row_lengths_0_to_13_and_skipped_entries(abi, dtype, combo):
+    """the walk over a row at every row length 0 .. 13 (run A), and the same rows with a self entry and two entries >= N each, at the
+    front, in the middle and at the end (run B): both give what the restatement gives for the clean list.  (The padding moves entries
+    between lanes, so the sums of B are taken in another order than those of A: no bits are compared.)"""
+    pos, L, types, nl, padded, ref = cluster_case(dtype)
+    assert len(padded[2]) == len(nl[2]) + 3 * len(pos)
+    for lists in (nl, padded):
+        g = run_gpu(abi, pos, types, L, lists, 1.4, 1.2, 6, 0, QL_46, dtype, opt=SKIP_COMBOS[combo])
+        compare(g, ref[combo], 0.9, dtype)

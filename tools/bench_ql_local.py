@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Developer tool: the config 5 snapshot of tools/bench_ql.py (256 000-particle noisy fcc crystal, lmax 6, degrees 4 and 6,
 r_cut 1.4, 512-point grid) with cv.steinhardt_local instead of the global variable; prints us/step.
-usage: tools/bench_ql_local.py [steps] [f32|f64] [--device-nlist] [--average] [--switch c0,p] [--gate lo,hi]
-(--device-nlist: cv.nlist_cell(device=True), r_buff 0.4; the other three: the options of cv.steinhardt_local, e.g. --average --switch 0.12,3)
+usage: tools/bench_ql_local.py [steps] [f32|f64] [--device-nlist] [--average] [--switch c0,p] [--gate lo,hi] [--lmax L --ql-ref a,b,...]
+(--device-nlist: cv.nlist_cell(device=True), r_buff 0.4; the next three: the options of cv.steinhardt_local, e.g. --average --switch 0.12,3;
+--lmax 12 --ql-ref 0,0,0,0,1,0,1,0,0,0,0.5,0.3,0.25: table rows of 784 bytes, which take the direct force pass instead of the LDS tiles)
 Run under rocprofv3 --kernel-trace --stats for the per-kernel table."""
 import os, sys, time
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,6 +18,17 @@ for flag, keys, kinds in (("--switch", ("c0", "p"), (float, int)), ("--gate", ("
         k = argv.index(flag)
         options[flag[2:]] = {key: kind(v) for key, kind, v in zip(keys, kinds, argv[k + 1].split(","))}
         del argv[k:k + 2]
+lmax, ql_ref = 6, [0, 0, 0, 0, 1, 0, 1]
+if "--lmax" in argv:
+    k = argv.index("--lmax")
+    lmax = int(argv[k + 1])
+    del argv[k:k + 2]
+if "--ql-ref" in argv:
+    k = argv.index("--ql-ref")
+    ql_ref = [float(v) for v in argv[k + 1].split(",")]
+    del argv[k:k + 2]
+if len(ql_ref) != lmax + 1:
+    sys.exit("--ql-ref needs lmax + 1 = %d values" % (lmax + 1))
 if "--average" in argv:
     options["average"] = True
 args = [a for a in argv if not a.startswith("--")]
@@ -33,7 +45,7 @@ def build(lo, hi, sigma):
     meta = integrate.mode_metadynamics(dt=0.005, stride=1, mode="well_tempered", W=1.0, deltaT=7.0, T=1.0)
     nl = cv.nlist_cell(r_cut=1.4, device=device_nlist)
     entries = None if device_nlist else len(nl.update()[2])
-    st = cv.steinhardt_local(r_cut=1.4, r_on=1.2, lmax=6, Ql_ref=[0, 0, 0, 0, 1, 0, 1], nlist=nl, type="A", sigma=sigma, **options)
+    st = cv.steinhardt_local(r_cut=1.4, r_on=1.2, lmax=lmax, Ql_ref=ql_ref, nlist=nl, type="A", sigma=sigma, **options)
     st.set_grid(lo, hi, 512)
     return meta, st, nl, entries
 
@@ -62,5 +74,5 @@ print("on grid: %s, hills %d, bias factors %s, V = %g, mean c_i %.6f, mean n_i %
          meta.cpp_integrator.getLogValue("bias", t_now), c.mean(), st.get_coordination().mean()))
 if options:
     print("options %s: mean v_i %.6f" % (options, st.get_switched().mean()))
-print("config 5 local (%s%s): %.1f us/step  (%.3e particle-CV-evals/s, %.3e list entries/s incl. CV + force pass)"
-      % (np.dtype(dtype).name, ", device list" if device_nlist else "", 1e6 * dt / steps, N * steps / dt, 2 * entries * steps / dt))
+print("config 5 local (%s%s%s): %.1f us/step  (%.3e particle-CV-evals/s, %.3e list entries/s incl. CV + force pass)"
+      % (np.dtype(dtype).name, ", device list" if device_nlist else "", "" if lmax == 6 else ", lmax %d" % lmax, 1e6 * dt / steps, N * steps / dt, 2 * entries * steps / dt))

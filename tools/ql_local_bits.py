@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
-"""Developer tool: did the PLAIN cv.steinhardt_local move a bit between two builds of libmtd_hip.so?  The config 5 snapshot
-(256 000-particle noisy fcc crystal, lmax 6, r_cut 1.4) through mtd_ql_local_accumulate / mtd_ql_local_forces, fp32 and fp64 arrays.
-usage: MTD_LIB_OVERRIDE=<lib> tools/ql_local_bits.py dump <out.npz>      c_i, n_i, block sums and the force array of both cases
+"""Developer tool: did cv.steinhardt_local move a bit between two builds of libmtd_hip.so?  The config 5 snapshot (256 000-particle noisy
+fcc crystal, lmax 6, r_cut 1.4) through mtd_ql_local_accumulate_opt / mtd_ql_local_forces_opt, fp32 and fp64 arrays: the plain variable
+and the option paths (average; switch + gate; average + switch + gate); and on a 16^3-cell snapshot of 16 384 particles the direct force
+pass (rows longer than 256 bytes), plain and averaged: lmax 12 (rows of 784 bytes, four gather windows) and every degree up to 6 and up to 8
+(448 and 720 bytes: the compiled bounds 6 and 8), and the tile force pass under the compiled bounds 8 and 12 (degrees 4 and 6 at lmax 8 and 12).
+usage: MTD_LIB_OVERRIDE=<lib> tools/ql_local_bits.py dump <out.npz>      c_i, n_i, v_i, block sums and the force array of every case
        tools/ql_local_bits.py compare <a.npz> <b.npz>                    np.array_equal on every array; exit status 1 when one differs"""
 import ctypes as C
 import os
@@ -12,42 +15,69 @@ import numpy as np
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(root, "metadynamics-plugin_amd"), os.path.join(root, "tests")]
 
+QL_46 = [0, 0, 0, 0, 1, 0, 1]
+QL_12 = [0, 0, 0, 0, 1, 0, 1, 0, 0, 0, 0.5, 0.3, 0.25]
+QL_ALL = [0.1, 0.2, 0.3, 0.4, 1, 0.5, 1, 0.6, 0.7]
+# (name, fcc cells, lmax, Ql_ref, options)
+CASES = (("plain", 40, 6, QL_46, {}),
+         ("average", 40, 6, QL_46, dict(average=True)),
+         ("switch+gate", 40, 6, QL_46, dict(switch=(0.25, 3), gate=(4, 8))),
+         ("average+switch+gate", 40, 6, QL_46, dict(average=True, switch=(0.12, 3), gate=(4, 8))),
+         ("lmax12", 16, 12, QL_12, {}),
+         # every degree in use: rows of 448 and 720 bytes, the direct force pass at the compiled bounds 6 and 8, with and without E
+         ("lmax6all", 16, 6, QL_ALL[:7], {}),
+         ("lmax6all+average", 16, 6, QL_ALL[:7], dict(average=True)),
+         ("lmax8all", 16, 8, QL_ALL, {}),
+         ("lmax8all+average", 16, 8, QL_ALL, dict(average=True)),
+         ("lmax12+average", 16, 12, QL_12, dict(average=True)),
+         # degrees 4 and 6 under the compiled bounds 8 and 12: rows of 208 bytes, the tile force pass of those instantiations
+         ("lmax8tile", 16, 8, QL_46 + [0] * 2, {}),
+         ("lmax8tile+average", 16, 8, QL_46 + [0] * 2, dict(average=True)),
+         ("lmax12tile", 16, 12, QL_46 + [0] * 6, {}),
+         ("lmax12tile+average", 16, 12, QL_46 + [0] * 6, dict(average=True)))
+
 
 def dump(path):
     import torch
     import util
     from metadynamics import _abi as abi
     lib = abi.load()
-    pos, L = util.fcc_lattice(40)
-    pos = pos + np.random.default_rng(777).normal(0, 0.05, pos.shape)
-    N = len(pos)
-    types = np.zeros(N, dtype=np.int32)
-    box = abi.Box.make(L)
-    Ql_ref = util.dbl_array([0, 0, 0, 0, 1, 0, 1])
-    nl = util.build_nlist(pos, L, 1.4)
-    d_head, d_nn, d_nl = (torch.from_numpy(x.astype(np.int32)).cuda() for x in nl)
-    out = {}
-    for dtype in (np.float32, np.float64):
-        dt = abi.MTD_F32 if dtype == np.float32 else abi.MTD_F64
-        d_pos = torch.from_numpy(util.pack_postype(pos.astype(dtype), types, dtype)).cuda()
-        scratch = torch.zeros(lib.mtd_ql_local_scratch_doubles(N, 6), dtype=torch.float64, device="cuda")
-        p_part, p_c, p_n = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        n_part = C.c_uint()
-        abi.check(lib.mtd_ql_local_accumulate(N, abi.ptr(d_pos), dt, C.byref(box), abi.ptr(d_head), abi.ptr(d_nn), abi.ptr(d_nl), 1.4, 1.2, 6, 0, Ql_ref,
-                                              N, abi.ptr(scratch), C.byref(p_part), C.byref(n_part), C.byref(p_c), C.byref(p_n), None))
-        force = torch.zeros((N, 4), dtype=d_pos.dtype, device="cuda")
-        d_bias = torch.tensor([0.9], dtype=torch.float64, device="cuda")
-        abi.check(lib.mtd_ql_local_forces(N, abi.ptr(d_pos), abi.ptr(force), dt, C.byref(box), abi.ptr(d_head), abi.ptr(d_nn), abi.ptr(d_nl), 1.4, 1.2,
-                                          6, 0, Ql_ref, N, abi.ptr(scratch), abi.ptr(d_bias), 0.0, None))
-        torch.cuda.synchronize()
-        s = scratch.cpu().numpy()
-        off = lambda p: (p.value - scratch.data_ptr()) // 8
-        key = np.dtype(dtype).name
-        out[key + "_partials"] = s[off(p_part):off(p_part) + n_part.value].copy()
-        out[key + "_c"] = s[off(p_c):off(p_c) + N].copy()
-        out[key + "_n"] = s[off(p_n):off(p_n) + N].copy()
-        out[key + "_force"] = force.cpu().numpy()
-        print("%s: s %.17g, max |F| %.6g" % (key, out[key + "_partials"].sum() / N, np.abs(out[key + "_force"]).max()))
+    out, systems = {}, {}
+    for name, cells, lmax, ql, opt in CASES:
+        if cells not in systems:
+            pos, L = util.fcc_lattice(cells)
+            pos = pos + np.random.default_rng(777).normal(0, 0.05, pos.shape)
+            systems[cells] = (pos, L, [torch.from_numpy(x.astype(np.int32)).cuda() for x in util.build_nlist(pos, L, 1.4)])
+        pos, L, (d_head, d_nn, d_nl) = systems[cells]
+        N = len(pos)
+        types = np.zeros(N, dtype=np.int32)
+        box = abi.Box.make(L)
+        Ql_ref = util.dbl_array(ql)
+        o = abi.QlLocalOptions.make(**opt)
+        for dtype in (np.float32, np.float64):
+            dt = abi.MTD_F32 if dtype == np.float32 else abi.MTD_F64
+            d_pos = torch.from_numpy(util.pack_postype(pos.astype(dtype), types, dtype)).cuda()
+            scratch = torch.zeros(lib.mtd_ql_local_scratch_doubles_opt(N, lmax, d_nl.numel(), C.byref(o)), dtype=torch.float64, device="cuda")
+            p_part, p_c, p_n, p_v = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+            n_part = C.c_uint()
+            common = (abi.ptr(d_head), abi.ptr(d_nn), abi.ptr(d_nl), 1.4, 1.2, lmax, 0, Ql_ref, N, abi.ptr(scratch))
+            abi.check(lib.mtd_ql_local_accumulate_opt(N, abi.ptr(d_pos), dt, C.byref(box), *common, C.byref(p_part), C.byref(n_part), C.byref(p_c),
+                                                      C.byref(p_n), None, C.byref(o), C.byref(p_v)))
+            force = torch.zeros((N, 4), dtype=d_pos.dtype, device="cuda")
+            d_bias = torch.tensor([0.9], dtype=torch.float64, device="cuda")
+            abi.check(lib.mtd_ql_local_forces_opt(N, abi.ptr(d_pos), abi.ptr(force), dt, C.byref(box), *common, abi.ptr(d_bias), 0.0, None, C.byref(o)))
+            torch.cuda.synchronize()
+            s = scratch.cpu().numpy()
+            off = lambda p: (p.value - scratch.data_ptr()) // 8
+            key = name + "_" + np.dtype(dtype).name
+            out[key + "_partials"] = s[off(p_part):off(p_part) + n_part.value].copy()
+            for tag, p in (("c", p_c), ("n", p_n), ("v", p_v)):
+                out[key + "_" + tag] = s[off(p):off(p) + N].copy()
+            out[key + "_force"] = force.cpu().numpy()
+            finite = all(np.isfinite(out[key + "_" + tag]).all() for tag in ("partials", "c", "n", "v", "force"))
+            print("%-28s N %6d: s %.17g, max |F| %.6g%s" % (key, N, out[key + "_partials"].sum() / N, np.abs(out[key + "_force"]).max(),
+                                                         "" if finite else "  NOT FINITE"))
+            del scratch, force, d_pos
     np.savez(path, **out)
     print("library %s -> %s" % (abi.LIB_PATH, path))
 
@@ -58,7 +88,7 @@ def compare(a, b):
     for k in sorted(A.files):
         eq = k in B.files and np.array_equal(A[k], B[k])
         same = same and eq
-        print("%-24s %s" % (k, "identical bits" if eq else "DIFFERS"))
+        print("%-44s %s" % (k, "identical bits" if eq else "DIFFERS"))
     print("all identical" if same else "NOT identical")
     return 0 if same else 1
 

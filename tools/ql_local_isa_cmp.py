@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""Developer tool (no GPU needed): do the PLAIN kernels of steinhardt_local.hip have the instruction streams of another revision's?
+"""Developer tool (no GPU needed): do the kernels of steinhardt_local.hip have the instruction streams of another revision's?
 Compiles csrc/steinhardt_local.hip of <git revision> and of this tree to gfx950 assembly with the Makefile's flags and compares, kernel
-by kernel, the 24 kernels of the revision with the plain instantiations of this tree (k_qll_accumulate<.., QLL_PLAIN>,
-k_qll_forces<.., false>, k_qll_forces_tile<.., false>): instruction count, identical text, identical opcode sequence.
-usage: tools/ql_local_isa_cmp.py <git revision>        (profiles/r8/qll_isa_cmp.txt: the parent commit)"""
+by kernel: instruction count, identical text, identical opcode sequence.  A revision with this tree's kernel names is compared name by
+name (all 60 instantiations: profiles/r10/qll_isa_cmp.txt); the 24 kernels of a revision from before the options with the plain
+instantiations of this tree (k_qll_accumulate<.., QLL_PLAIN>, k_qll_forces<.., false>, k_qll_forces_tile<.., false>:
+profiles/r8/qll_isa_cmp.txt).
+usage: tools/ql_local_isa_cmp.py <git revision>"""
 import os
 import re
 import subprocess
