@@ -38,8 +38,19 @@
 // Everything is double precision: the CV is quartic in the Fourier amplitudes, fp32 meshes cannot hold
 // 1e-6 on it.  Mesh sizes: 4 ... 256 per axis (any, direct transform in LDS for lengths that are not powers of two), or a
 // power of two up to 1024 (radix-2 stages); other sizes return MTD_ERR_UNSUPPORTED.
+// Host layer (below struct mtd_mesh; launches choose their template arguments through dispatch.hpp).  A step calls, in this order:
+//   mtd_mesh_compute_cv   fft_forward_from_tiles (may the transform read the tile images: no / unsplit / split) -> mesh_assign_local
+//                         (without the combine launch where it may) -> mesh_spectral (mtd_mesh_spectral: the same behind its own question)
+//   mesh_assign_local     checks, TileGeom and fixed-point scale, then ONE of assign_bin | assign_counting | assign_cells, then n_last,
+//                         rho_valid and mesh_combine if asked for (mtd_mesh_assign: always; mesh_need_rho: whoever reads d_rho later)
+//   mesh_spectral         forward: as decided / xy_fused, else fft_x_pass + launch_fft_y; k_fft_z_spectral (fft_z_pass,
+//                         fft_z_tpb); inverse: fft_inverse_split (split or unsplit), else launch_fft_y + fft_x_pass
+//   mtd_mesh_forces | mtd_mesh_forces_update_bias      the lists the assignment left (tile_force_blocks)
+// mtd_mesh_slab_compute_cv is mesh_assign_local + the separate passes (fft_x_pass, launch_fft_y) per slab between the exchanges;
+// mtd_mesh_create is create_tile_geom, create_slab, create_combine_table, create_twiddles.  Every environment switch has one reader.
 #include "mtd_device.hpp"
 #include "comm_host.hpp"
+#include "dispatch.hpp"
 #include "exact_div.hpp"
 #include "lamellar_host.hpp"
 #include "metad_host.hpp"
@@ -3567,13 +3578,48 @@ FftPass fft_z_pass(const mtd_mesh *m)
     return pz;
     }
 
-int launch_fft_y(const mtd_mesh *m, double2 *data, int inverse, hipStream_t s)
+// y pass over `n_planes` planes of the half-spectrum array (the whole mesh: nz; a rank's slab: nz / world)
+int launch_fft_y(const mtd_mesh *m, double2 *data, int inverse, unsigned int n_planes, hipStream_t s)
     {
     const FftPass p = fft_y_pass(m);
-    k_fft_lines<false, false><<<p.n_blocks, FFT_THREADS, fft_lds_bytes(p.n, p.tile), s>>>(
+    k_fft_lines<false, false><<<p.tiles_per_row * n_planes, FFT_THREADS, fft_lds_bytes(p.n, p.tile), s>>>(
         nullptr, data, nullptr, p.tw, p.n, ilog2(p.n), p.tile, p.elem_stride, p.line_stride, p.tiles_per_row, p.row_stride, inverse, p.p_fastest);
     MTD_LAUNCH_CHECK();
     return MTD_SUCCESS;
+    }
+
+// The order in which the templated kernels are FIRST NAMED in this file is the order of their code in the library, and a kernel's
+// time depends on where its code lies: with the same instructions, k_tile_bin<float4, 1, 2> took 19.1 instead of 18.2 us per step
+// when two kernels moved in front of it (profiles/r11/README.md).  So the order is set by these two tables and not by the structure of
+// the host code: name no templated kernel above them.  To verify: the kernel labels of `hipcc -S --cuda-device-only` of this file, in
+// file order, are profiles/r11/mesh_kernel_order.txt (k_fft_lines above comes first, k_fft_z_spectral<true, 1> of the slab path last).
+template<typename K> const void *fn(K *kernel) { return (const void *)kernel; }
+// the instantiations of k_tile_bin (S4 x rider kind x tiles per thread), for dyn_lds_ok
+const void *const bin_fns[24] = {
+    fn(k_tile_bin<float4, 1, 0>), fn(k_tile_bin<float4, 2, 0>), fn(k_tile_bin<float4, 4, 0>), fn(k_tile_bin<float4, 8, 0>), fn(k_tile_bin<float4, 1, 1>), fn(k_tile_bin<float4, 2, 1>),
+    fn(k_tile_bin<float4, 4, 1>), fn(k_tile_bin<float4, 8, 1>), fn(k_tile_bin<float4, 1, 2>), fn(k_tile_bin<float4, 2, 2>), fn(k_tile_bin<float4, 4, 2>), fn(k_tile_bin<float4, 8, 2>),
+    fn(k_tile_bin<double4, 1, 0>), fn(k_tile_bin<double4, 2, 0>), fn(k_tile_bin<double4, 4, 0>), fn(k_tile_bin<double4, 8, 0>), fn(k_tile_bin<double4, 1, 1>), fn(k_tile_bin<double4, 2, 1>),
+    fn(k_tile_bin<double4, 4, 1>), fn(k_tile_bin<double4, 8, 1>), fn(k_tile_bin<double4, 1, 2>), fn(k_tile_bin<double4, 2, 2>), fn(k_tile_bin<double4, 4, 2>), fn(k_tile_bin<double4, 8, 2>) };
+[[maybe_unused]] const void *const KERNEL_ORDER[] = {
+    fn(k_tile_scatter<float4>), fn(k_tile_scatter<double4>), fn(k_tile_count<float4, true, true>), fn(k_tile_count<float4, true, false>), fn(k_tile_count<double4, true, true>),
+    fn(k_tile_count<double4, true, false>), fn(k_tile_count<float4, false, false>), fn(k_tile_count<double4, false, false>), fn(k_tile_place_sorted<float4>),
+    fn(k_tile_place_sorted<double4>), fn(k_tile_place<float4>), fn(k_tile_place<double4>), fn(k_mesh_bin<float4>), fn(k_mesh_bin<double4>), fn(k_mesh_place<float4>),
+    fn(k_mesh_place<double4>), fn(k_fft_xy_forward<false>), fn(k_fft_xy_forward<true>), fn(k_fft_z_spectral<false, 1>), fn(k_fft_z_spectral<false, 3>), fn(k_fft_z_spectral<false, 2>),
+    fn(k_tile_forces<float4>), fn(k_tile_forces<double4>), fn(k_mesh_forces<float4>), fn(k_mesh_forces<double4>), fn(k_tile_forces_chain<float4, 1, true>),
+    fn(k_tile_forces_chain<float4, 2, true>), fn(k_tile_forces_chain<float4, 3, true>), fn(k_tile_forces_chain<float4, 1, false>), fn(k_tile_forces_chain<float4, 2, false>),
+    fn(k_tile_forces_chain<float4, 3, false>), fn(k_tile_forces_chain<double4, 1, true>), fn(k_tile_forces_chain<double4, 2, true>), fn(k_tile_forces_chain<double4, 3, true>),
+    fn(k_tile_forces_chain<double4, 1, false>), fn(k_tile_forces_chain<double4, 2, false>), fn(k_tile_forces_chain<double4, 3, false>) };
+
+// x passes (k_fft_x_r2c, k_fft_x_c2r) over `n_planes` planes: two real lines per complex transform, `tile` real lines per block (the
+// last block may run short)
+struct FftXPass { unsigned int n_lines, tile, blocks; size_t lds; };
+FftXPass fft_x_pass(const mtd_mesh *m, unsigned int n_planes, unsigned int pairs = 8)
+    {
+    // 8 pairs = 16 real lines per block: at nx = 128 that is 16.5 KB of LDS and 1024 blocks — four per compute unit, so that
+    // one block loads while another transforms and a third stores (16 pairs: 512 blocks, 12.0 + 12.2 us; 8: 10.4 + 10.9)
+    while (pairs > 1 && fft_x_lds_bytes(m->nx, pairs) > 64 * 1024) pairs >>= 1;
+    const unsigned int n_lines = m->ny * n_planes, tile = 2 * pairs;
+    return {n_lines, tile, (n_lines + tile - 1) / tile, fft_x_lds_bytes(m->nx, pairs)};
     }
 
 FastDiv fast_div(unsigned int d)
@@ -3618,8 +3664,7 @@ bool xy_tiles_ok(const mtd_mesh *m, XYTiles &tl)
         tl.tile_mul[a] = (unsigned int)tile_mul[a];
         tl.loc_mul[a] = (unsigned int)loc_mul[a];
         }
-    tl.buf = m->d_tilebuf;
-    tl.inv_scale = tg.inv_scale;
+    tl.buf = m->d_tilebuf;                                              // (inv_scale: set where the transform is launched)
     return true;
     }
 
@@ -3686,6 +3731,443 @@ bool xy_split_plan(const mtd_mesh *m, XYSplit &pl, size_t &lds)
     return lds <= XY_LDS_MAX && (size_t)pl.hx * pl.rows <= (size_t)XYS_SLOTS * XY_THREADS && (size_t)pl.hx * pl.rows * pl.hx < (1ull << 32);
     }
 
+// Raise the dynamic-LDS limit of a group of kernels once per DEVICE (a function attribute belongs to the device that is current when
+// it is set; a process that drives several GPUs sets it on each).  A runtime that refuses leaves the caller its fallback path.
+bool dyn_lds_ok(const int group, const void *const *fns, const int n, const size_t bytes)
+    {
+    static std::mutex mu;
+    static std::map<std::pair<int, int>, bool> done;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return false;
+    std::lock_guard<std::mutex> lock(mu);
+    const auto key = std::make_pair(dev, group);
+    auto it = done.find(key);
+    if (it != done.end()) return it->second;
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < n && e == hipSuccess; ++i) e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) (void)hipGetLastError();
+    done[key] = e == hipSuccess;
+    return e == hipSuccess;
+    }
+
+// ---- which transform kernels a mesh takes: one function per question
+// MTD_FFT_SPLIT=0: the unsplit x/y kernels, forward and inverse (read per call: a test runs both forms in one process)
+bool fft_split_off() { const char *e = std::getenv("MTD_FFT_SPLIT"); return e && e[0] == '0'; }
+
+// x and y of a plane in one launch where the plane fits the LDS (k_fft_xy_*), with the plans of both directions; MTD_FFT_XY=0 keeps
+// the separate passes
+struct XYFused { bool on; XYPlan f, i; size_t lds_f, lds_i; };
+void xy_fused(const mtd_mesh *m, XYFused &xy)
+    {
+    static const bool off = [] { const char *e = std::getenv("MTD_FFT_XY"); return e && e[0] == '0'; }();
+    // (a runtime that refuses the 160 KB of dynamic LDS leaves the separate passes, it does not fail the step)
+    static const void *const xy_fns[5] = { (const void *)k_fft_xy_forward<false>, (const void *)k_fft_xy_inverse, (const void *)k_fft_xy_forward<true>,
+                                           (const void *)k_fft_xy_inverse_split, (const void *)k_fft_xy_forward_split };
+    const bool lds_ok = dyn_lds_ok(2, xy_fns, 5, XY_LDS_MAX);
+    xy.on = !off && lds_ok && xy_plan(m, 0, xy.f, xy.lds_f) && xy_plan(m, 1, xy.i, xy.lds_i);
+    }
+
+// Does the forward transform read the per-tile images itself (the assignment then leaves the combine launch out)?  Asked once per
+// call of the interface: by mtd_mesh_compute_cv before it assigns, by mtd_mesh_spectral unless the real mesh is valid (`rho_valid`:
+// then no switch is read).  Fills p.xy either way.
+enum FwdTiles { FWD_COMBINED = 0, FWD_TILES, FWD_TILES_SPLIT };
+struct FwdPlan { XYFused xy; XYTiles tiles; XYSplitF split; size_t split_lds; };
+FwdTiles fft_forward_from_tiles(const mtd_mesh *m, FwdPlan &p, const bool rho_valid = false)
+    {
+    xy_fused(m, p.xy);
+    // (the row class of a thread's elements must not change over its elements nor over the batches: k_fft_xy_forward<true>)
+    // (two cells per lane: a wave spans a line of 128 cells; a thread's line pairs are 8 apart, the batches 32: multiples of the tile height)
+    const bool tile_rows_ok = p.xy.on && m->nx == 128 && XY_THREADS == 512 && p.xy.f.pb == 32 && m->tg.ty && 16 % m->tg.ty == 0 && (2 * p.xy.f.pb) % m->tg.ty == 0;
+    if (rho_valid || !tile_rows_ok || !xy_tiles_ok(m, p.tiles)) return FWD_COMBINED;
+    return !fft_split_off() && xy_split_plan_f(m, p.split, p.split_lds) ? FWD_TILES_SPLIT : FWD_TILES;
+    }
+
+// the inverse x/y launch of the fused path: split by the parity of its output rows (the default) or unsplit
+bool fft_inverse_split(const mtd_mesh *m, XYSplit &pl, size_t &lds) { return !fft_split_off() && xy_split_plan(m, pl, lds); }
+
+// the assignment's first kernel (k_tile_bin, k_tile_count): 4096 particles per block
+unsigned int assign_blocks(const mtd_mesh *m, unsigned int N) { return std::min(std::max((N + 4095) / 4096, 1u), m->tile_blocks_max); }
+// the tile force passes: a block per tile, rounded up to a multiple of 8
+unsigned int tile_force_blocks(const mtd_mesh *m) { return 8 * ((m->tg.n_tiles + 7) / 8); }
+
+// ---- mtd_mesh_create, step by step
+// tile path (k_tile_*): tiles of 64x8x8 cells clamped to the mesh; MTD_MESH_ASSIGN=cells keeps the cell-level pipeline
+void create_tile_geom(mtd_mesh *m, const double *mode)
+    {
+    const unsigned int nx = m->nx, ny = m->ny, nz = m->nz;
+    TileGeom &tg = m->tg;
+    tg.tx = nx < (unsigned int)TP_X ? nx : TP_X; tg.ty = ny < (unsigned int)TP_Y ? ny : TP_Y; tg.tz = nz < (unsigned int)TP_Z ? nz : TP_Z;
+    // a block per tile: a small mesh in 64x8x8 tiles gives the scatter and force passes fewer blocks than there are compute
+    // units (64^3: 128); halve the longest tile edge (not below 8) until there are at least two blocks per CU or 8^3 is reached
+    auto count_tiles = [&](const TileGeom &t) { return (unsigned long long)((nx + t.tx - 1) / t.tx) * ((ny + t.ty - 1) / t.ty) * ((nz + t.tz - 1) / t.tz); };
+    // (more, smaller tiles than that cost more than they bring: 128^3 in 2048 / 4096 tiles 191.7 / 208.6 us per step against 171.9)
+    while (count_tiles(tg) < 512 && (tg.tx > 8 || tg.ty > 8 || tg.tz > 8))
+        {
+        if (tg.tx >= tg.ty && tg.tx >= tg.tz && tg.tx > 8) tg.tx /= 2;
+        else if (tg.ty >= tg.tz && tg.ty > 8) tg.ty /= 2;
+        else if (tg.tz > 8) tg.tz /= 2;
+        else if (tg.tx > 8) tg.tx /= 2;
+        else tg.ty /= 2;
+        }
+    tg.ntx = (nx + tg.tx - 1) / tg.tx; tg.nty = (ny + tg.ty - 1) / tg.ty; tg.ntz = (nz + tg.tz - 1) / tg.tz;
+    const unsigned long long nt = (unsigned long long)tg.ntx * tg.nty * tg.ntz;
+    tg.hx = tg.tx + 2; tg.hy = tg.ty + 2; tg.hz = tg.tz + 2; tg.hcells = tg.hx * tg.hy * tg.hz;
+    const char *env = std::getenv("MTD_MESH_ASSIGN");
+    m->tile_path = nt <= TP_MAX_TILES && m->n_types <= 65536 && !(env && std::strcmp(env, "cells") == 0);   // (16 bits of a record hold the type)
+    tg.n_tiles = m->tile_path ? (unsigned int)nt : 0;
+    m->tile_blocks_max = std::min(std::max((m->max_particles + 4095) / 4096, 1u), 1024u);
+    m->amax = 0.0;
+    for (unsigned int t = 0; t < m->n_types; ++t) m->amax = std::fmax(m->amax, std::fabs(mode[t]));
+    }
+
+// one allocation for every device array of the mesh, cleared; on failure m->slab is null or the caller's to free
+hipError_t create_slab(mtd_mesh *m)
+    {
+    const unsigned int nx = m->nx, ny = m->ny, nz = m->nz;
+    const size_t M = m->M, N = m->max_particles, MH = (size_t)m->hxp * ny * nz, T = m->tg.n_tiles;
+    const size_t n_scan = std::max<size_t>(M, T * m->tile_blocks_max);   // entries the scan kernels may see
+    const size_t n_scan_tiles = (n_scan + SCAN_TILE - 1) / SCAN_TILE;
+    // tile-ordered arrays (ids, position records, force records): all segments' slots of the bin pipeline + an overflow list of N
+    const size_t n_slots = N + (m->tile_path ? tile_capacity_total_max(N, m->tg.n_tiles) : 0);
+    const size_t n_cursors = (size_t)TB_TILES_PER_MAX * TB_THREADS * TB_CSTRIDE;                  // (with the idle lanes' cursors)
+    // One entry per array: the pointer that is to point at it and its bytes.  The ORDER of the entries is the layout; every array is
+    // aligned to 256 bytes.
+    void *psort = nullptr;
+    unsigned int *q = nullptr, *ovf_tile = nullptr;
+    struct Part { void *pointer; size_t bytes; };
+    const Part parts[] = {
+        {&m->d_mode, sizeof(double) * m->n_types}, {&m->d_rho, sizeof(double) * (M + 1)}, {&m->d_modesq_partials, sizeof(double) * m->n_count_blocks},
+        {&m->d_cv_partials, sizeof(double) * m->n_cv_partials}, {&m->d_cv_folded, sizeof(double) * ((size_t)nz * XY_PARTS + 1)}, {&m->d_f, sizeof(double2) * MH},
+        {&m->d_g, sizeof(double2) * MH}, {&m->d_tw[0], sizeof(double2) * nx}, {&m->d_tw[1], sizeof(double2) * ny}, {&m->d_tw[2], sizeof(double2) * nz},
+        {&m->d_packed, sizeof(double4) * n_slots}, {&m->d_cell_of, sizeof(unsigned int) * N}, {&m->d_count, sizeof(unsigned int) * (n_scan + 1)},
+        {&m->d_start, sizeof(unsigned int) * (n_scan + 1)}, {&m->d_idcell, sizeof(uint2) * N}, {&m->d_tile_sums, sizeof(unsigned int) * n_scan_tiles},
+        {&m->d_inv, sizeof(double) * M}, {&m->d_slot_of, sizeof(unsigned int) * N}, {&m->d_itab, sizeof(double) * (nx + ny + nz)},
+        {&m->d_tilebuf, sizeof(long long) * T * m->tg.hcells}, {&m->d_ids, sizeof(unsigned int) * n_slots}, {&m->d_tsrc, sizeof(uint4) * (nx + ny + nz)},
+        {&m->d_tile_total, sizeof(unsigned int) * 2 * (T + 1)}, {&psort, m->tile_path ? sizeof(double4) * n_slots : 0},
+        {&q, m->tile_path ? sizeof(unsigned int) * (4 * T + 2 * n_cursors + 2 * TB_CSTRIDE) : 0}, {&ovf_tile, m->tile_path ? sizeof(unsigned int) * N : 0} };
+    size_t bytes = 0;
+    for (const Part &part : parts) bytes += (part.bytes + 255) / 256 * 256;
+    const hipError_t e = hipMalloc(&m->slab, bytes);
+    if (e != hipSuccess)
+        {
+        m->slab = nullptr;
+        return e;
+        }
+    if (const char *tr = std::getenv("MTD_TRACE_ALLOC")) if (tr[0] == '1') fprintf(stderr, "[mtd] mesh %ux%ux%u slab %p .. %p (%zu bytes)\n", nx, ny, nz, m->slab, (char *)m->slab + bytes, bytes);
+    char *at = (char *)m->slab;
+    for (const Part &part : parts)
+        {
+        std::memcpy(part.pointer, &at, sizeof(at));                // (every entry names an object pointer)
+        at += (part.bytes + 255) / 256 * 256;
+        }
+    m->d_mode_sq = m->d_rho + M;   // directly behind the real mesh: one exchange buffer of M + 1 doubles
+    m->d_tile_first = m->d_tile_total + T + 1;
+    if (m->tile_path)
+        {
+        m->d_possorted = psort;
+        for (int i = 0; i < 2; ++i) { m->d_plan_first[i] = q; q += T; m->d_plan_cap[i] = q; q += T; }
+        for (int i = 0; i < 2; ++i) { m->d_cursor[i] = q; q += n_cursors; }
+        for (int i = 0; i < 2; ++i) { m->d_ovf_count[i] = q; q += TB_CSTRIDE; }
+        m->d_ovf_tile = ovf_tile;
+        m->ovf_base = (unsigned int)(n_slots - N);
+        }
+    return hipMemset(m->slab, 0, bytes);
+    }
+
+// per-axis table of the tile-buffer offsets that stand for a mesh coordinate (k_tile_combine); sets combine_two
+hipError_t create_combine_table(mtd_mesh *m)
+    {
+    // entry offset = tile * hcells + lx + hx (ly + hy lz) with tile = tx + ntx (ty + nty tz): one term per axis
+    std::vector<unsigned int> tab(4 * (size_t)(m->nx + m->ny + m->nz), 0u);
+    m->combine_two = true;
+    const TileGeom &tg = m->tg;
+    const unsigned int dims[3] = {m->nx, m->ny, m->nz}, tws[3] = {tg.tx, tg.ty, tg.tz}, nts[3] = {tg.ntx, tg.nty, tg.ntz};
+    const unsigned long long tile_mul[3] = {1ull * tg.hcells, 1ull * tg.ntx * tg.hcells, 1ull * tg.ntx * tg.nty * tg.hcells};
+    const unsigned long long loc_mul[3] = {1ull, tg.hx, 1ull * tg.hx * tg.hy};
+    size_t o = 0;
+    for (int a = 0; a < 3; ++a)
+        for (unsigned int c = 0; c < dims[a]; ++c, ++o)
+            {
+            const unsigned int n = dims[a], tw = tws[a], nt = nts[a];
+            const unsigned int t0 = c / tw, first = t0 * tw, width = std::min(tw, n - first);
+            unsigned int k = 0;
+            auto put = [&](unsigned int tile, unsigned int loc) { tab[4 * o + k++] = (unsigned int)(tile * tile_mul[a] + loc * loc_mul[a]); };
+            put(t0, c - first + 1);
+            if (c == first)
+                {
+                const unsigned int tl = t0 == 0 ? nt - 1 : t0 - 1;
+                put(tl, std::min(tw, n - tl * tw) + 1);
+                }
+            if (c == first + width - 1) put(t0 == nt - 1 ? 0 : t0 + 1, 0);
+            tab[4 * o + 3] = k;
+            if (k > 2) m->combine_two = false;
+            }
+    return hipMemcpy(m->d_tsrc, tab.data(), sizeof(unsigned int) * tab.size(), hipMemcpyHostToDevice);
+    }
+
+// twiddles exp(-2 pi i j / n), j < n (the radix-2 stages use the first half), in double on the host
+hipError_t create_twiddles(mtd_mesh *m)
+    {
+    const unsigned int dims[3] = {m->nx, m->ny, m->nz};
+    hipError_t e = hipSuccess;
+    for (int a = 0; a < 3 && e == hipSuccess; ++a)
+        {
+        std::vector<double> tw(2 * (size_t)dims[a], 0.0);
+        for (unsigned int j = 0; j < dims[a]; ++j)
+            {
+            const double ang = -2.0 * M_PI * (double)j / (double)dims[a];
+            tw[2 * j] = std::cos(ang);
+            tw[2 * j + 1] = std::sin(ang);
+            }
+        e = hipMemcpy(m->d_tw[a], tw.data(), sizeof(double) * tw.size(), hipMemcpyHostToDevice);
+        }
+    return e;
+    }
+
+// per-tile images -> the real mesh (tile path); afterwards d_rho holds the last assignment
+int mesh_combine(mtd_mesh *m, hipStream_t s)
+    {
+    MeshGeom g;
+    std::memset(&g, 0, sizeof(g));
+    g.nx = m->nx; g.ny = m->ny; g.nz = m->nz; g.hxp = m->hxp;           // (the combine pass reads the dimensions only)
+    const unsigned int cthreads = m->nx >= 256 ? 256 : (m->nx > 64 ? 128 : 64);
+    if (m->combine_two)
+        k_tile_combine_rows<<<dim3((m->nx + cthreads - 1) / cthreads, (m->ny + TCB_ROWS - 1) / TCB_ROWS, m->nz), cthreads, 0, s>>>(g, m->tg, m->d_tilebuf, m->d_tsrc, m->d_rho);
+    else
+        k_tile_combine<<<dim3((m->nx + cthreads - 1) / cthreads, m->ny, m->nz), cthreads, 0, s>>>(g, m->tg, m->d_tilebuf, m->d_tsrc, m->d_rho);
+    MTD_LAUNCH_CHECK();
+    m->rho_valid = 1;
+    return MTD_SUCCESS;
+    }
+
+// whoever reads d_rho (the separate transform passes, the replicated-mesh exchange, mtd_mesh_get_array(0)) after an assignment that
+// left the mesh in the tile images only
+int mesh_need_rho(mtd_mesh *m, hipStream_t s)
+    {
+    return m->rho_valid || !m->tile_path ? MTD_SUCCESS : mesh_combine(m, s);
+    }
+
+template<int V> using int_c = std::integral_constant<int, V>;
+
+// The three pipelines.  Each leaves its LAST launch unchecked to mesh_assign_local; the tile pipelines read tg.n_blocks, chunk and
+// scale as mesh_assign_local set them for N.
+// ---- bin pipeline (steady state): one launch bins, sorts and stores the chunk; the scatter launch's extra block plans the next
+// snapshot.  Needs a plan for this particle number (the first assignment of a mesh goes through the counting pipeline and
+// plans from its exact counts), no riders of the counting kernel's own loop, a chunk and tables that fit the LDS (tb_lds).
+template<typename S4> int assign_bin(mtd_mesh *m, const MeshGeom &g, const unsigned int N, const S4 *postype, const size_t tb_lds, hipStream_t s)
+    {
+    const TileGeom &tg = m->tg;
+    const unsigned int nb = tg.n_blocks;
+    const int p = m->bin_parity;
+    mtd::MetadCfg apply_cfg{};                                       // (read by the scatter launch's passenger blocks only)
+    int rider_kind = 0;
+    unsigned int n_apply = 0;
+    if (m->rider_armed)
+        {
+        rider_kind = m->rider_fast ? 2 : 1;
+        if (m->rider_n_apply)
+            {
+            apply_cfg = m->h_rider->cfg;
+            n_apply = (apply_cfg.len + TP_THREADS - 1) / TP_THREADS;
+            }
+        m->rider_armed = 0;
+        if (m->rider_engine && m->rider_n_apply) m->rider_engine->pending_apply = 0;
+        }
+    // no riders: an engine that announced a pending deferred pass on this stream (a mesh variable without lamellar CVs beside
+    // it: mtd_mesh_forces_update_bias, mtd_metad_update_bias) still gets it carried by the scatter launch's extra blocks
+    mtd_metad *passenger = nullptr;
+    if (!n_apply && !rider_kind)
+        {
+        passenger = mtd::take_pending_apply(s, apply_cfg);
+        if (passenger) n_apply = (apply_cfg.len + TP_THREADS - 1) / TP_THREADS;
+        }
+    BinRiderArgs ra;
+    BinNoRider no_rider;
+    if (rider_kind)
+        {
+        ra.k = mtd::dense_cv_args(m->h_rider->k);                // (the visited modes as a dense list: flat table loads)
+        ra.partials = m->h_rider->partials;
+        }
+    // k_tile_bin<S4, PER, R>: PER tiles per thread of the prefix, the smallest of 1 | 2 | 4 | 8 that holds them all; R the rider kind
+    const unsigned int tiles_per = (tg.n_tiles + TB_THREADS - 1) / TB_THREADS;
+    auto with_per = [&](auto &&f) { return tiles_per <= 1 ? f(int_c<1>{}) : tiles_per <= 2 ? f(int_c<2>{}) : tiles_per <= 4 ? f(int_c<4>{}) : f(int_c<8>{}); };
+    with_per([&](auto per)
+        {
+        auto launch = [&](auto r, const auto &rider)
+            {
+            k_tile_bin<S4, decltype(per)::value, decltype(r)::value><<<nb, TB_THREADS, tb_lds, s>>>(g, tg, postype, N, m->d_mode, m->n_types, m->d_plan_first[p], m->d_plan_cap[p],
+                m->d_cursor[p], m->d_ovf_count[p], m->d_ovf_tile, m->ovf_base, m->d_ids, (S4 *)m->d_possorted, m->d_modesq_partials, rider);
+            };
+        return rider_kind == 2 ? launch(int_c<2>{}, ra) : rider_kind == 1 ? launch(int_c<1>{}, ra) : launch(int_c<0>{}, no_rider);
+        });
+    MTD_LAUNCH_CHECK();
+    TileLists L;
+    L.first = m->d_plan_first[p]; L.count = m->d_cursor[p]; L.cap = m->d_plan_cap[p]; L.ovf_count = m->d_ovf_count[p];
+    L.ovf_tile = m->d_ovf_tile; L.cstride = TB_CSTRIDE; L.ovf_base = m->ovf_base;
+    TilePlan plan{};
+    plan.count = m->d_cursor[p]; plan.cstride = TB_CSTRIDE; plan.n_tiles = tg.n_tiles;
+    plan.first_next = m->d_plan_first[1 - p]; plan.cap_next = m->d_plan_cap[1 - p];
+    plan.cursor_next = m->d_cursor[1 - p]; plan.ovf_count_next = m->d_ovf_count[1 - p]; plan.cstride_next = TB_CSTRIDE;
+    plan.modesq_partials = m->d_modesq_partials; plan.n_partials = nb; plan.mode_sq = m->d_mode_sq;
+    k_tile_scatter<S4><<<tg.n_tiles + 1 + n_apply, TP_THREADS, 0, s>>>(g, tg, postype, m->d_mode, L, m->d_ids, m->d_tilebuf, m->d_packed, m->n_types, (const S4 *)m->d_possorted, plan, apply_cfg);
+    if (passenger && hipPeekAtLastError() == hipSuccess) mtd::commit_pending_apply(passenger);     // (a failed launch leaves the pass pending)
+    m->lists = L;
+    m->plan_n = N;
+    m->last_pipeline = 2;
+    m->bin_parity = 1 - p;                                       // (planned and zeroed by the extra block)
+    return MTD_SUCCESS;
+    }
+
+// ---- counting pipeline: count (with the riders), row scan, place, scatter; with `plan_next` its exact counts plan the segments of the
+// next snapshot's bin pipeline
+template<typename S4> int assign_counting(mtd_mesh *m, const MeshGeom &g, const unsigned int N, const S4 *postype, const bool plan_next, hipStream_t s)
+    {
+    const TileGeom &tg = m->tg;
+    const unsigned int nb = tg.n_blocks;
+    const size_t lds = sizeof(unsigned int) * tg.n_tiles;
+    unsigned int n_apply_blocks = 0;
+    auto count = [&](auto rider, auto fast)
+        {
+        k_tile_count<S4, decltype(rider)::value, decltype(fast)::value><<<nb, TC_THREADS, lds, s>>>(g, tg, postype, N, m->d_mode, m->d_cell_of, m->d_slot_of,
+                                                                                                 m->d_count, m->d_modesq_partials, m->n_types, m->d_rider);
+        };
+    if (m->rider_armed)
+        {
+        if (m->rider_dirty)
+            {
+            MTD_HIP_TRY(hipMemcpyAsync(m->d_rider, m->h_rider, sizeof(CountRider), hipMemcpyHostToDevice, s));
+            m->rider_dirty = 0;
+            }
+        n_apply_blocks = m->rider_n_apply;
+        mtd::dispatch_bool(m->rider_fast != 0, [&](auto fast) { count(std::true_type{}, fast); });
+        m->rider_armed = 0;
+        if (m->rider_engine && m->rider_n_apply) m->rider_engine->pending_apply = 0;
+        }
+    else
+        count(std::false_type{}, std::false_type{});
+    MTD_LAUNCH_CHECK();
+    k_tile_rowscan<<<tg.n_tiles + 1 + n_apply_blocks, 256, 0, s>>>(m->d_count, m->d_start, m->d_tile_total, tg.n_tiles, nb, m->d_modesq_partials, nb, m->d_mode_sq, m->d_rider);
+    MTD_LAUNCH_CHECK();
+    const unsigned int pb = std::min(std::max((N + 1023) / 1024, 1u), 512u);   // >= four particles per thread: the LDS prefix of the tile totals is formed once per block
+    // sorted place (the default): raw position records and ids leave in tile order, in runs; MTD_MESH_PLACE=ids keeps the
+    // one-store-per-particle form, which is also the fallback when a chunk or the tables do not fit
+    const size_t ps_lds = place_sorted_lds_bytes<S4>(tg.n_tiles, tg.chunk);
+    const char *ps_env = std::getenv("MTD_MESH_PLACE");           // (read per call: a test runs both forms in one process)
+    const bool ps_off = ps_env && std::strcmp(ps_env, "ids") == 0;
+    static const void *const ps_fns[2] = { (const void *)k_tile_place_sorted<float4>, (const void *)k_tile_place_sorted<double4> };
+    const bool ps_lds_ok = dyn_lds_ok(1, ps_fns, 2, PS_LDS_MAX);
+    const bool sorted = !ps_off && ps_lds_ok && m->d_possorted && tg.chunk <= TPS_CHUNK_MAX && ps_lds <= PS_LDS_MAX;
+    if (sorted)
+        k_tile_place_sorted<S4><<<nb, TPS_THREADS, ps_lds, s>>>(tg, N, postype, m->d_cell_of, m->d_slot_of, m->d_count, m->d_start, m->d_tile_total, m->d_ids, (S4 *)m->d_possorted, m->d_tile_first);
+    else
+        k_tile_place<S4><<<pb, 256, sizeof(unsigned int) * tg.n_tiles, s>>>(tg, N, m->d_cell_of, m->d_slot_of, m->d_start, m->d_tile_total, m->d_ids, m->d_tile_first);
+    MTD_LAUNCH_CHECK();
+    TileLists L{};
+    L.first = m->d_tile_first; L.count = m->d_tile_total; L.cstride = 1;
+    TilePlan plan{};
+    mtd::MetadCfg apply_cfg{};                                       // (this pipeline's scatter launch has no extra blocks)
+    k_tile_scatter<S4><<<tg.n_tiles, TP_THREADS, 0, s>>>(g, tg, postype, m->d_mode, L, m->d_ids, m->d_tilebuf, m->d_packed, m->n_types, sorted ? (const S4 *)m->d_possorted : nullptr, plan, apply_cfg);
+    m->lists = L;
+    m->last_pipeline = 1;
+    if (plan_next)
+        {
+        // the exact counts of this snapshot plan the segments of the next one
+        MTD_LAUNCH_CHECK();
+        const int p = m->bin_parity;
+        plan.count = m->d_tile_total; plan.cstride = 1; plan.n_tiles = tg.n_tiles;
+        plan.first_next = m->d_plan_first[p]; plan.cap_next = m->d_plan_cap[p];
+        plan.cursor_next = m->d_cursor[p]; plan.ovf_count_next = m->d_ovf_count[p]; plan.cstride_next = TB_CSTRIDE;
+        k_tile_plan<<<1, 1024, 0, s>>>(plan);
+        m->plan_valid = 1;
+        m->plan_n = N;
+        }
+    return MTD_SUCCESS;
+    }
+
+// ---- cell-level pipeline (meshes with more than 8192 tiles, MTD_MESH_ASSIGN=cells): the gather pass writes d_rho itself
+template<typename S4> int assign_cells(mtd_mesh *m, const MeshGeom &g, const unsigned int N, const S4 *postype, hipStream_t s)
+    {
+    const unsigned int M = m->M;
+    const unsigned int cell_blocks = (M + 255) / 256;
+    const unsigned int n_tiles = (M + SCAN_TILE - 1) / SCAN_TILE;
+    // the counters are zero on entry: cleared at creation and by k_scan_finish of the previous call
+    k_mesh_bin<S4><<<m->n_count_blocks, 256, 0, s>>>(g, postype, N, m->d_mode, m->d_cell_of, m->d_slot_of, m->d_count, m->d_modesq_partials);
+    MTD_LAUNCH_CHECK();
+    k_scan_tiles<<<n_tiles + 1, 256, 0, s>>>(m->d_count, m->d_start, m->d_tile_sums, M, m->d_modesq_partials, m->n_count_blocks, m->d_mode_sq);
+    MTD_LAUNCH_CHECK();
+    k_scan_finish<<<n_tiles, 256, 0, s>>>(m->d_start, m->d_tile_sums, m->d_count, M, N);
+    MTD_LAUNCH_CHECK();
+    k_mesh_place<S4><<<m->n_count_blocks, 256, 0, s>>>(g, postype, N, m->d_mode, m->d_cell_of, m->d_slot_of, m->d_start, m->d_idcell, m->d_packed);
+    MTD_LAUNCH_CHECK();
+    k_mesh_sortfix<<<cell_blocks, 256, 0, s>>>(M, m->d_start, m->d_idcell, m->d_packed);
+    MTD_LAUNCH_CHECK();
+    GatherTiling tl;
+    tl.tx = m->nx < (unsigned int)GT_X ? m->nx : GT_X;
+    tl.ty = m->ny < (unsigned int)GT_Y ? m->ny : GT_Y;
+    tl.tz = m->nz < (unsigned int)GT_Z ? m->nz : GT_Z;
+    tl.ntx = (m->nx + tl.tx - 1) / tl.tx; tl.nty = (m->ny + tl.ty - 1) / tl.ty; tl.ntz = (m->nz + tl.tz - 1) / tl.tz;   // edge tiles may be partial
+    k_mesh_gather<<<tl.ntx * tl.nty * tl.ntz, GT_THREADS, 0, s>>>(g, tl, m->d_start, m->d_packed, m->d_rho);
+    return MTD_SUCCESS;
+    }
+
+// One snapshot onto the mesh.  `combine` = false leaves a tile pipeline's result in the per-tile images (rho_valid = 0).
+int mesh_assign_local(mtd_mesh *m, unsigned int n_particles, const void *d_postype, int dtype, const mtd_box *box, mtd_stream_t stream, bool combine = true)
+    {
+    if (!m || (n_particles && !d_postype)) return MTD_ERR_INVALID_ARGUMENT;
+    if (dtype != MTD_F32 && dtype != MTD_F64) return MTD_ERR_INVALID_ARGUMENT;
+    if (n_particles > m->max_particles) return MTD_ERR_INVALID_ARGUMENT;
+    MeshGeom g;
+    int rc = fill_geom(g, m, box);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned int N = n_particles;
+    size_t tb_lds = 0;
+    bool bin_fits = false, plan_usable = false, rider_in_count = false;
+    if (m->tile_path)
+        {
+        TileGeom &tg = m->tg;
+        const unsigned int nb = assign_blocks(m, N);
+        tg.n_blocks = nb;
+        tg.chunk = N ? (N + nb - 1) / nb : 1;
+        // fixed point: 2^k * N * max|a| < 2^62 even if every particle sat in one cell
+        int k = 40;
+        if (m->amax > 0.0)
+            {
+            k = (int)std::floor(62.0 - std::log2((double)(N ? N : 1) * m->amax)) - 1;
+            const int k_one = 50 - (int)std::ceil(std::log2(m->amax));        // one deposit stays below 2^51 (mantissa rounding)
+            k = k > k_one ? k_one : k;
+            k = k > 60 ? 60 : (k < -900 ? -900 : k);
+            }
+        tg.scale = std::ldexp(1.0, k);
+        tg.inv_scale = std::ldexp(1.0, -k);
+        const char *bin_env = std::getenv("MTD_MESH_BIN");               // (read per call: tests run both pipelines in one process)
+        const bool bin_off = bin_env && bin_env[0] == '0';
+        tb_lds = mtd::dispatch_s4(dtype, [&](auto s4) { return tile_bin_lds_bytes<typename decltype(s4)::type>(tg.n_tiles, tg.chunk); });
+        const bool tb_lds_ok = dyn_lds_ok(0, bin_fns, 24, TB_LDS_MAX);
+        bin_fits = !bin_off && tb_lds_ok && m->d_possorted && tg.chunk <= TPS_CHUNK_MAX && tb_lds <= TB_LDS_MAX &&
+                   tg.n_tiles <= (unsigned int)(TB_TILES_PER_MAX * TB_THREADS);
+        // (riders of the counting kernel's own loop — MTD_MESH_RIDER=count — keep the counting pipeline)
+        const char *rider_env = std::getenv("MTD_MESH_RIDER");
+        rider_in_count = rider_env && std::strcmp(rider_env, "count") == 0;
+        // a plan made for another particle number still is a plan (a domain-decomposed run's local count changes every step: what does
+        // not fit overflows); only a count that differs by a factor of two or more is counted and planned afresh
+        plan_usable = m->plan_valid && N >= m->plan_n / 2 && N / 2 <= m->plan_n;
+        }
+    // 0 cells, 1 counting, 2 bin (mtd_mesh_assign_info's numbers)
+    const int pipeline = !m->tile_path ? 0 : (bin_fits && plan_usable && !(m->rider_armed && rider_in_count) ? 2 : 1);
+    rc = mtd::dispatch_s4(dtype, [&](auto s4)
+        {
+        const auto *postype = (const typename decltype(s4)::type *)d_postype;
+        return pipeline == 2 ? assign_bin(m, g, N, postype, tb_lds, s) : pipeline == 1 ? assign_counting(m, g, N, postype, bin_fits && !plan_usable, s) : assign_cells(m, g, N, postype, s);
+        });
+    if (rc) return rc;
+    MTD_LAUNCH_CHECK();
+    m->n_last = N;
+    m->rho_valid = pipeline == 0;                                    // (the tile pipelines leave the mesh in the per-tile images)
+    if (combine && !m->rho_valid) return mesh_combine(m, s);
+    return MTD_SUCCESS;
+    }
+
 } // namespace
 
 #ifdef MTD_STAMPS
@@ -3722,157 +4204,24 @@ int mtd_mesh_create(mtd_mesh **out, unsigned int nx, unsigned int ny, unsigned i
     m->nx = nx; m->ny = ny; m->nz = nz; m->M = (unsigned int)M64;
     m->n_types = n_types;
     m->max_particles = max_particles;
-    m->bug_compat = 1;
     m->keep_fourier = 1;
-    const size_t M = m->M, N = max_particles;
     m->n_count_blocks = 4096;
-    {
     const unsigned int hx = nx / 2 + 1, unit = nx < 8 ? nx : 8;     // (a pitch of 80 with 16-column tiles measured slower: y 10.5 -> 12.3, z 17.1 -> 20.3 us)
     m->hxp = (hx + unit - 1) / unit * unit;                    // 72 at nx = 128
-    }
-    const size_t MH = (size_t)m->hxp * ny * nz;
     m->n_cv_partials = fft_z_pass(m).n_blocks;                 // one partial sum per block of the fused z pass (an upper bound: the
                                                                // whole-mesh path puts several tiles into a block, fft_z_tpb)
-    // tile path (k_tile_*): tiles of 64x8x8 cells clamped to the mesh; MTD_MESH_ASSIGN=cells keeps the cell-level pipeline
-    {
-    TileGeom &tg = m->tg;
-    tg.tx = nx < (unsigned int)TP_X ? nx : TP_X; tg.ty = ny < (unsigned int)TP_Y ? ny : TP_Y; tg.tz = nz < (unsigned int)TP_Z ? nz : TP_Z;
-    // a block per tile: a small mesh in 64x8x8 tiles gives the scatter and force passes fewer blocks than there are compute
-    // units (64^3: 128); halve the longest tile edge (not below 8) until there are at least two blocks per CU or 8^3 is reached
-    auto count_tiles = [&](const TileGeom &t) { return (unsigned long long)((nx + t.tx - 1) / t.tx) * ((ny + t.ty - 1) / t.ty) * ((nz + t.tz - 1) / t.tz); };
-    // (more, smaller tiles than that cost more than they bring: 128^3 in 2048 / 4096 tiles 191.7 / 208.6 us per step against 171.9)
-    while (count_tiles(tg) < 512 && (tg.tx > 8 || tg.ty > 8 || tg.tz > 8))
+    m->rho_valid = 1;
+    create_tile_geom(m, mode);
+    int rc = (int)create_slab(m);
+    if (!rc && m->tile_path) rc = (int)create_combine_table(m);
+    if (!rc) rc = (int)hipMemcpy(m->d_mode, mode, sizeof(double) * n_types, hipMemcpyHostToDevice);
+    if (!rc) rc = (int)create_twiddles(m);
+    if (!rc) rc = mtd_mesh_set_bug_compat(m, 1);               // the interpolation tables (k_interp_tables); synchronises
+    if (rc)
         {
-        if (tg.tx >= tg.ty && tg.tx >= tg.tz && tg.tx > 8) tg.tx /= 2;
-        else if (tg.ty >= tg.tz && tg.ty > 8) tg.ty /= 2;
-        else if (tg.tz > 8) tg.tz /= 2;
-        else if (tg.tx > 8) tg.tx /= 2;
-        else tg.ty /= 2;
-        }
-    tg.ntx = (nx + tg.tx - 1) / tg.tx; tg.nty = (ny + tg.ty - 1) / tg.ty; tg.ntz = (nz + tg.tz - 1) / tg.tz;
-    const unsigned long long nt = (unsigned long long)tg.ntx * tg.nty * tg.ntz;
-    tg.hx = tg.tx + 2; tg.hy = tg.ty + 2; tg.hz = tg.tz + 2; tg.hcells = tg.hx * tg.hy * tg.hz;
-    const char *env = std::getenv("MTD_MESH_ASSIGN");
-    m->tile_path = nt <= TP_MAX_TILES && n_types <= 65536 && !(env && std::strcmp(env, "cells") == 0);   // (16 bits of a record hold the type)
-    tg.n_tiles = m->tile_path ? (unsigned int)nt : 0;
-    unsigned int nb = (max_particles + 4095) / 4096;
-    m->tile_blocks_max = nb < 1 ? 1 : (nb > 1024 ? 1024 : nb);
-    m->amax = 0.0;
-    for (unsigned int t = 0; t < n_types; ++t) m->amax = std::fmax(m->amax, std::fabs(mode[t]));
-    }
-    const size_t n_scan = std::max<size_t>(m->M, (size_t)m->tg.n_tiles * m->tile_blocks_max);   // entries the scan kernels may see
-    const unsigned int n_tiles = (unsigned int)((n_scan + SCAN_TILE - 1) / SCAN_TILE);
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    // tile-ordered arrays (ids, position records, force records): all segments' slots of the bin pipeline + an overflow list of N
-    const size_t n_slots_extra = m->tile_path ? tile_capacity_total_max(N, m->tg.n_tiles) : 0;
-    size_t off = 0;
-    auto take = [&](size_t b) { size_t o = off; off += al(b); return o; };
-    const size_t o_mode = take(sizeof(double) * n_types), o_rho = take(sizeof(double) * (M + 1)), o_msqp = take(sizeof(double) * m->n_count_blocks), o_cvp = take(sizeof(double) * m->n_cv_partials), o_cvf = take(sizeof(double) * ((size_t)nz * XY_PARTS + 1)), o_f = take(sizeof(double2) * MH),
-                 o_g = take(sizeof(double2) * MH), o_tw0 = take(sizeof(double2) * nx), o_tw1 = take(sizeof(double2) * ny),
-                 o_tw2 = take(sizeof(double2) * nz), o_packed = take(sizeof(double4) * (N + n_slots_extra)), o_cell = take(sizeof(unsigned int) * N),
-                 o_count = take(sizeof(unsigned int) * (n_scan + 1)), o_start = take(sizeof(unsigned int) * (n_scan + 1)),
-                 o_ids = take(sizeof(uint2) * N), o_tiles = take(sizeof(unsigned int) * n_tiles),
-                 o_inv = take(sizeof(double) * M), o_slot = take(sizeof(unsigned int) * N),
-                 o_itab = take(sizeof(double) * (nx + ny + nz)),
-                 o_tilebuf = take(sizeof(long long) * (size_t)m->tg.n_tiles * m->tg.hcells), o_ids2 = take(sizeof(unsigned int) * (N + n_slots_extra)),
-                 o_tsrc = take(sizeof(uint4) * (nx + ny + nz)), o_ttot = take(sizeof(unsigned int) * 2 * ((size_t)m->tg.n_tiles + 1)),
-                 o_psort = take(m->tile_path ? sizeof(double4) * (N + n_slots_extra) : 0),
-                 o_plan = take(m->tile_path ? sizeof(unsigned int) * (4 * (size_t)m->tg.n_tiles + 2 * (size_t)TB_TILES_PER_MAX * TB_THREADS * TB_CSTRIDE + 2 * TB_CSTRIDE) : 0),
-                 o_ovft = take(m->tile_path ? sizeof(unsigned int) * N : 0);
-    hipError_t e = hipMalloc(&m->slab, off);
-    if (e != hipSuccess)
-        {
+        if (m->slab) (void)hipFree(m->slab);
         delete m;
-        return (int)e;
-        }
-    if (const char *tr = std::getenv("MTD_TRACE_ALLOC")) if (tr[0] == '1') fprintf(stderr, "[mtd] mesh %ux%ux%u slab %p .. %p (%zu bytes)\n", nx, ny, nz, m->slab, (char *)m->slab + off, off);
-    char *p = (char *)m->slab;
-    m->d_mode = (double *)(p + o_mode); m->d_rho = (double *)(p + o_rho); m->d_modesq_partials = (double *)(p + o_msqp);
-    m->d_mode_sq = m->d_rho + M;   // directly behind the real mesh: one exchange buffer of M + 1 doubles
-    m->d_cv_partials = (double *)(p + o_cvp); m->d_cv_folded = (double *)(p + o_cvf); m->d_f = (double2 *)(p + o_f);
-    m->d_g = (double2 *)(p + o_g); m->d_tw[0] = (double2 *)(p + o_tw0); m->d_tw[1] = (double2 *)(p + o_tw1);
-    m->d_tw[2] = (double2 *)(p + o_tw2); m->d_packed = (double4 *)(p + o_packed); m->d_cell_of = (unsigned int *)(p + o_cell);
-    m->d_count = (unsigned int *)(p + o_count); m->d_start = (unsigned int *)(p + o_start); m->d_idcell = (uint2 *)(p + o_ids);
-    m->d_tile_sums = (unsigned int *)(p + o_tiles);
-    m->d_inv = (double *)(p + o_inv);
-    m->d_slot_of = (unsigned int *)(p + o_slot);
-    m->d_itab = (double *)(p + o_itab);
-    m->d_tilebuf = (long long *)(p + o_tilebuf);
-    m->d_ids = (unsigned int *)(p + o_ids2);
-    m->d_possorted = m->tile_path ? (void *)(p + o_psort) : nullptr;
-    if (m->tile_path)
-        {
-        const size_t T = m->tg.n_tiles;
-        unsigned int *q = (unsigned int *)(p + o_plan);
-        for (int i = 0; i < 2; ++i) { m->d_plan_first[i] = q; q += T; m->d_plan_cap[i] = q; q += T; }
-        for (int i = 0; i < 2; ++i) { m->d_cursor[i] = q; q += (size_t)TB_TILES_PER_MAX * TB_THREADS * TB_CSTRIDE; }   // (with the idle lanes' cursors)
-        for (int i = 0; i < 2; ++i) { m->d_ovf_count[i] = q; q += TB_CSTRIDE; }
-        m->d_ovf_tile = (unsigned int *)(p + o_ovft);
-        m->ovf_base = (unsigned int)n_slots_extra;
-        }
-    m->plan_valid = 0; m->bin_parity = 0; m->plan_n = 0; m->last_pipeline = 0; m->rho_valid = 1;
-    std::memset(&m->lists, 0, sizeof(m->lists));
-    m->d_tsrc = (uint4 *)(p + o_tsrc);
-    m->d_tile_total = (unsigned int *)(p + o_ttot);
-    m->d_tile_first = m->d_tile_total + m->tg.n_tiles + 1;
-    e = hipMemset(m->slab, 0, off);
-    if (e == hipSuccess && m->tile_path)
-        {
-        // entry offset = tile * hcells + lx + hx (ly + hy lz) with tile = tx + ntx (ty + nty tz): one term per axis
-        std::vector<unsigned int> tab(4 * (size_t)(nx + ny + nz), 0u);
-        m->combine_two = true;
-        const TileGeom &tg = m->tg;
-        const unsigned int dims[3] = {nx, ny, nz}, tws[3] = {tg.tx, tg.ty, tg.tz}, nts[3] = {tg.ntx, tg.nty, tg.ntz};
-        const unsigned long long tile_mul[3] = {1ull * tg.hcells, 1ull * tg.ntx * tg.hcells, 1ull * tg.ntx * tg.nty * tg.hcells};
-        const unsigned long long loc_mul[3] = {1ull, tg.hx, 1ull * tg.hx * tg.hy};
-        size_t o = 0;
-        for (int a = 0; a < 3; ++a)
-            for (unsigned int c = 0; c < dims[a]; ++c, ++o)
-                {
-                const unsigned int n = dims[a], tw = tws[a], nt = nts[a];
-                const unsigned int t0 = c / tw, first = t0 * tw, width = std::min(tw, n - first);
-                unsigned int k = 0;
-                auto put = [&](unsigned int tile, unsigned int loc) { tab[4 * o + k++] = (unsigned int)(tile * tile_mul[a] + loc * loc_mul[a]); };
-                put(t0, c - first + 1);
-                if (c == first)
-                    {
-                    const unsigned int tl = t0 == 0 ? nt - 1 : t0 - 1;
-                    put(tl, std::min(tw, n - tl * tw) + 1);
-                    }
-                if (c == first + width - 1) put(t0 == nt - 1 ? 0 : t0 + 1, 0);
-                tab[4 * o + 3] = k;
-                if (k > 2) m->combine_two = false;
-                }
-        e = hipMemcpy(m->d_tsrc, tab.data(), sizeof(unsigned int) * tab.size(), hipMemcpyHostToDevice);
-        }
-    if (e == hipSuccess) e = hipMemcpy(m->d_mode, mode, sizeof(double) * n_types, hipMemcpyHostToDevice);
-    // twiddles exp(-2 pi i j / n), j < n (the radix-2 stages use the first half), in double on the host
-    const unsigned int dims[3] = {nx, ny, nz};
-    for (int a = 0; a < 3 && e == hipSuccess; ++a)
-        {
-        std::vector<double> tw(2 * (size_t)dims[a], 0.0);
-        for (unsigned int j = 0; j < dims[a]; ++j)
-            {
-            const double ang = -2.0 * M_PI * (double)j / (double)dims[a];
-            tw[2 * j] = std::cos(ang);
-            tw[2 * j + 1] = std::sin(ang);
-            }
-        e = hipMemcpy(m->d_tw[a], tw.data(), sizeof(double) * tw.size(), hipMemcpyHostToDevice);
-        }
-    if (e != hipSuccess)
-        {
-        (void)hipFree(m->slab);
-        delete m;
-        return (int)e;
-        }
-    k_interp_tables<<<(nx + ny + nz + 255) / 256, 256>>>(nx, ny, nz, m->bug_compat, m->d_itab);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess)
-        {
-        (void)hipFree(m->slab);
-        delete m;
-        return (int)e;
+        return rc;
         }
     *out = m;
     return MTD_SUCCESS;
@@ -3903,8 +4252,7 @@ int mtd_mesh_set_lamellar_rider(mtd_mesh *mesh, mtd_metad *engine, const mtd_lam
     std::memset(&r, 0, sizeof(r));
     int rc = mtd::fill_kargs(r.k, set, global_box);
     if (rc) return rc;
-    unsigned int nb = (n_particles + 4095) / 4096;                  // as mesh_assign_local
-    nb = nb < 1 ? 1 : (nb > mesh->tile_blocks_max ? mesh->tile_blocks_max : nb);
+    const unsigned int nb = assign_blocks(mesh, n_particles);
     r.partials = d_partials;
     r.n_apply = 0;
     if (engine)
@@ -3967,288 +4315,9 @@ int mtd_mesh_set_bug_compat(mtd_mesh *m, int on)
     return MTD_SUCCESS;
     }
 
-// Raise the dynamic-LDS limit of a group of kernels once per DEVICE (a function attribute belongs to the device that is current when
-// it is set; a process that drives several GPUs sets it on each).  A runtime that refuses leaves the caller its fallback path.
-static bool dyn_lds_ok(const int group, const void *const *fns, const int n, const size_t bytes)
-    {
-    static std::mutex mu;
-    static std::map<std::pair<int, int>, bool> done;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return false;
-    std::lock_guard<std::mutex> lock(mu);
-    const auto key = std::make_pair(dev, group);
-    auto it = done.find(key);
-    if (it != done.end()) return it->second;
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < n && e == hipSuccess; ++i) e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) (void)hipGetLastError();
-    done[key] = e == hipSuccess;
-    return e == hipSuccess;
-    }
-
-static int mesh_assign_local(mtd_mesh *m, unsigned int n_particles, const void *d_postype, int dtype, const mtd_box *box, mtd_stream_t stream,
-                             bool combine = true);
-
-// per-tile images -> the real mesh (tile path); afterwards d_rho holds the last assignment
-static int mesh_combine(mtd_mesh *m, const MeshGeom &g, hipStream_t s)
-    {
-    const unsigned int cthreads = m->nx >= 256 ? 256 : (m->nx > 64 ? 128 : 64);
-    if (m->combine_two)
-        k_tile_combine_rows<<<dim3((m->nx + cthreads - 1) / cthreads, (m->ny + TCB_ROWS - 1) / TCB_ROWS, m->nz), cthreads, 0, s>>>(g, m->tg, m->d_tilebuf, m->d_tsrc, m->d_rho);
-    else
-        k_tile_combine<<<dim3((m->nx + cthreads - 1) / cthreads, m->ny, m->nz), cthreads, 0, s>>>(g, m->tg, m->d_tilebuf, m->d_tsrc, m->d_rho);
-    MTD_LAUNCH_CHECK();
-    m->rho_valid = 1;
-    return MTD_SUCCESS;
-    }
-
-// whoever reads d_rho (the separate transform passes, the replicated-mesh exchange, mtd_mesh_get_array(0)) after an assignment that
-// left the mesh in the tile images only
-static int mesh_need_rho(mtd_mesh *m, hipStream_t s)
-    {
-    if (m->rho_valid || !m->tile_path) return MTD_SUCCESS;
-    MeshGeom g;
-    std::memset(&g, 0, sizeof(g));
-    g.nx = m->nx; g.ny = m->ny; g.nz = m->nz; g.hxp = m->hxp;           // (the combine pass reads the dimensions only)
-    return mesh_combine(m, g, s);
-    }
-
 int mtd_mesh_assign(mtd_mesh *m, unsigned int n_particles, const void *d_postype, int dtype, const mtd_box *box, mtd_stream_t stream)
     {
     return mesh_assign_local(m, n_particles, d_postype, dtype, box, stream, true);
-    }
-
-static int mesh_assign_local(mtd_mesh *m, unsigned int n_particles, const void *d_postype, int dtype, const mtd_box *box, mtd_stream_t stream,
-                             bool combine)
-    {
-    if (!m || (n_particles && !d_postype)) return MTD_ERR_INVALID_ARGUMENT;
-    if (dtype != MTD_F32 && dtype != MTD_F64) return MTD_ERR_INVALID_ARGUMENT;
-    if (n_particles > m->max_particles) return MTD_ERR_INVALID_ARGUMENT;
-    MeshGeom g;
-    int rc = fill_geom(g, m, box);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const unsigned int M = m->M, N = n_particles;
-    const unsigned int cell_blocks = (M + 255) / 256;
-    const unsigned int n_tiles = (M + SCAN_TILE - 1) / SCAN_TILE;
-
-    if (m->tile_path)
-        {
-        TileGeom &tg = m->tg;
-        unsigned int nb = (N + 4095) / 4096;
-        nb = nb < 1 ? 1 : (nb > m->tile_blocks_max ? m->tile_blocks_max : nb);
-        tg.n_blocks = nb;
-        tg.chunk = N ? (N + nb - 1) / nb : 1;
-        // fixed point: 2^k * N * max|a| < 2^62 even if every particle sat in one cell
-        int k = 40;
-        if (m->amax > 0.0)
-            {
-            k = (int)std::floor(62.0 - std::log2((double)(N ? N : 1) * m->amax)) - 1;
-            const int k_one = 50 - (int)std::ceil(std::log2(m->amax));        // one deposit stays below 2^51 (mantissa rounding)
-            k = k > k_one ? k_one : k;
-            k = k > 60 ? 60 : (k < -900 ? -900 : k);
-            }
-        tg.scale = std::ldexp(1.0, k);
-        tg.inv_scale = std::ldexp(1.0, -k);
-        const bool f32 = dtype == MTD_F32;
-        // ---- bin pipeline (steady state): one launch bins, sorts and stores the chunk; the scatter launch's extra block plans the next
-        // snapshot.  Needs a plan for this particle number (the first assignment of a mesh goes through the counting pipeline and
-        // plans from its exact counts), no riders (they travel in the counting / row-scan kernels), a chunk and tables that fit the LDS.
-        const char *bin_env = std::getenv("MTD_MESH_BIN");               // (read per call: tests run both pipelines in one process)
-        const bool bin_off = bin_env && bin_env[0] == '0';
-        const size_t tb_lds = f32 ? tile_bin_lds_bytes<float4>(tg.n_tiles, tg.chunk) : tile_bin_lds_bytes<double4>(tg.n_tiles, tg.chunk);
-#define MTD_BIN_FNS(S4, R) (const void *)k_tile_bin<S4, 1, R>, (const void *)k_tile_bin<S4, 2, R>, (const void *)k_tile_bin<S4, 4, R>, (const void *)k_tile_bin<S4, 8, R>
-        static const void *const bin_fns[24] = { MTD_BIN_FNS(float4, 0), MTD_BIN_FNS(float4, 1), MTD_BIN_FNS(float4, 2), MTD_BIN_FNS(double4, 0), MTD_BIN_FNS(double4, 1), MTD_BIN_FNS(double4, 2) };
-#undef MTD_BIN_FNS
-        const bool tb_lds_ok = dyn_lds_ok(0, bin_fns, 24, TB_LDS_MAX);
-        const bool bin_fits = !bin_off && tb_lds_ok && m->d_possorted && tg.chunk <= TPS_CHUNK_MAX && tb_lds <= TB_LDS_MAX &&
-                              tg.n_tiles <= (unsigned int)(TB_TILES_PER_MAX * TB_THREADS);
-        TilePlan plan;
-        std::memset(&plan, 0, sizeof(plan));
-        mtd::MetadCfg apply_cfg;                                         // (read by the scatter launch's passenger blocks only)
-        std::memset(&apply_cfg, 0, sizeof(apply_cfg));
-        // (riders of the counting kernel's own loop — MTD_MESH_RIDER=count — keep the counting pipeline)
-        const char *rider_env = std::getenv("MTD_MESH_RIDER");
-        const bool rider_in_count = rider_env && std::strcmp(rider_env, "count") == 0;
-        // a plan made for another particle number still is a plan (a domain-decomposed run's local count changes every step: what does
-        // not fit overflows); only a count that differs by a factor of two or more is counted and planned afresh
-        const bool plan_usable = m->plan_valid && N >= m->plan_n / 2 && N / 2 <= m->plan_n;
-        if (bin_fits && plan_usable && !(m->rider_armed && rider_in_count))
-            {
-            const int p = m->bin_parity;
-            int rider_kind = 0;
-            unsigned int n_apply = 0;
-            if (m->rider_armed)
-                {
-                rider_kind = m->rider_fast ? 2 : 1;
-                if (m->rider_n_apply)
-                    {
-                    apply_cfg = m->h_rider->cfg;
-                    n_apply = (apply_cfg.len + TP_THREADS - 1) / TP_THREADS;
-                    }
-                m->rider_armed = 0;
-                if (m->rider_engine && m->rider_n_apply) m->rider_engine->pending_apply = 0;
-                }
-            // no riders: an engine that announced a pending deferred pass on this stream (a mesh variable without lamellar CVs beside
-            // it: mtd_mesh_forces_update_bias, mtd_metad_update_bias) still gets it carried by the scatter launch's extra blocks
-            mtd_metad *passenger = nullptr;
-            if (!n_apply && !rider_kind)
-                {
-                passenger = mtd::take_pending_apply(s, apply_cfg);
-                if (passenger) n_apply = (apply_cfg.len + TP_THREADS - 1) / TP_THREADS;
-                }
-            const unsigned int tiles_per = (tg.n_tiles + TB_THREADS - 1) / TB_THREADS;
-            BinRiderArgs ra;
-            BinNoRider no_rider;
-            if (rider_kind)
-                {
-                ra.k = mtd::dense_cv_args(m->h_rider->k);                // (the visited modes as a dense list: flat table loads)
-                ra.partials = m->h_rider->partials;
-                }
-#define MTD_TILE_BIN(S4, PER, R, RA) \
-            k_tile_bin<S4, PER, R><<<nb, TB_THREADS, tb_lds, s>>>(g, tg, (const S4 *)d_postype, N, m->d_mode, m->n_types, m->d_plan_first[p], m->d_plan_cap[p], \
-                                                                  m->d_cursor[p], m->d_ovf_count[p], m->d_ovf_tile, m->ovf_base, m->d_ids, (S4 *)m->d_possorted, \
-                                                                  m->d_modesq_partials, RA)
-#define MTD_TILE_BIN_R(S4, PER) \
-            do { if (rider_kind == 2) MTD_TILE_BIN(S4, PER, 2, ra); else if (rider_kind == 1) MTD_TILE_BIN(S4, PER, 1, ra); else MTD_TILE_BIN(S4, PER, 0, no_rider); } while (0)
-            if (f32)
-                {
-                if (tiles_per <= 1) MTD_TILE_BIN_R(float4, 1); else if (tiles_per <= 2) MTD_TILE_BIN_R(float4, 2);
-                else if (tiles_per <= 4) MTD_TILE_BIN_R(float4, 4); else MTD_TILE_BIN_R(float4, 8);
-                }
-            else
-                {
-                if (tiles_per <= 1) MTD_TILE_BIN_R(double4, 1); else if (tiles_per <= 2) MTD_TILE_BIN_R(double4, 2);
-                else if (tiles_per <= 4) MTD_TILE_BIN_R(double4, 4); else MTD_TILE_BIN_R(double4, 8);
-                }
-#undef MTD_TILE_BIN_R
-#undef MTD_TILE_BIN
-            MTD_LAUNCH_CHECK();
-            TileLists L;
-            L.first = m->d_plan_first[p]; L.count = m->d_cursor[p]; L.cap = m->d_plan_cap[p]; L.ovf_count = m->d_ovf_count[p];
-            L.ovf_tile = m->d_ovf_tile; L.cstride = TB_CSTRIDE; L.ovf_base = m->ovf_base;
-            plan.count = m->d_cursor[p]; plan.cstride = TB_CSTRIDE; plan.n_tiles = tg.n_tiles;
-            plan.first_next = m->d_plan_first[1 - p]; plan.cap_next = m->d_plan_cap[1 - p];
-            plan.cursor_next = m->d_cursor[1 - p]; plan.ovf_count_next = m->d_ovf_count[1 - p]; plan.cstride_next = TB_CSTRIDE;
-            plan.modesq_partials = m->d_modesq_partials; plan.n_partials = nb; plan.mode_sq = m->d_mode_sq;
-            if (f32)
-                k_tile_scatter<float4><<<tg.n_tiles + 1 + n_apply, TP_THREADS, 0, s>>>(g, tg, (const float4 *)d_postype, m->d_mode, L, m->d_ids, m->d_tilebuf, m->d_packed, m->n_types, (const float4 *)m->d_possorted, plan, apply_cfg);
-            else
-                k_tile_scatter<double4><<<tg.n_tiles + 1 + n_apply, TP_THREADS, 0, s>>>(g, tg, (const double4 *)d_postype, m->d_mode, L, m->d_ids, m->d_tilebuf, m->d_packed, m->n_types, (const double4 *)m->d_possorted, plan, apply_cfg);
-            if (passenger && hipPeekAtLastError() == hipSuccess) mtd::commit_pending_apply(passenger);     // (a failed launch leaves the pass pending)
-            m->lists = L;
-            m->plan_n = N;
-            m->last_pipeline = 2;
-            m->bin_parity = 1 - p;                                       // (planned and zeroed by the extra block)
-            }
-        else
-            {
-        const size_t lds = sizeof(unsigned int) * tg.n_tiles;
-        unsigned int n_apply_blocks = 0;
-#define MTD_TILE_COUNT(S4, RIDER, FAST, GRID) \
-        k_tile_count<S4, RIDER, FAST><<<GRID, TC_THREADS, lds, s>>>(g, tg, (const S4 *)d_postype, N, m->d_mode, m->d_cell_of, m->d_slot_of, \
-                                                                    m->d_count, m->d_modesq_partials, m->n_types, m->d_rider)
-        if (m->rider_armed)
-            {
-            if (m->rider_dirty)
-                {
-                MTD_HIP_TRY(hipMemcpyAsync(m->d_rider, m->h_rider, sizeof(CountRider), hipMemcpyHostToDevice, s));
-                m->rider_dirty = 0;
-                }
-            const unsigned int grid = nb;
-            const bool fast = m->rider_fast != 0;
-            n_apply_blocks = m->rider_n_apply;
-            if (dtype == MTD_F32) { if (fast) MTD_TILE_COUNT(float4, true, true, grid); else MTD_TILE_COUNT(float4, true, false, grid); }
-            else { if (fast) MTD_TILE_COUNT(double4, true, true, grid); else MTD_TILE_COUNT(double4, true, false, grid); }
-            m->rider_armed = 0;
-            if (m->rider_engine && m->rider_n_apply) m->rider_engine->pending_apply = 0;
-            }
-        else if (dtype == MTD_F32)
-            MTD_TILE_COUNT(float4, false, false, nb);
-        else
-            MTD_TILE_COUNT(double4, false, false, nb);
-#undef MTD_TILE_COUNT
-        MTD_LAUNCH_CHECK();
-        k_tile_rowscan<<<tg.n_tiles + 1 + n_apply_blocks, 256, 0, s>>>(m->d_count, m->d_start, m->d_tile_total, tg.n_tiles, nb, m->d_modesq_partials, nb, m->d_mode_sq, m->d_rider);
-        MTD_LAUNCH_CHECK();
-        unsigned int pb = (N + 1023) / 1024;                        // >= four particles per thread: the LDS prefix of the tile totals is formed once per block
-        pb = pb < 1 ? 1 : (pb > 512 ? 512 : pb);
-        // sorted place (the default): raw position records and ids leave in tile order, in runs; MTD_MESH_PLACE=ids keeps the
-        // one-store-per-particle form, which is also the fallback when a chunk or the tables do not fit
-        const size_t ps_lds = f32 ? place_sorted_lds_bytes<float4>(tg.n_tiles, tg.chunk) : place_sorted_lds_bytes<double4>(tg.n_tiles, tg.chunk);
-        const char *ps_env = std::getenv("MTD_MESH_PLACE");           // (read per call: a test runs both forms in one process)
-        const bool ps_off = ps_env && std::strcmp(ps_env, "ids") == 0;
-        static const void *const ps_fns[2] = { (const void *)k_tile_place_sorted<float4>, (const void *)k_tile_place_sorted<double4> };
-        const bool ps_lds_ok = dyn_lds_ok(1, ps_fns, 2, PS_LDS_MAX);
-        const bool sorted = !ps_off && ps_lds_ok && m->d_possorted && tg.chunk <= TPS_CHUNK_MAX && ps_lds <= PS_LDS_MAX;
-        if (sorted)
-            {
-            if (f32)
-                k_tile_place_sorted<float4><<<nb, TPS_THREADS, ps_lds, s>>>(tg, N, (const float4 *)d_postype, m->d_cell_of, m->d_slot_of, m->d_count, m->d_start, m->d_tile_total, m->d_ids, (float4 *)m->d_possorted, m->d_tile_first);
-            else
-                k_tile_place_sorted<double4><<<nb, TPS_THREADS, ps_lds, s>>>(tg, N, (const double4 *)d_postype, m->d_cell_of, m->d_slot_of, m->d_count, m->d_start, m->d_tile_total, m->d_ids, (double4 *)m->d_possorted, m->d_tile_first);
-            }
-        else if (f32)
-            k_tile_place<float4><<<pb, 256, sizeof(unsigned int) * tg.n_tiles, s>>>(tg, N, m->d_cell_of, m->d_slot_of, m->d_start, m->d_tile_total, m->d_ids, m->d_tile_first);
-        else
-            k_tile_place<double4><<<pb, 256, sizeof(unsigned int) * tg.n_tiles, s>>>(tg, N, m->d_cell_of, m->d_slot_of, m->d_start, m->d_tile_total, m->d_ids, m->d_tile_first);
-        MTD_LAUNCH_CHECK();
-        TileLists L;
-        std::memset(&L, 0, sizeof(L));
-        L.first = m->d_tile_first; L.count = m->d_tile_total; L.cstride = 1;
-        if (f32)
-            k_tile_scatter<float4><<<tg.n_tiles, TP_THREADS, 0, s>>>(g, tg, (const float4 *)d_postype, m->d_mode, L, m->d_ids, m->d_tilebuf, m->d_packed, m->n_types, sorted ? (const float4 *)m->d_possorted : nullptr, plan, apply_cfg);
-        else
-            k_tile_scatter<double4><<<tg.n_tiles, TP_THREADS, 0, s>>>(g, tg, (const double4 *)d_postype, m->d_mode, L, m->d_ids, m->d_tilebuf, m->d_packed, m->n_types, sorted ? (const double4 *)m->d_possorted : nullptr, plan, apply_cfg);
-        m->lists = L;
-        m->last_pipeline = 1;
-        if (bin_fits && !plan_usable)
-            {
-            // the exact counts of this snapshot plan the segments of the next one
-            MTD_LAUNCH_CHECK();
-            const int p = m->bin_parity;
-            plan.count = m->d_tile_total; plan.cstride = 1; plan.n_tiles = tg.n_tiles;
-            plan.first_next = m->d_plan_first[p]; plan.cap_next = m->d_plan_cap[p];
-            plan.cursor_next = m->d_cursor[p]; plan.ovf_count_next = m->d_ovf_count[p]; plan.cstride_next = TB_CSTRIDE;
-            k_tile_plan<<<1, 1024, 0, s>>>(plan);
-            m->plan_valid = 1;
-            m->plan_n = N;
-            }
-            }
-        MTD_LAUNCH_CHECK();
-        m->n_last = N;
-        m->rho_valid = 0;
-        if (combine) return mesh_combine(m, g, s);
-        return MTD_SUCCESS;
-        }
-
-    // the counters are zero on entry: cleared at creation and by k_scan_finish of the previous call
-    if (dtype == MTD_F32)
-        k_mesh_bin<float4><<<m->n_count_blocks, 256, 0, s>>>(g, (const float4 *)d_postype, N, m->d_mode, m->d_cell_of, m->d_slot_of, m->d_count, m->d_modesq_partials);
-    else
-        k_mesh_bin<double4><<<m->n_count_blocks, 256, 0, s>>>(g, (const double4 *)d_postype, N, m->d_mode, m->d_cell_of, m->d_slot_of, m->d_count, m->d_modesq_partials);
-    MTD_LAUNCH_CHECK();
-    k_scan_tiles<<<n_tiles + 1, 256, 0, s>>>(m->d_count, m->d_start, m->d_tile_sums, M, m->d_modesq_partials, m->n_count_blocks, m->d_mode_sq);
-    MTD_LAUNCH_CHECK();
-    k_scan_finish<<<n_tiles, 256, 0, s>>>(m->d_start, m->d_tile_sums, m->d_count, M, N);
-    MTD_LAUNCH_CHECK();
-    if (dtype == MTD_F32)
-        k_mesh_place<float4><<<m->n_count_blocks, 256, 0, s>>>(g, (const float4 *)d_postype, N, m->d_mode, m->d_cell_of, m->d_slot_of, m->d_start, m->d_idcell, m->d_packed);
-    else
-        k_mesh_place<double4><<<m->n_count_blocks, 256, 0, s>>>(g, (const double4 *)d_postype, N, m->d_mode, m->d_cell_of, m->d_slot_of, m->d_start, m->d_idcell, m->d_packed);
-    MTD_LAUNCH_CHECK();
-    k_mesh_sortfix<<<cell_blocks, 256, 0, s>>>(M, m->d_start, m->d_idcell, m->d_packed);
-    MTD_LAUNCH_CHECK();
-    GatherTiling tl;
-    tl.tx = m->nx < (unsigned int)GT_X ? m->nx : GT_X;
-    tl.ty = m->ny < (unsigned int)GT_Y ? m->ny : GT_Y;
-    tl.tz = m->nz < (unsigned int)GT_Z ? m->nz : GT_Z;
-    tl.ntx = (m->nx + tl.tx - 1) / tl.tx; tl.nty = (m->ny + tl.ty - 1) / tl.ty; tl.ntz = (m->nz + tl.tz - 1) / tl.tz;   // edge tiles may be partial
-    k_mesh_gather<<<tl.ntx * tl.nty * tl.ntz, GT_THREADS, 0, s>>>(g, tl, m->d_start, m->d_packed, m->d_rho);
-    MTD_LAUNCH_CHECK();
-    m->n_last = N;
-    m->rho_valid = 1;
-    return MTD_SUCCESS;
     }
 
 int mtd_mesh_assign_info(mtd_mesh *m, int *pipeline, unsigned int *n_overflow, mtd_stream_t stream)
@@ -4283,71 +4352,39 @@ int mtd_mesh_exchange_buffer(mtd_mesh *m, double **d_buffer, size_t *count)
     return MTD_SUCCESS;
     }
 
-int mtd_mesh_spectral(mtd_mesh *m, const mtd_box *box, unsigned int n_global, const double **d_partials, unsigned int *n_partials,
-                      mtd_stream_t stream)
+// the transforms, with the caller's answer to "forward transform from the tile images?" (fft_forward_from_tiles)
+static int mesh_spectral(mtd_mesh *m, const mtd_box *box, unsigned int n_global, const double **d_partials, unsigned int *n_partials,
+                         mtd_stream_t stream, FwdPlan &fp, const FwdTiles from_tiles)
     {
-    if (!m || !d_partials || !n_partials || n_global == 0) return MTD_ERR_INVALID_ARGUMENT;
     MeshGeom g;
     int rc = fill_geom(g, m, box);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    // x passes: two real lines per complex transform, `x_tile` real lines per block (the last block may run short)
-    const unsigned int n_lines = m->ny * m->nz;
-    // 8 pairs = 16 real lines per block: at nx = 128 that is 16.5 KB of LDS and 1024 blocks — four per compute unit, so that
-    // one block loads while another transforms and a third stores (16 pairs: 512 blocks, 12.0 + 12.2 us; 8: 10.4 + 10.9)
-    unsigned int x_pairs = 8;
-    { static const unsigned int forced = [] { const char *e = std::getenv("MTD_FFT_XPAIRS"); return e ? (unsigned int)std::atoi(e) : 0u; }(); if (forced) x_pairs = forced; }
-    while (x_pairs > 1 && fft_x_lds_bytes(m->nx, x_pairs) > 64 * 1024) x_pairs >>= 1;
-    const unsigned int x_tile = 2 * x_pairs, x_blocks = (n_lines + x_tile - 1) / x_tile;
-    const size_t x_lds = fft_x_lds_bytes(m->nx, x_pairs);
-    // x and y of a plane in one launch where the plane fits the LDS (k_fft_xy_*); MTD_FFT_XY=0 keeps the separate passes
-    XYPlan xy_f, xy_i;
-    size_t xy_lds_f = 0, xy_lds_i = 0;
-    static const bool xy_off = [] { const char *e = std::getenv("MTD_FFT_XY"); return e && e[0] == '0'; }();
-    // (a runtime that refuses the 160 KB of dynamic LDS leaves the separate passes, it does not fail the step)
-    static const void *const xy_fns[5] = { (const void *)k_fft_xy_forward<false>, (const void *)k_fft_xy_inverse, (const void *)k_fft_xy_forward<true>,
-                                           (const void *)k_fft_xy_inverse_split, (const void *)k_fft_xy_forward_split };
-    const bool xy_lds_ok = dyn_lds_ok(2, xy_fns, 5, XY_LDS_MAX);
-    const bool xy = !xy_off && xy_lds_ok && xy_plan(m, 0, xy_f, xy_lds_f) && xy_plan(m, 1, xy_i, xy_lds_i);
-    XYTiles tiles;
-    std::memset(&tiles, 0, sizeof(tiles));
-    // (the row class of a thread's elements must not change over its elements nor over the batches: k_fft_xy_forward<true>)
-    // (two cells per lane: a wave spans a line of 128 cells; a thread's line pairs are 8 apart, the batches 32: multiples of the tile height)
-    const bool tile_rows_ok = xy && m->nx == 128 && XY_THREADS == 512 && xy_f.pb == 32 && m->tg.ty && 16 % m->tg.ty == 0 && (2 * xy_f.pb) % m->tg.ty == 0;
-    if (xy && tile_rows_ok && !m->rho_valid && xy_tiles_ok(m, tiles))
-        {
-        // the assignment left the mesh in the per-tile images (mtd_mesh_compute_cv): the transform sums them itself
-        XYSplitF sf;
-        size_t sf_lds = 0;
-        const char *split_env = std::getenv("MTD_FFT_SPLIT");              // (read per call: a test runs both forms in one process)
-        if (!(split_env && split_env[0] == '0') && xy_split_plan_f(m, sf, sf_lds))
-            k_fft_xy_forward_split<<<m->nz * 2, XY_THREADS, sf_lds, s>>>(m->d_f, m->d_tw[0], m->d_tw[1], sf, tiles);
-        else
-            k_fft_xy_forward<true><<<m->nz * XY_PARTS, XY_THREADS, xy_lds_f, s>>>(nullptr, m->d_f, m->d_tw[0], m->d_tw[1], xy_f, tiles);
-        MTD_LAUNCH_CHECK();
-        m->last_forward = 2;
-        }
-    else if (xy)
-        {
-        rc = mesh_need_rho(m, s);
-        if (rc) return rc;
-        k_fft_xy_forward<false><<<m->nz * XY_PARTS, XY_THREADS, xy_lds_f, s>>>(m->d_rho, m->d_f, m->d_tw[0], m->d_tw[1], xy_f, tiles);
-        MTD_LAUNCH_CHECK();
-        m->last_forward = 1;
-        }
+    // the separate x passes of the whole mesh; MTD_FFT_XPAIRS forces another number of line pairs per block (here only, not on the slab path)
+    static const unsigned int x_pairs_forced = [] { const char *e = std::getenv("MTD_FFT_XPAIRS"); return e ? (unsigned int)std::atoi(e) : 0u; }();
+    const FftXPass px = fft_x_pass(m, m->nz, x_pairs_forced ? x_pairs_forced : 8);
+    const XYFused &xy = fp.xy;
+    if (from_tiles == FWD_COMBINED) rc = mesh_need_rho(m, s);
+    if (rc) return rc;
+    // from the tile images: the assignment left the mesh there (mtd_mesh_compute_cv) and the transform sums them itself
+    fp.tiles.inv_scale = m->tg.inv_scale;                                  // (the fixed-point scale of THAT assignment)
+    if (from_tiles == FWD_TILES_SPLIT)
+        k_fft_xy_forward_split<<<m->nz * 2, XY_THREADS, fp.split_lds, s>>>(m->d_f, m->d_tw[0], m->d_tw[1], fp.split, fp.tiles);
+    else if (from_tiles == FWD_TILES)
+        k_fft_xy_forward<true><<<m->nz * XY_PARTS, XY_THREADS, xy.lds_f, s>>>(nullptr, m->d_f, m->d_tw[0], m->d_tw[1], xy.f, fp.tiles);
+    else if (xy.on)
+        k_fft_xy_forward<false><<<m->nz * XY_PARTS, XY_THREADS, xy.lds_f, s>>>(m->d_rho, m->d_f, m->d_tw[0], m->d_tw[1], xy.f, XYTiles{});
     else
         {
-        rc = mesh_need_rho(m, s);
-        if (rc) return rc;
-        k_fft_x_r2c<<<x_blocks, FFT_THREADS, x_lds, s>>>(m->d_rho, m->d_f, m->d_tw[0], m->nx, ilog2(m->nx), x_tile, m->hxp, n_lines);
+        k_fft_x_r2c<<<px.blocks, FFT_THREADS, px.lds, s>>>(m->d_rho, m->d_f, m->d_tw[0], m->nx, ilog2(m->nx), px.tile, m->hxp, px.n_lines);
         MTD_LAUNCH_CHECK();
-        rc = launch_fft_y(m, m->d_f, 0, s);
+        rc = launch_fft_y(m, m->d_f, 0, m->nz, s);
         if (rc) return rc;
-        m->last_forward = 0;
         }
+    MTD_LAUNCH_CHECK();
+    m->last_forward = from_tiles != FWD_COMBINED ? 2 : (xy.on ? 1 : 0);
     const FftPass pz = fft_z_pass(m);
-    SlabArgs none;
-    std::memset(&none, 0, sizeof(none));
+    const SlabArgs none{};
     const unsigned int tpb = fft_z_tpb(pz);
     unsigned int z_blocks_whole = pz.n_blocks / tpb;
     // a half spectrum of 8 k + 1 columns: the lone last column goes to edge blocks instead of a ninth tile per row (k_fft_z_spectral)
@@ -4365,21 +4402,18 @@ int mtd_mesh_spectral(mtd_mesh *m, const mtd_box *box, unsigned int n_global, co
             g, m->d_f, m->d_g, pz.tw, ilog2(pz.n), pz.tile, full, m->d_mode_sq, (double)n_global, m->d_itab, m->d_cv_partials, none, m->keep_fourier,
             n_regular, full * pz.tile);
         }
-    else if (tpb == 3)
-        k_fft_z_spectral<false, 3><<<z_blocks_whole, FFT_THREADS, fft_lds_bytes(pz.n, pz.tile), s>>>(
-            g, m->d_f, m->d_g, pz.tw, ilog2(pz.n), pz.tile, pz.tiles_per_row, m->d_mode_sq, (double)n_global, m->d_itab, m->d_cv_partials, none, m->keep_fourier, 0xffffffffu, 0u);
-    else if (tpb == 2)
-        k_fft_z_spectral<false, 2><<<z_blocks_whole, FFT_THREADS, fft_lds_bytes(pz.n, pz.tile), s>>>(
-            g, m->d_f, m->d_g, pz.tw, ilog2(pz.n), pz.tile, pz.tiles_per_row, m->d_mode_sq, (double)n_global, m->d_itab, m->d_cv_partials, none, m->keep_fourier, 0xffffffffu, 0u);
     else
-        k_fft_z_spectral<false, 1><<<z_blocks_whole, FFT_THREADS, fft_lds_bytes(pz.n, pz.tile), s>>>(
-            g, m->d_f, m->d_g, pz.tw, ilog2(pz.n), pz.tile, pz.tiles_per_row, m->d_mode_sq, (double)n_global, m->d_itab, m->d_cv_partials, none, m->keep_fourier, 0xffffffffu, 0u);
+        mtd::dispatch_count<3>(tpb, [&](auto t)                            // (1 | 2 | 3 tiles per block: fft_z_tpb)
+            {
+            k_fft_z_spectral<false, decltype(t)::value><<<z_blocks_whole, FFT_THREADS, fft_lds_bytes(pz.n, pz.tile), s>>>(
+                g, m->d_f, m->d_g, pz.tw, ilog2(pz.n), pz.tile, pz.tiles_per_row, m->d_mode_sq, (double)n_global, m->d_itab, m->d_cv_partials, none, m->keep_fourier,
+                0xffffffffu, 0u);
+            });
     m->fourier_valid = m->keep_fourier;
     bool fold_cv = false;
-    unsigned int n_folded = 0;
     if (m->cv_event) MTD_HIP_TRY(hipEventRecord(m->cv_event, s));          // the CV partial sums are complete from here on
     MTD_LAUNCH_CHECK();
-    if (xy)
+    if (xy.on)
         {
         // (the CV's partial sums folded to one per block of this launch when that is fewer — and nobody was promised them earlier:
         // mtd_mesh_set_cv_event marks the z pass as the point where the sums are complete)
@@ -4387,27 +4421,32 @@ int mtd_mesh_spectral(mtd_mesh *m, const mtd_box *box, unsigned int n_global, co
         fold_cv = !m->cv_event && z_blocks_whole > xy_blocks && z_blocks_whole <= 64 * xy_blocks;
         XYSplit xs_i;
         size_t xs_lds = 0;
-        const char *split_env = std::getenv("MTD_FFT_SPLIT");              // (read per call: a test runs both forms in one process)
-        const bool split = !(split_env && split_env[0] == '0') && xy_split_plan(m, xs_i, xs_lds);
-        if (split)
+        if (fft_inverse_split(m, xs_i, xs_lds))
             k_fft_xy_inverse_split<<<xy_blocks, XY_THREADS, xs_lds, s>>>(m->d_g, m->d_inv, m->d_tw[0], m->d_tw[1], xs_i, m->d_cv_partials,
                                                                          fold_cv ? z_blocks_whole : 0u, m->d_cv_folded);
         else
-            k_fft_xy_inverse<<<xy_blocks, XY_THREADS, xy_lds_i, s>>>(m->d_g, m->d_inv, m->d_tw[0], m->d_tw[1], xy_i, m->d_cv_partials,
+            k_fft_xy_inverse<<<xy_blocks, XY_THREADS, xy.lds_i, s>>>(m->d_g, m->d_inv, m->d_tw[0], m->d_tw[1], xy.i, m->d_cv_partials,
                                                                      fold_cv ? z_blocks_whole : 0u, m->d_cv_folded);   // Re(inv)
         MTD_LAUNCH_CHECK();
-        if (fold_cv) n_folded = xy_blocks;
         }
     else
         {
-        rc = launch_fft_y(m, m->d_g, 1, s);
+        rc = launch_fft_y(m, m->d_g, 1, m->nz, s);
         if (rc) return rc;
-        k_fft_x_c2r<<<x_blocks, FFT_THREADS, x_lds, s>>>(m->d_g, m->d_inv, m->d_tw[0], m->nx, ilog2(m->nx), x_tile, m->hxp, n_lines);   // Re(inv)
+        k_fft_x_c2r<<<px.blocks, FFT_THREADS, px.lds, s>>>(m->d_g, m->d_inv, m->d_tw[0], m->nx, ilog2(m->nx), px.tile, m->hxp, px.n_lines);   // Re(inv)
         MTD_LAUNCH_CHECK();
         }
     *d_partials = fold_cv ? m->d_cv_folded : m->d_cv_partials;
-    *n_partials = fold_cv ? n_folded : z_blocks_whole;
+    *n_partials = fold_cv ? m->nz * XY_PARTS : z_blocks_whole;
     return MTD_SUCCESS;
+    }
+
+int mtd_mesh_spectral(mtd_mesh *m, const mtd_box *box, unsigned int n_global, const double **d_partials, unsigned int *n_partials,
+                      mtd_stream_t stream)
+    {
+    if (!m || !d_partials || !n_partials || n_global == 0) return MTD_ERR_INVALID_ARGUMENT;
+    FwdPlan fp;
+    return mesh_spectral(m, box, n_global, d_partials, n_partials, stream, fp, fft_forward_from_tiles(m, fp, m->rho_valid));
     }
 
 int mtd_mesh_compute_cv(mtd_mesh *m, unsigned int n_particles, const void *d_postype, int dtype, const mtd_box *box,
@@ -4416,15 +4455,11 @@ int mtd_mesh_compute_cv(mtd_mesh *m, unsigned int n_particles, const void *d_pos
     if (!m || !d_partials || !n_partials || n_global == 0) return MTD_ERR_INVALID_ARGUMENT;
     // assignment and transforms in one call: the combine pass (tile images -> real mesh, a 10 us launch whose output the forward
     // transform would read back one launch later) is skipped where the transform can sum the tile images itself
-    XYPlan xy_probe;
-    XYTiles tl_probe;
-    size_t lds_probe = 0;
-    static const bool xy_off = [] { const char *e = std::getenv("MTD_FFT_XY"); return e && e[0] == '0'; }();
-    const bool from_tiles = m->tile_path && !xy_off && xy_plan(m, 0, xy_probe, lds_probe) && xy_tiles_ok(m, tl_probe) && m->tg.ty &&
-                            m->nx == 128 && XY_THREADS == 512 && xy_probe.pb == 32 && 16 % m->tg.ty == 0 && (2 * xy_probe.pb) % m->tg.ty == 0;
-    int rc = mesh_assign_local(m, n_particles, d_postype, dtype, box, stream, !from_tiles);
+    FwdPlan fp;
+    const FwdTiles from_tiles = fft_forward_from_tiles(m, fp);
+    int rc = mesh_assign_local(m, n_particles, d_postype, dtype, box, stream, from_tiles == FWD_COMBINED);
     if (rc) return rc;
-    return mtd_mesh_spectral(m, box, n_global, d_partials, n_partials, stream);
+    return mesh_spectral(m, box, n_global, d_partials, n_partials, stream, fp, from_tiles);
     }
 
 int mtd_mesh_forces(mtd_mesh *m, unsigned int n_particles, const void *d_postype, void *d_force, int dtype, const mtd_box *box,
@@ -4437,24 +4472,18 @@ int mtd_mesh_forces(mtd_mesh *m, unsigned int n_particles, const void *d_postype
     int rc = fill_geom(g, m, box);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    unsigned int blocks = (n_particles + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
+    const unsigned int blocks = std::min((n_particles + 255) / 256, 4096u);
     const double two_over_n = 2.0 / (double)n_global;
     // the force pass walks the cell-sorted list built by the last mtd_mesh_compute_cv of the same snapshot
     if (n_particles != m->n_last) return MTD_ERR_INVALID_ARGUMENT;
-    if (m->tile_path)
+    mtd::dispatch_s4(dtype, [&](auto s4)
         {
-        if (dtype == MTD_F32)
-            k_tile_forces<float4><<<8 * ((m->tg.n_tiles + 7) / 8), TF_THREADS, 0, s>>>(g, m->tg, m->lists, m->d_mode, m->d_packed, m->d_inv, (float4 *)d_force, d_bias, bias_host, two_over_n, m->n_types);
+        using S4 = typename decltype(s4)::type;
+        if (m->tile_path)
+            k_tile_forces<S4><<<tile_force_blocks(m), TF_THREADS, 0, s>>>(g, m->tg, m->lists, m->d_mode, m->d_packed, m->d_inv, (S4 *)d_force, d_bias, bias_host, two_over_n, m->n_types);
         else
-            k_tile_forces<double4><<<8 * ((m->tg.n_tiles + 7) / 8), TF_THREADS, 0, s>>>(g, m->tg, m->lists, m->d_mode, m->d_packed, m->d_inv, (double4 *)d_force, d_bias, bias_host, two_over_n, m->n_types);
-        MTD_LAUNCH_CHECK();
-        return MTD_SUCCESS;
-        }
-    if (dtype == MTD_F32)
-        k_mesh_forces<float4><<<blocks, 256, 0, s>>>(g, n_particles, m->d_idcell, m->d_packed, m->d_inv, (float4 *)d_force, d_bias, bias_host, two_over_n);
-    else
-        k_mesh_forces<double4><<<blocks, 256, 0, s>>>(g, n_particles, m->d_idcell, m->d_packed, m->d_inv, (double4 *)d_force, d_bias, bias_host, two_over_n);
+            k_mesh_forces<S4><<<blocks, 256, 0, s>>>(g, n_particles, m->d_idcell, m->d_packed, m->d_inv, (S4 *)d_force, d_bias, bias_host, two_over_n);
+        });
     MTD_LAUNCH_CHECK();
     return MTD_SUCCESS;
     }
@@ -4491,7 +4520,7 @@ int mtd_mesh_forces_update_bias(mtd_mesh *mesh, mtd_metad *m, unsigned int mesh_
         }
     const int dep = deposit_due(m, timestep);   // .cc:368
     const unsigned int n_grid = dep ? m->cfg.n_gblocks : 0;
-    const unsigned int blocks = 8 * ((mesh->tg.n_tiles + 7) / 8);
+    const unsigned int blocks = tile_force_blocks(mesh);
     if (n_grid > blocks) return MTD_ERR_UNSUPPORTED;
     if ((unsigned long long)blocks * TFC_STREAM_THREADS * TFC_U >= (1ull << 31)) return MTD_ERR_UNSUPPORTED;
     MeshGeom g;
@@ -4505,21 +4534,17 @@ int mtd_mesh_forces_update_bias(mtd_mesh *mesh, mtd_metad *m, unsigned int mesh_
     const double two_over_n = 2.0 / (double)n_global;
     const bool fast = n_lam ? mtd::lam_fast_trig(k) != 0 : true;
     const unsigned int n_stream = n_lam ? n_particles : 0u;        // particles the blocks stream for the lamellar forces
-#define MTD_LAUNCH_TFC(S4, NCV, FASTV) \
-    k_tile_forces_chain<S4, NCV, FASTV><<<blocks, TF_THREADS, 0, s>>>(g, mesh->tg, mesh->lists, mesh->d_mode, mesh->d_packed, mesh->d_inv, (S4 *)d_force_mesh, \
-        two_over_n, mesh->n_types, mesh_slot, k, (const S4 *)d_postype, out, n_stream, m->cfg, dep, n_grid)
-#define MTD_LAUNCH_TFC_NCV(S4, FASTV) \
-    switch (n_lam) { case 0: case 1: MTD_LAUNCH_TFC(S4, 1, FASTV); break; case 2: MTD_LAUNCH_TFC(S4, 2, FASTV); break; default: MTD_LAUNCH_TFC(S4, 3, FASTV); break; }
-    if (dtype == MTD_F32)
+    // NCV 1 | 2 | 3 (no set: 1, with nothing to stream; n_lam > 3 was refused above)
+    mtd::dispatch_s4_fast(dtype, fast, [&](auto s4, auto fast_c)
         {
-        if (fast) { MTD_LAUNCH_TFC_NCV(float4, true) } else { MTD_LAUNCH_TFC_NCV(float4, false) }
-        }
-    else
-        {
-        if (fast) { MTD_LAUNCH_TFC_NCV(double4, true) } else { MTD_LAUNCH_TFC_NCV(double4, false) }
-        }
-#undef MTD_LAUNCH_TFC_NCV
-#undef MTD_LAUNCH_TFC
+        using S4 = typename decltype(s4)::type;
+        mtd::dispatch_count<3>(n_lam ? n_lam : 1u, [&](auto ncv)
+            {
+            k_tile_forces_chain<S4, decltype(ncv)::value, decltype(fast_c)::value><<<blocks, TF_THREADS, 0, s>>>(
+                g, mesh->tg, mesh->lists, mesh->d_mode, mesh->d_packed, mesh->d_inv, (S4 *)d_force_mesh, two_over_n, mesh->n_types, mesh_slot, k,
+                (const S4 *)d_postype, out, n_stream, m->cfg, dep, n_grid);
+            });
+        });
     MTD_LAUNCH_CHECK();
     m->pending_apply = dep;
     m->w_stale = dep;
@@ -4595,18 +4620,11 @@ int mtd_mesh_slab_compute_cv(mtd_mesh *m, unsigned int n_particles, const void *
     peers_of(m->slab_rho);
     k_slab_pull_rho<<<1024, 256, 0, s>>>(pp, W, (size_t)r * slab_cells, slab_cells, m->d_slab_rho);
     MTD_LAUNCH_CHECK();
-    const unsigned int n_lines = m->ny * nzl;
-    unsigned int x_pairs = 8;
-    while (x_pairs > 1 && fft_x_lds_bytes(m->nx, x_pairs) > 64 * 1024) x_pairs >>= 1;
-    const unsigned int x_tile = 2 * x_pairs, x_blocks = (n_lines + x_tile - 1) / x_tile;
-    const size_t x_lds = fft_x_lds_bytes(m->nx, x_pairs);
-    k_fft_x_r2c<<<x_blocks, FFT_THREADS, x_lds, s>>>(m->d_slab_rho, m->d_f, m->d_tw[0], m->nx, ilog2(m->nx), x_tile, m->hxp, n_lines);
+    const FftXPass px = fft_x_pass(m, nzl);
+    k_fft_x_r2c<<<px.blocks, FFT_THREADS, px.lds, s>>>(m->d_slab_rho, m->d_f, m->d_tw[0], m->nx, ilog2(m->nx), px.tile, m->hxp, px.n_lines);
     MTD_LAUNCH_CHECK();
-    FftPass py = fft_y_pass(m);
-    py.n_blocks = py.tiles_per_row * nzl;
-    k_fft_lines<false, false><<<py.n_blocks, FFT_THREADS, fft_lds_bytes(py.n, py.tile), s>>>(
-        nullptr, m->d_f, nullptr, py.tw, py.n, ilog2(py.n), py.tile, py.elem_stride, py.line_stride, py.tiles_per_row, py.row_stride, 0, py.p_fastest);
-    MTD_LAUNCH_CHECK();
+    rc = launch_fft_y(m, m->d_f, 0, nzl, s);
+    if (rc) return rc;
     k_copy_doubles<<<1024, 256, 0, s>>>((const double *)m->d_f, (double *)f_x, 2 * (size_t)nzl * m->ny * m->hxp);
     MTD_LAUNCH_CHECK();
     rc = mtd_comm_allreduce_small(m->slab_comm, m->d_mode_sq, 1, stream);                       // barrier + global sum mode^2 (:630)
@@ -4630,10 +4648,9 @@ int mtd_mesh_slab_compute_cv(mtd_mesh *m, unsigned int n_particles, const void *
     peers_of(m->slab_g);
     k_slab_pull_g<<<1024, 256, 0, s>>>(pp, r * nzl, nzl, m->ny, nyl, m->hxp, m->d_g);
     MTD_LAUNCH_CHECK();
-    k_fft_lines<false, false><<<py.n_blocks, FFT_THREADS, fft_lds_bytes(py.n, py.tile), s>>>(
-        nullptr, m->d_g, nullptr, py.tw, py.n, ilog2(py.n), py.tile, py.elem_stride, py.line_stride, py.tiles_per_row, py.row_stride, 1, py.p_fastest);
-    MTD_LAUNCH_CHECK();
-    k_fft_x_c2r<<<x_blocks, FFT_THREADS, x_lds, s>>>(m->d_g, inv_x, m->d_tw[0], m->nx, ilog2(m->nx), x_tile, m->hxp, n_lines);
+    rc = launch_fft_y(m, m->d_g, 1, nzl, s);
+    if (rc) return rc;
+    k_fft_x_c2r<<<px.blocks, FFT_THREADS, px.lds, s>>>(m->d_g, inv_x, m->d_tw[0], m->nx, ilog2(m->nx), px.tile, m->hxp, px.n_lines);
     MTD_LAUNCH_CHECK();
     rc = mtd_comm_allreduce_small(m->slab_comm, m->d_slab_sum + 1, 1, stream);                 // barrier
     if (rc) return rc;

@@ -779,3 +779,79 @@ def test_force_pass_with_the_bias_update_inside(abi, ref, dtype, fast, n_lam, st
             m.close()
         for h in (ha, hb):
             abi.check(lib.mtd_metad_destroy(h))
+
+
+# (mesh, environment, how a snapshot is evaluated) -> (pipeline, forward form) reported for the first and the second snapshot of a
+# mesh (mtd_mesh_assign_info: 0 cells, 1 counting, 2 bin; mtd_mesh_transform_info: 0 separate x / y passes, 1 k_fft_xy_forward on
+# the combined mesh, 2 on the tile images).  "cv": mtd_mesh_compute_cv; "assign+spectral": mtd_mesh_assign, then mtd_mesh_spectral
+# (the real mesh is valid, so the combined form runs); "cv+array+spectral": mtd_mesh_compute_cv, mtd_mesh_get_array(0) (which makes
+# the real mesh valid), then mtd_mesh_spectral again: two forward forms per snapshot.
+HOST_LAYER_CASES = [
+    ((16, 16, 16), {}, "cv", [(1, (1,)), (2, (1,))]),
+    ((16, 16, 16), {"MTD_MESH_BIN": "0"}, "cv", [(1, (1,)), (1, (1,))]),
+    ((16, 16, 16), {"MTD_MESH_ASSIGN": "cells"}, "cv", [(0, (1,)), (0, (1,))]),
+    ((12, 20, 6), {}, "cv", [(1, (0,)), (2, (0,))]),                       # not powers of two
+    ((256, 256, 4), {}, "cv", [(1, (0,)), (2, (0,))]),                     # planes that do not fit the LDS
+    ((128, 64, 8), {}, "cv", [(1, (2,)), (2, (2,))]),
+    ((128, 64, 8), {}, "assign+spectral", [(1, (1,)), (2, (1,))]),
+    ((128, 64, 8), {}, "cv+array+spectral", [(1, (2, 1)), (2, (2, 1))]),
+    ((128, 64, 8), {"MTD_FFT_FROM_TILES": "0"}, "cv", [(1, (1,)), (2, (1,))]),
+]
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("dims,env,how,expected", HOST_LAYER_CASES, ids=["%dx%dx%d-%s-%s" % (c[0] + ("+".join("%s=%s" % kv for kv in c[1].items()) or "defaults", c[2])) for c in HOST_LAYER_CASES])
+def test_host_layer_takes_the_parents_path(abi, monkeypatch, dtype, dims, env, how, expected):
+    """Which launch sequence the host layer of mesh.hip picks: the smallest shapes that reach every branch of the two decisions
+    "which assignment pipeline" and "does the forward transform read the tile images", 3 000 particles, two snapshots through one
+    mesh and both once more.  The expected values are what the library reported before the host layer was rearranged (the same
+    test body run against that build).  In every case the CV and the forces are non-zero and the repeat of a snapshot gives the
+    same bits (also where the repeat takes the bin pipeline and the first evaluation took the counting one: integer sums)."""
+    N, L = 3000, 17.0
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    box = abi.Box.make(L)
+    dt = abi.MTD_F32 if dtype == np.float32 else abi.MTD_F64
+    snaps = []
+    for seed in (21, 22):
+        pos, types = util.snapshot_random(N, L, seed=seed, modulated=True, dtype=dtype)
+        snaps.append(torch.from_numpy(util.pack_postype(pos, types, dtype)).cuda())
+    g = GpuMesh(abi, dims, [1.0, -0.6], N)
+    lib = g.lib
+
+    def forward():
+        fwd = C.c_int(-1)
+        abi.check(lib.mtd_mesh_transform_info(g.h, C.byref(fwd)))
+        return fwd.value
+
+    def spectral():
+        parts, n = C.c_void_p(), C.c_uint()
+        abi.check(lib.mtd_mesh_spectral(g.h, C.byref(box), N, C.byref(parts), C.byref(n), None))
+        out = torch.zeros(1, dtype=torch.float64, device="cuda")
+        abi.check(lib.mtd_reduce_partials(parts.value, n.value, 1, 1, 0.5, 0.0, abi.ptr(out), None))
+        torch.cuda.synchronize()
+        return out.item()
+
+    try:
+        res = []
+        for d_pos in snaps + snaps:
+            if how == "assign+spectral":
+                abi.check(lib.mtd_mesh_assign(g.h, N, abi.ptr(d_pos), dt, C.byref(box), None))
+                s, fwds = spectral(), (forward(),)
+            else:
+                s, fwds = g.cv(d_pos, dt, box, N), (forward(),)
+                if how == "cv+array+spectral":
+                    rho = g.array(0)
+                    assert np.abs(rho).max() > 0
+                    s2 = spectral()
+                    fwds += (forward(),)
+                    assert s2 == s                                      # (tile images or combined mesh: the same integer sums)
+            F = g.forces(d_pos, dt, box, N, 0.7)
+            res.append((s, F, (assign_info(abi, g)[0], fwds)))
+    finally:
+        g.close()
+    print("host layer", dims, env, how, np.dtype(dtype).name, [r[2] for r in res])
+    assert [r[2] for r in res[:2]] == expected
+    for first, again in zip(res[:2], res[2:]):
+        assert first[0] != 0.0 and np.abs(first[1]).max() > 0
+        assert again[0] == first[0] and np.array_equal(again[1], first[1])
