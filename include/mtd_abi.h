@@ -653,6 +653,25 @@ int mtd_ql_local_forces_opt(unsigned int n_particles, const void *d_postype, voi
                             unsigned int lmax, unsigned int type, const double *Ql_ref, unsigned int n_global, const double *d_scratch,
                             const double *d_bias, double bias_host, mtd_stream_t stream, const mtd_ql_local_options *opt);
 
+/* The force pass with the virial of the bias force beside it, for constant-pressure runs.  Let fp_kj be what the entry (k, j) of row k
+ * adds to F_k: the force on k from the unordered pair {k, j}, bias and 1 / N_global included, antisymmetric in k <-> j; and
+ * d_kj = minImage(r_k - r_j).  For the six components c = xx, xy, xz, yy, yz, zz (HOOMD's order; (a, b) with a <= b):
+ *     virial_k[ab] = 1/2 sum_{j in row k} d_kj,a fp_kj,b          stored at d_virial[c * virial_pitch + k]
+ * in the scalar type of the arrays (dtype), like HOOMD's ForceCompute::m_virial: half of each pair to each of its ends, HOOMD's
+ * convention for pair forces.  In the scatter form of the gradient above, an ordered entry (i centre, j neighbour) with gradient
+ * G_ij gives 1/2 d_ij,a (-bias G_ij,b / N_global) to i and the same to j.  sum_k virial_k[ab] = -bias ds/d eps_ab under an affine
+ * strain of positions and box; the summed tensor is symmetric (the variable is rotation invariant), the per-particle one need not
+ * be.  The same with every option: average, switch and gate act through the rows and E_kj, which are inside fp_kj.
+ * d_virial == NULL is mtd_ql_local_forces_opt: the same kernels, the same bits.  Otherwise virial_pitch >= n_particles
+ * (MTD_ERR_INVALID_ARGUMENT before a device is touched) and all six rows [0, n_particles) are written at every call, 0 for particles
+ * of another type or without a neighbour; [n_particles, virial_pitch) is left alone.  d_force is the array of the _opt call, bit for
+ * bit.  No atomics: bitwise reproducible like the force. */
+int mtd_ql_local_forces_virial(unsigned int n_particles, const void *d_postype, void *d_force, int dtype, const mtd_box *box,
+                               const unsigned int *d_head_list, const unsigned int *d_n_neigh, const unsigned int *d_nlist, double rcut, double ron,
+                               unsigned int lmax, unsigned int type, const double *Ql_ref, unsigned int n_global, const double *d_scratch,
+                               const double *d_bias, double bias_host, mtd_stream_t stream, const mtd_ql_local_options *opt, void *d_virial,
+                               unsigned int virial_pitch);
+
 /* ================================================================================================
  * Neighbour list of the stand-alone path (cell list, built on the device)
  * no reference counterpart: HOOMD's md::NeighborList is HOOMD core.  Produces the three arrays SteinhardtQl.cc:80-85 reads, in

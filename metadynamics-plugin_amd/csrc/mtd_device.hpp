@@ -152,6 +152,7 @@ __device__ __forceinline__ void nt_store(const double2 v, double2 *p)
     __builtin_nontemporal_store(x, (mtd_v2d *)p);
     }
 __device__ __forceinline__ void nt_store(const double v, double *p) { __builtin_nontemporal_store(v, p); }
+__device__ __forceinline__ void nt_store(const float v, float *p) { __builtin_nontemporal_store(v, p); }
 
 // ---- particle loads: Scalar4 with the type id bit-cast into w -----------------------------------
 

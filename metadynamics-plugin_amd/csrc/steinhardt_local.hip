@@ -49,6 +49,9 @@
 //                    into an LDS tile of its own, R(k) of its 16 particles once per chunk; times bias / N_global at the end
 //   k_qll_forces     the same with R(k) and R(j) read per lane and (l, m) straight from memory: rows longer than 256 bytes (more
 //                    than 16 complex slots) whose tiles would not fit
+//   virial           both force kernels carry a compile-time switch VIR (mtd_ql_local_forces_virial, for constant-pressure runs): the
+//                    entry's pair force fp and pair vector d are in hand, so virial_k[ab] = 1/2 sum_j d_a fp_b is six more sums per
+//                    lane beside the force (QllVirial), quad-summed and stored by lane 0; VIR = false is the kernel without it
 // Double precision throughout.  Host side: the compiled LMAX, the array type, AVG and the mode of pass 1 are chosen through dispatch.hpp.
 //
 // Options (mtd_ql_local_options; definition and gradient in include/mtd_abi.h): per-particle transforms of the quantities above.
@@ -505,13 +508,45 @@ template<bool AVG, typename ROW> struct QllWeights
 
 template<int LMAX> constexpr int qll_force_waves() { return LMAX <= 4 ? 3 : (LMAX <= 6 ? 2 : 1); }
 
-template<typename S4, int LMAX, bool AVG>
+// VIR: the virial of the bias force beside it (definition: include/mtd_abi.h).  fp is the complete force of the pair {k, j} on k and d
+// its pair vector, so the entry gives 1/2 d_a fp_b to k — the other half is formed in row j, from -d and -fp.  Six more sums per lane,
+// added over the quad in the order of the force and stored by lane 0, component c at virial[c * pitch + k]: no atomics, no LDS.  The
+// VIR = false instantiations are the kernels without the switch, instruction for instruction (profiles/r12).
+struct QllVirial
+    {
+    double xx, xy, xz, yy, yz, zz;
+    __device__ __forceinline__ void add(const double dx, const double dy, const double dz, const double fx, const double fy, const double fz)
+        {
+        xx += dx * fx, xy += dx * fy, xz += dx * fz;
+        yy += dy * fy, yz += dy * fz, zz += dz * fz;
+        }
+    template<typename scalar> __device__ __forceinline__ void store(scalar *virial, const unsigned int pitch, const unsigned int k, const unsigned int q,
+                                                                     const unsigned int N, const double scale)
+        {
+        xx = quad_sum(xx), xy = quad_sum(xy), xz = quad_sum(xz);
+        yy = quad_sum(yy), yz = quad_sum(yz), zz = quad_sum(zz);
+        if (q == 0 && k < N)
+            {
+            const double h = 0.5 * scale;
+            scalar *v = virial + k;
+            nt_store((scalar)(xx * h), v);
+            nt_store((scalar)(xy * h), v + pitch);
+            nt_store((scalar)(xz * h), v + 2 * (size_t)pitch);
+            nt_store((scalar)(yy * h), v + 3 * (size_t)pitch);
+            nt_store((scalar)(yz * h), v + 4 * (size_t)pitch);
+            nt_store((scalar)(zz * h), v + 5 * (size_t)pitch);
+            }
+        }
+    };
+
+template<typename S4, int LMAX, bool AVG, bool VIR>
 __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_forces(const QlArgs<LMAX> a, const QllLayout lay, const S4 *__restrict__ postype,
                                                             const unsigned int *__restrict__ head_list,
                                                             const unsigned int *__restrict__ n_neigh,
                                                             const unsigned int *__restrict__ nlist, const double *__restrict__ rows,
                                                             S4 *__restrict__ force, const double *__restrict__ d_bias, const double bias_host,
-                                                            const double *__restrict__ tab, const double *__restrict__ epair)
+                                                            const double *__restrict__ tab, const double *__restrict__ epair,
+                                                            typename scalar4_traits<S4>::scalar *__restrict__ virial, const unsigned int virial_pitch)
     {
     typedef typename scalar4_traits<S4>::scalar scalar;
     const unsigned int tid = threadIdx.x, p = tid / QLL_G, q = tid % QLL_G;
@@ -525,6 +560,7 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
         const Particle pk = ck.p;
         const double *__restrict__ rk = rows + (size_t)ck.row(a.N) * lay.row_doubles;
         double Fx = 0.0, Fy = 0.0, Fz = 0.0;
+        QllVirial W = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         unsigned int e = q;
         unsigned int j0 = e < cnt ? nlist[start + e] : QLL_NONE;
         unsigned int j1 = e + QLL_G < cnt ? nlist[start + e + QLL_G] : QLL_NONE;
@@ -554,6 +590,7 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
                     Fx += fpx;
                     Fy += fpy;
                     Fz += fpz;
+                    if constexpr (VIR) W.add(dx, dy, dz, fpx, fpy, fpz);
                     }
                 }
             j0 = j1;
@@ -566,6 +603,7 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
         Fz = quad_sum(Fz);
         if (q == 0 && k < a.N)
             nt_store(scalar4_traits<S4>::make((scalar)(Fx * scale), (scalar)(Fy * scale), (scalar)(Fz * scale), (scalar)0), force + k);
+        if constexpr (VIR) W.store(virial, virial_pitch, k, q, a.N, scale);
         }
     }
 
@@ -586,14 +624,15 @@ __device__ __forceinline__ void qll_wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
 
-template<typename S4, int LMAX, bool AVG>
+template<typename S4, int LMAX, bool AVG, bool VIR>
 __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_forces_tile(const QlArgs<LMAX> a, const QllLayout lay, const S4 *__restrict__ postype,
                                                             const unsigned int *__restrict__ head_list,
                                                             const unsigned int *__restrict__ n_neigh,
                                                             const unsigned int *__restrict__ nlist, const double *__restrict__ rows,
                                                             S4 *__restrict__ force, const double *__restrict__ d_bias, const double bias_host,
                                                             const double *__restrict__ tab, const unsigned int ts /* tile row stride, 16-byte units */,
-                                                            const double *__restrict__ epair)
+                                                            const double *__restrict__ epair,
+                                                            typename scalar4_traits<S4>::scalar *__restrict__ virial, const unsigned int virial_pitch)
     {
     typedef typename scalar4_traits<S4>::scalar scalar;
     extern __shared__ double2 s_tiles[];
@@ -623,6 +662,7 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
                 }
             }
         double Fx = 0.0, Fy = 0.0, Fz = 0.0;
+        QllVirial W = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         unsigned int e = q;
         unsigned int j0 = e < cnt ? nlist[start + e] : QLL_NONE;
         unsigned int j1 = e + QLL_G < cnt ? nlist[start + e + QLL_G] : QLL_NONE;
@@ -678,6 +718,7 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
                     Fx += fpx;
                     Fy += fpy;
                     Fz += fpz;
+                    if constexpr (VIR) W.add(dx, dy, dz, fpx, fpy, fpz);
                     }
                 qll_wave_sync();                            // the tile is free for the next iteration
                 }
@@ -692,6 +733,7 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
         Fz = quad_sum(Fz);
         if (q == 0 && k < a.N)
             nt_store(scalar4_traits<S4>::make((scalar)(Fx * scale), (scalar)(Fy * scale), (scalar)(Fz * scale), (scalar)0), force + k);
+        if constexpr (VIR) W.store(virial, virial_pitch, k, q, a.N, scale);
         }
     }
 
@@ -1032,10 +1074,11 @@ int qll_accumulate_impl(unsigned int N, const void *d_postype, const mtd_box *bo
     }
 
 // the force pass: through LDS tiles while a table row fits one, else straight from memory
-template<typename S4, int LMAX, bool AVG>
+template<typename S4, int LMAX, bool AVG, bool VIR>
 int qll_forces_impl(unsigned int N, const void *d_postype, void *d_force, const mtd_box *box, const unsigned int *d_head,
                     const unsigned int *d_nneigh, const unsigned int *d_nlist, double rcut, double ron, unsigned int lmax, unsigned int type,
-                    const double *ql_ref, unsigned int n_global, const QllScratch &sc, const double *d_bias, double bias_host, hipStream_t s)
+                    const double *ql_ref, unsigned int n_global, const QllScratch &sc, const double *d_bias, double bias_host, hipStream_t s,
+                    void *d_virial, unsigned int virial_pitch)
     {
     QlArgs<LMAX> a;
     int rc = fill_args<LMAX>(a, N, box, rcut, ron, lmax, type, ql_ref, n_global, 0);
@@ -1046,20 +1089,21 @@ int qll_forces_impl(unsigned int N, const void *d_postype, void *d_force, const 
     const unsigned int blocks = qll_blocks(N);
     const S4 *postype = (const S4 *)d_postype;
     S4 *force = (S4 *)d_force;
+    typename scalar4_traits<S4>::scalar *virial = VIR ? (typename scalar4_traits<S4>::scalar *)d_virial : nullptr;
     const double *epair = AVG ? sc.epair : nullptr;
     const unsigned int rs16 = lay.row_doubles / 2;
     if (rs16 <= QLL_TILE_MAX16)
         {
         const unsigned int ts = rs16 | 1u;                  // odd: rows of a tile start in different banks
         const size_t bytes = (size_t)QLL_TILE_ROWS * ts * sizeof(double2);
-        MTD_HIP_TRY(hipFuncSetAttribute((const void *)k_qll_forces_tile<S4, LMAX, AVG>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        MTD_HIP_TRY(hipFuncSetAttribute((const void *)k_qll_forces_tile<S4, LMAX, AVG, VIR>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int)((size_t)QLL_TILE_ROWS * (QLL_TILE_MAX16 | 1u) * sizeof(double2))));
-        k_qll_forces_tile<S4, LMAX, AVG><<<blocks, QLL_THREADS, bytes, s>>>(a, lay, postype, d_head, d_nneigh, d_nlist, sc.rows, force, d_bias, bias_host,
-                                                                            tab, ts, epair);
+        k_qll_forces_tile<S4, LMAX, AVG, VIR><<<blocks, QLL_THREADS, bytes, s>>>(a, lay, postype, d_head, d_nneigh, d_nlist, sc.rows, force, d_bias,
+                                                                                 bias_host, tab, ts, epair, virial, virial_pitch);
         }
     else
-        k_qll_forces<S4, LMAX, AVG><<<blocks, QLL_THREADS, 0, s>>>(a, lay, postype, d_head, d_nneigh, d_nlist, sc.rows, force, d_bias, bias_host, tab,
-                                                                   epair);
+        k_qll_forces<S4, LMAX, AVG, VIR><<<blocks, QLL_THREADS, 0, s>>>(a, lay, postype, d_head, d_nneigh, d_nlist, sc.rows, force, d_bias, bias_host,
+                                                                        tab, epair, virial, virial_pitch);
     MTD_LAUNCH_CHECK();
     return MTD_SUCCESS;
     }
@@ -1158,11 +1202,22 @@ int mtd_ql_local_forces_opt(unsigned int n_particles, const void *d_postype, voi
                             unsigned int lmax, unsigned int type, const double *Ql_ref, unsigned int n_global, const double *d_scratch,
                             const double *d_bias, double bias_host, mtd_stream_t stream, const mtd_ql_local_options *opt)
     {
+    return mtd_ql_local_forces_virial(n_particles, d_postype, d_force, dtype, box, d_head_list, d_n_neigh, d_nlist, rcut, ron, lmax, type, Ql_ref,
+                                      n_global, d_scratch, d_bias, bias_host, stream, opt, nullptr, 0);
+    }
+
+int mtd_ql_local_forces_virial(unsigned int n_particles, const void *d_postype, void *d_force, int dtype, const mtd_box *box,
+                               const unsigned int *d_head_list, const unsigned int *d_n_neigh, const unsigned int *d_nlist, double rcut, double ron,
+                               unsigned int lmax, unsigned int type, const double *Ql_ref, unsigned int n_global, const double *d_scratch,
+                               const double *d_bias, double bias_host, mtd_stream_t stream, const mtd_ql_local_options *opt, void *d_virial,
+                               unsigned int virial_pitch)
+    {
     int rc = qll_validate(n_particles, d_postype, dtype, box, d_head_list, d_n_neigh, rcut, ron, lmax, Ql_ref, n_global, d_scratch);
     if (rc) return rc;
     rc = qll_validate_options(opt);
     if (rc) return rc;
     if (n_particles && !d_force) return MTD_ERR_INVALID_ARGUMENT;
+    if (d_virial && virial_pitch < n_particles) return MTD_ERR_INVALID_ARGUMENT;
     if (n_particles == 0) return MTD_SUCCESS;
     const int mode = qll_mode(opt);
     const QllScratch sc = qll_scratch(const_cast<double *>(d_scratch), n_particles, lmax, mode);
@@ -1173,8 +1228,12 @@ int mtd_ql_local_forces_opt(unsigned int n_particles, const void *d_postype, voi
             {
             return dispatch_bool(mode == QLL_AVERAGE, [&](auto avg)
                 {
-                return qll_forces_impl<typename decltype(t)::type, decltype(lm)::value, decltype(avg)::value>(
-                    n_particles, d_postype, d_force, box, d_head_list, d_n_neigh, d_nlist, rcut, ron, lmax, type, Ql_ref, n_global, sc, d_bias, bias_host, s);
+                return dispatch_bool(d_virial != nullptr, [&](auto vir)
+                    {
+                    return qll_forces_impl<typename decltype(t)::type, decltype(lm)::value, decltype(avg)::value, decltype(vir)::value>(
+                        n_particles, d_postype, d_force, box, d_head_list, d_n_neigh, d_nlist, rcut, ron, lmax, type, Ql_ref, n_global, sc, d_bias,
+                        bias_host, s, d_virial, virial_pitch);
+                    });
                 });
             });
         });

@@ -854,12 +854,19 @@ void SteinhardtLocal::computeBiasForces(unsigned int timestep)
     if (!m_have_computed || m_cv_last_updated != timestep) computeCV(timestep);      // the table of THIS step's positions
     m_nlist->compute(timestep);
     const mtd_box box = m_pdata->getBox().toMtd();
-    mtd_check(mtd_ql_local_forces_opt(m_pdata->getN(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &box,
-                                      (const unsigned int *)m_nlist->getHeadList().data(), (const unsigned int *)m_nlist->getNNeighArray().data(),
-                                      (const unsigned int *)m_nlist->getNListArray().data(), m_rcut, m_ron, m_lmax, m_type, m_Ql_ref.data(),
-                                      m_pdata->getNGlobal(), (const double *)m_scratch.data(), m_bias_device, m_bias, m_exec_conf->getStream(),
-                                      &m_opt),
-              "mtd_ql_local_forces_opt");
+    // constant pressure: the per-particle virial of the bias force beside it (include/mtd_abi.h).  Without the flag today's call; a
+    // virial array somebody has allocated earlier is zeroed then, so that a stale virial is never read (as the mesh's external virial)
+    void *virial = nullptr;
+    if (m_pdata->getPressureFlag())
+        virial = getVirialArray().data();
+    else if (m_virial.bytes())
+        hip_check(hipMemsetAsync(m_virial.data(), 0, m_virial.bytes(), m_exec_conf->getStream()), "virial reset");
+    mtd_check(mtd_ql_local_forces_virial(m_pdata->getN(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &box,
+                                         (const unsigned int *)m_nlist->getHeadList().data(), (const unsigned int *)m_nlist->getNNeighArray().data(),
+                                         (const unsigned int *)m_nlist->getNListArray().data(), m_rcut, m_ron, m_lmax, m_type, m_Ql_ref.data(),
+                                         m_pdata->getNGlobal(), (const double *)m_scratch.data(), m_bias_device, m_bias, m_exec_conf->getStream(),
+                                         &m_opt, virial, getVirialPitch()),
+              "mtd_ql_local_forces_virial");
     }
 
 std::vector<double> SteinhardtLocal::getSwitchedValues(unsigned int timestep)

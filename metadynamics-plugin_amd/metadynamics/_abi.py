@@ -229,6 +229,8 @@ _SIGNATURES = {
                                                C.POINTER(QlLocalOptions), C.POINTER(_vp)]),
     "mtd_ql_local_forces_opt": (C.c_int, [C.c_uint, _vp, _vp, C.c_int, C.POINTER(Box), _vp, _vp, _vp, C.c_double, C.c_double, C.c_uint, C.c_uint,
                                            _dp, C.c_uint, _vp, _vp, C.c_double, _vp, C.POINTER(QlLocalOptions)]),
+    "mtd_ql_local_forces_virial": (C.c_int, [C.c_uint, _vp, _vp, C.c_int, C.POINTER(Box), _vp, _vp, _vp, C.c_double, C.c_double, C.c_uint, C.c_uint,
+                                              _dp, C.c_uint, _vp, _vp, C.c_double, _vp, C.POINTER(QlLocalOptions), _vp, C.c_uint]),
     "mtd_nlist_create": (C.c_int, [C.POINTER(_vp)]),
     "mtd_nlist_destroy": (C.c_int, [_vp]),
     "mtd_nlist_build": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp, C.c_int, C.POINTER(Box), C.c_double, C.c_int, C.c_int,

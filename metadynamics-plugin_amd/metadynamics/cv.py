@@ -277,6 +277,18 @@ class steinhardt_local(_collective_variable, metaclass=_local_options):
         """v_i = g(n_i) h(c_i) of every particle at the current time step: what the CV averages (c_i itself without options)"""
         return self.cpp_force.getSwitchedValues(context.current.system.getCurrentTimeStep())
 
+    def get_virial(self, per_particle=False):
+        """the virial of the bias force the last step wrote (include/mtd_abi.h, mtd_ql_local_forces_virial): the six sums xx, xy, xz, yy,
+        yz, zz as float64, or with ``per_particle=True`` the (6, N) array, half of every pair at each of its ends.  It is formed only
+        while the pressure flag of the particle data is set (a constant-pressure run); without the flag this raises."""
+        pdata = context.current.system_definition.getParticleData()
+        if not pdata.getPressureFlag():
+            raise RuntimeError("cv.steinhardt_local: the virial is computed only while the pressure flag is set")
+        import numpy as np
+        n = pdata.getN()
+        v = np.asarray(self.cpp_force.getVirial(), dtype=np.float64)[:, :n]
+        return v.copy() if per_particle else v.sum(axis=1)
+
     def set_options(self, average=False, switch=None, gate=None):
         """set all three options (the defaults switch them off); takes effect with the next step"""
         try:

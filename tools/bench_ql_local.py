@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Developer tool: the config 5 snapshot of tools/bench_ql.py (256 000-particle noisy fcc crystal, lmax 6, degrees 4 and 6,
 r_cut 1.4, 512-point grid) with cv.steinhardt_local instead of the global variable; prints us/step.
-usage: tools/bench_ql_local.py [steps] [f32|f64] [--device-nlist] [--average] [--switch c0,p] [--gate lo,hi] [--lmax L --ql-ref a,b,...]
-(--device-nlist: cv.nlist_cell(device=True), r_buff 0.4; the next three: the options of cv.steinhardt_local, e.g. --average --switch 0.12,3;
+usage: tools/bench_ql_local.py [steps] [f32|f64] [--device-nlist] [--average] [--switch c0,p] [--gate lo,hi] [--lmax L --ql-ref a,b,...] [--pressure]
+(--pressure: sets the pressure flag before the run, as a barostat would: the force pass also writes the per-particle virial;
+--device-nlist: cv.nlist_cell(device=True), r_buff 0.4; the next three: the options of cv.steinhardt_local, e.g. --average --switch 0.12,3;
 --lmax 12 --ql-ref 0,0,0,0,1,0,1,0,0,0,0.5,0.3,0.25: table rows of 784 bytes, which take the direct force pass instead of the LDS tiles)
 Run under rocprofv3 --kernel-trace --stats for the per-kernel table."""
 import os, sys, time
@@ -33,6 +34,7 @@ if "--average" in argv:
     options["average"] = True
 args = [a for a in argv if not a.startswith("--")]
 device_nlist = "--device-nlist" in argv
+pressure = "--pressure" in argv
 steps = int(args[0]) if len(args) > 0 else 100
 dtype = np.float32 if (len(args) > 1 and args[1] == "f32") else np.float64
 pos, L = util.fcc_lattice(40)
@@ -42,6 +44,7 @@ N = len(pos)
 
 def build(lo, hi, sigma):
     context.initialize(pos, np.zeros(N, dtype=np.int32), ["A"], L, dtype=dtype)
+    context.current.system_definition.getParticleData().setPressureFlag(pressure)
     meta = integrate.mode_metadynamics(dt=0.005, stride=1, mode="well_tempered", W=1.0, deltaT=7.0, T=1.0)
     nl = cv.nlist_cell(r_cut=1.4, device=device_nlist)
     entries = None if device_nlist else len(nl.update()[2])
@@ -72,7 +75,9 @@ c = st.get_local()
 print("on grid: %s, hills %d, bias factors %s, V = %g, mean c_i %.6f, mean n_i %.3f"
       % (0.0 <= st.cpp_force.getCurrentValue(t_now) < 2.0 * s0, meta.cpp_integrator.getNumGaussians(), list(meta.cpp_integrator.getBiasFactors()),
          meta.cpp_integrator.getLogValue("bias", t_now), c.mean(), st.get_coordination().mean()))
+if pressure:
+    print("virial of the bias force (xx xy xz yy yz zz): %s" % " ".join("%.6e" % w for w in st.get_virial()))
 if options:
     print("options %s: mean v_i %.6f" % (options, st.get_switched().mean()))
 print("config 5 local (%s%s%s): %.1f us/step  (%.3e particle-CV-evals/s, %.3e list entries/s incl. CV + force pass)"
-      % (np.dtype(dtype).name, ", device list" if device_nlist else "", "" if lmax == 6 else ", lmax %d" % lmax, 1e6 * dt / steps, N * steps / dt, 2 * entries * steps / dt))
+      % (np.dtype(dtype).name + (", virial" if pressure else ""), ", device list" if device_nlist else "", "" if lmax == 6 else ", lmax %d" % lmax, 1e6 * dt / steps, N * steps / dt, 2 * entries * steps / dt))

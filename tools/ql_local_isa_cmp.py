@@ -4,7 +4,8 @@ Compiles csrc/steinhardt_local.hip of <git revision> and of this tree to gfx950 
 by kernel: instruction count, identical text, identical opcode sequence.  A revision with this tree's kernel names is compared name by
 name (all 60 instantiations: profiles/r10/qll_isa_cmp.txt); the 24 kernels of a revision from before the options with the plain
 instantiations of this tree (k_qll_accumulate<.., QLL_PLAIN>, k_qll_forces<.., false>, k_qll_forces_tile<.., false>:
-profiles/r8/qll_isa_cmp.txt).
+profiles/r8/qll_isa_cmp.txt); the force kernels of a revision from before the virial switch with the VIR = false instantiations
+(k_qll_forces<.., AVG, false>, k_qll_forces_tile<.., AVG, false>: profiles/r12/qll_isa_cmp.txt).
 usage: tools/ql_local_isa_cmp.py <git revision>"""
 import os
 import re
@@ -56,7 +57,7 @@ def main(rev):
     same = True
     ops = lambda body: [x.split()[0] for x in body]
     for k, body in sorted(old.items()):
-        k2 = k if k in new else k[:-1] + (", 0>" if "accumulate" in k else ", false>")          # the plain instantiation of this tree
+        k2 = k if k in new else k[:-1] + (", 0>" if "accumulate" in k else ", false>")          # the plain / VIR = false instantiation of this tree
         b2 = new.get(k2)
         if b2 is None:
             print("%-40s has no counterpart %s" % (k, k2))
