@@ -567,6 +567,35 @@ int mtd_ql_forces(unsigned int n_particles, const void *d_postype, void *d_force
                   double rcut, double ron, unsigned int lmax, unsigned int type, const double *Ql_ref, unsigned int n_global,
                   const double *d_scratch, const double *d_bias, double bias_host, mtd_stream_t stream);
 
+/* mtd_ql_forces with the virial of the bias force beside it, for constant-pressure runs.  For entry (k, j) of row k the pass forms
+ * fp_kj, the `force` of SteinhardtQl.cc:278-322: -bias sum_l Ql_ref[l] 4 pi / ((2l + 1) N_global^2) 2 Re sum_m conj(Q_lm) grad_d (f Y_lm)(d_kj)
+ * with d_kj = minImage(r_k - r_j), and adds it to particle k only (the reference's central terms).  The virial is that
+ * of the force the pass applies: for the six components c = xx, xy, xz, yy, yz, zz (HOOMD's order; (a, b) with a <= b)
+ *     virial_k[ab] = 1/2 sum_{j in row k} d_kj,a fp_kj,b          stored at d_virial[c * virial_pitch + k]
+ * in the scalar type of the arrays (dtype), like HOOMD's ForceCompute::m_virial and mtd_ql_local_forces_virial: half of each pair at
+ * each of its ends, the other half is formed in row j.  On a symmetric full list (half_nlist 0 or 2) the even-degree terms of fp are
+ * antisymmetric in k <-> j and the odd-degree weights conj(Q_lm) vanish to rounding, so sum_k virial_k is the virial of the applied
+ * forces, and modes 0 and 2 give the same per-particle values.
+ * Relation to the strain derivative: the full-list force of the reference is HALF the gradient of the variable s, because only the
+ * central terms are kept (the terms in which k appears as somebody's neighbour are dropped).  So
+ *     sum_k virial_k[ab] = -1/2 bias ds/d eps_ab
+ * under an affine strain of positions and box with the list kept: the virial of the force that is applied, not of -bias grad s.
+ * (Checked on the CPU against central differences of the oracle's CV: tests/test_ql_virial_ref.py.)
+ * Ghost particles: with a full list that indexes ghosts (j >= n_particles, stored behind the local particles) every rank writes the
+ * rows of its local particles, and the ranks' sums add up to the single-rank sum.
+ * d_virial == NULL is mtd_ql_forces: the same kernels, the same bits, any list mode.  Otherwise virial_pitch >= n_particles
+ * (MTD_ERR_INVALID_ARGUMENT) and half_nlist != 1: the third-law pass of a half list scatters its reaction forces and forms no virial
+ * (MTD_ERR_UNSUPPORTED; pass the symmetric full list of mtd_ql_symmetrize_half_list with half_nlist = 2).  Everything mtd_ql_forces
+ * refuses is refused with the same code; all of it before a device is touched.  All six rows [0, n_particles) are written at every
+ * call, 0 for particles of another type or without a neighbour; [n_particles, virial_pitch) is left alone.  d_force is the array of
+ * mtd_ql_forces, bit for bit.  No atomics: bitwise reproducible like the force.  A deferred pass of the bias grid that is waiting on
+ * the stream does not ride in this launch (it stays pending and runs as a launch of its own: the same grid, bit for bit). */
+int mtd_ql_forces_virial(unsigned int n_particles, const void *d_postype, void *d_force, int dtype, const mtd_box *box,
+                         const unsigned int *d_head_list, const unsigned int *d_n_neigh, const unsigned int *d_nlist, int half_nlist,
+                         double rcut, double ron, unsigned int lmax, unsigned int type, const double *Ql_ref, unsigned int n_global,
+                         const double *d_scratch, const double *d_bias, double bias_host, mtd_stream_t stream, void *d_virial,
+                         unsigned int virial_pitch);
+
 /* ================================================================================================
  * Local Steinhardt bond order (cv.steinhardt_local) — no reference counterpart.  The harmonics summed over one particle's own
  * neighbours, turned into a rotational invariant PER PARTICLE, then averaged; conventions of mtd_ql_accumulate in every respect

@@ -30,6 +30,8 @@
 //                     vectors alpha = d f'/r, beta = (f/r) e_theta, gamma = (f/rho) e_phi; m < 0 terms equal their m > 0
 //                     partners (weight 2), degrees with Ql_ref[l] = 0 are skipped as a whole.  Per-particle sums over the
 //                     pairs of a unit in a fixed order through LDS (deterministic, no atomics for full lists).
+//                     VIR (mtd_ql_forces_virial): the pair vectors go through LDS beside the pair forces and the summing
+//                     threads form virial_k[ab] = 1/2 sum_j d_kj,a fp_kj,b in the same order
 // Double precision throughout.
 #include "mtd_device.hpp"
 #include "steinhardt_device.hpp"
@@ -758,15 +760,29 @@ struct QlCarry { mtd::MetadCfg cfg; unsigned int n_apply; };
 template<bool CARRY> struct QlCarryArg { typedef QlNoCarry type; };
 template<> struct QlCarryArg<true> { typedef QlCarry type; };
 
-template<typename S4, int LMAX, bool HALF, bool EXACT, bool CARRY = false>
-__global__ __launch_bounds__(QL_THREADS, (LMAX <= 6 ? 3 : 2)) void k_ql_forces(const QlArgs<LMAX> a, const S4 *__restrict__ postype,
+// VIR (full lists only): the per-particle virial of the force the pass applies, virial_k[ab] = 1/2 sum_{j in row k} d_kj,a fp_kj,b
+// (include/mtd_abi.h, mtd_ql_forces_virial).  The pair thread publishes d_kj beside fp_kj (three more arrays of QL_CAP doubles:
+// 58.9 KB of LDS per block at LMAX 6 instead of 34.3, two blocks per compute unit instead of three — the bounds below promise two,
+// and the launch sizes itself with ql_resident_blocks as ever); the summing threads form the six products from the LDS values in
+// the order of the force sums, add them over the quad and lane 0 stores them.  The force sums are the same operations on the same
+// values.  NoVir: an empty struct, the plain instantiations keep their argument list, their LDS and their code.
+struct QlNoVir { };
+struct QlVir { void *virial; unsigned int pitch; };
+template<bool VIR> struct QlVirArg { typedef QlNoVir type; };
+template<> struct QlVirArg<true> { typedef QlVir type; };
+constexpr int ql_force_blocks_per_cu(const int lmax, const bool vir) { return lmax <= 6 && !vir ? 3 : 2; }
+
+template<typename S4, int LMAX, bool HALF, bool EXACT, bool CARRY = false, bool VIR = false>
+__global__ __launch_bounds__(QL_THREADS, (ql_force_blocks_per_cu(LMAX, VIR))) void k_ql_forces(const QlArgs<LMAX> a, const S4 *__restrict__ postype,
                                                              const unsigned int *__restrict__ head_list,
                                                              const unsigned int *__restrict__ n_neigh,
                                                              const unsigned int *__restrict__ nlist, const double *__restrict__ qlm_full,
                                                              S4 *__restrict__ force, const double *__restrict__ d_bias, const double bias_host,
                                                              unsigned long long *__restrict__ exact_acc, double *__restrict__ own,
-                                                             const double *__restrict__ tab, const typename QlCarryArg<CARRY>::type carry)
+                                                             const double *__restrict__ tab, const typename QlCarryArg<CARRY>::type carry,
+                                                             const typename QlVirArg<VIR>::type vir)
     {
+    static_assert(!VIR || (!HALF && !EXACT && !CARRY), "the virial is formed by the gathering pass of a full list, without a passenger");
     unsigned int n_work = gridDim.x;
     if constexpr (CARRY)
         {
@@ -787,6 +803,7 @@ __global__ __launch_bounds__(QL_THREADS, (LMAX <= 6 ? 3 : 2)) void k_ql_forces(c
     __shared__ double s_qw[2 * NLM];                 // w_l (2 or 4) conj(Q_lm), m >= 0, index l(l+1)/2 + m
     __shared__ QlUnit su[3];
     __shared__ double s_fx[CAP], s_fy[CAP], s_fz[CAP];          // pair forces of the unit, by list entry
+    __shared__ double s_dx[VIR ? CAP : 1], s_dy[VIR ? CAP : 1], s_dz[VIR ? CAP : 1];   // VIR: their pair vectors (never referenced otherwise)
     const unsigned int tid = threadIdx.x;
     const bool setup_wave = (tid >> 6) == QL_THREADS / MTD_WAVE - 1;
     const double bias = d_bias ? *d_bias : bias_host;
@@ -825,6 +842,7 @@ __global__ __launch_bounds__(QL_THREADS, (LMAX <= 6 ? 3 : 2)) void k_ql_forces(c
     S4 pos_raw = zero_s4<S4>();
     if (su[0].valid && tid < min(su[0].total, CAP)) pos_raw = postype[j_cur[0]];
     double Fx = 0.0, Fy = 0.0, Fz = 0.0;             // thread (p = tid / 4, q = tid % 4): every fourth pair force of particle p
+    double V[VIR ? 6 : 1] = {};                      // VIR: and every fourth sum d_a fp_b of particle p (xx, xy, xz, yy, yz, zz)
 
     for (unsigned int n = 0;; ++n)
         {
@@ -883,6 +901,12 @@ __global__ __launch_bounds__(QL_THREADS, (LMAX <= 6 ? 3 : 2)) void k_ql_forces(c
                 s_fx[t] = fpx;
                 s_fy[t] = fpy;
                 s_fz[t] = fpz;
+                if constexpr (VIR)
+                    {
+                    s_dx[t] = dx;
+                    s_dy[t] = dy;
+                    s_dz[t] = dz;
+                    }
                 }
             pos_raw = pos_ahead;
             j0 = j1; j1 = j2; j2 = j3;
@@ -901,6 +925,16 @@ __global__ __launch_bounds__(QL_THREADS, (LMAX <= 6 ? 3 : 2)) void k_ql_forces(c
                 Fx += s_fx[t];
                 Fy += s_fy[t];
                 Fz += s_fz[t];
+                if constexpr (VIR)
+                    {
+                    const double ex = s_dx[t], ey = s_dy[t], ez = s_dz[t], gx = s_fx[t], gy = s_fy[t], gz = s_fz[t];
+                    V[0] = fma(ex, gx, V[0]);
+                    V[1] = fma(ex, gy, V[1]);
+                    V[2] = fma(ex, gz, V[2]);
+                    V[3] = fma(ey, gy, V[3]);
+                    V[4] = fma(ey, gz, V[4]);
+                    V[5] = fma(ez, gz, V[5]);
+                    }
                 }
             if (base + CAP >= total)               // the chunk's last batch: (q0 + q1) + (q2 + q3), every lane of the quad gets it
                 {
@@ -911,6 +945,23 @@ __global__ __launch_bounds__(QL_THREADS, (LMAX <= 6 ? 3 : 2)) void k_ql_forces(c
                 Fy += dpp_move<MTD_DPP_QUAD_XOR2>(Fy);
                 Fz += dpp_move<MTD_DPP_QUAD_XOR2>(Fz);
                 const unsigned int i = chunk * PPB + p;
+                if constexpr (VIR)
+                    {
+#pragma unroll
+                    for (int c = 0; c < 6; ++c)
+                        {
+                        V[c] += dpp_move<MTD_DPP_QUAD_XOR1>(V[c]);
+                        V[c] += dpp_move<MTD_DPP_QUAD_XOR2>(V[c]);
+                        }
+                    if (q == 0 && i < a.N)                 // (i < N <= pitch: mtd_ql_forces_virial)
+                        {
+                        scalar *__restrict__ w = (scalar *)vir.virial;
+#pragma unroll
+                        for (int c = 0; c < 6; ++c) nt_store((scalar)(0.5 * V[c]), w + (size_t)c * vir.pitch + i);
+                        }
+#pragma unroll
+                    for (int c = 0; c < 6; ++c) V[c] = 0.0;
+                    }
                 if (q == 0 && i < a.N)
                     {
                     if (HALF && EXACT)
@@ -1046,10 +1097,24 @@ int accumulate_impl(unsigned int N, const void *d_postype, int dtype, const mtd_
 template<typename S4, int LMAX, bool HALF, bool EXACT>
 void launch_forces(const QlArgs<LMAX> &a, const S4 *postype, const unsigned int *d_head, const unsigned int *d_nneigh, const unsigned int *d_nlist,
                    const double *d_qlm, S4 *force, const double *d_bias, const double bias_host, unsigned long long *acc, double *own, const double *tab,
-                   hipStream_t s)
+                   void *d_virial, const unsigned int virial_pitch, hipStream_t s)
     {
     if constexpr (!HALF && !EXACT)
         {
+        if (d_virial)
+            {
+            // the VIR kernel takes no passenger (one instantiation per array type and LMAX instead of two of the unit's largest
+            // kernel): a deferred pass stays pending and metad_flush runs it as a launch of its own, as below — the same cells, the
+            // same arithmetic, the same grid
+            QlVir vir;
+            vir.virial = d_virial;
+            vir.pitch = virial_pitch;
+            const unsigned int cap = ql_resident_blocks(k_ql_forces<S4, LMAX, false, false, false, true>);
+            const unsigned int blocks = ql_blocks(a.N, QL_PPB, cap);
+            k_ql_forces<S4, LMAX, false, false, false, true><<<blocks, QL_THREADS, 0, s>>>(a, postype, d_head, d_nneigh, d_nlist, d_qlm, force, d_bias, bias_host,
+                                                                                           acc, own, tab, QlNoCarry(), vir);
+            return;
+            }
         QlCarry carry;
         if (mtd_metad *engine = mtd::take_pending_apply(s, carry.cfg))
             {
@@ -1059,7 +1124,7 @@ void launch_forces(const QlArgs<LMAX> &a, const S4 *postype, const unsigned int 
                 {
                 const unsigned int blocks = ql_blocks(a.N, QL_PPB, cap - carry.n_apply);
                 k_ql_forces<S4, LMAX, false, false, true><<<blocks + carry.n_apply, QL_THREADS, 0, s>>>(a, postype, d_head, d_nneigh, d_nlist, d_qlm, force, d_bias,
-                                                                                                     bias_host, acc, own, tab, carry);
+                                                                                                     bias_host, acc, own, tab, carry, QlNoVir());
                 if (hipPeekAtLastError() == hipSuccess) mtd::commit_pending_apply(engine);      // a failed launch leaves the pass pending
                 return;
                 }
@@ -1068,19 +1133,20 @@ void launch_forces(const QlArgs<LMAX> &a, const S4 *postype, const unsigned int 
         }
     const unsigned int cap = ql_resident_blocks(k_ql_forces<S4, LMAX, HALF, EXACT>);
     const unsigned int blocks = ql_blocks(a.N, QL_PPB, cap);
-    k_ql_forces<S4, LMAX, HALF, EXACT><<<blocks, QL_THREADS, 0, s>>>(a, postype, d_head, d_nneigh, d_nlist, d_qlm, force, d_bias, bias_host, acc, own, tab, QlNoCarry());
+    k_ql_forces<S4, LMAX, HALF, EXACT><<<blocks, QL_THREADS, 0, s>>>(a, postype, d_head, d_nneigh, d_nlist, d_qlm, force, d_bias, bias_host, acc, own, tab, QlNoCarry(), QlNoVir());
     }
 
 template<int LMAX>
 int forces_impl(unsigned int N, const void *d_postype, void *d_force, int dtype, const mtd_box *box, const unsigned int *d_head,
                 const unsigned int *d_nneigh, const unsigned int *d_nlist, int half, double rcut, double ron, unsigned int lmax,
                 unsigned int type, const double *ql_ref, unsigned int n_global, const double *d_qlm, const double *d_bias,
-                double bias_host, hipStream_t s)
+                double bias_host, void *d_virial, unsigned int virial_pitch, hipStream_t s)
     {
     half = half == 1 ? 1 : 0;                                                // a symmetric full list (2) is a full list here
     QlArgs<LMAX> a;
     int rc = fill_args<LMAX>(a, N, box, rcut, ron, lmax, type, ql_ref, n_global, half);
     if (rc) return rc;
+    if (half && d_virial) return MTD_ERR_UNSUPPORTED;                        // the third-law pass forms no virial (mtd_ql_forces_virial)
     const double *tab = ql_device_table<LMAX>(s, rc);
     if (rc) return rc;
     // half lists: exact integer accumulators (memset of :236 = clearing them), stream-ordered scratch from the device's pool
@@ -1141,20 +1207,20 @@ int forces_impl(unsigned int N, const void *d_postype, void *d_force, int dtype,
     if (dtype == MTD_F32)
         {
         if (exact)
-            launch_forces<float4, LMAX, true, true>(a, (const float4 *)d_postype, d_head, d_nneigh, d_nlist, d_qlm, (float4 *)d_force, d_bias, bias_host, acc, own, tab, s);
+            launch_forces<float4, LMAX, true, true>(a, (const float4 *)d_postype, d_head, d_nneigh, d_nlist, d_qlm, (float4 *)d_force, d_bias, bias_host, acc, own, tab, d_virial, virial_pitch, s);
         else if (half)
-            launch_forces<float4, LMAX, true, false>(a, (const float4 *)d_postype, d_head, d_nneigh, d_nlist, d_qlm, (float4 *)d_force, d_bias, bias_host, nullptr, nullptr, tab, s);
+            launch_forces<float4, LMAX, true, false>(a, (const float4 *)d_postype, d_head, d_nneigh, d_nlist, d_qlm, (float4 *)d_force, d_bias, bias_host, nullptr, nullptr, tab, d_virial, virial_pitch, s);
         else
-            launch_forces<float4, LMAX, false, false>(a, (const float4 *)d_postype, d_head, d_nneigh, d_nlist, d_qlm, (float4 *)d_force, d_bias, bias_host, nullptr, nullptr, tab, s);
+            launch_forces<float4, LMAX, false, false>(a, (const float4 *)d_postype, d_head, d_nneigh, d_nlist, d_qlm, (float4 *)d_force, d_bias, bias_host, nullptr, nullptr, tab, d_virial, virial_pitch, s);
         }
     else
         {
         if (exact)
-            launch_forces<double4, LMAX, true, true>(a, (const double4 *)d_postype, d_head, d_nneigh, d_nlist, d_qlm, (double4 *)d_force, d_bias, bias_host, acc, own, tab, s);
+            launch_forces<double4, LMAX, true, true>(a, (const double4 *)d_postype, d_head, d_nneigh, d_nlist, d_qlm, (double4 *)d_force, d_bias, bias_host, acc, own, tab, d_virial, virial_pitch, s);
         else if (half)
-            launch_forces<double4, LMAX, true, false>(a, (const double4 *)d_postype, d_head, d_nneigh, d_nlist, d_qlm, (double4 *)d_force, d_bias, bias_host, nullptr, nullptr, tab, s);
+            launch_forces<double4, LMAX, true, false>(a, (const double4 *)d_postype, d_head, d_nneigh, d_nlist, d_qlm, (double4 *)d_force, d_bias, bias_host, nullptr, nullptr, tab, d_virial, virial_pitch, s);
         else
-            launch_forces<double4, LMAX, false, false>(a, (const double4 *)d_postype, d_head, d_nneigh, d_nlist, d_qlm, (double4 *)d_force, d_bias, bias_host, nullptr, nullptr, tab, s);
+            launch_forces<double4, LMAX, false, false>(a, (const double4 *)d_postype, d_head, d_nneigh, d_nlist, d_qlm, (double4 *)d_force, d_bias, bias_host, nullptr, nullptr, tab, d_virial, virial_pitch, s);
         }
     hipError_t launch_err = hipGetLastError();
     if (exact && N)
@@ -1558,17 +1624,28 @@ int mtd_ql_forces(unsigned int n_particles, const void *d_postype, void *d_force
                   double rcut, double ron, unsigned int lmax, unsigned int type, const double *Ql_ref, unsigned int n_global,
                   const double *d_scratch, const double *d_bias, double bias_host, mtd_stream_t stream)
     {
+    return mtd_ql_forces_virial(n_particles, d_postype, d_force, dtype, box, d_head_list, d_n_neigh, d_nlist, half_nlist, rcut, ron, lmax, type, Ql_ref,
+                                n_global, d_scratch, d_bias, bias_host, stream, nullptr, 0);
+    }
+
+int mtd_ql_forces_virial(unsigned int n_particles, const void *d_postype, void *d_force, int dtype, const mtd_box *box,
+                         const unsigned int *d_head_list, const unsigned int *d_n_neigh, const unsigned int *d_nlist, int half_nlist,
+                         double rcut, double ron, unsigned int lmax, unsigned int type, const double *Ql_ref, unsigned int n_global,
+                         const double *d_scratch, const double *d_bias, double bias_host, mtd_stream_t stream, void *d_virial,
+                         unsigned int virial_pitch)
+    {
     if (!d_scratch || (n_particles && (!d_postype || !d_force || !d_head_list || !d_n_neigh))) return MTD_ERR_INVALID_ARGUMENT;
     if (dtype != MTD_F32 && dtype != MTD_F64) return MTD_ERR_INVALID_ARGUMENT;
     if (lmax > 12) return MTD_ERR_UNSUPPORTED;
     if (n_particles == 0) return MTD_SUCCESS;
+    if (d_virial && virial_pitch < n_particles) return MTD_ERR_INVALID_ARGUMENT;
     double *partials, *qprime, *qlm, *ql, *value;
     ql_layout((double *)d_scratch, lmax, &partials, &qprime, &qlm, &ql, &value);
     hipStream_t s = (hipStream_t)stream;
     return dispatch_lmax(lmax, [&](auto lm)
         {
         return forces_impl<decltype(lm)::value>(n_particles, d_postype, d_force, dtype, box, d_head_list, d_n_neigh, d_nlist, half_nlist, rcut, ron, lmax, type,
-                                                Ql_ref, n_global, qlm, d_bias, bias_host, s);
+                                                Ql_ref, n_global, qlm, d_bias, bias_host, d_virial, virial_pitch, s);
         });
     }
 

@@ -712,10 +712,24 @@ void SteinhardtQl::computeBiasForces(unsigned int timestep)
     if (!m_have_computed) computeCV(timestep);
     const mtd_box box = m_pdata->getBox().toMtd();
     const Lists l = lists();
-    mtd_check(mtd_ql_forces(m_pdata->getN(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &box, l.head, l.n_neigh, l.nlist, l.mode,
-                            m_rcut, m_ron, m_lmax, m_type, m_Ql_ref.data(), m_pdata->getNGlobal(), (const double *)m_scratch.data(),
-                            m_bias_device, m_bias, m_exec_conf->getStream()),
-              "mtd_ql_forces");
+    // constant pressure: the per-particle virial of the bias force beside it (include/mtd_abi.h).  Without the flag today's call; a
+    // virial array somebody has allocated earlier is zeroed then, so that a stale virial is never read (as SteinhardtLocal).  A half
+    // list reaches this point as its symmetric full list (mode 2); the third-law pass (kept by the diagnostic MTD_QL_HALF_THIRD_LAW, or
+    // for a half list that indexes ghost particles) forms no virial
+    void *virial = nullptr;
+    if (m_pdata->getPressureFlag())
+        {
+        if (l.mode == 1)
+            throw std::runtime_error("cv.steinhardt: the third-law pass of a half neighbour list (MTD_QL_HALF_THIRD_LAW, or a half list "
+                                     "with ghost particles) forms no virial: unset the variable or use a full list in a constant-pressure run");
+        virial = getVirialArray().data();
+        }
+    else if (m_virial.bytes())
+        hip_check(hipMemsetAsync(m_virial.data(), 0, m_virial.bytes(), m_exec_conf->getStream()), "virial reset");
+    mtd_check(mtd_ql_forces_virial(m_pdata->getN(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &box, l.head, l.n_neigh, l.nlist,
+                                   l.mode, m_rcut, m_ron, m_lmax, m_type, m_Ql_ref.data(), m_pdata->getNGlobal(), (const double *)m_scratch.data(),
+                                   m_bias_device, m_bias, m_exec_conf->getStream(), virial, getVirialPitch()),
+              "mtd_ql_forces_virial");
     }
 
 std::vector<std::string> SteinhardtQl::getProvidedLogQuantities()

@@ -213,6 +213,21 @@ class steinhardt(_collective_variable):
         names = context.current.type_names
         return {(a, b): (self.r_cut if a == b == self.type else -1.0) for i, a in enumerate(names) for b in names[i:]}
 
+    def get_virial(self, per_particle=False):
+        """the virial of the bias force the last step wrote (include/mtd_abi.h, mtd_ql_forces_virial): the six sums xx, xy, xz, yy, yz,
+        zz as float64, or with ``per_particle=True`` the (6, N) array, half of every pair at each of its ends.  It is the virial of the
+        force that is applied: the full-list force keeps only the central terms of the gradient (as the reference's), so the sums are
+        -1/2 * bias * ds/d(strain), not -bias * ds/d(strain).  In a domain-decomposed run every rank holds the rows of its local
+        particles.  It is formed only while the pressure flag of the particle data is set (a constant-pressure run); without the flag
+        this raises."""
+        pdata = context.current.system_definition.getParticleData()
+        if not pdata.getPressureFlag():
+            raise RuntimeError("cv.steinhardt: the virial is computed only while the pressure flag is set")
+        import numpy as np
+        n = pdata.getN()
+        v = np.asarray(self.cpp_force.getVirial(), dtype=np.float64)[:, :n]
+        return v.copy() if per_particle else v.sum(axis=1)
+
 
 class _local_options(type):
     """``cv.steinhardt_local(..., average=False, switch=None, gate=None)``: the three options are keyword arguments of the CALL.  They

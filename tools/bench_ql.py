@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Developer tool: BASELINE.json configs[4] / SURVEY config 5 (256 000-particle noisy fcc crystal, cv.steinhardt lmax 6,
 full neighbour list r_cut 1.4, 512-point grid) through the reference-shaped API; prints us/step.
+usage: tools/bench_ql.py [steps] [f32|f64] [--pressure]
+(--pressure: sets the pressure flag before the run, as a barostat would: the force pass also writes the per-particle virial)
 Run under rocprofv3 --kernel-trace --stats for the per-kernel table."""
 import os, sys, time
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -8,8 +10,10 @@ sys.path[:0] = [os.path.join(root, "metadynamics-plugin_amd"), os.path.join(root
 import numpy as np, torch
 import util
 from metadynamics import context, cv, integrate
-steps = int(sys.argv[1]) if len(sys.argv) > 1 else 100
-dtype = np.float32 if (len(sys.argv) > 2 and sys.argv[2] == "f32") else np.float64
+pressure = "--pressure" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if not a.startswith("--")]
+steps = int(args[0]) if len(args) > 0 else 100
+dtype = np.float32 if (len(args) > 1 and args[1] == "f32") else np.float64
 pos, L = util.fcc_lattice(40)
 pos = pos + np.random.default_rng(777).normal(0, 0.05, pos.shape)
 N = len(pos)
@@ -17,6 +21,7 @@ N = len(pos)
 
 def build(hi, sigma):
     context.initialize(pos, np.zeros(N, dtype=np.int32), ["A"], L, dtype=dtype)
+    context.current.system_definition.getParticleData().setPressureFlag(pressure)
     meta = integrate.mode_metadynamics(dt=0.005, stride=1, mode="well_tempered", W=1.0, deltaT=7.0, T=1.0)
     nl = cv.nlist_cell(r_cut=1.4)
     lists = nl.update()
@@ -45,5 +50,7 @@ pairs = len(lists[2])
 t_now = context.current.system.getCurrentTimeStep()
 print("on grid: %s, hills %d, bias factors %s, V = %g" % (0.0 <= st.cpp_force.getCurrentValue(t_now) < 2.0 * s0, meta.cpp_integrator.getNumGaussians(),
                                                          list(meta.cpp_integrator.getBiasFactors()), meta.cpp_integrator.getLogValue("bias", t_now)))
+if pressure:
+    print("virial of the bias force (xx xy xz yy yz zz): %s" % " ".join("%.6e" % w for w in st.get_virial()))
 print("config 5 (%s): %.1f us/step  (%.3e particle-CV-evals/s, %.3e pair visits/s incl. CV + force pass)"
-      % (np.dtype(dtype).name, 1e6 * dt / steps, N * steps / dt, 2 * pairs * steps / dt))
+      % (np.dtype(dtype).name + (", virial" if pressure else ""), 1e6 * dt / steps, N * steps / dt, 2 * pairs * steps / dt))
