@@ -701,6 +701,53 @@ int mtd_ql_local_forces_virial(unsigned int n_particles, const void *d_postype, 
                                const double *d_bias, double bias_host, mtd_stream_t stream, const mtd_ql_local_options *opt, void *d_virial,
                                unsigned int virial_pitch);
 
+/* The solid-bond count (ten Wolde, Ruiz-Montero and Frenkel, J. Chem. Phys. 104, 9932; PLUMED's LOCAL_Q6 followed by MORE_THAN):
+ * a bond is solid when the normalised scalar product of the q vectors of its two ends exceeds a threshold, a particle is solid when
+ * it has enough solid bonds.  With g_l = Ql_ref[l] 4 pi / (2l + 1), <a, b> = sum_l g_l Re sum_m a_lm conj(b_lm) over the degrees in
+ * use and q_lm(i) = A_lm(i) / n_i (0 when n_i == 0):
+ *     c_i   = <q(i), q(i)>                        the plain local value (what *d_c holds)
+ *     u(i)  = q(i) / sqrt(c_i)                    0 when c_i == 0
+ *     d_ij  = <u(i), u(j)>                        in [-1, 1], symmetric in i, j
+ *     sigma = 3 t^2 - 2 t^3,  t = clip((d - d_lo) / (d_hi - d_lo), 0, 1),  -1 <= d_lo < d_hi <= 1
+ *     b_i   = sum_{j in row i} f(r_ij) sigma(d_ij)                     the smooth number of solid bonds (what *d_b holds)
+ *     v_i   = g(n_i) h(b_i)                       the switch of the options acts on b_i (x = max(b, 0) / c0; h(b) = b without one),
+ *                                                 the gate on n_i (what *d_v holds)
+ *     s     = (1 / N_global) sum_i v_i
+ * With Ql_ref = e_6, bonds (0.5, 0.7) and a switch (6.5, 12), s N_global is the smooth number of solid particles of the literature.
+ * <.,.> must be a norm: a negative Ql_ref[l] with bonds on is MTD_ERR_INVALID_ARGUMENT, as are bonds without
+ * -1 <= d_lo < d_hi <= 1 (NaN included); `average` together with bonds is MTD_ERR_UNSUPPORTED.  All before a device is touched.
+ * Gradient: with beta_i = g(n_i) h'(b_i) and t_kj = (beta_k + beta_j) f_kj sigma'(d_kj),
+ *     P(k)    = [ sum_{j in row k} t_kj u(j) - (sum_j t_kj d_kj) u(k) ] / sqrt(c_k)          (<P(k), u(k)> = 0 identically)
+ *     B_lm(k) = g_l conj(P_lm(k)),  C = B                                                   (no neighbour average)
+ *     a_k     = g'(n_k) h(b_k) - Re sum_lm C_lm(k) q_lm(k) / n_k                             (the second term vanishes analytically)
+ *     G_kj    = Re sum_lm (C_lm(k) / n_k) grad(f Y_lm)(d_kj) + ( a_k + beta_k sigma(d_kj) ) grad f(d_kj)
+ *     N_global ds/dr_k = sum_j G_kj - sum_j G_jk
+ * Like the average it reaches second neighbours and needs the full, symmetric list, two gather passes inside the accumulate call and
+ * one double per list entry in the scratch.  The virial is that of mtd_ql_local_forces_virial: sigma and beta act through the rows
+ * and the per-entry scalar, which are inside fp_kj.  Known limit: 1 / sqrt(c_i) makes the gradient large where a particle's q vector
+ * nearly vanishes.
+ * bonds == NULL or on == 0: the _opt / _virial entry points, bit for bit (those forward here).  The same opt and bonds go to both
+ * passes; the scratch is sized with mtd_ql_local_scratch_doubles_bonds, again whenever the list grows.  d_b may be NULL; *d_b is NULL when bonds
+ * are off. */
+typedef struct
+    {
+    int on;
+    double d_lo, d_hi;
+    } mtd_ql_local_bonds;                                                      /* all-zero = off */
+
+size_t mtd_ql_local_scratch_doubles_bonds(unsigned int n_particles, unsigned int lmax, size_t n_list_entries, const mtd_ql_local_options *opt,
+                                          const mtd_ql_local_bonds *bonds);
+int mtd_ql_local_accumulate_bonds(unsigned int n_particles, const void *d_postype, int dtype, const mtd_box *box, const unsigned int *d_head_list,
+                                  const unsigned int *d_n_neigh, const unsigned int *d_nlist, double rcut, double ron, unsigned int lmax,
+                                  unsigned int type, const double *Ql_ref, unsigned int n_global, double *d_scratch, const double **d_partials,
+                                  unsigned int *n_partials, const double **d_c, const double **d_n, mtd_stream_t stream,
+                                  const mtd_ql_local_options *opt, const double **d_v, const mtd_ql_local_bonds *bonds, const double **d_b);
+int mtd_ql_local_forces_bonds(unsigned int n_particles, const void *d_postype, void *d_force, int dtype, const mtd_box *box,
+                              const unsigned int *d_head_list, const unsigned int *d_n_neigh, const unsigned int *d_nlist, double rcut, double ron,
+                              unsigned int lmax, unsigned int type, const double *Ql_ref, unsigned int n_global, const double *d_scratch,
+                              const double *d_bias, double bias_host, mtd_stream_t stream, const mtd_ql_local_options *opt, void *d_virial,
+                              unsigned int virial_pitch, const mtd_ql_local_bonds *bonds);
+
 /* ================================================================================================
  * Neighbour list of the stand-alone path (cell list, built on the device)
  * no reference counterpart: HOOMD's md::NeighborList is HOOMD core.  Produces the three arrays SteinhardtQl.cc:80-85 reads, in

@@ -63,6 +63,11 @@
 //                    k_qll_average (gathers q(j): qbar, c_i, v_i, the rows B(i)), k_qll_backprop (gathers B(j) and q(j): the table row
 //                    C(k) / n_k with a_k folded in, and one double E_kj per list entry), then the force pass, which streams E beside
 //                    the list and adds it to the (0, 0) weight of the pair.  See the block above k_qll_average.
+//   bonds            (mtd_ql_local_bonds) the solid-bond count: d_ij = the normalised scalar product of q(i) and q(j), b_i = sum_j f_ij sigma(d_ij),
+//                    v_i = g(n_i) h(b_i).  Four launches in the frame of the average: k_qll_accumulate<QLL_BONDS> (n_i, c_i, the rows
+//                    q(i) / sqrt(c_i)), k_qll_bonds (gathers u(j): d per list entry, b_i, v_i, beta_i), k_qll_bonds_backprop (gathers u(j)
+//                    and beta_j: the table row and E_kj = (beta_k + beta_j) sigma(d_kj) per list entry), then the AVG force pass as it is.
+//                    See the block above k_qll_bonds.
 #include "mtd_device.hpp"
 #include "steinhardt_device.hpp"
 #include "dispatch.hpp"
@@ -214,7 +219,19 @@ struct QllOpt
     double inv_c0, n_lo, inv_dn;                           // 1 / c0, n_lo, 1 / (n_hi - n_lo)
     };
 
-enum { QLL_PLAIN = 0, QLL_TRANSFORM = 1, QLL_AVERAGE = 2 };
+enum { QLL_PLAIN = 0, QLL_TRANSFORM = 1, QLL_AVERAGE = 2, QLL_BONDS = 3 };
+
+// the ramp of the solid-bond count: sigma = 3 t^2 - 2 t^3, t = clip((d - d_lo) / (d_hi - d_lo), 0, 1), and d sigma / dd
+struct QllRamp
+    {
+    double d_lo, inv_dd;                                   // d_lo, 1 / (d_hi - d_lo)
+    __device__ __forceinline__ void operator()(const double d, double &sg, double &dsg) const
+        {
+        const double t = fmin(fmax((d - d_lo) * inv_dd, 0.0), 1.0);
+        sg = t * t * (3.0 - 2.0 * t);
+        dsg = 6.0 * t * (1.0 - t) * inv_dd;
+        }
+    };
 
 // h = x^p / (1 + x^p), x = max(c, 0) / c0 (h = c without a switch); g = 3 t^2 - 2 t^3, t = clip((n - n_lo) / (n_hi - n_lo), 0, 1)
 // (g = 1 without a gate); and their derivatives.  x^(p - 1) by squaring: p is uniform, the loop is a scalar one.
@@ -256,6 +273,8 @@ __device__ __forceinline__ void qll_transform(const QllOpt &o, const double c, c
 //                      with g'(n_i) h(c_i) added to its (0, 0) slot, v_i = g h is written and block-summed in place of c_i
 //       QLL_AVERAGE    writes n_i and the monic row S_lm(i) / n_i (q_lm = nrm(l, m) times it) for the two gather passes below, and
 //                      (block 0) the weight of every slot, wtab[off[l] + m] = Ql_ref[l] 4 pi / (2l + 1) (m > 0 ? 2 : 1) nrm(l, m)^2
+//       QLL_BONDS      the sums of QLL_AVERAGE and the slot weights; writes n_i, the plain c_i = sum_c w_c |qm_c(i)|^2 and the monic row
+//                      NORMALISED, u_c(i) = qm_c(i) / sqrt(c_i) (0 when c_i == 0), for the two gather passes of the bond count
 template<typename S4, int LMAX, int MODE>
 __global__ __launch_bounds__(QLL_THREADS) void k_qll_accumulate(const QlArgs<LMAX> a, const QllLayout lay, const QllOpt o, const S4 *__restrict__ postype,
                                                                 const unsigned int *__restrict__ head_list,
@@ -440,6 +459,76 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_accumulate(const QlArgs<LMA
                 }
             c = g * h;                                                              // what the blocks sum
             }
+        else if constexpr (MODE == QLL_BONDS)
+            {
+            // c_i first: the row is scaled with 1 / sqrt(c_i).  Up to LMAX = 6 the sums wait in registers for it.  Above, that costs a wave
+            // per SIMD (LMAX = 8: 256 + 9 registers against 243) or does not fit at all (LMAX = 12: spills), so there the row is written
+            // monic as QLL_AVERAGE writes it and the lane scales what it wrote itself
+            constexpr bool KEEP = LMAX <= 6;
+            if (write)
+                {
+                row[0] = 0.0;
+                row[1] = 0.0;
+                n_out[i] = nsum;
+                }
+#pragma unroll
+            for (int l = 0; l <= LMAX; ++l)
+                if (lay.act & (1u << l))
+                    {
+                    const double gl = a.ql_ref[l] * (4.0 * M_PI / (2 * l + 1));
+                    double sq = 0.0;
+#pragma unroll
+                    for (int m = 0; m <= l; ++m)
+                        {
+                        S[m][l].re = quad_sum(S[m][l].re);
+                        if (m > 0) S[m][l].im = quad_sum(S[m][l].im);
+                        const double nr = tab[T::nrm(l, m)];
+                        const double w = (m > 0 ? 2.0 : 1.0) * (nr * nr);
+                        sq += w * (S[m][l].re * S[m][l].re + S[m][l].im * S[m][l].im);
+                        if (!KEEP && write)
+                            {
+                            row[2 * (lay.off[l] + m)] = S[m][l].re * inv_n;
+                            row[2 * (lay.off[l] + m) + 1] = m > 0 ? S[m][l].im * inv_n : 0.0;
+                            }
+                        if (chunk == 0 && tid == 0) wtab[lay.off[l] + m] = gl * w;
+                        }
+                    c += (gl * inv_n2) * sq;
+                    }
+            if (chunk == 0 && tid == 0 && !(lay.act & 1u)) wtab[0] = 0.0;
+            const double inv_rc = c > 0.0 ? 1.0 / sqrt(c) : 0.0;
+            if (write) c_out[i] = c;
+            if constexpr (KEEP)
+                {
+                const double un = inv_n * inv_rc;
+#pragma unroll
+                for (int l = 0; l <= LMAX; ++l)
+                    if (lay.act & (1u << l))
+                        {
+#pragma unroll
+                        for (int m = 0; m <= l; ++m)
+                            if (write)
+                                {
+                                row[2 * (lay.off[l] + m)] = S[m][l].re * un;
+                                row[2 * (lay.off[l] + m) + 1] = m > 0 ? S[m][l].im * un : 0.0;
+                                }
+                        }
+                }
+            else if (write)
+                {
+                double2 *row2 = reinterpret_cast<double2 *>(row);
+                const unsigned int rs16 = lay.row_doubles / 2;
+#pragma unroll 1
+                for (unsigned int cc = 0; cc < rs16; cc += 4)                        // four loads in flight, then their stores
+                    {
+                    double2 r[4];
+#pragma unroll
+                    for (unsigned int v = 0; v < 4; ++v) r[v] = row2[cc + v < rs16 ? cc + v : rs16 - 1];
+#pragma unroll
+                    for (unsigned int v = 0; v < 4; ++v)
+                        if (cc + v < rs16) row2[cc + v] = make_double2(r[v].x * inv_rc, r[v].y * inv_rc);
+                    }
+                }
+            }
         else
             {
             if (write)
@@ -471,7 +560,7 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_accumulate(const QlArgs<LMA
                     }
             if (chunk == 0 && tid == 0 && !(lay.act & 1u)) wtab[0] = 0.0;
             }
-        if constexpr (MODE != QLL_AVERAGE)
+        if constexpr (MODE == QLL_PLAIN || MODE == QLL_TRANSFORM)
             {
             // the chunk's sum of c_i (v_i with a switch or a gate): wave 0, fixed order
             __syncthreads();
@@ -480,7 +569,7 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_accumulate(const QlArgs<LMA
             if (tid < MTD_WAVE) block_c += wave_sum(s_c[tid]);
             }
         }
-    if constexpr (MODE == QLL_AVERAGE) return;                                      // k_qll_average sums the v_i
+    if constexpr (MODE == QLL_AVERAGE || MODE == QLL_BONDS) return;                 // k_qll_average / k_qll_bonds sum the v_i
     if (tid == 0) partials[blockIdx.x] = block_c;
     }
 
@@ -942,6 +1031,208 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_backprop(const QlArgs<12> a
         }
     }
 
+// ---- the solid-bond count: two gather passes between pass 1 and the force pass ---------------------------------------------------
+// Rows here are the NORMALISED monic ones of pass 1 <QLL_BONDS>, u_c(i) = qm_c(i) / sqrt(c_i), so that with the slot weights w_c
+//   d_kj = sum_c w_c Re(u_c(k) conj(u_c(j)))    in [-1, 1]: the normalised scalar product of the q vectors of the two ends of a bond.
+//   k_qll_bonds           d_kj per list entry (parked in the per-entry scratch),  b_k = sum_j f_kj sigma(d_kj),  v_k = g(n_k) h(b_k),
+//                         beta_k = g h'(b_k),  a0_k = g'(n_k) h(b_k),  block sums of v_k
+//   k_qll_bonds_backprop  t_kj = (beta_k + beta_j) f_kj sigma'(d_kj),  Pm_c(k) = [sum_j t_kj u_c(j) - (sum_j t_kj d_kj) u_c(k)] / sqrt(c_k),
+//                         Bm_c(k) = w_c conj(Pm_c(k));  the table row of the force pass R_c(k) = Bm_c(k) / n_k with
+//                         a_k = a0_k - sum_c Re Bm_c(k) qm_c(k) / n_k added to slot 0 (the sum vanishes analytically: <P(k), u(k)> = 0);
+//                         per list entry E_kj = (beta_k + beta_j) sigma(d_kj) in place of d_kj
+// The force pass is the one of the averaged variable (AVG = true), unchanged.  Gather pattern: that of k_qll_average.  beta of EVERY
+// particle is complete before the second pass reads it: a launch of its own.  With more than one window the list is walked once per
+// window: d_kj is the sum over the windows (the lane adds to what it wrote in the last window, as k_qll_backprop does for E) and is
+// read in every window of the second pass, so E replaces it in the LAST window only.  An entry that does not count gets E = 0.
+template<typename S4>
+__global__ __launch_bounds__(QLL_THREADS) void k_qll_bonds(const QlArgs<12> a, const QllOpt o, const QllRamp ramp, const unsigned int rs16,
+                                                           const S4 *__restrict__ postype, const unsigned int *__restrict__ head_list,
+                                                           const unsigned int *__restrict__ n_neigh, const unsigned int *__restrict__ nlist,
+                                                           const double *__restrict__ n_in, const double2 *__restrict__ urows,
+                                                           const double *__restrict__ wtab, double *epair, double *__restrict__ b_out,
+                                                           double *__restrict__ v_out, double *__restrict__ beta_out, double *__restrict__ a0_out,
+                                                           double *__restrict__ partials, const double *__restrict__ tab)
+    {
+    __shared__ double s_c[QLL_PPB];
+    const unsigned int tid = threadIdx.x, p = tid / QLL_G, q = tid % QLL_G;
+    const unsigned int n_chunks = (a.N + QLL_PPB - 1) / QLL_PPB;
+    double block_v = 0.0;
+    for (unsigned int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
+        {
+        const QllCentre ci = qll_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
+        const unsigned int i = ci.i, ii = ci.row(a.N);
+        const double ni = i < a.N ? n_in[i] : 0.0;
+        double bsum = 0.0;
+        for (unsigned int w0 = 0; w0 < rs16; w0 += QLL_G * QLL_GV)
+            {
+            const bool last = w0 + QLL_G * QLL_GV >= rs16;
+            unsigned int cs[QLL_GV];                                                 // this lane's slots, clamped into the row
+            double2 uk[QLL_GV];                                                      // w_c u_c(i); 0 for a slot past the row
+#pragma unroll
+            for (unsigned int v = 0; v < QLL_GV; ++v)
+                {
+                const unsigned int c = w0 + QLL_G * v + q;
+                cs[v] = c < rs16 ? c : rs16 - 1;
+                const double2 r = urows[(size_t)ii * rs16 + cs[v]];
+                const double w = c < rs16 ? wtab[cs[v]] : 0.0;
+                uk[v] = make_double2(w * r.x, w * r.y);
+                }
+            QllWalker<S4> w;
+            w.begin(a.N, postype, nlist, ci, q);
+#pragma unroll 1
+            for (unsigned int eb = 0; eb < ci.cnt; eb += QLL_G, w.step())           // cnt is the quad's: its four lanes stay together
+                {
+                const double *__restrict__ tab_k = qll_loop_table(tab);
+                w.ahead(a.N, postype, nlist, ci);
+                double f = 0.0;
+                unsigned int jv = ii;
+                w.pair(a, ci, [&](double, double, double, const double rsq)
+                    {
+                    double fprime_divr;
+                    smoothing_tab<12>(a, tab_k, rsq, rsqrt(rsq), f, fprime_divr);
+                    jv = w.j0;
+                    });
+                const unsigned int ju[QLL_G] = {quad_bcast<0>(jv), quad_bcast<1>(jv), quad_bcast<2>(jv), quad_bcast<3>(jv)};
+                double mine = 0.0;
+#pragma unroll
+                for (unsigned int u = 0; u < QLL_G; ++u)
+                    {
+                    double dd = 0.0;
+#pragma unroll
+                    for (unsigned int v = 0; v < QLL_GV; ++v)
+                        {
+                        const double2 r = urows[(size_t)ju[u] * rs16 + cs[v]];
+                        dd += uk[v].x * r.x + uk[v].y * r.y;
+                        }
+                    dd = quad_sum(dd);
+                    if (q == u) mine = dd;
+                    }
+                if (w.e < ci.cnt)
+                    {
+                    if (w0 > 0) mine += epair[ci.start + w.e];                       // the lane adds to what it wrote in the last window
+                    epair[ci.start + w.e] = mine;
+                    if (last)
+                        {
+                        double sg, dsg;
+                        ramp(mine, sg, dsg);
+                        bsum += f * sg;                                              // f = 0 for an entry that does not count
+                        }
+                    }
+                }
+            }
+        const double b = quad_sum(bsum);
+        double h, dh, g, dg;
+        qll_transform(o, b, ni, h, dh, g, dg);
+        if (q == 0 && i < a.N)
+            {
+            b_out[i] = b;
+            v_out[i] = g * h;
+            beta_out[i] = g * dh;
+            a0_out[i] = dg * h;
+            }
+        // the chunk's sum of v_i: wave 0, fixed order
+        __syncthreads();
+        if (q == 0) s_c[p] = i < a.N ? g * h : 0.0;
+        __syncthreads();
+        if (tid < MTD_WAVE) block_v += wave_sum(s_c[tid]);
+        }
+    if (tid == 0) partials[blockIdx.x] = block_v;
+    }
+
+template<typename S4>
+__global__ __launch_bounds__(QLL_THREADS) void k_qll_bonds_backprop(const QlArgs<12> a, const QllRamp ramp, const unsigned int rs16,
+                                                                    const S4 *__restrict__ postype, const unsigned int *__restrict__ head_list,
+                                                                    const unsigned int *__restrict__ n_neigh, const unsigned int *__restrict__ nlist,
+                                                                    const double *__restrict__ n_in, const double *__restrict__ c_in,
+                                                                    const double *__restrict__ beta_in, const double *__restrict__ a0_in,
+                                                                    const double2 *__restrict__ urows, const double *__restrict__ wtab,
+                                                                    double2 *__restrict__ rows, double *epair, const double *__restrict__ tab)
+    {
+    const unsigned int tid = threadIdx.x, p = tid / QLL_G, q = tid % QLL_G;
+    const unsigned int n_chunks = (a.N + QLL_PPB - 1) / QLL_PPB;
+    for (unsigned int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
+        {
+        const QllCentre ck = qll_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
+        const unsigned int k = ck.i, kk = ck.row(a.N);
+        const bool there = k < a.N;
+        const double nk = there ? n_in[k] : 0.0, a0 = there ? a0_in[k] : 0.0, c_k = there ? c_in[k] : 0.0, beta_k = there ? beta_in[k] : 0.0;
+        const double inv_n = nk > 0.0 ? 1.0 / nk : 0.0;
+        const double root_c = sqrt(c_k), inv_rc = c_k > 0.0 ? 1.0 / root_c : 0.0;
+        double cq = 0.0, r00 = 0.0;
+        for (unsigned int w0 = 0; w0 < rs16; w0 += QLL_G * QLL_GV)
+            {
+            const bool last = w0 + QLL_G * QLL_GV >= rs16;
+            unsigned int cs[QLL_GV];
+            double2 acc[QLL_GV], uk[QLL_GV];
+#pragma unroll
+            for (unsigned int v = 0; v < QLL_GV; ++v)
+                {
+                const unsigned int c = w0 + QLL_G * v + q;
+                cs[v] = c < rs16 ? c : rs16 - 1;
+                uk[v] = urows[(size_t)kk * rs16 + cs[v]];
+                acc[v] = make_double2(0.0, 0.0);
+                }
+            double td = 0.0;                                                         // this lane's share of sum_j t_kj d_kj: whole in every window
+            QllWalker<S4> w;
+            w.begin(a.N, postype, nlist, ck, q);
+#pragma unroll 1
+            for (unsigned int eb = 0; eb < ck.cnt; eb += QLL_G, w.step())
+                {
+                const double *__restrict__ tab_k = qll_loop_table(tab);
+                w.ahead(a.N, postype, nlist, ck);
+                double f = 0.0;
+                unsigned int jv = kk;
+                bool visit = false;
+                w.pair(a, ck, [&](double, double, double, const double rsq)
+                    {
+                    double fprime_divr;
+                    smoothing_tab<12>(a, tab_k, rsq, rsqrt(rsq), f, fprime_divr);
+                    jv = w.j0;
+                    visit = true;
+                    });
+                const bool mine = w.e < ck.cnt;
+                const double d = mine ? epair[ck.start + w.e] : 0.0;
+                const double bsum = beta_k + beta_in[jv];
+                double sg, dsg;
+                ramp(d, sg, dsg);
+                const double t = visit ? bsum * f * dsg : 0.0;
+                td += t * d;
+                if (mine && last) epair[ck.start + w.e] = visit ? bsum * sg : 0.0;   // E replaces d once no window needs d again
+                const unsigned int ju[QLL_G] = {quad_bcast<0>(jv), quad_bcast<1>(jv), quad_bcast<2>(jv), quad_bcast<3>(jv)};
+                const double tu[QLL_G] = {quad_bcast<0>(t), quad_bcast<1>(t), quad_bcast<2>(t), quad_bcast<3>(t)};
+#pragma unroll
+                for (unsigned int u = 0; u < QLL_G; ++u)
+#pragma unroll
+                    for (unsigned int v = 0; v < QLL_GV; ++v)
+                        {
+                        const double2 r = urows[(size_t)ju[u] * rs16 + cs[v]];
+                        acc[v].x += tu[u] * r.x;
+                        acc[v].y += tu[u] * r.y;
+                        }
+                }
+            td = quad_sum(td);
+            // Bm of this window: its share of sum Re Bm qm, and the row of the force pass
+#pragma unroll
+            for (unsigned int v = 0; v < QLL_GV; ++v)
+                {
+                const unsigned int c = w0 + QLL_G * v + q;
+                if (c < rs16)
+                    {
+                    const double wc = wtab[c] * inv_rc;
+                    const double bx = wc * (acc[v].x - td * uk[v].x), by = -(wc * (acc[v].y - td * uk[v].y));
+                    cq += root_c * (bx * uk[v].x - by * uk[v].y);
+                    if (c == 0)
+                        r00 = bx * inv_n;
+                    else if (there)
+                        rows[(size_t)k * rs16 + c] = make_double2(bx * inv_n, by * inv_n);
+                    }
+                }
+            }
+        cq = quad_sum(cq);
+        if (q == 0 && there) rows[(size_t)k * rs16] = make_double2(r00 + (a0 - cq * inv_n), 0.0);
+        }
+    }
+
 // ---- host side ------------------------------------------------------------------------------------------------------------
 QllLayout qll_layout(const unsigned int lmax, const double *ql_ref)
     {
@@ -964,18 +1255,23 @@ QllLayout qll_layout(const unsigned int lmax, const double *ql_ref)
 // with a switch or a gate, behind these:  (one double when the above is an odd number) v_i [N] (+ one when N is odd)
 // with the average, behind those:         a0_i [N] (+ one) | slot weights [(lmax + 1)(lmax + 2) / 2] (+ one when odd)
 //                                         | monic rows [N][..] | B rows [N][..] | E [list entries]
+// with bonds, behind v_i:                 a0_i [N] (+ one) | b_i [N] (+ one) | beta_i [N] (+ one) | slot weights (+ one when odd)
+//                                         | normalised monic rows [N][..] | d, then E [list entries]
 struct QllScratch
     {
-    double *partials, *n, *c, *rows, *v, *a0, *wtab, *qrows, *brows, *epair;
+    double *partials, *n, *c, *rows, *v, *a0, *b, *beta, *wtab, *qrows, *brows, *epair;
     };
 
 struct QllSizes
     {
-    size_t base, pad, v, a0, wtab, rows, total;
+    size_t base, pad, v, a0, bb, wtab, rows, total;
     };
 
-int qll_mode(const mtd_ql_local_options *opt)
+bool qll_bonds_on(const mtd_ql_local_bonds *bonds) { return bonds && bonds->on; }
+
+int qll_mode(const mtd_ql_local_options *opt, const mtd_ql_local_bonds *bonds = nullptr)
     {
+    if (qll_bonds_on(bonds)) return QLL_BONDS;
     if (!opt) return QLL_PLAIN;
     if (opt->average) return QLL_AVERAGE;
     return opt->switch_on || opt->gate_on ? QLL_TRANSFORM : QLL_PLAIN;
@@ -988,10 +1284,12 @@ QllSizes qll_sizes(const size_t n, const unsigned int lmax, const size_t n_list_
     z.base = (size_t)QLL_MAX_BLOCKS + 2 * n + (n & 1u) + z.rows;
     z.pad = mode == QLL_PLAIN ? 0 : z.base & 1u;                // what the options add starts on a 16-byte boundary
     z.v = mode == QLL_PLAIN ? 0 : n + (n & 1u);
-    z.a0 = mode == QLL_AVERAGE ? n + (n & 1u) : 0;
+    const bool gathers = mode == QLL_AVERAGE || mode == QLL_BONDS;
+    z.a0 = gathers ? n + (n & 1u) : 0;
+    z.bb = mode == QLL_BONDS ? 2 * (n + (n & 1u)) : 0;
     const size_t slots = (size_t)(lmax + 1) * (lmax + 2) / 2;
-    z.wtab = mode == QLL_AVERAGE ? slots + (slots & 1u) : 0;
-    z.total = z.base + z.pad + z.v + z.a0 + z.wtab + (mode == QLL_AVERAGE ? 2 * z.rows + n_list_entries : 0);
+    z.wtab = gathers ? slots + (slots & 1u) : 0;
+    z.total = z.base + z.pad + z.v + z.a0 + z.bb + z.wtab + (gathers ? (mode == QLL_AVERAGE ? 2 : 1) * z.rows + n_list_entries : 0);
     return z;
     }
 
@@ -1005,10 +1303,12 @@ QllScratch qll_scratch(double *scratch, const unsigned int N, const unsigned int
     s.rows = s.c + N + (N & 1u);
     s.v = mode == QLL_PLAIN ? s.c : scratch + z.base + z.pad;
     s.a0 = scratch + z.base + z.pad + z.v;
-    s.wtab = s.a0 + z.a0;
+    s.b = s.a0 + z.a0;
+    s.beta = s.b + z.bb / 2;
+    s.wtab = s.a0 + z.a0 + z.bb;
     s.qrows = s.wtab + z.wtab;
     s.brows = s.qrows + z.rows;
-    s.epair = s.brows + z.rows;
+    s.epair = mode == QLL_BONDS ? s.brows : s.brows + z.rows;
     return s;
     }
 
@@ -1036,7 +1336,8 @@ QllOpt qll_opt(const mtd_ql_local_options *opt)
 template<typename S4, int LMAX>
 int qll_accumulate_impl(unsigned int N, const void *d_postype, const mtd_box *box, const unsigned int *d_head, const unsigned int *d_nneigh,
                         const unsigned int *d_nlist, double rcut, double ron, unsigned int lmax, unsigned int type, const double *ql_ref,
-                        unsigned int n_global, const QllScratch &sc, const mtd_ql_local_options *opt, unsigned int *n_partials, hipStream_t s)
+                        unsigned int n_global, const QllScratch &sc, const mtd_ql_local_options *opt, const mtd_ql_local_bonds *bonds,
+                        unsigned int *n_partials, hipStream_t s)
     {
     QlArgs<LMAX> a;
     int rc = fill_args<LMAX>(a, N, box, rcut, ron, lmax, type, ql_ref, n_global, 0);
@@ -1049,16 +1350,28 @@ int qll_accumulate_impl(unsigned int N, const void *d_postype, const mtd_box *bo
     const QllLayout lay = qll_layout(lmax, ql_ref);
     const unsigned int blocks = qll_blocks(N);
     const QllOpt o = qll_opt(opt);
-    const int mode = qll_mode(opt);
+    const int mode = qll_mode(opt, bonds);
     const S4 *postype = (const S4 *)d_postype;
-    static_assert(QLL_PLAIN == 0 && QLL_TRANSFORM == 1 && QLL_AVERAGE == 2, "the mode is dispatched as the count mode + 1 of 3");
-    dispatch_count<3>(mode + 1, [&](auto m1)
+    static_assert(QLL_PLAIN == 0 && QLL_TRANSFORM == 1 && QLL_AVERAGE == 2 && QLL_BONDS == 3, "the mode is dispatched as the count mode + 1 of 4");
+    dispatch_count<4>(mode + 1, [&](auto m1)
         {
         constexpr int MODE = decltype(m1)::value - 1;
         k_qll_accumulate<S4, LMAX, MODE><<<blocks, QLL_THREADS, 0, s>>>(a, lay, o, postype, d_head, d_nneigh, d_nlist, sc.n, sc.c, sc.v,
-                                                                         MODE == QLL_AVERAGE ? sc.qrows : sc.rows, sc.wtab, sc.partials, tab);
+                                                                         MODE == QLL_AVERAGE || MODE == QLL_BONDS ? sc.qrows : sc.rows, sc.wtab,
+                                                                         sc.partials, tab);
         });
     MTD_LAUNCH_CHECK();
+    if (mode == QLL_BONDS)
+        {
+        const unsigned int rs16 = lay.row_doubles / 2;
+        const QllRamp ramp = {bonds->d_lo, 1.0 / (bonds->d_hi - bonds->d_lo)};
+        k_qll_bonds<S4><<<blocks, QLL_THREADS, 0, s>>>(a12, o, ramp, rs16, postype, d_head, d_nneigh, d_nlist, sc.n, (const double2 *)sc.qrows, sc.wtab,
+                                                        sc.epair, sc.b, sc.v, sc.beta, sc.a0, sc.partials, tab);
+        MTD_LAUNCH_CHECK();
+        k_qll_bonds_backprop<S4><<<blocks, QLL_THREADS, 0, s>>>(a12, ramp, rs16, postype, d_head, d_nneigh, d_nlist, sc.n, sc.c, sc.beta, sc.a0,
+                                                                 (const double2 *)sc.qrows, sc.wtab, (double2 *)sc.rows, sc.epair, tab);
+        MTD_LAUNCH_CHECK();
+        }
     if (mode == QLL_AVERAGE)
         {
         const unsigned int rs16 = lay.row_doubles / 2;
@@ -1134,6 +1447,18 @@ int qll_validate_options(const mtd_ql_local_options *opt)
     return MTD_SUCCESS;
     }
 
+// the bond count: a ramp with -1 <= d_lo < d_hi <= 1 (NaN fails every comparison), a scalar product that is a norm (no negative
+// Ql_ref[l]), and not on the averaged vectors
+int qll_validate_bonds(const mtd_ql_local_options *opt, const mtd_ql_local_bonds *bonds, unsigned int lmax, const double *ql_ref)
+    {
+    if (!qll_bonds_on(bonds)) return MTD_SUCCESS;
+    if (!(bonds->d_lo >= -1.0) || !(bonds->d_lo < bonds->d_hi) || !(bonds->d_hi <= 1.0)) return MTD_ERR_INVALID_ARGUMENT;
+    for (unsigned int l = 0; l <= lmax; ++l)
+        if (!(ql_ref[l] >= 0.0)) return MTD_ERR_INVALID_ARGUMENT;
+    if (opt && opt->average) return MTD_ERR_UNSUPPORTED;
+    return MTD_SUCCESS;
+    }
+
 } // namespace
 
 extern "C" {
@@ -1145,7 +1470,13 @@ size_t mtd_ql_local_scratch_doubles(unsigned int n_particles, unsigned int lmax)
 
 size_t mtd_ql_local_scratch_doubles_opt(unsigned int n_particles, unsigned int lmax, size_t n_list_entries, const mtd_ql_local_options *opt)
     {
-    return qll_sizes(n_particles, lmax, n_list_entries, qll_mode(opt)).total;
+    return mtd_ql_local_scratch_doubles_bonds(n_particles, lmax, n_list_entries, opt, nullptr);
+    }
+
+size_t mtd_ql_local_scratch_doubles_bonds(unsigned int n_particles, unsigned int lmax, size_t n_list_entries, const mtd_ql_local_options *opt,
+                                          const mtd_ql_local_bonds *bonds)
+    {
+    return qll_sizes(n_particles, lmax, n_list_entries, qll_mode(opt, bonds)).total;
     }
 
 int mtd_ql_local_accumulate(unsigned int n_particles, const void *d_postype, int dtype, const mtd_box *box, const unsigned int *d_head_list,
@@ -1163,12 +1494,25 @@ int mtd_ql_local_accumulate_opt(unsigned int n_particles, const void *d_postype,
                                 unsigned int *n_partials, const double **d_c, const double **d_n, mtd_stream_t stream,
                                 const mtd_ql_local_options *opt, const double **d_v)
     {
+    return mtd_ql_local_accumulate_bonds(n_particles, d_postype, dtype, box, d_head_list, d_n_neigh, d_nlist, rcut, ron, lmax, type, Ql_ref, n_global,
+                                         d_scratch, d_partials, n_partials, d_c, d_n, stream, opt, d_v, nullptr, nullptr);
+    }
+
+int mtd_ql_local_accumulate_bonds(unsigned int n_particles, const void *d_postype, int dtype, const mtd_box *box, const unsigned int *d_head_list,
+                                  const unsigned int *d_n_neigh, const unsigned int *d_nlist, double rcut, double ron, unsigned int lmax,
+                                  unsigned int type, const double *Ql_ref, unsigned int n_global, double *d_scratch, const double **d_partials,
+                                  unsigned int *n_partials, const double **d_c, const double **d_n, mtd_stream_t stream,
+                                  const mtd_ql_local_options *opt, const double **d_v, const mtd_ql_local_bonds *bonds, const double **d_b)
+    {
     if (!d_partials || !n_partials) return MTD_ERR_INVALID_ARGUMENT;
     int rc = qll_validate(n_particles, d_postype, dtype, box, d_head_list, d_n_neigh, rcut, ron, lmax, Ql_ref, n_global, d_scratch);
     if (rc) return rc;
     rc = qll_validate_options(opt);
     if (rc) return rc;
-    const QllScratch sc = qll_scratch(d_scratch, n_particles, lmax, qll_mode(opt));
+    rc = qll_validate_bonds(opt, bonds, lmax, Ql_ref);
+    if (rc) return rc;
+    const int mode = qll_mode(opt, bonds);
+    const QllScratch sc = qll_scratch(d_scratch, n_particles, lmax, mode);
     hipStream_t s = (hipStream_t)stream;
     unsigned int n = 0;
     rc = dispatch_lmax(lmax, [&](auto lm)
@@ -1176,7 +1520,7 @@ int mtd_ql_local_accumulate_opt(unsigned int n_particles, const void *d_postype,
         return dispatch_s4(dtype, [&](auto t)
             {
             return qll_accumulate_impl<typename decltype(t)::type, decltype(lm)::value>(n_particles, d_postype, box, d_head_list, d_n_neigh, d_nlist, rcut,
-                                                                                        ron, lmax, type, Ql_ref, n_global, sc, opt, &n, s);
+                                                                                        ron, lmax, type, Ql_ref, n_global, sc, opt, bonds, &n, s);
             });
         });
     if (rc) return rc;
@@ -1185,6 +1529,7 @@ int mtd_ql_local_accumulate_opt(unsigned int n_particles, const void *d_postype,
     if (d_c) *d_c = sc.c;
     if (d_n) *d_n = sc.n;
     if (d_v) *d_v = sc.v;
+    if (d_b) *d_b = mode == QLL_BONDS ? sc.b : nullptr;
     return MTD_SUCCESS;
     }
 
@@ -1212,21 +1557,33 @@ int mtd_ql_local_forces_virial(unsigned int n_particles, const void *d_postype, 
                                const double *d_bias, double bias_host, mtd_stream_t stream, const mtd_ql_local_options *opt, void *d_virial,
                                unsigned int virial_pitch)
     {
+    return mtd_ql_local_forces_bonds(n_particles, d_postype, d_force, dtype, box, d_head_list, d_n_neigh, d_nlist, rcut, ron, lmax, type, Ql_ref,
+                                     n_global, d_scratch, d_bias, bias_host, stream, opt, d_virial, virial_pitch, nullptr);
+    }
+
+int mtd_ql_local_forces_bonds(unsigned int n_particles, const void *d_postype, void *d_force, int dtype, const mtd_box *box,
+                              const unsigned int *d_head_list, const unsigned int *d_n_neigh, const unsigned int *d_nlist, double rcut, double ron,
+                              unsigned int lmax, unsigned int type, const double *Ql_ref, unsigned int n_global, const double *d_scratch,
+                              const double *d_bias, double bias_host, mtd_stream_t stream, const mtd_ql_local_options *opt, void *d_virial,
+                              unsigned int virial_pitch, const mtd_ql_local_bonds *bonds)
+    {
     int rc = qll_validate(n_particles, d_postype, dtype, box, d_head_list, d_n_neigh, rcut, ron, lmax, Ql_ref, n_global, d_scratch);
     if (rc) return rc;
     rc = qll_validate_options(opt);
     if (rc) return rc;
+    rc = qll_validate_bonds(opt, bonds, lmax, Ql_ref);
+    if (rc) return rc;
     if (n_particles && !d_force) return MTD_ERR_INVALID_ARGUMENT;
     if (d_virial && virial_pitch < n_particles) return MTD_ERR_INVALID_ARGUMENT;
     if (n_particles == 0) return MTD_SUCCESS;
-    const int mode = qll_mode(opt);
+    const int mode = qll_mode(opt, bonds);
     const QllScratch sc = qll_scratch(const_cast<double *>(d_scratch), n_particles, lmax, mode);
     hipStream_t s = (hipStream_t)stream;
     return dispatch_lmax(lmax, [&](auto lm)
         {
         return dispatch_s4(dtype, [&](auto t)
             {
-            return dispatch_bool(mode == QLL_AVERAGE, [&](auto avg)
+            return dispatch_bool(mode == QLL_AVERAGE || mode == QLL_BONDS, [&](auto avg)
                 {
                 return dispatch_bool(d_virial != nullptr, [&](auto vir)
                     {

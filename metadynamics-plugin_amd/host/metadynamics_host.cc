@@ -761,7 +761,7 @@ SteinhardtLocal::SteinhardtLocal(std::shared_ptr<SystemDefinition> sysdef, doubl
                                  const std::string &log_suffix)
     : CollectiveVariable(sysdef, "steinhardt_local" + log_suffix), m_rcut(rcut), m_ron(ron), m_lmax(lmax), m_nlist(nlist), m_type(type),
       m_Ql_ref(Ql_ref), m_cv_last_updated(0), m_have_computed(false), m_d_partials(nullptr), m_d_c(nullptr), m_d_n(nullptr), m_d_v(nullptr),
-      m_n_partials(0), m_opt()
+      m_d_b(nullptr), m_n_partials(0), m_opt(), m_bonds()
     {
     if (Ql_ref.size() != lmax + 1) throw std::runtime_error("Error setting up local Steinhardt CV");
     if (lmax > 12) throw std::runtime_error("cv.steinhardt_local: lmax <= 12 in this build");
@@ -785,16 +785,17 @@ void SteinhardtLocal::computeCV(unsigned int timestep)
                                  "neighbour would have to be exchanged)");
     m_nlist->compute(timestep);                                      // a device-built list rebuilds here when particles have moved
     const mtd_box box = m_pdata->getBox().toMtd();
-    // the averaged variable keeps one double per list entry: the scratch grows with the list and with the options (never shrinks)
-    const size_t need = sizeof(double) * mtd_ql_local_scratch_doubles_opt(m_pdata->getN(), m_lmax,
-                                                                          m_nlist->getNListArray().bytes() / sizeof(unsigned int), &m_opt);
+    // the averaged variable and the bond count keep one double per list entry: the scratch grows with the list and with the options
+    // (never shrinks)
+    const size_t need = sizeof(double) * mtd_ql_local_scratch_doubles_bonds(m_pdata->getN(), m_lmax,
+                                                                            m_nlist->getNListArray().bytes() / sizeof(unsigned int), &m_opt, &m_bonds);
     if (need > m_scratch.bytes()) m_scratch.resize(need);
-    mtd_check(mtd_ql_local_accumulate_opt(m_pdata->getN(), m_pdata->positionsPtr(), m_pdata->getDtype(), &box,
-                                          (const unsigned int *)m_nlist->getHeadList().data(), (const unsigned int *)m_nlist->getNNeighArray().data(),
-                                          (const unsigned int *)m_nlist->getNListArray().data(), m_rcut, m_ron, m_lmax, m_type, m_Ql_ref.data(),
-                                          m_pdata->getNGlobal(), (double *)m_scratch.data(), &m_d_partials, &m_n_partials, &m_d_c, &m_d_n,
-                                          m_exec_conf->getStream(), &m_opt, &m_d_v),
-              "mtd_ql_local_accumulate_opt");
+    mtd_check(mtd_ql_local_accumulate_bonds(m_pdata->getN(), m_pdata->positionsPtr(), m_pdata->getDtype(), &box,
+                                            (const unsigned int *)m_nlist->getHeadList().data(), (const unsigned int *)m_nlist->getNNeighArray().data(),
+                                            (const unsigned int *)m_nlist->getNListArray().data(), m_rcut, m_ron, m_lmax, m_type, m_Ql_ref.data(),
+                                            m_pdata->getNGlobal(), (double *)m_scratch.data(), &m_d_partials, &m_n_partials, &m_d_c, &m_d_n,
+                                            m_exec_conf->getStream(), &m_opt, &m_d_v, &m_bonds, &m_d_b),
+              "mtd_ql_local_accumulate_bonds");
     m_have_computed = true;
     m_cv_last_updated = timestep;
     }
@@ -806,6 +807,7 @@ void SteinhardtLocal::optionsChanged()
 
 void SteinhardtLocal::setAverage(bool on)
     {
+    if (on && m_bonds.on) throw std::runtime_error("cv.steinhardt_local: the bond count is not available on the averaged vectors");
     m_opt.average = on ? 1 : 0;
     optionsChanged();
     }
@@ -843,6 +845,25 @@ void SteinhardtLocal::clearGate()
     optionsChanged();
     }
 
+void SteinhardtLocal::setBonds(double d_lo, double d_hi)
+    {
+    if (!(d_lo >= -1.0) || !(d_lo < d_hi) || !(d_hi <= 1.0)) throw std::runtime_error("cv.steinhardt_local: bonds need -1 <= d_lo < d_hi <= 1");
+    for (const double ql : m_Ql_ref)
+        if (!(ql >= 0.0)) throw std::runtime_error("cv.steinhardt_local: bonds need every Ql_ref[l] >= 0 (the scalar product must be a norm)");
+    if (m_opt.average) throw std::runtime_error("cv.steinhardt_local: the bond count is not available on the averaged vectors");
+    m_bonds.on = 1;
+    m_bonds.d_lo = d_lo;
+    m_bonds.d_hi = d_hi;
+    optionsChanged();
+    }
+
+void SteinhardtLocal::clearBonds()
+    {
+    m_bonds.on = 0;
+    m_bonds.d_lo = m_bonds.d_hi = 0.0;
+    optionsChanged();
+    }
+
 void SteinhardtLocal::enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot)
     {
     computeCV(timestep);
@@ -875,12 +896,22 @@ void SteinhardtLocal::computeBiasForces(unsigned int timestep)
         virial = getVirialArray().data();
     else if (m_virial.bytes())
         hip_check(hipMemsetAsync(m_virial.data(), 0, m_virial.bytes(), m_exec_conf->getStream()), "virial reset");
-    mtd_check(mtd_ql_local_forces_virial(m_pdata->getN(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &box,
-                                         (const unsigned int *)m_nlist->getHeadList().data(), (const unsigned int *)m_nlist->getNNeighArray().data(),
-                                         (const unsigned int *)m_nlist->getNListArray().data(), m_rcut, m_ron, m_lmax, m_type, m_Ql_ref.data(),
-                                         m_pdata->getNGlobal(), (const double *)m_scratch.data(), m_bias_device, m_bias, m_exec_conf->getStream(),
-                                         &m_opt, virial, getVirialPitch()),
-              "mtd_ql_local_forces_virial");
+    mtd_check(mtd_ql_local_forces_bonds(m_pdata->getN(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &box,
+                                        (const unsigned int *)m_nlist->getHeadList().data(), (const unsigned int *)m_nlist->getNNeighArray().data(),
+                                        (const unsigned int *)m_nlist->getNListArray().data(), m_rcut, m_ron, m_lmax, m_type, m_Ql_ref.data(),
+                                        m_pdata->getNGlobal(), (const double *)m_scratch.data(), m_bias_device, m_bias, m_exec_conf->getStream(),
+                                        &m_opt, virial, getVirialPitch(), &m_bonds),
+              "mtd_ql_local_forces_bonds");
+    }
+
+std::vector<double> SteinhardtLocal::getBondCounts(unsigned int timestep)
+    {
+    if (!m_bonds.on) throw std::runtime_error("cv.steinhardt_local: no bond count without the bonds option");
+    computeCV(timestep);
+    m_exec_conf->sync();
+    std::vector<double> out(m_pdata->getN());
+    if (!out.empty()) hip_check(hipMemcpy(out.data(), m_d_b, sizeof(double) * out.size(), hipMemcpyDeviceToHost), "b_i read-back");
+    return out;
     }
 
 std::vector<double> SteinhardtLocal::getSwitchedValues(unsigned int timestep)

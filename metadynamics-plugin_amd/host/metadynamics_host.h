@@ -337,7 +337,11 @@ class SteinhardtLocal : public CollectiveVariable
         void clearSwitch();
         void setGate(double n_lo, double n_hi);                        //!< g(n) = smoothstep from n_lo to n_hi
         void clearGate();
-        std::vector<double> getSwitchedValues(unsigned int timestep);  //!< v_i = g(n_i) h(c_i) (c_i without options)
+        std::vector<double> getSwitchedValues(unsigned int timestep);  //!< v_i = g(n_i) h(c_i) (c_i without options; h(b_i) with bonds)
+        //! the solid-bond count of mtd_ql_local_bonds: switch and gate then act on b_i = sum_j f sigma(d_ij); not with the average
+        void setBonds(double d_lo, double d_hi);                       //!< sigma = smoothstep of d_ij from d_lo to d_hi, -1 <= d_lo < d_hi <= 1
+        void clearBonds();
+        std::vector<double> getBondCounts(unsigned int timestep);      //!< b_i of every local particle; throws without bonds
 
     private:
         void computeCV(unsigned int timestep);
@@ -350,9 +354,10 @@ class SteinhardtLocal : public CollectiveVariable
         unsigned int m_cv_last_updated;
         bool m_have_computed;
         DeviceBuffer m_scratch, m_sum;
-        const double *m_d_partials, *m_d_c, *m_d_n, *m_d_v;
+        const double *m_d_partials, *m_d_c, *m_d_n, *m_d_v, *m_d_b;
         unsigned int m_n_partials;
         mtd_ql_local_options m_opt;
+        mtd_ql_local_bonds m_bonds;
     };
 
 //! AspectRatio.h / AspectRatio.cc:5-130 — box-shape CV, external virial only

@@ -342,7 +342,13 @@ PYBIND11_MODULE(_metadynamics, m)
         .def("setSwitch", &SteinhardtLocal::setSwitch)
         .def("clearSwitch", &SteinhardtLocal::clearSwitch)
         .def("setGate", &SteinhardtLocal::setGate)
-        .def("clearGate", &SteinhardtLocal::clearGate);
+        .def("clearGate", &SteinhardtLocal::clearGate)
+        .def("setBonds", &SteinhardtLocal::setBonds)
+        .def("clearBonds", &SteinhardtLocal::clearBonds)
+        .def("getBondCounts", [](SteinhardtLocal &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getBondCounts(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        });
 
     py::class_<WellTemperedEnsemble, CollectiveVariable, std::shared_ptr<WellTemperedEnsemble>>(m, "WellTemperedEnsemble")
         .def(py::init<std::shared_ptr<SystemDefinition>, const std::string &>());

@@ -101,6 +101,19 @@ class QlLocalOptions(C.Structure):
         return o
 
 
+class QlLocalBonds(C.Structure):
+    """mtd_ql_local_bonds: all-zero is off; the ramp of the solid-bond count, -1 <= d_lo < d_hi <= 1"""
+    _fields_ = [("on", C.c_int), ("d_lo", C.c_double), ("d_hi", C.c_double)]
+
+    @classmethod
+    def make(cls, bonds=None):
+        """bonds: (d_lo, d_hi) or None"""
+        o = cls()
+        if bonds is not None:
+            o.on, o.d_lo, o.d_hi = 1, float(bonds[0]), float(bonds[1])
+        return o
+
+
 _vp = C.c_void_p
 _dp = C.POINTER(C.c_double)
 _up = C.POINTER(C.c_uint)
@@ -233,6 +246,13 @@ _SIGNATURES = {
                                            _dp, C.c_uint, _vp, _vp, C.c_double, _vp, C.POINTER(QlLocalOptions)]),
     "mtd_ql_local_forces_virial": (C.c_int, [C.c_uint, _vp, _vp, C.c_int, C.POINTER(Box), _vp, _vp, _vp, C.c_double, C.c_double, C.c_uint, C.c_uint,
                                               _dp, C.c_uint, _vp, _vp, C.c_double, _vp, C.POINTER(QlLocalOptions), _vp, C.c_uint]),
+    "mtd_ql_local_scratch_doubles_bonds": (C.c_size_t, [C.c_uint, C.c_uint, C.c_size_t, C.POINTER(QlLocalOptions), C.POINTER(QlLocalBonds)]),
+    "mtd_ql_local_accumulate_bonds": (C.c_int, [C.c_uint, _vp, C.c_int, C.POINTER(Box), _vp, _vp, _vp, C.c_double, C.c_double, C.c_uint, C.c_uint,
+                                                 _dp, C.c_uint, _vp, C.POINTER(_vp), _up, C.POINTER(_vp), C.POINTER(_vp), _vp,
+                                                 C.POINTER(QlLocalOptions), C.POINTER(_vp), C.POINTER(QlLocalBonds), C.POINTER(_vp)]),
+    "mtd_ql_local_forces_bonds": (C.c_int, [C.c_uint, _vp, _vp, C.c_int, C.POINTER(Box), _vp, _vp, _vp, C.c_double, C.c_double, C.c_uint, C.c_uint,
+                                             _dp, C.c_uint, _vp, _vp, C.c_double, _vp, C.POINTER(QlLocalOptions), _vp, C.c_uint,
+                                             C.POINTER(QlLocalBonds)]),
     "mtd_nlist_create": (C.c_int, [C.POINTER(_vp)]),
     "mtd_nlist_destroy": (C.c_int, [_vp]),
     "mtd_nlist_build": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp, C.c_int, C.POINTER(Box), C.c_double, C.c_int, C.c_int,

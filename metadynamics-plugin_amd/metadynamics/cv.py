@@ -230,16 +230,16 @@ class steinhardt(_collective_variable):
 
 
 class _local_options(type):
-    """``cv.steinhardt_local(..., average=False, switch=None, gate=None)``: the three options are keyword arguments of the CALL.  They
+    """``cv.steinhardt_local(..., average=False, switch=None, gate=None, bonds=None)``: the options are keyword arguments of the CALL.  They
     are taken off here and applied to the finished object, so that ``__init__`` keeps the argument list of the variable without options,
-    which tests/test_ql_local_abi.py pins.  The price: ``inspect.signature(cv.steinhardt_local)`` and ``help()`` do not show the three
-    options, and subclasses inherit this metaclass.  Once that test may change, move the three keywords into ``__init__`` (ending with a
+    which tests/test_ql_local_abi.py pins.  The price: ``inspect.signature(cv.steinhardt_local)`` and ``help()`` do not show the
+    options, and subclasses inherit this metaclass.  Once that test may change, move the keywords into ``__init__`` (ending with a
     call of ``set_options``) and delete this class."""
 
-    def __call__(cls, *args, average=False, switch=None, gate=None, **kwargs):
+    def __call__(cls, *args, average=False, switch=None, gate=None, bonds=None, **kwargs):
         obj = super().__call__(*args, **kwargs)
         try:
-            obj.set_options(average=average, switch=switch, gate=gate)
+            obj.set_options(average=average, switch=switch, gate=gate, bonds=bonds)
         except RuntimeError:
             context.current.forces.remove(obj)                       # refused: the run must not find a half-made variable
             raise
@@ -256,7 +256,12 @@ class steinhardt_local(_collective_variable, metaclass=_local_options):
     ``average=True``: the Lechner-Dellago neighbour average, qbar_lm(i) = [q_lm(i) + sum_j f_ij q_lm(j)] / (1 + n_i), before the invariant;
     ``switch=dict(c0=..., p=...)``: h(c) = x^p / (1 + x^p), x = max(c, 0) / c0 per particle — CV * N is then the smooth number of solid-like
     particles; ``gate=dict(n_lo=..., n_hi=...)``: a smoothstep in the coordination n_i that takes under-coordinated particles out.
-    CV = (1 / N) sum_i g(n_i) h(c_i)."""
+    CV = (1 / N) sum_i g(n_i) h(c_i).
+    ``bonds=dict(d_lo=..., d_hi=...)``: the solid-bond count of ten Wolde, Ruiz-Montero and Frenkel.  d_ij is the normalised scalar product
+    of the q vectors of i and j (weights Ql_ref[l] 4 pi / (2l + 1), all >= 0), a bond counts with the smoothstep sigma of d_ij from d_lo to
+    d_hi (-1 <= d_lo < d_hi <= 1), b_i = sum_j f(r_ij) sigma(d_ij), and switch and gate act on it: CV = (1 / N) sum_i g(n_i) h(b_i).
+    With ``Ql_ref = e_6``, ``bonds=dict(d_lo=0.5, d_hi=0.7)`` and ``switch=dict(c0=6.5, p=12)``, CV * N is the smooth number of solid
+    particles of the literature.  Not together with ``average``."""
 
     def __init__(self, r_cut, r_on, lmax, Ql_ref, nlist, type, name=None, sigma=1.0):
         suffix = ""
@@ -289,8 +294,13 @@ class steinhardt_local(_collective_variable, metaclass=_local_options):
         return self.cpp_force.getCoordination(context.current.system.getCurrentTimeStep())
 
     def get_switched(self):
-        """v_i = g(n_i) h(c_i) of every particle at the current time step: what the CV averages (c_i itself without options)"""
+        """v_i = g(n_i) h(c_i) of every particle at the current time step: what the CV averages (c_i itself without options, g(n_i) h(b_i)
+        with bonds)"""
         return self.cpp_force.getSwitchedValues(context.current.system.getCurrentTimeStep())
+
+    def get_bonds(self):
+        """b_i = sum_j f(r_ij) sigma(d_ij): the smooth number of solid bonds of every particle at the current time step (needs ``bonds``)"""
+        return self.cpp_force.getBondCounts(context.current.system.getCurrentTimeStep())
 
     def get_virial(self, per_particle=False):
         """the virial of the bias force the last step wrote (include/mtd_abi.h, mtd_ql_local_forces_virial): the six sums xx, xy, xz, yy,
@@ -304,8 +314,8 @@ class steinhardt_local(_collective_variable, metaclass=_local_options):
         v = np.asarray(self.cpp_force.getVirial(), dtype=np.float64)[:, :n]
         return v.copy() if per_particle else v.sum(axis=1)
 
-    def set_options(self, average=False, switch=None, gate=None):
-        """set all three options (the defaults switch them off); takes effect with the next step"""
+    def set_options(self, average=False, switch=None, gate=None, bonds=None):
+        """set all four options (the defaults switch them off); takes effect with the next step"""
         try:
             sw = None if switch is None else (float(switch["c0"]), int(switch["p"]))
             gt = None if gate is None else (float(gate["n_lo"]), float(gate["n_hi"]))
@@ -313,6 +323,10 @@ class steinhardt_local(_collective_variable, metaclass=_local_options):
                 raise ValueError
             if gt is not None and (set(gate.keys()) != {"n_lo", "n_hi"} or not 0.0 <= gt[0] < gt[1]):
                 raise ValueError
+            bd = None if bonds is None else (float(bonds["d_lo"]), float(bonds["d_hi"]))
+            if bd is not None and (set(bonds.keys()) != {"d_lo", "d_hi"} or not -1.0 <= bd[0] < bd[1] <= 1.0 or average):
+                raise ValueError
+            self.cpp_force.clearBonds()
             if sw is None:
                 self.cpp_force.clearSwitch()
             else:
@@ -322,6 +336,8 @@ class steinhardt_local(_collective_variable, metaclass=_local_options):
             else:
                 self.cpp_force.setGate(*gt)
             self.cpp_force.setAverage(bool(average))
+            if bd is not None:
+                self.cpp_force.setBonds(*bd)
         except (TypeError, KeyError, ValueError, AttributeError, RuntimeError):
             raise RuntimeError("Error creating collective variable.")
 
