@@ -35,9 +35,15 @@
 //                    ((q0 + q1) + (q2 + q3), the same bits in all four lanes)
 //   memory trips     list entry two iterations ahead, neighbour position one iteration ahead of the arithmetic
 //   one walk         the centre of a quad (QllCentre / qll_centre) and the zero that keeps the table loads in the loop
-//                    (qll_loop_table) are written once for all five kernels; the look-ahead and the pair test once (QllWalker) for
-//                    average and backprop (loop condition per quad).  accumulate, forces (per lane) and forces_tile (per wave) keep
-//                    them written out: see the note above QllWalker
+//                    (qll_loop_table) are written once for all seven kernels; the look-ahead and the pair test once (QllWalker) for the
+//                    four gather passes of the options, which share their whole frame (below).  accumulate, forces (per lane) and
+//                    forces_tile (per wave) keep the walk written out: see the note above QllWalker
+//   one gather frame k_qll_average, k_qll_backprop, k_qll_bonds and k_qll_bonds_backprop are one frame with four bodies: the window of a
+//                    row and its slots (QllWindow), the loop over the entries of a row that yields (f, j, counts) per entry
+//                    (qll_entries), the hand-round of the quad's four entries (quad_all, qll_add_rows), the quad's sum that only the
+//                    entry's own lane keeps (quad_keep), the per-entry scratch summed over the windows (qll_park) and the chunk's sum
+//                    into the block's (qll_chunk_sum, also in k_qll_accumulate).  A change to the window size, the look-ahead, the skip
+//                    rule or the row format of the gather passes is made there, once
 //   k_qll_accumulate monic sums S_lm = sum f p_m,l-m(cos theta) h^m (QlTab, as k_ql_accumulate) for every (l, m >= 0) of the compiled
 //                    LMAX; then per particle n_i, c_i and the table row
 //                        R_lm(i) = nrm(l, m)^2 (m > 0 ? 2 : 1) g_l(i) conj(S_lm(i))        degrees in use only, m >= 0
@@ -62,9 +68,10 @@
 //                    gradient on its second neighbours.  Four launches: k_qll_accumulate<QLL_AVERAGE> (n_i, the rows q(i)),
 //                    k_qll_average (gathers q(j): qbar, c_i, v_i, the rows B(i)), k_qll_backprop (gathers B(j) and q(j): the table row
 //                    C(k) / n_k with a_k folded in, and one double E_kj per list entry), then the force pass, which streams E beside
-//                    the list and adds it to the (0, 0) weight of the pair.  See the block above k_qll_average.
+//                    the list and adds it to the (0, 0) weight of the pair.  The two gather kernels are bodies in the gather frame: see
+//                    the block above QllWindow for the frame and the one above k_qll_average for the sums.
 //   bonds            (mtd_ql_local_bonds) the solid-bond count: d_ij = the normalised scalar product of q(i) and q(j), b_i = sum_j f_ij sigma(d_ij),
-//                    v_i = g(n_i) h(b_i).  Four launches in the frame of the average: k_qll_accumulate<QLL_BONDS> (n_i, c_i, the rows
+//                    v_i = g(n_i) h(b_i).  Four launches, the two in the middle in the gather frame: k_qll_accumulate<QLL_BONDS> (n_i, c_i, the rows
 //                    q(i) / sqrt(c_i)), k_qll_bonds (gathers u(j): d per list entry, b_i, v_i, beta_i), k_qll_bonds_backprop (gathers u(j)
 //                    and beta_j: the table row and E_kj = (beta_k + beta_j) sigma(d_kj) per list entry), then the AVG force pass as it is.
 //                    See the block above k_qll_bonds.
@@ -103,6 +110,16 @@ __device__ __forceinline__ double quad_sum(double v)
     return v;
     }
 
+// The chunk's sum of a per-particle value, added to the block's running sum: every lane brings the value of its quad's particle (0
+// past the end), wave 0 adds the 64 in the fixed order of wave_sum.  Every lane of the block is here: the chunk loop is uniform.
+__device__ __forceinline__ void qll_chunk_sum(double (&s_c)[QLL_PPB], const unsigned int tid, const double v, double &block_sum)
+    {
+    __syncthreads();
+    if (tid % QLL_G == 0) s_c[tid / QLL_G] = v;
+    __syncthreads();
+    if (tid < MTD_WAVE) block_sum += wave_sum(s_c[tid]);
+    }
+
 // value of lane u of the quad in all four of its lanes
 template<int U> __device__ __forceinline__ double quad_bcast(const double v) { return dpp_move<U * 0x55>(v); }
 template<int U> __device__ __forceinline__ unsigned int quad_bcast(const unsigned int v)
@@ -110,7 +127,7 @@ template<int U> __device__ __forceinline__ unsigned int quad_bcast(const unsigne
     return (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, U * 0x55, 0xf, 0xf, false);
     }
 
-// ---- the walk over a row: a quad's central particle (all five kernels) and its lane's share of the row ----------------------------
+// ---- the walk over a row: a quad's central particle (all seven kernels) and its lane's share of the row ----------------------------
 // the central particle of a quad: particle i of the chunk, its row of the list (empty for i >= N and for a particle of another type)
 struct QllCentre
     {
@@ -118,6 +135,7 @@ struct QllCentre
     Particle p;
     unsigned int start, cnt;
     __device__ __forceinline__ unsigned int row(const unsigned int N) const { return i < N ? i : 0; }   // a table row that is safe to address
+    __device__ __forceinline__ double own(const unsigned int N, const double *of) const { return i < N ? of[i] : 0.0; }   // its per-particle value
     };
 
 template<typename S4, int LMAX>
@@ -141,7 +159,7 @@ __device__ __forceinline__ QllCentre qll_centre(const QlArgs<LMAX> &a, const S4 
 // Lane q of the quad takes entries q, q + 4, ... of the row.  The walker owns the look-ahead: the list entry is asked for two
 // iterations, the neighbour's position one iteration ahead of the arithmetic on (j0, pos0).  A loop is
 //     w.begin(..); while (its own condition on w.e) { w.ahead(..); w.pair(.., what to do with the pair); w.step(); }
-// Used by k_qll_average and k_qll_backprop.  k_qll_accumulate, k_qll_forces and k_qll_forces_tile keep the same walk written out:
+// Used by the four gather passes, through qll_entries.  k_qll_accumulate, k_qll_forces and k_qll_forces_tile keep the same walk written out:
 // through the walker their bits or their speed did not stay the parent's (profiles/r10/README.md).  A change to the look-ahead, the
 // list format or the skip rule is made here AND in those three loops.  The walker holds the look-ahead only; what it reads from is
 // handed to begin and ahead.
@@ -562,11 +580,7 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_accumulate(const QlArgs<LMA
             }
         if constexpr (MODE == QLL_PLAIN || MODE == QLL_TRANSFORM)
             {
-            // the chunk's sum of c_i (v_i with a switch or a gate): wave 0, fixed order
-            __syncthreads();
-            if (q == 0) s_c[p] = i < a.N ? c : 0.0;
-            __syncthreads();
-            if (tid < MTD_WAVE) block_c += wave_sum(s_c[tid]);
+            qll_chunk_sum(s_c, tid, i < a.N ? c : 0.0, block_c);                  // c_i; v_i with a switch or a gate
             }
         }
     if constexpr (MODE == QLL_AVERAGE || MODE == QLL_BONDS) return;                 // k_qll_average / k_qll_bonds sum the v_i
@@ -826,7 +840,116 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
         }
     }
 
-// ---- the averaged variable: two gather passes between pass 1 and the force pass ---------------------------------------------------
+// ---- the gather passes: the averaged variable and the solid-bond count, two passes each between pass 1 and the force pass --------
+// Gather pattern (DESIGN.md 4.11): a quad still owns one central particle and its lanes still take entries q, q + 4, ... of the row for
+// the pair geometry (same look-ahead), but the ROWS are split by slot: lane q holds slots q, q + 4, ... of its particle.  Each of the
+// quad's four entries is handed round with a DPP quad broadcast (index and a scalar), and the four lanes read 64 consecutive bytes of
+// that neighbour's row: sixteen rows per wave instruction, whole 64-byte segments, no LDS, and the sums stay in registers in list order.
+// Rows longer than QLL_GV x 64 bytes are taken in windows of QLL_GV x 4 slots, the list walked once per window.  Entries that do not
+// count (beyond r_cut, other type, self, j >= N) read the particle's own row with f = 0: the loads need no branch.
+// The frame of all four kernels is written once, below: the window and its slots (QllWindow), the walk over the entries of a row
+// (qll_entries, on QllWalker), the hand-round of the quad's four entries (quad_all; with the rows added up, qll_add_rows), the quad's
+// sum for an entry that only the entry's own lane keeps (quad_keep) and the per-entry scratch that is summed over the windows
+// (qll_park).  What is left in a kernel is its sums.
+constexpr unsigned int QLL_GV = 4;                                  // 16-byte slots per lane and window: one window up to 256-byte rows
+
+// one window of a row of rs16 slots: lane q of the quad holds slots w0 + q, w0 + 4 + q, ... (QLL_GV of them)
+struct QllWindow
+    {
+    unsigned int w0;
+    const unsigned int rs16, q;
+    __device__ __forceinline__ QllWindow(const unsigned int rs16_, const unsigned int q_) : w0(0), rs16(rs16_), q(q_) {}
+    __device__ __forceinline__ bool more() const { return w0 < rs16; }
+    __device__ __forceinline__ void next() { w0 += QLL_G * QLL_GV; }
+    __device__ __forceinline__ bool first() const { return w0 == 0; }
+    __device__ __forceinline__ bool last() const { return w0 + QLL_G * QLL_GV >= rs16; }
+    __device__ __forceinline__ unsigned int slot(const unsigned int v) const { return w0 + QLL_G * v + q; }
+    __device__ __forceinline__ bool inside(const unsigned int v) const { return slot(v) < rs16; }        // a slot past the row adds nothing
+    __device__ __forceinline__ unsigned int clamped(const unsigned int v) const { return inside(v) ? slot(v) : rs16 - 1; }   // safe to load
+    };
+
+// what the walk hands to a gather pass for the entry a lane has in hand
+struct QllEntry
+    {
+    double f;                                              // the smoothing function; 0 for an entry that does not count
+    unsigned int j;                                        // the neighbour; the central particle's own (safe) row for one that does not count
+    bool counts;
+    unsigned int e, start, cnt;                            // entry e of the row that starts at `start` and has cnt entries
+    __device__ __forceinline__ bool mine() const { return e < cnt; }               // the lane has an entry at all: the quad walks its row together
+    __device__ __forceinline__ unsigned int at() const { return start + e; }       // where it sits in the list, and in the per-entry scratch
+    };
+
+// the entries of the quad's row, four per round: body(QllEntry) for the entry of this lane, every lane of the quad in every round
+template<typename S4, typename F>
+__device__ __forceinline__ void qll_entries(const QlArgs<12> &a, const S4 *postype, const unsigned int *nlist, const QllCentre &c,
+                                            const unsigned int q, const double *tab, F &&body)
+    {
+    QllWalker<S4> w;
+    w.begin(a.N, postype, nlist, c, q);
+#pragma unroll 1
+    for (unsigned int eb = 0; eb < c.cnt; eb += QLL_G, w.step())                    // cnt is the quad's: its four lanes stay together
+        {
+        const double *__restrict__ tab_k = qll_loop_table(tab);
+        w.ahead(a.N, postype, nlist, c);
+        QllEntry en = {0.0, c.row(a.N), false, w.e, c.start, c.cnt};
+        w.pair(a, c, [&](double, double, double, const double rsq)
+            {
+            double fprime_divr;
+            smoothing_tab<12>(a, tab_k, rsq, rsqrt(rsq), en.f, fprime_divr);
+            en.j = w.j0;
+            en.counts = true;
+            });
+        body(en);
+        }
+    }
+
+// the quad's four values of v, lane by lane, in all four of its lanes
+template<typename T> __device__ __forceinline__ void quad_all(const T v, T (&of)[QLL_G])
+    {
+    of[0] = quad_bcast<0>(v), of[1] = quad_bcast<1>(v), of[2] = quad_bcast<2>(v), of[3] = quad_bcast<3>(v);
+    }
+
+// acc_c += sum over the quad's four entries (neighbour j, scalar s, lane by lane: list order) of s row_c(j), for this lane's slots cs
+__device__ __forceinline__ void qll_add_rows(double2 (&acc)[QLL_GV], const double2 *rows, const unsigned int rs16, const unsigned int (&cs)[QLL_GV],
+                                             const unsigned int j, const double s)
+    {
+    unsigned int ju[QLL_G];
+    double su[QLL_G];
+    quad_all(j, ju);
+    quad_all(s, su);
+#pragma unroll
+    for (unsigned int u = 0; u < QLL_G; ++u)
+#pragma unroll
+        for (unsigned int v = 0; v < QLL_GV; ++v)
+            {
+            const double2 r = rows[(size_t)ju[u] * rs16 + cs[v]];
+            acc[v].x += su[u] * r.x;
+            acc[v].y += su[u] * r.y;
+            }
+    }
+
+// share(u) is this lane's share of a sum that belongs to the entry of lane u: the quad's sums, of which every lane keeps its own
+template<typename F> __device__ __forceinline__ double quad_keep(const unsigned int q, F &&share)
+    {
+    double mine = 0.0;
+#pragma unroll
+    for (unsigned int u = 0; u < QLL_G; ++u)
+        {
+        const double sum = quad_sum(share(u));
+        if (q == u) mine = sum;
+        }
+    return mine;
+    }
+
+// a per-entry value that is summed over the windows: the lane adds to what it wrote in the last window; returns the sum so far
+__device__ __forceinline__ double qll_park(double *epair, const QllEntry &en, const QllWindow &win, double val)
+    {
+    if (!win.first()) val += epair[en.at()];
+    epair[en.at()] = val;
+    return val;
+    }
+
+// ---- the averaged variable ----------------------------------------------------------------------------------------------------
 // Rows here are the MONIC ones of pass 1, qm_c(i) = S_lm(i) / n_i per slot c = off[l] + m (q_lm = nrm(l, m) qm), and the slot weights
 // w_c = Ql_ref[l] 4 pi / (2l + 1) (m > 0 ? 2 : 1) nrm(l, m)^2 carry everything that depends on (l, m):
 //   k_qll_average   qbar_c(i) = [qm_c(i) + sum_j f_ij qm_c(j)] / (1 + n_i),  c_i = sum_c w_c |qbar_c(i)|^2,  v_i = g(n_i) h(c_i),
@@ -834,14 +957,6 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
 //                   a0_i = g'(n_i) h(c_i) - g h' 2 c_i / (1 + n_i),  block sums of v_i
 //   k_qll_backprop  Cm_c(k) = Bm_c(k) + sum_i f_ik Bm_c(i);  the table row of the force pass R_c(k) = Cm_c(k) / n_k with
 //                   a_k = a0_k - sum_c Re Cm_c(k) qm_c(k) / n_k added to slot 0;  per list entry E_kj = sum_c Re[Bm_c(k) qm_c(j) + Bm_c(j) qm_c(k)]
-// Gather pattern (DESIGN.md 4.11): a quad still owns one central particle and its lanes still take entries q, q + 4, ... of the row for
-// the pair geometry (same look-ahead), but the ROWS are split by slot: lane q holds slots q, q + 4, ... of its particle.  Each of the
-// quad's four entries is handed round with a DPP quad broadcast (index and f), and the four lanes read 64 consecutive bytes of that
-// neighbour's row: sixteen rows per wave instruction, whole 64-byte segments, no LDS, and the sums stay in registers in list order.
-// Rows longer than QLL_GV x 64 bytes are taken in windows of QLL_GV x 4 slots, the list walked once per window.  Entries that do not
-// count (beyond r_cut, other type, self, j >= N) read the particle's own row with f = 0: the loads need no branch.
-constexpr unsigned int QLL_GV = 4;                                  // 16-byte slots per lane and window: one window up to 256-byte rows
-
 template<typename S4>
 __global__ __launch_bounds__(QLL_THREADS) void k_qll_average(const QlArgs<12> a, const QllOpt o, const unsigned int rs16, const S4 *__restrict__ postype,
                                                              const unsigned int *__restrict__ head_list, const unsigned int *__restrict__ n_neigh,
@@ -858,60 +973,34 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_average(const QlArgs<12> a,
         {
         const QllCentre ci = qll_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
         const unsigned int i = ci.i, ii = ci.row(a.N);
-        const double ni = i < a.N ? n_in[i] : 0.0;
+        const double ni = ci.own(a.N, n_in);
         const double inv_1n = 1.0 / (1.0 + ni);
         double csum = 0.0;
-        for (unsigned int w0 = 0; w0 < rs16; w0 += QLL_G * QLL_GV)
+        for (QllWindow win(rs16, q); win.more(); win.next())
             {
             unsigned int cs[QLL_GV];                                                 // this lane's slots, clamped into the row
             double2 acc[QLL_GV];
 #pragma unroll
             for (unsigned int v = 0; v < QLL_GV; ++v)
                 {
-                const unsigned int c = w0 + QLL_G * v + q;
-                cs[v] = c < rs16 ? c : rs16 - 1;
+                cs[v] = win.clamped(v);
                 acc[v] = qrows[(size_t)ii * rs16 + cs[v]];
                 }
-            QllWalker<S4> w;
-            w.begin(a.N, postype, nlist, ci, q);
-#pragma unroll 1
-            for (unsigned int eb = 0; eb < ci.cnt; eb += QLL_G, w.step())           // cnt is the quad's: its four lanes stay together
+            qll_entries(a, postype, nlist, ci, q, tab, [&](const QllEntry &en)
                 {
-                const double *__restrict__ tab_k = qll_loop_table(tab);
-                w.ahead(a.N, postype, nlist, ci);
-                double f = 0.0;
-                unsigned int jv = ii;
-                w.pair(a, ci, [&](double, double, double, const double rsq)
-                    {
-                    double fprime_divr;
-                    smoothing_tab<12>(a, tab_k, rsq, rsqrt(rsq), f, fprime_divr);
-                    jv = w.j0;
-                    });
-                const unsigned int ju[QLL_G] = {quad_bcast<0>(jv), quad_bcast<1>(jv), quad_bcast<2>(jv), quad_bcast<3>(jv)};
-                const double fu[QLL_G] = {quad_bcast<0>(f), quad_bcast<1>(f), quad_bcast<2>(f), quad_bcast<3>(f)};
-#pragma unroll
-                for (unsigned int u = 0; u < QLL_G; ++u)
-#pragma unroll
-                    for (unsigned int v = 0; v < QLL_GV; ++v)
-                        {
-                        const double2 r = qrows[(size_t)ju[u] * rs16 + cs[v]];
-                        acc[v].x += fu[u] * r.x;
-                        acc[v].y += fu[u] * r.y;
-                        }
-                }
+                qll_add_rows(acc, qrows, rs16, cs, en.j, en.f);
+                });
             // this window of qbar: its share of c_i, and 2 w conj(qbar) / (1 + n) parked in the B row until h'(c_i) is known
 #pragma unroll
             for (unsigned int v = 0; v < QLL_GV; ++v)
-                {
-                const unsigned int c = w0 + QLL_G * v + q;
-                if (c < rs16)
+                if (win.inside(v))
                     {
+                    const unsigned int c = win.slot(v);
                     const double w = wtab[c];
                     const double qx = acc[v].x * inv_1n, qy = acc[v].y * inv_1n;
                     csum += w * (qx * qx + qy * qy);
                     if (i < a.N) brows[(size_t)i * rs16 + c] = make_double2(2.0 * w * inv_1n * qx, -(2.0 * w * inv_1n * qy));
                     }
-                }
             }
         const double c = quad_sum(csum);
         double h, dh, g, dg;
@@ -929,11 +1018,7 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_average(const QlArgs<12> a,
             v_out[i] = g * h;
             a0_out[i] = dg * h - gh * (2.0 * c * inv_1n);
             }
-        // the chunk's sum of v_i: wave 0, fixed order
-        __syncthreads();
-        if (q == 0) s_c[p] = i < a.N ? g * h : 0.0;
-        __syncthreads();
-        if (tid < MTD_WAVE) block_v += wave_sum(s_c[tid]);
+        qll_chunk_sum(s_c, tid, i < a.N ? g * h : 0.0, block_v);
         }
     if (tid == 0) partials[blockIdx.x] = block_v;
     }
@@ -952,45 +1037,29 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_backprop(const QlArgs<12> a
         {
         const QllCentre ck = qll_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
         const unsigned int k = ck.i, kk = ck.row(a.N);
-        const double nk = k < a.N ? n_in[k] : 0.0, a0 = k < a.N ? a0_in[k] : 0.0;
+        const double nk = ck.own(a.N, n_in), a0 = ck.own(a.N, a0_in);
         const double inv_n = nk > 0.0 ? 1.0 / nk : 0.0;
         double cq = 0.0, r00 = 0.0;
-        for (unsigned int w0 = 0; w0 < rs16; w0 += QLL_G * QLL_GV)
+        for (QllWindow win(rs16, q); win.more(); win.next())
             {
             unsigned int cs[QLL_GV];
             double2 acc[QLL_GV], bk[QLL_GV], qk[QLL_GV];
 #pragma unroll
             for (unsigned int v = 0; v < QLL_GV; ++v)
                 {
-                const unsigned int c = w0 + QLL_G * v + q;
-                cs[v] = c < rs16 ? c : rs16 - 1;
+                cs[v] = win.clamped(v);
                 bk[v] = brows[(size_t)kk * rs16 + cs[v]];
                 qk[v] = qrows[(size_t)kk * rs16 + cs[v]];
-                if (c >= rs16) bk[v] = qk[v] = make_double2(0.0, 0.0);              // a slot past the row adds nothing to E
+                if (!win.inside(v)) bk[v] = qk[v] = make_double2(0.0, 0.0);         // a slot past the row adds nothing to E
                 acc[v] = bk[v];
                 }
-            QllWalker<S4> w;
-            w.begin(a.N, postype, nlist, ck, q);
-#pragma unroll 1
-            for (unsigned int eb = 0; eb < ck.cnt; eb += QLL_G, w.step())
+            qll_entries(a, postype, nlist, ck, q, tab, [&](const QllEntry &en)
                 {
-                const double *__restrict__ tab_k = qll_loop_table(tab);
-                w.ahead(a.N, postype, nlist, ck);
-                double f = 0.0;
-                unsigned int jv = kk;
-                bool visit = false;
-                w.pair(a, ck, [&](double, double, double, const double rsq)
-                    {
-                    double fprime_divr;
-                    smoothing_tab<12>(a, tab_k, rsq, rsqrt(rsq), f, fprime_divr);
-                    jv = w.j0;
-                    visit = true;
-                    });
-                const unsigned int ju[QLL_G] = {quad_bcast<0>(jv), quad_bcast<1>(jv), quad_bcast<2>(jv), quad_bcast<3>(jv)};
-                const double fu[QLL_G] = {quad_bcast<0>(f), quad_bcast<1>(f), quad_bcast<2>(f), quad_bcast<3>(f)};
-                double mine = 0.0;
-#pragma unroll
-                for (unsigned int u = 0; u < QLL_G; ++u)
+                unsigned int ju[QLL_G];
+                double fu[QLL_G];
+                quad_all(en.j, ju);
+                quad_all(en.f, fu);
+                const double e_kj = quad_keep(q, [&](const unsigned int u)
                     {
                     double ee = 0.0;
 #pragma unroll
@@ -1001,37 +1070,29 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_backprop(const QlArgs<12> a
                         acc[v].y += fu[u] * bj.y;
                         ee += (bk[v].x * qj.x - bk[v].y * qj.y) + (bj.x * qk[v].x - bj.y * qk[v].y);
                         }
-                    ee = quad_sum(ee);
-                    if (q == u) mine = ee;
-                    }
-                if (w.e < ck.cnt)
-                    {
-                    double val = visit ? mine : 0.0;
-                    if (w0 > 0) val += epair[ck.start + w.e];                        // the lane adds to what it wrote in the last window
-                    epair[ck.start + w.e] = val;
-                    }
-                }
+                    return ee;
+                    });
+                if (en.mine()) qll_park(epair, en, win, en.counts ? e_kj : 0.0);
+                });
             // Cm of this window: its share of sum Re Cm qm, and the row of the force pass
 #pragma unroll
             for (unsigned int v = 0; v < QLL_GV; ++v)
-                {
-                const unsigned int c = w0 + QLL_G * v + q;
-                if (c < rs16)
+                if (win.inside(v))
                     {
+                    const unsigned int c = win.slot(v);
                     cq += acc[v].x * qk[v].x - acc[v].y * qk[v].y;
                     if (c == 0)
                         r00 = acc[v].x * inv_n;
                     else if (k < a.N)
                         rows[(size_t)k * rs16 + c] = make_double2(acc[v].x * inv_n, acc[v].y * inv_n);
                     }
-                }
             }
         cq = quad_sum(cq);
         if (q == 0 && k < a.N) rows[(size_t)k * rs16] = make_double2(r00 + (a0 - cq * inv_n), 0.0);
         }
     }
 
-// ---- the solid-bond count: two gather passes between pass 1 and the force pass ---------------------------------------------------
+// ---- the solid-bond count ------------------------------------------------------------------------------------------------------
 // Rows here are the NORMALISED monic ones of pass 1 <QLL_BONDS>, u_c(i) = qm_c(i) / sqrt(c_i), so that with the slot weights w_c
 //   d_kj = sum_c w_c Re(u_c(k) conj(u_c(j)))    in [-1, 1]: the normalised scalar product of the q vectors of the two ends of a bond.
 //   k_qll_bonds           d_kj per list entry (parked in the per-entry scratch),  b_k = sum_j f_kj sigma(d_kj),  v_k = g(n_k) h(b_k),
@@ -1040,10 +1101,10 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_backprop(const QlArgs<12> a
 //                         Bm_c(k) = w_c conj(Pm_c(k));  the table row of the force pass R_c(k) = Bm_c(k) / n_k with
 //                         a_k = a0_k - sum_c Re Bm_c(k) qm_c(k) / n_k added to slot 0 (the sum vanishes analytically: <P(k), u(k)> = 0);
 //                         per list entry E_kj = (beta_k + beta_j) sigma(d_kj) in place of d_kj
-// The force pass is the one of the averaged variable (AVG = true), unchanged.  Gather pattern: that of k_qll_average.  beta of EVERY
-// particle is complete before the second pass reads it: a launch of its own.  With more than one window the list is walked once per
-// window: d_kj is the sum over the windows (the lane adds to what it wrote in the last window, as k_qll_backprop does for E) and is
-// read in every window of the second pass, so E replaces it in the LAST window only.  An entry that does not count gets E = 0.
+// The force pass is the one of the averaged variable (AVG = true), unchanged.  beta of EVERY particle is complete before the second
+// pass reads it: a launch of its own.  With more than one window the list is walked once per window: d_kj is the sum over the windows
+// (qll_park, as for E in k_qll_backprop) and is read in every window of the second pass, so E replaces it in the LAST window only.  An
+// entry that does not count gets E = 0.
 template<typename S4>
 __global__ __launch_bounds__(QLL_THREADS) void k_qll_bonds(const QlArgs<12> a, const QllOpt o, const QllRamp ramp, const unsigned int rs16,
                                                            const S4 *__restrict__ postype, const unsigned int *__restrict__ head_list,
@@ -1061,41 +1122,26 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_bonds(const QlArgs<12> a, c
         {
         const QllCentre ci = qll_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
         const unsigned int i = ci.i, ii = ci.row(a.N);
-        const double ni = i < a.N ? n_in[i] : 0.0;
+        const double ni = ci.own(a.N, n_in);
         double bsum = 0.0;
-        for (unsigned int w0 = 0; w0 < rs16; w0 += QLL_G * QLL_GV)
+        for (QllWindow win(rs16, q); win.more(); win.next())
             {
-            const bool last = w0 + QLL_G * QLL_GV >= rs16;
+            const bool last = win.last();
             unsigned int cs[QLL_GV];                                                 // this lane's slots, clamped into the row
             double2 uk[QLL_GV];                                                      // w_c u_c(i); 0 for a slot past the row
 #pragma unroll
             for (unsigned int v = 0; v < QLL_GV; ++v)
                 {
-                const unsigned int c = w0 + QLL_G * v + q;
-                cs[v] = c < rs16 ? c : rs16 - 1;
+                cs[v] = win.clamped(v);
                 const double2 r = urows[(size_t)ii * rs16 + cs[v]];
-                const double w = c < rs16 ? wtab[cs[v]] : 0.0;
+                const double w = win.inside(v) ? wtab[cs[v]] : 0.0;
                 uk[v] = make_double2(w * r.x, w * r.y);
                 }
-            QllWalker<S4> w;
-            w.begin(a.N, postype, nlist, ci, q);
-#pragma unroll 1
-            for (unsigned int eb = 0; eb < ci.cnt; eb += QLL_G, w.step())           // cnt is the quad's: its four lanes stay together
+            qll_entries(a, postype, nlist, ci, q, tab, [&](const QllEntry &en)
                 {
-                const double *__restrict__ tab_k = qll_loop_table(tab);
-                w.ahead(a.N, postype, nlist, ci);
-                double f = 0.0;
-                unsigned int jv = ii;
-                w.pair(a, ci, [&](double, double, double, const double rsq)
-                    {
-                    double fprime_divr;
-                    smoothing_tab<12>(a, tab_k, rsq, rsqrt(rsq), f, fprime_divr);
-                    jv = w.j0;
-                    });
-                const unsigned int ju[QLL_G] = {quad_bcast<0>(jv), quad_bcast<1>(jv), quad_bcast<2>(jv), quad_bcast<3>(jv)};
-                double mine = 0.0;
-#pragma unroll
-                for (unsigned int u = 0; u < QLL_G; ++u)
+                unsigned int ju[QLL_G];
+                quad_all(en.j, ju);
+                const double d_part = quad_keep(q, [&](const unsigned int u)
                     {
                     double dd = 0.0;
 #pragma unroll
@@ -1104,21 +1150,19 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_bonds(const QlArgs<12> a, c
                         const double2 r = urows[(size_t)ju[u] * rs16 + cs[v]];
                         dd += uk[v].x * r.x + uk[v].y * r.y;
                         }
-                    dd = quad_sum(dd);
-                    if (q == u) mine = dd;
-                    }
-                if (w.e < ci.cnt)
+                    return dd;
+                    });
+                if (en.mine())
                     {
-                    if (w0 > 0) mine += epair[ci.start + w.e];                       // the lane adds to what it wrote in the last window
-                    epair[ci.start + w.e] = mine;
+                    const double d = qll_park(epair, en, win, d_part);
                     if (last)
                         {
                         double sg, dsg;
-                        ramp(mine, sg, dsg);
-                        bsum += f * sg;                                              // f = 0 for an entry that does not count
+                        ramp(d, sg, dsg);
+                        bsum += en.f * sg;                                           // f = 0 for an entry that does not count
                         }
                     }
-                }
+                });
             }
         const double b = quad_sum(bsum);
         double h, dh, g, dg;
@@ -1130,11 +1174,7 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_bonds(const QlArgs<12> a, c
             beta_out[i] = g * dh;
             a0_out[i] = dg * h;
             }
-        // the chunk's sum of v_i: wave 0, fixed order
-        __syncthreads();
-        if (q == 0) s_c[p] = i < a.N ? g * h : 0.0;
-        __syncthreads();
-        if (tid < MTD_WAVE) block_v += wave_sum(s_c[tid]);
+        qll_chunk_sum(s_c, tid, i < a.N ? g * h : 0.0, block_v);
         }
     if (tid == 0) partials[blockIdx.x] = block_v;
     }
@@ -1155,69 +1195,41 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_bonds_backprop(const QlArgs
         const QllCentre ck = qll_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
         const unsigned int k = ck.i, kk = ck.row(a.N);
         const bool there = k < a.N;
-        const double nk = there ? n_in[k] : 0.0, a0 = there ? a0_in[k] : 0.0, c_k = there ? c_in[k] : 0.0, beta_k = there ? beta_in[k] : 0.0;
+        const double nk = ck.own(a.N, n_in), a0 = ck.own(a.N, a0_in), c_k = ck.own(a.N, c_in), beta_k = ck.own(a.N, beta_in);
         const double inv_n = nk > 0.0 ? 1.0 / nk : 0.0;
         const double root_c = sqrt(c_k), inv_rc = c_k > 0.0 ? 1.0 / root_c : 0.0;
         double cq = 0.0, r00 = 0.0;
-        for (unsigned int w0 = 0; w0 < rs16; w0 += QLL_G * QLL_GV)
+        for (QllWindow win(rs16, q); win.more(); win.next())
             {
-            const bool last = w0 + QLL_G * QLL_GV >= rs16;
+            const bool last = win.last();
             unsigned int cs[QLL_GV];
             double2 acc[QLL_GV], uk[QLL_GV];
 #pragma unroll
             for (unsigned int v = 0; v < QLL_GV; ++v)
                 {
-                const unsigned int c = w0 + QLL_G * v + q;
-                cs[v] = c < rs16 ? c : rs16 - 1;
+                cs[v] = win.clamped(v);
                 uk[v] = urows[(size_t)kk * rs16 + cs[v]];
                 acc[v] = make_double2(0.0, 0.0);
                 }
             double td = 0.0;                                                         // this lane's share of sum_j t_kj d_kj: whole in every window
-            QllWalker<S4> w;
-            w.begin(a.N, postype, nlist, ck, q);
-#pragma unroll 1
-            for (unsigned int eb = 0; eb < ck.cnt; eb += QLL_G, w.step())
+            qll_entries(a, postype, nlist, ck, q, tab, [&](const QllEntry &en)
                 {
-                const double *__restrict__ tab_k = qll_loop_table(tab);
-                w.ahead(a.N, postype, nlist, ck);
-                double f = 0.0;
-                unsigned int jv = kk;
-                bool visit = false;
-                w.pair(a, ck, [&](double, double, double, const double rsq)
-                    {
-                    double fprime_divr;
-                    smoothing_tab<12>(a, tab_k, rsq, rsqrt(rsq), f, fprime_divr);
-                    jv = w.j0;
-                    visit = true;
-                    });
-                const bool mine = w.e < ck.cnt;
-                const double d = mine ? epair[ck.start + w.e] : 0.0;
-                const double bsum = beta_k + beta_in[jv];
+                const double d = en.mine() ? epair[en.at()] : 0.0;
+                const double bsum = beta_k + beta_in[en.j];
                 double sg, dsg;
                 ramp(d, sg, dsg);
-                const double t = visit ? bsum * f * dsg : 0.0;
+                const double t = en.counts ? bsum * en.f * dsg : 0.0;
                 td += t * d;
-                if (mine && last) epair[ck.start + w.e] = visit ? bsum * sg : 0.0;   // E replaces d once no window needs d again
-                const unsigned int ju[QLL_G] = {quad_bcast<0>(jv), quad_bcast<1>(jv), quad_bcast<2>(jv), quad_bcast<3>(jv)};
-                const double tu[QLL_G] = {quad_bcast<0>(t), quad_bcast<1>(t), quad_bcast<2>(t), quad_bcast<3>(t)};
-#pragma unroll
-                for (unsigned int u = 0; u < QLL_G; ++u)
-#pragma unroll
-                    for (unsigned int v = 0; v < QLL_GV; ++v)
-                        {
-                        const double2 r = urows[(size_t)ju[u] * rs16 + cs[v]];
-                        acc[v].x += tu[u] * r.x;
-                        acc[v].y += tu[u] * r.y;
-                        }
-                }
+                if (en.mine() && last) epair[en.at()] = en.counts ? bsum * sg : 0.0;   // E replaces d once no window needs d again
+                qll_add_rows(acc, urows, rs16, cs, en.j, t);
+                });
             td = quad_sum(td);
             // Bm of this window: its share of sum Re Bm qm, and the row of the force pass
 #pragma unroll
             for (unsigned int v = 0; v < QLL_GV; ++v)
-                {
-                const unsigned int c = w0 + QLL_G * v + q;
-                if (c < rs16)
+                if (win.inside(v))
                     {
+                    const unsigned int c = win.slot(v);
                     const double wc = wtab[c] * inv_rc;
                     const double bx = wc * (acc[v].x - td * uk[v].x), by = -(wc * (acc[v].y - td * uk[v].y));
                     cq += root_c * (bx * uk[v].x - by * uk[v].y);
@@ -1226,7 +1238,6 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_bonds_backprop(const QlArgs
                     else if (there)
                         rows[(size_t)k * rs16 + c] = make_double2(bx * inv_n, by * inv_n);
                     }
-                }
             }
         cq = quad_sum(cq);
         if (q == 0 && there) rows[(size_t)k * rs16] = make_double2(r00 + (a0 - cq * inv_n), 0.0);
@@ -1251,25 +1262,9 @@ QllLayout qll_layout(const unsigned int lmax, const double *ql_ref)
     return lay;
     }
 
-// scratch: block sums [QLL_MAX_BLOCKS] | n_i [N] | c_i [N] (+ one double when N is odd) | rows [N][<= (lmax + 1)(lmax + 2)]
-// with a switch or a gate, behind these:  (one double when the above is an odd number) v_i [N] (+ one when N is odd)
-// with the average, behind those:         a0_i [N] (+ one) | slot weights [(lmax + 1)(lmax + 2) / 2] (+ one when odd)
-//                                         | monic rows [N][..] | B rows [N][..] | E [list entries]
-// with bonds, behind v_i:                 a0_i [N] (+ one) | b_i [N] (+ one) | beta_i [N] (+ one) | slot weights (+ one when odd)
-//                                         | normalised monic rows [N][..] | d, then E [list entries]
-struct QllScratch
-    {
-    double *partials, *n, *c, *rows, *v, *a0, *b, *beta, *wtab, *qrows, *brows, *epair;
-    };
-
-struct QllSizes
-    {
-    size_t base, pad, v, a0, bb, wtab, rows, total;
-    };
-
 bool qll_bonds_on(const mtd_ql_local_bonds *bonds) { return bonds && bonds->on; }
 
-int qll_mode(const mtd_ql_local_options *opt, const mtd_ql_local_bonds *bonds = nullptr)
+int qll_mode(const mtd_ql_local_options *opt, const mtd_ql_local_bonds *bonds)
     {
     if (qll_bonds_on(bonds)) return QLL_BONDS;
     if (!opt) return QLL_PLAIN;
@@ -1277,38 +1272,48 @@ int qll_mode(const mtd_ql_local_options *opt, const mtd_ql_local_bonds *bonds = 
     return opt->switch_on || opt->gate_on ? QLL_TRANSFORM : QLL_PLAIN;
     }
 
-QllSizes qll_sizes(const size_t n, const unsigned int lmax, const size_t n_list_entries, const int mode)
+// The scratch, one segment behind the other in the order of qll_scratch below; `even(x)` is x plus one double when x is odd:
+//   every mode          block sums [QLL_MAX_BLOCKS] | n_i [N] | c_i [even(N)] | rows [N][(lmax + 1)(lmax + 2)]   (the most a row can take)
+//   all but the plain   (one double when the above is an odd number: what the options add starts on an even offset) | v_i [even(N)]
+//                       (the plain mode has no v_i: the pointer is that of c_i)
+//   average and bonds   a0_i [even(N)]
+//   bonds               b_i [even(N)] | beta_i [even(N)]
+//   average and bonds   slot weights [even((lmax + 1)(lmax + 2) / 2)] | monic rows [N][..] (bonds: normalised)
+//   average             B rows [N][..]
+//   average and bonds   one double per list entry: E (bonds: d first, then E)
+// A segment that a mode does not have is empty: its pointer is where the next one starts and is handed to no kernel that reads it.
+struct QllScratch
     {
-    QllSizes z;
-    z.rows = n * (size_t)(lmax + 1) * (lmax + 2);
-    z.base = (size_t)QLL_MAX_BLOCKS + 2 * n + (n & 1u) + z.rows;
-    z.pad = mode == QLL_PLAIN ? 0 : z.base & 1u;                // what the options add starts on a 16-byte boundary
-    z.v = mode == QLL_PLAIN ? 0 : n + (n & 1u);
-    const bool gathers = mode == QLL_AVERAGE || mode == QLL_BONDS;
-    z.a0 = gathers ? n + (n & 1u) : 0;
-    z.bb = mode == QLL_BONDS ? 2 * (n + (n & 1u)) : 0;
-    const size_t slots = (size_t)(lmax + 1) * (lmax + 2) / 2;
-    z.wtab = gathers ? slots + (slots & 1u) : 0;
-    z.total = z.base + z.pad + z.v + z.a0 + z.bb + z.wtab + (gathers ? (mode == QLL_AVERAGE ? 2 : 1) * z.rows + n_list_entries : 0);
-    return z;
-    }
+    double *partials, *n, *c, *rows, *v, *a0, *b, *beta, *wtab, *qrows, *brows, *epair;
+    size_t total;                                          // doubles
+    };
 
-QllScratch qll_scratch(double *scratch, const unsigned int N, const unsigned int lmax, const int mode)
+QllScratch qll_scratch(double *scratch, const size_t n, const unsigned int lmax, const size_t n_list_entries, const int mode)
     {
-    const QllSizes z = qll_sizes(N, lmax, 0, mode);
+    const bool opts = mode != QLL_PLAIN, bonds = mode == QLL_BONDS, gathers = mode == QLL_AVERAGE || bonds;
+    const size_t even_n = n + (n & 1u), row = (size_t)(lmax + 1) * (lmax + 2), slots = row / 2;
+    size_t at = 0;
+    const auto take = [&](const size_t len)
+        {
+        double *p = scratch ? scratch + at : nullptr;        // null: the caller wants the total only
+        at += len;
+        return p;
+        };
     QllScratch s;
-    s.partials = scratch;
-    s.n = scratch + QLL_MAX_BLOCKS;
-    s.c = s.n + N;
-    s.rows = s.c + N + (N & 1u);
-    s.v = mode == QLL_PLAIN ? s.c : scratch + z.base + z.pad;
-    s.a0 = scratch + z.base + z.pad + z.v;
-    s.b = s.a0 + z.a0;
-    s.beta = s.b + z.bb / 2;
-    s.wtab = s.a0 + z.a0 + z.bb;
-    s.qrows = s.wtab + z.wtab;
-    s.brows = s.qrows + z.rows;
-    s.epair = mode == QLL_BONDS ? s.brows : s.brows + z.rows;
+    s.partials = take(QLL_MAX_BLOCKS);
+    s.n = take(n);
+    s.c = take(even_n);
+    s.rows = take(n * row);
+    take(opts ? at & 1u : 0);
+    s.v = opts ? take(even_n) : s.c;
+    s.a0 = take(gathers ? even_n : 0);
+    s.b = take(bonds ? even_n : 0);
+    s.beta = take(bonds ? even_n : 0);
+    s.wtab = take(gathers ? slots + (slots & 1u) : 0);
+    s.qrows = take(gathers ? n * row : 0);
+    s.brows = take(mode == QLL_AVERAGE ? n * row : 0);
+    s.epair = take(gathers ? n_list_entries : 0);
+    s.total = at;
     return s;
     }
 
@@ -1333,98 +1338,37 @@ QllOpt qll_opt(const mtd_ql_local_options *opt)
     return o;
     }
 
-template<typename S4, int LMAX>
-int qll_accumulate_impl(unsigned int N, const void *d_postype, const mtd_box *box, const unsigned int *d_head, const unsigned int *d_nneigh,
-                        const unsigned int *d_nlist, double rcut, double ron, unsigned int lmax, unsigned int type, const double *ql_ref,
-                        unsigned int n_global, const QllScratch &sc, const mtd_ql_local_options *opt, const mtd_ql_local_bonds *bonds,
-                        unsigned int *n_partials, hipStream_t s)
+// ---- one prepared call: what both terminal entry points are given, checked, and what follows from it --------------------------------
+struct QllCall
     {
-    QlArgs<LMAX> a;
-    int rc = fill_args<LMAX>(a, N, box, rcut, ron, lmax, type, ql_ref, n_global, 0);
-    if (rc) return rc;
-    QlArgs<12> a12;                                              // the gather passes need the box and the window only: one instantiation
-    rc = fill_args<12>(a12, N, box, rcut, ron, lmax, type, ql_ref, n_global, 0);
-    if (rc) return rc;
-    const double *tab = ql_device_table<LMAX>(s, rc);            // (the smoothing coefficients sit at the same place for every LMAX)
-    if (rc) return rc;
-    const QllLayout lay = qll_layout(lmax, ql_ref);
-    const unsigned int blocks = qll_blocks(N);
-    const QllOpt o = qll_opt(opt);
-    const int mode = qll_mode(opt, bonds);
-    const S4 *postype = (const S4 *)d_postype;
-    static_assert(QLL_PLAIN == 0 && QLL_TRANSFORM == 1 && QLL_AVERAGE == 2 && QLL_BONDS == 3, "the mode is dispatched as the count mode + 1 of 4");
-    dispatch_count<4>(mode + 1, [&](auto m1)
-        {
-        constexpr int MODE = decltype(m1)::value - 1;
-        k_qll_accumulate<S4, LMAX, MODE><<<blocks, QLL_THREADS, 0, s>>>(a, lay, o, postype, d_head, d_nneigh, d_nlist, sc.n, sc.c, sc.v,
-                                                                         MODE == QLL_AVERAGE || MODE == QLL_BONDS ? sc.qrows : sc.rows, sc.wtab,
-                                                                         sc.partials, tab);
-        });
-    MTD_LAUNCH_CHECK();
-    if (mode == QLL_BONDS)
-        {
-        const unsigned int rs16 = lay.row_doubles / 2;
-        const QllRamp ramp = {bonds->d_lo, 1.0 / (bonds->d_hi - bonds->d_lo)};
-        k_qll_bonds<S4><<<blocks, QLL_THREADS, 0, s>>>(a12, o, ramp, rs16, postype, d_head, d_nneigh, d_nlist, sc.n, (const double2 *)sc.qrows, sc.wtab,
-                                                        sc.epair, sc.b, sc.v, sc.beta, sc.a0, sc.partials, tab);
-        MTD_LAUNCH_CHECK();
-        k_qll_bonds_backprop<S4><<<blocks, QLL_THREADS, 0, s>>>(a12, ramp, rs16, postype, d_head, d_nneigh, d_nlist, sc.n, sc.c, sc.beta, sc.a0,
-                                                                 (const double2 *)sc.qrows, sc.wtab, (double2 *)sc.rows, sc.epair, tab);
-        MTD_LAUNCH_CHECK();
-        }
-    if (mode == QLL_AVERAGE)
-        {
-        const unsigned int rs16 = lay.row_doubles / 2;
-        k_qll_average<S4><<<blocks, QLL_THREADS, 0, s>>>(a12, o, rs16, postype, d_head, d_nneigh, d_nlist, sc.n, (const double2 *)sc.qrows, sc.wtab,
-                                                          (double2 *)sc.brows, sc.c, sc.v, sc.a0, sc.partials, tab);
-        MTD_LAUNCH_CHECK();
-        k_qll_backprop<S4><<<blocks, QLL_THREADS, 0, s>>>(a12, rs16, postype, d_head, d_nneigh, d_nlist, sc.n, sc.a0, (const double2 *)sc.qrows,
-                                                           (const double2 *)sc.brows, (double2 *)sc.rows, sc.epair, tab);
-        MTD_LAUNCH_CHECK();
-        }
-    *n_partials = blocks;
-    return MTD_SUCCESS;
-    }
+    unsigned int N;
+    const void *postype;
+    int dtype;
+    const mtd_box *box;
+    const unsigned int *head, *nneigh, *nlist;
+    double rcut, ron;
+    unsigned int lmax, type;
+    const double *ql_ref;
+    unsigned int n_global;
+    hipStream_t s;
+    int mode;
+    QllLayout lay;
+    QllOpt opt;
+    QllRamp ramp;
+    QllScratch sc;
+    unsigned int blocks;
+    };
 
-// the force pass: through LDS tiles while a table row fits one, else straight from memory
-template<typename S4, int LMAX, bool AVG, bool VIR>
-int qll_forces_impl(unsigned int N, const void *d_postype, void *d_force, const mtd_box *box, const unsigned int *d_head,
-                    const unsigned int *d_nneigh, const unsigned int *d_nlist, double rcut, double ron, unsigned int lmax, unsigned int type,
-                    const double *ql_ref, unsigned int n_global, const QllScratch &sc, const double *d_bias, double bias_host, hipStream_t s,
-                    void *d_virial, unsigned int virial_pitch)
-    {
-    QlArgs<LMAX> a;
-    int rc = fill_args<LMAX>(a, N, box, rcut, ron, lmax, type, ql_ref, n_global, 0);
-    if (rc) return rc;
-    const double *tab = ql_device_table<LMAX>(s, rc);
-    if (rc) return rc;
-    const QllLayout lay = qll_layout(lmax, ql_ref);
-    const unsigned int blocks = qll_blocks(N);
-    const S4 *postype = (const S4 *)d_postype;
-    S4 *force = (S4 *)d_force;
-    typename scalar4_traits<S4>::scalar *virial = VIR ? (typename scalar4_traits<S4>::scalar *)d_virial : nullptr;
-    const double *epair = AVG ? sc.epair : nullptr;
-    const unsigned int rs16 = lay.row_doubles / 2;
-    if (rs16 <= QLL_TILE_MAX16)
-        {
-        const unsigned int ts = rs16 | 1u;                  // odd: rows of a tile start in different banks
-        const size_t bytes = (size_t)QLL_TILE_ROWS * ts * sizeof(double2);
-        MTD_HIP_TRY(hipFuncSetAttribute((const void *)k_qll_forces_tile<S4, LMAX, AVG, VIR>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)((size_t)QLL_TILE_ROWS * (QLL_TILE_MAX16 | 1u) * sizeof(double2))));
-        k_qll_forces_tile<S4, LMAX, AVG, VIR><<<blocks, QLL_THREADS, bytes, s>>>(a, lay, postype, d_head, d_nneigh, d_nlist, sc.rows, force, d_bias,
-                                                                                 bias_host, tab, ts, epair, virial, virial_pitch);
-        }
-    else
-        k_qll_forces<S4, LMAX, AVG, VIR><<<blocks, QLL_THREADS, 0, s>>>(a, lay, postype, d_head, d_nneigh, d_nlist, sc.rows, force, d_bias, bias_host,
-                                                                        tab, epair, virial, virial_pitch);
-    MTD_LAUNCH_CHECK();
-    return MTD_SUCCESS;
-    }
-
-// what both entry points refuse before a device is touched
-int qll_validate(unsigned int n_particles, const void *d_postype, int dtype, const mtd_box *box, const unsigned int *d_head,
-                 const unsigned int *d_nneigh, double rcut, double ron, unsigned int lmax, const double *ql_ref, unsigned int n_global,
-                 const double *d_scratch)
+// Refuses, before a device is touched and in this order: the arguments themselves; the options (a switch needs c0 > 0 and p >= 1, a gate
+// 0 <= n_lo < n_hi; NaN fails every comparison); the bond count (a ramp with -1 <= d_lo < d_hi <= 1, a scalar product that is a norm: no
+// negative Ql_ref[l], and not on the averaged vectors).
+// NOT checked, deliberately: a scratch sized for fewer list entries than the list holds.  Neither pass is told the size of the scratch
+// or the length of d_nlist (the entry points keep the argument lists of the plain ones), so it cannot be known here; the caller sizes the
+// scratch with mtd_ql_local_scratch_doubles_opt(N, lmax, length of d_nlist, opt), as SteinhardtLocal::computeCV does at every step.
+int qll_prepare(QllCall &k, unsigned int n_particles, const void *d_postype, int dtype, const mtd_box *box, const unsigned int *d_head,
+                const unsigned int *d_nneigh, const unsigned int *d_nlist, double rcut, double ron, unsigned int lmax, unsigned int type,
+                const double *ql_ref, unsigned int n_global, const double *d_scratch, mtd_stream_t stream, const mtd_ql_local_options *opt,
+                const mtd_ql_local_bonds *bonds)
     {
     if (!box || !ql_ref || !d_scratch || n_global == 0) return MTD_ERR_INVALID_ARGUMENT;
     if (n_particles && (!d_postype || !d_head || !d_nneigh)) return MTD_ERR_INVALID_ARGUMENT;
@@ -1432,30 +1376,99 @@ int qll_validate(unsigned int n_particles, const void *d_postype, int dtype, con
     if (!(rcut > 0.0) || !(ron >= 0.0) || !(ron < rcut)) return MTD_ERR_INVALID_ARGUMENT;
     if (((uintptr_t)d_scratch & 15u) != 0) return MTD_ERR_INVALID_ARGUMENT;       // table rows are read 16 bytes at a time
     if (lmax > 12) return MTD_ERR_UNSUPPORTED;
+    if (opt && opt->switch_on && (!(opt->c0 > 0.0) || !std::isfinite(opt->c0) || opt->p == 0)) return MTD_ERR_INVALID_ARGUMENT;
+    if (opt && opt->gate_on && (!(opt->n_lo >= 0.0) || !(opt->n_lo < opt->n_hi) || !std::isfinite(opt->n_hi))) return MTD_ERR_INVALID_ARGUMENT;
+    QllRamp ramp = {0.0, 0.0};
+    if (qll_bonds_on(bonds))
+        {
+        if (!(bonds->d_lo >= -1.0) || !(bonds->d_lo < bonds->d_hi) || !(bonds->d_hi <= 1.0)) return MTD_ERR_INVALID_ARGUMENT;
+        for (unsigned int l = 0; l <= lmax; ++l)
+            if (!(ql_ref[l] >= 0.0)) return MTD_ERR_INVALID_ARGUMENT;
+        if (opt && opt->average) return MTD_ERR_UNSUPPORTED;
+        ramp = {bonds->d_lo, 1.0 / (bonds->d_hi - bonds->d_lo)};
+        }
+    const int mode = qll_mode(opt, bonds);
+    k = {n_particles, d_postype, dtype, box, d_head, d_nneigh, d_nlist, rcut, ron, lmax, type, ql_ref, n_global, (hipStream_t)stream, mode,
+         qll_layout(lmax, ql_ref), qll_opt(opt), ramp, qll_scratch(const_cast<double *>(d_scratch), n_particles, lmax, 0, mode),
+         qll_blocks(n_particles)};
     return MTD_SUCCESS;
     }
 
-// the options: a switch needs c0 > 0 and p >= 1, a gate 0 <= n_lo < n_hi (NaN fails every comparison).
-// NOT checked, deliberately: a scratch sized for fewer list entries than the list holds.  Neither pass is told the size of the scratch
-// or the length of d_nlist (the entry points keep the argument lists of the plain ones), so it cannot be known here; the caller sizes the
-// scratch with mtd_ql_local_scratch_doubles_opt(N, lmax, length of d_nlist, opt), as SteinhardtLocal::computeCV does at every step.
-int qll_validate_options(const mtd_ql_local_options *opt)
+template<int LMAX> int qll_args(QlArgs<LMAX> &a, const QllCall &k)
     {
-    if (!opt) return MTD_SUCCESS;
-    if (opt->switch_on && (!(opt->c0 > 0.0) || !std::isfinite(opt->c0) || opt->p == 0)) return MTD_ERR_INVALID_ARGUMENT;
-    if (opt->gate_on && (!(opt->n_lo >= 0.0) || !(opt->n_lo < opt->n_hi) || !std::isfinite(opt->n_hi))) return MTD_ERR_INVALID_ARGUMENT;
+    return fill_args<LMAX>(a, k.N, k.box, k.rcut, k.ron, k.lmax, k.type, k.ql_ref, k.n_global, 0);
+    }
+
+template<typename S4, int LMAX> int qll_accumulate_impl(const QllCall &k)
+    {
+    QlArgs<LMAX> a;
+    int rc = qll_args(a, k);
+    if (rc) return rc;
+    QlArgs<12> a12;                                              // the gather passes need the box and the window only: one instantiation
+    rc = qll_args(a12, k);
+    if (rc) return rc;
+    const double *tab = ql_device_table<LMAX>(k.s, rc);          // (the smoothing coefficients sit at the same place for every LMAX)
+    if (rc) return rc;
+    const QllScratch &sc = k.sc;
+    const S4 *postype = (const S4 *)k.postype;
+    const unsigned int rs16 = k.lay.row_doubles / 2;
+    static_assert(QLL_PLAIN == 0 && QLL_TRANSFORM == 1 && QLL_AVERAGE == 2 && QLL_BONDS == 3, "the mode is dispatched as the count mode + 1 of 4");
+    dispatch_count<4>(k.mode + 1, [&](auto m1)
+        {
+        constexpr int MODE = decltype(m1)::value - 1;
+        k_qll_accumulate<S4, LMAX, MODE><<<k.blocks, QLL_THREADS, 0, k.s>>>(a, k.lay, k.opt, postype, k.head, k.nneigh, k.nlist, sc.n, sc.c, sc.v,
+                                                                             MODE == QLL_AVERAGE || MODE == QLL_BONDS ? sc.qrows : sc.rows, sc.wtab,
+                                                                             sc.partials, tab);
+        });
+    MTD_LAUNCH_CHECK();
+    if (k.mode == QLL_BONDS)
+        {
+        k_qll_bonds<S4><<<k.blocks, QLL_THREADS, 0, k.s>>>(a12, k.opt, k.ramp, rs16, postype, k.head, k.nneigh, k.nlist, sc.n, (const double2 *)sc.qrows,
+                                                            sc.wtab, sc.epair, sc.b, sc.v, sc.beta, sc.a0, sc.partials, tab);
+        MTD_LAUNCH_CHECK();
+        k_qll_bonds_backprop<S4><<<k.blocks, QLL_THREADS, 0, k.s>>>(a12, k.ramp, rs16, postype, k.head, k.nneigh, k.nlist, sc.n, sc.c, sc.beta, sc.a0,
+                                                                     (const double2 *)sc.qrows, sc.wtab, (double2 *)sc.rows, sc.epair, tab);
+        MTD_LAUNCH_CHECK();
+        }
+    if (k.mode == QLL_AVERAGE)
+        {
+        k_qll_average<S4><<<k.blocks, QLL_THREADS, 0, k.s>>>(a12, k.opt, rs16, postype, k.head, k.nneigh, k.nlist, sc.n, (const double2 *)sc.qrows,
+                                                              sc.wtab, (double2 *)sc.brows, sc.c, sc.v, sc.a0, sc.partials, tab);
+        MTD_LAUNCH_CHECK();
+        k_qll_backprop<S4><<<k.blocks, QLL_THREADS, 0, k.s>>>(a12, rs16, postype, k.head, k.nneigh, k.nlist, sc.n, sc.a0, (const double2 *)sc.qrows,
+                                                               (const double2 *)sc.brows, (double2 *)sc.rows, sc.epair, tab);
+        MTD_LAUNCH_CHECK();
+        }
     return MTD_SUCCESS;
     }
 
-// the bond count: a ramp with -1 <= d_lo < d_hi <= 1 (NaN fails every comparison), a scalar product that is a norm (no negative
-// Ql_ref[l]), and not on the averaged vectors
-int qll_validate_bonds(const mtd_ql_local_options *opt, const mtd_ql_local_bonds *bonds, unsigned int lmax, const double *ql_ref)
+// the force pass: through LDS tiles while a table row fits one, else straight from memory
+template<typename S4, int LMAX, bool AVG, bool VIR>
+int qll_forces_impl(const QllCall &k, void *d_force, const double *d_bias, double bias_host, void *d_virial, unsigned int virial_pitch)
     {
-    if (!qll_bonds_on(bonds)) return MTD_SUCCESS;
-    if (!(bonds->d_lo >= -1.0) || !(bonds->d_lo < bonds->d_hi) || !(bonds->d_hi <= 1.0)) return MTD_ERR_INVALID_ARGUMENT;
-    for (unsigned int l = 0; l <= lmax; ++l)
-        if (!(ql_ref[l] >= 0.0)) return MTD_ERR_INVALID_ARGUMENT;
-    if (opt && opt->average) return MTD_ERR_UNSUPPORTED;
+    QlArgs<LMAX> a;
+    int rc = qll_args(a, k);
+    if (rc) return rc;
+    const double *tab = ql_device_table<LMAX>(k.s, rc);
+    if (rc) return rc;
+    const S4 *postype = (const S4 *)k.postype;
+    S4 *force = (S4 *)d_force;
+    typename scalar4_traits<S4>::scalar *virial = VIR ? (typename scalar4_traits<S4>::scalar *)d_virial : nullptr;
+    const double *epair = AVG ? k.sc.epair : nullptr;
+    const unsigned int rs16 = k.lay.row_doubles / 2;
+    if (rs16 <= QLL_TILE_MAX16)
+        {
+        const unsigned int ts = rs16 | 1u;                  // odd: rows of a tile start in different banks
+        const size_t bytes = (size_t)QLL_TILE_ROWS * ts * sizeof(double2);
+        MTD_HIP_TRY(hipFuncSetAttribute((const void *)k_qll_forces_tile<S4, LMAX, AVG, VIR>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)((size_t)QLL_TILE_ROWS * (QLL_TILE_MAX16 | 1u) * sizeof(double2))));
+        k_qll_forces_tile<S4, LMAX, AVG, VIR><<<k.blocks, QLL_THREADS, bytes, k.s>>>(a, k.lay, postype, k.head, k.nneigh, k.nlist, k.sc.rows, force,
+                                                                                     d_bias, bias_host, tab, ts, epair, virial, virial_pitch);
+        }
+    else
+        k_qll_forces<S4, LMAX, AVG, VIR><<<k.blocks, QLL_THREADS, 0, k.s>>>(a, k.lay, postype, k.head, k.nneigh, k.nlist, k.sc.rows, force, d_bias,
+                                                                            bias_host, tab, epair, virial, virial_pitch);
+    MTD_LAUNCH_CHECK();
     return MTD_SUCCESS;
     }
 
@@ -1476,7 +1489,7 @@ size_t mtd_ql_local_scratch_doubles_opt(unsigned int n_particles, unsigned int l
 size_t mtd_ql_local_scratch_doubles_bonds(unsigned int n_particles, unsigned int lmax, size_t n_list_entries, const mtd_ql_local_options *opt,
                                           const mtd_ql_local_bonds *bonds)
     {
-    return qll_sizes(n_particles, lmax, n_list_entries, qll_mode(opt, bonds)).total;
+    return qll_scratch(nullptr, n_particles, lmax, n_list_entries, qll_mode(opt, bonds)).total;
     }
 
 int mtd_ql_local_accumulate(unsigned int n_particles, const void *d_postype, int dtype, const mtd_box *box, const unsigned int *d_head_list,
@@ -1505,31 +1518,21 @@ int mtd_ql_local_accumulate_bonds(unsigned int n_particles, const void *d_postyp
                                   const mtd_ql_local_options *opt, const double **d_v, const mtd_ql_local_bonds *bonds, const double **d_b)
     {
     if (!d_partials || !n_partials) return MTD_ERR_INVALID_ARGUMENT;
-    int rc = qll_validate(n_particles, d_postype, dtype, box, d_head_list, d_n_neigh, rcut, ron, lmax, Ql_ref, n_global, d_scratch);
+    QllCall k;
+    int rc = qll_prepare(k, n_particles, d_postype, dtype, box, d_head_list, d_n_neigh, d_nlist, rcut, ron, lmax, type, Ql_ref, n_global, d_scratch,
+                         stream, opt, bonds);
     if (rc) return rc;
-    rc = qll_validate_options(opt);
-    if (rc) return rc;
-    rc = qll_validate_bonds(opt, bonds, lmax, Ql_ref);
-    if (rc) return rc;
-    const int mode = qll_mode(opt, bonds);
-    const QllScratch sc = qll_scratch(d_scratch, n_particles, lmax, mode);
-    hipStream_t s = (hipStream_t)stream;
-    unsigned int n = 0;
     rc = dispatch_lmax(lmax, [&](auto lm)
         {
-        return dispatch_s4(dtype, [&](auto t)
-            {
-            return qll_accumulate_impl<typename decltype(t)::type, decltype(lm)::value>(n_particles, d_postype, box, d_head_list, d_n_neigh, d_nlist, rcut,
-                                                                                        ron, lmax, type, Ql_ref, n_global, sc, opt, bonds, &n, s);
-            });
+        return dispatch_s4(dtype, [&](auto t) { return qll_accumulate_impl<typename decltype(t)::type, decltype(lm)::value>(k); });
         });
     if (rc) return rc;
-    *d_partials = sc.partials;
-    *n_partials = n;
-    if (d_c) *d_c = sc.c;
-    if (d_n) *d_n = sc.n;
-    if (d_v) *d_v = sc.v;
-    if (d_b) *d_b = mode == QLL_BONDS ? sc.b : nullptr;
+    *d_partials = k.sc.partials;
+    *n_partials = k.blocks;
+    if (d_c) *d_c = k.sc.c;
+    if (d_n) *d_n = k.sc.n;
+    if (d_v) *d_v = k.sc.v;
+    if (d_b) *d_b = k.mode == QLL_BONDS ? k.sc.b : nullptr;
     return MTD_SUCCESS;
     }
 
@@ -1567,29 +1570,23 @@ int mtd_ql_local_forces_bonds(unsigned int n_particles, const void *d_postype, v
                               const double *d_bias, double bias_host, mtd_stream_t stream, const mtd_ql_local_options *opt, void *d_virial,
                               unsigned int virial_pitch, const mtd_ql_local_bonds *bonds)
     {
-    int rc = qll_validate(n_particles, d_postype, dtype, box, d_head_list, d_n_neigh, rcut, ron, lmax, Ql_ref, n_global, d_scratch);
-    if (rc) return rc;
-    rc = qll_validate_options(opt);
-    if (rc) return rc;
-    rc = qll_validate_bonds(opt, bonds, lmax, Ql_ref);
+    QllCall k;
+    const int rc = qll_prepare(k, n_particles, d_postype, dtype, box, d_head_list, d_n_neigh, d_nlist, rcut, ron, lmax, type, Ql_ref, n_global,
+                               d_scratch, stream, opt, bonds);
     if (rc) return rc;
     if (n_particles && !d_force) return MTD_ERR_INVALID_ARGUMENT;
     if (d_virial && virial_pitch < n_particles) return MTD_ERR_INVALID_ARGUMENT;
     if (n_particles == 0) return MTD_SUCCESS;
-    const int mode = qll_mode(opt, bonds);
-    const QllScratch sc = qll_scratch(const_cast<double *>(d_scratch), n_particles, lmax, mode);
-    hipStream_t s = (hipStream_t)stream;
     return dispatch_lmax(lmax, [&](auto lm)
         {
         return dispatch_s4(dtype, [&](auto t)
             {
-            return dispatch_bool(mode == QLL_AVERAGE || mode == QLL_BONDS, [&](auto avg)
+            return dispatch_bool(k.mode == QLL_AVERAGE || k.mode == QLL_BONDS, [&](auto avg)
                 {
                 return dispatch_bool(d_virial != nullptr, [&](auto vir)
                     {
                     return qll_forces_impl<typename decltype(t)::type, decltype(lm)::value, decltype(avg)::value, decltype(vir)::value>(
-                        n_particles, d_postype, d_force, box, d_head_list, d_n_neigh, d_nlist, rcut, ron, lmax, type, Ql_ref, n_global, sc, d_bias,
-                        bias_host, s, d_virial, virial_pitch);
+                        k, d_force, d_bias, bias_host, d_virial, virial_pitch);
                     });
                 });
             });
