@@ -749,6 +749,58 @@ int mtd_ql_local_forces_bonds(unsigned int n_particles, const void *d_postype, v
                               unsigned int virial_pitch, const mtd_ql_local_bonds *bonds);
 
 /* ================================================================================================
+ * Pair entropy (cv.pair_entropy) — no reference counterpart.  The two-body excess entropy S2 from a Gaussian-smoothed g(r) (Piaggi,
+ * Valsson and Parrinello, PRL 119, 015701; PLUMED's PAIRENTROPY): a bias variable for nucleation that needs no knowledge of the target
+ * structure.  Parameters r_max > 0, sigma_r > 0, n_bins = B (1 .. 256) and a particle type t.
+ *     Delta = r_max / B,  r_b = (b + 1/2) Delta (b = 0 .. B-1),  r_on = r_max + 3 sigma_r,  r_cut = r_max + 4 sigma_r,
+ *     w = ceil(6 sigma_r / Delta),  K(x) = exp(-x^2 / 2 sigma_r^2) / (sqrt(2 pi) sigma_r),  g_min = 1e-10
+ * Entries (i, j) of a FULL list take part when i and j are both of type t, j != i and r = |minImage(r_i - r_j)| <= r_cut.  The central
+ * particles are the n_particles local ones; neighbour indices may address ghost particles stored behind them, as in
+ * mtd_ql_accumulate_local.  f(r) is the cosine window of the Steinhardt passes between r_on and r_cut (SteinhardtQl.cc:36-60); an entry
+ * counts in bin b iff |b - b_c| <= w and 0 <= b < B, with b_c = floor(r (B / r_max)) in fp64.
+ *     H_b = sum_entries f(r) K(r_b - r)             N_t = central particles of type t (slot B of the sums: the all-reduce makes it global)
+ *     rho = N_t / V,  V = Lx Ly Lz                  g_b = H_b / (4 pi N_t rho r_b^2)
+ *     phi_b = g_b ln g_b - g_b + 1 where g_b >= g_min, else 1        (PLUMED's convention)
+ *     S = -2 pi rho Delta sum_b r_b^2 phi_b         in units of k_B; N_t == 0: S = 0 and no forces
+ * Gradient: W_b = dS/dH_b = -Delta ln g_b / (2 N_t) where g_b >= g_min, else 0; an entry with pair vector d = r_i - r_j has
+ *     u = sum_{b in window} W_b [ f'(r) K_b + f(r) K_b (r_b - r) / sigma_r^2 ]
+ * and gives +u d / r to dS/dr_i and -u d / r to dS/dr_j.  As a gather over row k of a full list: dS/dr_k = 2 sum_{j in row k} u_kj d_kj / r_kj
+ * (the mirror entry (j, k) gives the same amount, whether j is local or a ghost: no reaction force on ghosts).  F = -bias dS/dr.
+ * Virial (only with a virial pointer): sum_k virial_k = -bias dS/d eps under an affine strain of positions and box.  With
+ * G_kj = 2 u_kj d_kj / r_kj, virial_k[ab] = -bias 1/2 sum_{j in row k} d_kj,a G_kj,b; and because rho and the normalisation of g depend
+ * on V, dS/d eps_ab|explicit = -(S + 2 pi rho Delta sum_{g_b >= g_min} r_b^2 g_b ln g_b) delta_ab, spread evenly: every central particle
+ * of type t gets -bias (that value) / N_t on xx, yy, zz.  Layout and scalar type of mtd_ql_forces_virial (virial[c * pitch + k], six
+ * components); every row [0, n_particles) is written at every call.
+ * A step is _accumulate, (mtd_comm_allreduce_small of *d_sums in a domain-decomposed run), _finalize, _forces, with the same r_max,
+ * sigma_r, n_bins, type and scratch.  Sums are fixed-point integers inside a block and fixed-order sums elsewhere: two identical calls
+ * give identical bits (csrc/pair_entropy.hip has the rounding bound).  Arguments are checked before a device is touched:
+ * MTD_ERR_INVALID_ARGUMENT for null pointers, a non-finite or non-positive r_max or sigma_r, n_bins == 0, an unknown dtype, a d_scratch
+ * that is not 16-byte aligned or a virial pitch below n_particles; MTD_ERR_UNSUPPORTED for n_bins > 256.
+ * ============================================================================================== */
+
+/* device doubles the calls of a step share (sums, value, g_b, W_b, block sums) */
+size_t mtd_pe_scratch_doubles(unsigned int n_bins);
+
+/* This rank's sums: on return *d_sums points at *n_sums = n_bins + 1 doubles inside d_scratch, H_0 .. H_{B-1} and N_t, ready for
+ * mtd_comm_allreduce_small. */
+int mtd_pe_accumulate(unsigned int n_particles, const void *d_postype, int dtype, const mtd_box *box, const unsigned int *d_head_list,
+                      const unsigned int *d_n_neigh, const unsigned int *d_nlist, double r_max, double sigma_r, unsigned int n_bins,
+                      unsigned int type, double *d_scratch, double **d_sums, unsigned int *n_sums, mtd_stream_t stream);
+
+/* The (reduced) sums -> g_b, S, W_b and the explicit virial term.  *d_value points at S, one device double (consume with
+ * mtd_metad_set_cv_source(engine, slot, *d_value, 1, 1, 0, 1.0, 0.0)), *d_g (d_g may be NULL) at g_b[n_bins], both inside d_scratch. */
+int mtd_pe_finalize(const mtd_box *box, double r_max, double sigma_r, unsigned int n_bins, double *d_scratch, const double **d_value,
+                    const double **d_g, mtd_stream_t stream);
+
+/* Writes d_force[0..n_particles) (w component 0; 0 for particles of another type) with the W_b the last mtd_pe_finalize left in
+ * d_scratch; bias = *d_bias when d_bias != NULL, else bias_host.  d_virial == NULL: no virial, the kernel without the switch; the force
+ * array is the same, bit for bit, either way.  No atomics: bitwise reproducible. */
+int mtd_pe_forces(unsigned int n_particles, const void *d_postype, void *d_force, int dtype, const mtd_box *box, const unsigned int *d_head_list,
+                  const unsigned int *d_n_neigh, const unsigned int *d_nlist, double r_max, double sigma_r, unsigned int n_bins, unsigned int type,
+                  const double *d_scratch, const double *d_bias, double bias_host, mtd_stream_t stream, void *d_virial,
+                  unsigned int virial_pitch);
+
+/* ================================================================================================
  * Neighbour list of the stand-alone path (cell list, built on the device)
  * no reference counterpart: HOOMD's md::NeighborList is HOOMD core.  Produces the three arrays SteinhardtQl.cc:80-85 reads, in
  * HOOMD's layout: the neighbours of particle i are d_nlist[d_head_list[i] .. d_head_list[i] + d_n_neigh[i]).

@@ -955,6 +955,105 @@ double SteinhardtLocal::getLogValue(const std::string &quantity, unsigned int ti
     }
 
 // ------------------------------------------------------------------------------------------------
+// PairEntropy
+// ------------------------------------------------------------------------------------------------
+
+PairEntropy::PairEntropy(std::shared_ptr<SystemDefinition> sysdef, double r_max, double sigma_r, unsigned int n_bins,
+                         std::shared_ptr<NeighborList> nlist, unsigned int type, const std::string &log_suffix)
+    : CollectiveVariable(sysdef, "pair_entropy" + log_suffix), m_r_max(r_max), m_sigma_r(sigma_r), m_n_bins(n_bins), m_nlist(nlist), m_type(type),
+      m_cv_last_updated(0), m_have_computed(false), m_d_value(nullptr), m_d_g(nullptr)
+    {
+    if (!nlist) throw std::runtime_error("cv.pair_entropy: a neighbour list is required");
+    if (!(r_max > 0.0) || !std::isfinite(r_max) || !(sigma_r > 0.0) || !std::isfinite(sigma_r))
+        throw std::runtime_error("cv.pair_entropy: r_max > 0 and sigma_r > 0 are required");
+    if (n_bins == 0 || n_bins > 256) throw std::runtime_error("cv.pair_entropy: 1 <= n_bins <= 256 in this build");
+    m_scratch.resize(sizeof(double) * mtd_pe_scratch_doubles(n_bins));
+    }
+
+void PairEntropy::computeCV(unsigned int timestep)
+    {
+    ProfRange prof_range("CV");
+    if (m_cv_last_updated == timestep && m_have_computed) return;
+    // the force pass gathers both roles of a particle from its own row
+    if (m_nlist->getStorageMode() == NeighborList::half)
+        throw std::runtime_error("cv.pair_entropy: a full neighbour list is required (the force pass gathers both roles of a particle "
+                                 "from its own row)");
+    if (m_nlist->isDeviceBuild() && m_nlist->getRCut() < getRCut())
+        throw std::runtime_error("cv.pair_entropy: the neighbour list must reach r_max + 4 sigma_r");
+    m_nlist->compute(timestep);
+    const mtd_box box = m_pdata->getBox().toMtd();
+    hipStream_t s = m_exec_conf->getStream();
+    double *d_sums = nullptr;
+    unsigned int n_sums = 0;
+    mtd_check(mtd_pe_accumulate(m_pdata->getN(), m_pdata->positionsPtr(), m_pdata->getDtype(), &box, (const unsigned int *)m_nlist->getHeadList().data(),
+                                (const unsigned int *)m_nlist->getNNeighArray().data(), (const unsigned int *)m_nlist->getNListArray().data(), m_r_max,
+                                m_sigma_r, m_n_bins, m_type, (double *)m_scratch.data(), &d_sums, &n_sums, s),
+              "mtd_pe_accumulate");
+    // H_b and N_t over the ranks: the central particles of a rank are its local ones, their neighbours may be ghosts
+    if (distributed()) m_exec_conf->allreduceSmall(d_sums, n_sums, s);
+    mtd_check(mtd_pe_finalize(&box, m_r_max, m_sigma_r, m_n_bins, (double *)m_scratch.data(), &m_d_value, &m_d_g, s), "mtd_pe_finalize");
+    m_have_computed = true;
+    m_cv_last_updated = timestep;
+    }
+
+void PairEntropy::enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot)
+    {
+    computeCV(timestep);
+    mtd_check(mtd_metad_set_cv_source(engine, slot, m_d_value, 1, 1, 0, 1.0, 0.0), "mtd_metad_set_cv_source");
+    }
+
+double PairEntropy::getCurrentValue(unsigned int timestep)
+    {
+    computeCV(timestep);
+    m_exec_conf->sync();
+    double value = 0.0;
+    hip_check(hipMemcpy(&value, m_d_value, sizeof(double), hipMemcpyDeviceToHost), "cv read-back");
+    return value;
+    }
+
+std::vector<double> PairEntropy::getGr(unsigned int timestep)
+    {
+    computeCV(timestep);
+    m_exec_conf->sync();
+    std::vector<double> out(m_n_bins);
+    hip_check(hipMemcpy(out.data(), m_d_g, sizeof(double) * out.size(), hipMemcpyDeviceToHost), "g(r) read-back");
+    return out;
+    }
+
+void PairEntropy::computeBiasForces(unsigned int timestep)
+    {
+    ProfRange prof_range("Force");
+    if (!m_have_computed || m_cv_last_updated != timestep) computeCV(timestep);      // the W_b of THIS step's positions
+    m_nlist->compute(timestep);
+    const mtd_box box = m_pdata->getBox().toMtd();
+    // constant pressure: the per-particle virial of the bias force beside it (include/mtd_abi.h).  Without the flag the plain call; a
+    // virial array somebody has allocated earlier is zeroed then, so that a stale virial is never read (as SteinhardtQl)
+    void *virial = nullptr;
+    if (m_pdata->getPressureFlag())
+        virial = getVirialArray().data();
+    else if (m_virial.bytes())
+        hip_check(hipMemsetAsync(m_virial.data(), 0, m_virial.bytes(), m_exec_conf->getStream()), "virial reset");
+    mtd_check(mtd_pe_forces(m_pdata->getN(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &box,
+                            (const unsigned int *)m_nlist->getHeadList().data(), (const unsigned int *)m_nlist->getNNeighArray().data(),
+                            (const unsigned int *)m_nlist->getNListArray().data(), m_r_max, m_sigma_r, m_n_bins, m_type,
+                            (const double *)m_scratch.data(), m_bias_device, m_bias, m_exec_conf->getStream(), virial, getVirialPitch()),
+              "mtd_pe_forces");
+    }
+
+std::vector<std::string> PairEntropy::getProvidedLogQuantities()
+    {
+    auto list = CollectiveVariable::getProvidedLogQuantities();
+    list.push_back("cv_" + m_cv_name);
+    return list;
+    }
+
+double PairEntropy::getLogValue(const std::string &quantity, unsigned int timestep)
+    {
+    if (quantity == "cv_" + m_cv_name) return getCurrentValue(timestep);
+    return CollectiveVariable::getLogValue(quantity, timestep);
+    }
+
+// ------------------------------------------------------------------------------------------------
 // AspectRatio, Density
 // ------------------------------------------------------------------------------------------------
 

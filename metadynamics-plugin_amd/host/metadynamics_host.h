@@ -360,6 +360,34 @@ class SteinhardtLocal : public CollectiveVariable
         mtd_ql_local_bonds m_bonds;
     };
 
+//! Pair entropy (no reference counterpart; include/mtd_abi.h "Pair entropy"): S2 from a Gaussian-smoothed g(r) of one particle type.
+//! Works domain-decomposed: the only exchange is one allreduceSmall of the n_bins + 1 sums.
+class PairEntropy : public CollectiveVariable
+    {
+    public:
+        PairEntropy(std::shared_ptr<SystemDefinition> sysdef, double r_max, double sigma_r, unsigned int n_bins,
+                    std::shared_ptr<NeighborList> nlist, unsigned int type, const std::string &log_suffix = "");
+        double getCurrentValue(unsigned int timestep) override;
+        //! device-resident: the value in the scratch becomes the engine's source of this variable, no host synchronisation
+        void enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot) override;
+        void computeBiasForces(unsigned int timestep) override;
+        std::vector<std::string> getProvidedLogQuantities() override;
+        double getLogValue(const std::string &quantity, unsigned int timestep) override;
+        std::vector<double> getGr(unsigned int timestep);              //!< g_b of the n_bins bins (r_b = (b + 1/2) r_max / n_bins)
+        double getRCut() const { return m_r_max + 4.0 * m_sigma_r; }   //!< what the neighbour list must reach
+
+    private:
+        void computeCV(unsigned int timestep);
+        double m_r_max, m_sigma_r;
+        unsigned int m_n_bins;
+        std::shared_ptr<NeighborList> m_nlist;
+        unsigned int m_type;
+        unsigned int m_cv_last_updated;
+        bool m_have_computed;
+        DeviceBuffer m_scratch;
+        const double *m_d_value, *m_d_g;
+    };
+
 //! AspectRatio.h / AspectRatio.cc:5-130 — box-shape CV, external virial only
 class AspectRatio : public CollectiveVariable
     {

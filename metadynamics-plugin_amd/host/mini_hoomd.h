@@ -482,6 +482,8 @@ class NeighborList
             m_force_rebuild = true;
             }
         bool isDeviceBuild() const { return m_device_build; }
+        //! the cut-off of a device build (pairs up to r_cut are listed whenever the list is used); 0 for a list handed in, whose cut-off is not known here
+        double getRCut() const { return m_device_build ? m_r_cut : 0.0; }
         //! the next compute() rebuilds whatever the displacement check would say
         void forceRebuild() { m_force_rebuild = true; }
         //! device builds so far (the first one included)

@@ -281,6 +281,7 @@ PYBIND11_MODULE(_metadynamics, m)
         })
         .def("setDeviceBuild", &NeighborList::setDeviceBuild, py::arg("r_cut"), py::arg("r_buff"), py::arg("check_period") = 1, py::arg("type") = -1)
         .def("isDeviceBuild", &NeighborList::isDeviceBuild)
+        .def("getRCut", &NeighborList::getRCut)
         .def("forceRebuild", &NeighborList::forceRebuild)
         .def("getNumRebuilds", &NeighborList::getNumRebuilds)
         .def("getNumEntries", &NeighborList::getNumEntries)
@@ -347,6 +348,16 @@ PYBIND11_MODULE(_metadynamics, m)
         .def("clearBonds", &SteinhardtLocal::clearBonds)
         .def("getBondCounts", [](SteinhardtLocal &cv, unsigned int timestep) {
             const std::vector<double> v = cv.getBondCounts(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        });
+
+    // no reference counterpart: the pair entropy from a smoothed g(r)
+    py::class_<PairEntropy, CollectiveVariable, std::shared_ptr<PairEntropy>>(m, "PairEntropy")
+        .def(py::init<std::shared_ptr<SystemDefinition>, double, double, unsigned int, std::shared_ptr<NeighborList>, unsigned int,
+                      const std::string &>())
+        .def("getRCut", &PairEntropy::getRCut)
+        .def("getGr", [](PairEntropy &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getGr(timestep);
             return py::array_t<double>((ssize_t)v.size(), v.data());
         });
 

@@ -253,6 +253,12 @@ _SIGNATURES = {
     "mtd_ql_local_forces_bonds": (C.c_int, [C.c_uint, _vp, _vp, C.c_int, C.POINTER(Box), _vp, _vp, _vp, C.c_double, C.c_double, C.c_uint, C.c_uint,
                                              _dp, C.c_uint, _vp, _vp, C.c_double, _vp, C.POINTER(QlLocalOptions), _vp, C.c_uint,
                                              C.POINTER(QlLocalBonds)]),
+    "mtd_pe_scratch_doubles": (C.c_size_t, [C.c_uint]),
+    "mtd_pe_accumulate": (C.c_int, [C.c_uint, _vp, C.c_int, C.POINTER(Box), _vp, _vp, _vp, C.c_double, C.c_double, C.c_uint, C.c_uint, _vp,
+                                     C.POINTER(_vp), _up, _vp]),
+    "mtd_pe_finalize": (C.c_int, [C.POINTER(Box), C.c_double, C.c_double, C.c_uint, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    "mtd_pe_forces": (C.c_int, [C.c_uint, _vp, _vp, C.c_int, C.POINTER(Box), _vp, _vp, _vp, C.c_double, C.c_double, C.c_uint, C.c_uint, _vp, _vp,
+                                 C.c_double, _vp, _vp, C.c_uint]),
     "mtd_nlist_create": (C.c_int, [C.POINTER(_vp)]),
     "mtd_nlist_destroy": (C.c_int, [_vp]),
     "mtd_nlist_build": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp, C.c_int, C.POINTER(Box), C.c_double, C.c_int, C.c_int,

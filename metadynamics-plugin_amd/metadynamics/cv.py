@@ -342,6 +342,63 @@ class steinhardt_local(_collective_variable, metaclass=_local_options):
             raise RuntimeError("Error creating collective variable.")
 
 
+class pair_entropy(_collective_variable):
+    """this build (no reference counterpart; include/mtd_abi.h "Pair entropy"): the two-body excess entropy of the particles of one type
+    from a Gaussian-smoothed radial distribution function (Piaggi, Valsson and Parrinello, PRL 119, 015701; PLUMED's PAIRENTROPY),
+    CV = -2 pi rho int_0^r_max [g ln g - g + 1] r^2 dr in units of k_B, on ``n_bins`` midpoints with Gaussians of width ``sigma_r``.
+    It needs no knowledge of the target structure and is normally biased together with ``cv.potential_energy`` on a 2-d grid.
+    Needs a full list that reaches ``r_max + 4 * sigma_r`` (``get_rcut``); works in domain-decomposed runs; n_bins <= 256."""
+
+    def __init__(self, r_max, sigma_r, n_bins, nlist, type, name=None, sigma=1.0):
+        suffix = ""
+        if name is not None:
+            suffix = "_" + name
+        _collective_variable.__init__(self, sigma, name)
+        try:
+            type_list = context.current.type_names
+            r_max, sigma_r = float(r_max), float(sigma_r)
+            if type not in type_list or int(n_bins) != n_bins or not 1 <= int(n_bins) <= 256 or not 0.0 < r_max < float("inf") \
+                    or not 0.0 < sigma_r < float("inf") or float(nlist.r_cut) < r_max + 4.0 * sigma_r:
+                raise ValueError
+            self.type = type
+            self.nlist = nlist
+            self.r_max, self.sigma_r, self.n_bins = r_max, sigma_r, int(n_bins)
+            self.r_cut = r_max + 4.0 * sigma_r
+            self.nlist.cpp_nlist.setStorageMode(_metadynamics.NeighborList.storageMode.full)
+            self.cpp_force = _metadynamics.PairEntropy(context.current.system_definition, r_max, sigma_r, int(n_bins), nlist.cpp_nlist,
+                                                       type_list.index(type), suffix)
+        except (TypeError, ValueError, AttributeError, RuntimeError):
+            context.current.forces.remove(self)                      # refused: the run must not find a half-made variable
+            raise RuntimeError("Error creating collective variable.")
+        if getattr(nlist, "device", False):
+            nlist._attach(type_list.index(type))      # a device-built list only needs the pairs of this CV's type
+
+    def get_rcut(self):
+        """the cut-off this CV asks of the neighbour list, by type pair — only (type, type) interacts, up to r_max + 4 sigma_r"""
+        names = context.current.type_names
+        return {(a, b): (self.r_cut if a == b == self.type else -1.0) for i, a in enumerate(names) for b in names[i:]}
+
+    def get_gr(self):
+        """(r_b, g_b): the bin midpoints and the smoothed radial distribution function of the current time step"""
+        import numpy as np
+        r_b = (np.arange(self.n_bins) + 0.5) * (self.r_max / self.n_bins)
+        return r_b, np.asarray(self.cpp_force.getGr(context.current.system.getCurrentTimeStep()))
+
+    def get_virial(self, per_particle=False):
+        """the virial of the bias force the last step wrote (include/mtd_abi.h, mtd_pe_forces): the six sums xx, xy, xz, yy, yz, zz as
+        float64, or with ``per_particle=True`` the (6, N) array: half of every pair at each of its ends, and the explicit volume term
+        spread evenly over the particles of the type.  The sums are -bias * dS/d(strain); in a domain-decomposed run every rank holds the
+        rows of its local particles.  It is formed only while the pressure flag of the particle data is set; without the flag this
+        raises."""
+        pdata = context.current.system_definition.getParticleData()
+        if not pdata.getPressureFlag():
+            raise RuntimeError("cv.pair_entropy: the virial is computed only while the pressure flag is set")
+        import numpy as np
+        n = pdata.getN()
+        v = np.asarray(self.cpp_force.getVirial(), dtype=np.float64)[:, :n]
+        return v.copy() if per_particle else v.sum(axis=1)
+
+
 class nlist_cell(object):
     """Stand-in for ``hoomd.md.nlist.cell``: HOOMD's NeighborList is not part of the plugin.
 
