@@ -163,9 +163,8 @@ template<> struct ff_groups<double4, 1, false> { static constexpr int value = 2;
 
 // ORTHO: the B of `a` is diagonal (LamKArgs::ortho)
 template<typename S4, int NCV, bool FAST, int GROUPS, bool COMM, bool ORTHO>
-__global__ __launch_bounds__(FF_THREADS, 4) void k_fused_force(const LamKArgs a, const S4 *__restrict__ postype, const ForcePtrs out,
-                                                            const unsigned int N, const double two_over_n, const MetadCfg c,
-                                                            const int deposit, const unsigned int n_grid_blocks, const CommK ck)
+__global__ __launch_bounds__(FF_THREADS, 4) void k_fused_force(const FusedEntry e, const LamKArgs a, const ForcePtrs out,
+                                                            const double two_over_n, const MetadCfg c, const int deposit, const CommK ck)
     {
     __shared__ ChainResult s_chain;
     __shared__ float s_wcoef[MTD_MAX_CV * MTD_MAX_TYPES];
@@ -174,9 +173,17 @@ __global__ __launch_bounds__(FF_THREADS, 4) void k_fused_force(const LamKArgs a,
 
     const int wave = threadIdx.x >> 6;
     const int lane = threadIdx.x & 63;
+    // The entry block, read once and ahead of the role branch: ONE scalar round trip in front of wave 0's table and chain loads
+    // and of the streaming waves' first particles (they were two, five and seven dependent trips of ~0.14 us).  The grid blocks
+    // keep the lowest block indices (force blocks first, measured: the step +0.7 us, the chain of a force block 3.5 -> 4.2 us —
+    // profiles/r17).
+    const unsigned int n_grid_blocks = fused_entry_read(e);        // (= e.n_passenger_blocks)
+    const unsigned int n_blocks = e.n_particle_blocks;
+    const S4 *__restrict__ postype = (const S4 *)e.postype;
+    const unsigned int N = e.N;
+    const unsigned int n_modes = e.n_modes;
     const bool grid_block = blockIdx.x < n_grid_blocks;
     const unsigned int block_id = blockIdx.x - n_grid_blocks;
-    const unsigned int n_blocks = gridDim.x - n_grid_blocks;
     const unsigned int stride = n_blocks * FF_STREAM_THREADS;
     const unsigned int first = block_id * FF_STREAM_THREADS + (wave - 1) * MTD_WAVE + lane;
     const unsigned int first1 = first + FF_U * stride;
@@ -192,6 +199,7 @@ __global__ __launch_bounds__(FF_THREADS, 4) void k_fused_force(const LamKArgs a,
     // requests, the streaming waves start 1.4 us late — both measured.)
     constexpr int NCH = CHAIN_MAX_CV;                  // (a mixed set's grid has more variables than this launch has lamellar CVs)
     ChainPre<NCH> pre;
+    int pre_meta = 0;                                  // the patch's validity flag and origin, still in flight (chain_preload_resolve)
     constexpr bool early = !COMM;                      // (sharded step: the sums come out of the mailbox, the chain polls for them)
     float4 th = make_float4(0.f, 0.f, 0.f, 0.f), tq = th;
     float tc = 0.0f;
@@ -199,20 +207,19 @@ __global__ __launch_bounds__(FF_THREADS, 4) void k_fused_force(const LamKArgs a,
         {
         if (!grid_block)
             {
-            // first in the queue: the mode tables and this lane's mode coefficient (for the weights formed right behind the chain)
-            if (lane < (int)a.n_modes)
-                {
-                th = a.h[lane];
-                tq = a.q[lane];
-                }
-            if (lane < NCV * MTD_MAX_TYPES) tc = a.coeff[lane / MTD_MAX_TYPES][lane % MTD_MAX_TYPES];
+            // first in the queue: the mode tables and this lane's mode coefficient (for the weights formed right behind the chain),
+            // unconditional from clamped indices like stage_cv_tables_request: nothing here waits for a count
+            static_assert(MTD_MAX_MODES >= MTD_WAVE && MTD_MAX_CV * MTD_MAX_TYPES >= MTD_WAVE, "a lane is a valid index");
+            th = a.h[lane];
+            tq = a.q[lane];
+            tc = (&a.coeff[0][0])[lane];
             }
         // (asking here for one field of every 64-byte line of the grid's configuration, so that the chain finds them in the scalar
         // cache, measured 0.15 us SLOWER per step: the chain's stalls are not scalar-cache misses)
         if (early)
-            chain_preload<NCH>(c, pre);
+            pre_meta = chain_preload<NCH>(e, pre);
         else
-            chain_preload<NCH, false>(c, pre);         // sharded step: the grid patch alone
+            pre_meta = chain_preload<NCH, false>(e, pre);      // sharded step: the grid patch alone
         }
     // the streaming waves ask for their particles now: the loads need no table, and the barrier below does not wait for them
     // (the first group only: the registers of both groups, live across the barrier beside the chain's preloaded sums — the
@@ -223,7 +230,7 @@ __global__ __launch_bounds__(FF_THREADS, 4) void k_fused_force(const LamKArgs a,
         {
         if (wave == 0)
             {
-            if (lane < (int)a.n_modes)
+            if (lane < (int)n_modes)
                 {
                 s_mt.h[lane] = th;
                 s_mt.q[lane] = tq;
@@ -236,6 +243,7 @@ __global__ __launch_bounds__(FF_THREADS, 4) void k_fused_force(const LamKArgs a,
     if (wave == 0)
         {
         ChainResult r;
+        chain_preload_resolve<NCH>(pre_meta, pre);
         if constexpr (early)
             {
             double vi[3];
@@ -290,21 +298,27 @@ __global__ __launch_bounds__(FF_THREADS, 4) void k_fused_force(const LamKArgs a,
 
 // General form (any n_cv the grid engine supports): block-cooperative prologue, then the force pass.
 template<typename S4, bool FAST>
-__global__ __launch_bounds__(FF_THREADS) void k_fused_force_general(const LamKArgs a, const S4 *__restrict__ postype, const ForcePtrs out,
-                                                            const unsigned int N, const double two_over_n, const MetadCfg c,
-                                                            const int deposit, const unsigned int n_grid_blocks)
+__global__ __launch_bounds__(FF_THREADS) void k_fused_force_general(const FusedEntry e, const LamKArgs a, const ForcePtrs out,
+                                                            const double two_over_n, const MetadCfg c, const int deposit)
     {
     __shared__ EvalShared sh;
     __shared__ float s_wcoef[MTD_MAX_CV * MTD_MAX_TYPES];
     __shared__ double s_red[16];
     __shared__ ModeTables s_mt;
 
+    // grid blocks first, the force blocks behind them, as in k_fused_force
+    const unsigned int n_grid_blocks = fused_entry_read_head(e);   // (= e.n_passenger_blocks)
+    const unsigned int n_blocks = e.n_particle_blocks;
+    const S4 *__restrict__ postype = (const S4 *)e.postype;
+    const unsigned int N = e.N;
+    const bool grid_block = blockIdx.x < n_grid_blocks;
+
     load_modes(a, s_mt, true);
     reduce_cv_sources(c, sh.cv, s_red);             // replaces getCurrentValue's D2H + host sum (.cc:323-327)
     __syncthreads();
     evaluate_bias(c, sh, deposit != 0, true);
 
-    if (blockIdx.x < n_grid_blocks)
+    if (grid_block)
         {
         // ---- first grid pass of a deposit step: updateGrid (:1002-1047), updateHistogram (:1092-1119),
         //      updateSigmaGrid (:1122-1155), first loop of updateReweightedEstimator (:1070-1075)
@@ -360,11 +374,10 @@ __global__ __launch_bounds__(FF_THREADS) void k_fused_force_general(const LamKAr
             if (sh.oob[0]) c.st->n_oob += (deposit && c.mode == MTD_MODE_WELL_TEMPERED) ? 2 : 1;
             }
         }
-    if (blockIdx.x < n_grid_blocks) return;
+    if (grid_block) return;
 
     // ---- force blocks
     const unsigned int block_id = blockIdx.x - n_grid_blocks;
-    const unsigned int n_blocks = gridDim.x - n_grid_blocks;
     for (unsigned int i = threadIdx.x; i < MTD_MAX_CV * MTD_MAX_TYPES; i += blockDim.x)
         {
         const unsigned int cv = i / MTD_MAX_TYPES;
@@ -569,11 +582,12 @@ int mtd_fused_force_pass_slots(mtd_metad *m, const mtd_lamellar_set *set, const 
                     dispatch_bool(k.ortho != 0, [&](auto ortho_c)
                         {
                         const auto kernel = k_fused_force<S4, NCV, FAST, G, decltype(comm_c)::value, decltype(ortho_c)::value>;
+                        const FusedEntry e = fused_entry(m->cfg, d_postype, n_particles, fblocks, n_grid, k.n_modes, k.n_cv);
                         if (timed)
-                            hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(FF_THREADS), 0, s, ev_start, ev_stop, 0, k, (const S4 *)d_postype, out,
-                                                  n_particles, two_over_n, m->cfg, dep, n_grid, ck);
+                            hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(FF_THREADS), 0, s, ev_start, ev_stop, 0, e, k, out, two_over_n,
+                                                  m->cfg, dep, ck);
                         else
-                            kernel<<<grid, FF_THREADS, 0, s>>>(k, (const S4 *)d_postype, out, n_particles, two_over_n, m->cfg, dep, n_grid, ck);
+                            kernel<<<grid, FF_THREADS, 0, s>>>(e, k, out, two_over_n, m->cfg, dep, ck);
                         });
                     });
                 });
@@ -587,8 +601,8 @@ int mtd_fused_force_pass_slots(mtd_metad *m, const mtd_lamellar_set *set, const 
         dispatch_s4_fast(dtype, fast, [&](auto s4, auto fast_c)
             {
             using S4 = typename decltype(s4)::type;
-            k_fused_force_general<S4, decltype(fast_c)::value><<<grid, FF_THREADS, 0, s>>>(k, (const S4 *)d_postype, out, n_particles, two_over_n,
-                                                                                        m->cfg, dep, n_grid);
+            const FusedEntry e = fused_entry(m->cfg, d_postype, n_particles, fblocks, n_grid, k.n_modes, k.n_cv);
+            k_fused_force_general<S4, decltype(fast_c)::value><<<grid, FF_THREADS, 0, s>>>(e, k, out, two_over_n, m->cfg, dep);
             });
         }
     MTD_LAUNCH_CHECK();
@@ -662,14 +676,16 @@ int fused_grid_step(mtd_metad *m, unsigned int timestep, hipStream_t s)
     for (unsigned int c = 0; c < MTD_MAX_CV; ++c) out.f[c] = nullptr;
     const int dep = deposit_due(m, timestep);
     const unsigned int n_grid = dep ? m->cfg.n_gblocks : 0;
-    const unsigned int grid = n_grid ? n_grid : 1;                  // still one block to publish the scalars
+    const unsigned int fblocks = n_grid ? 0 : 1;                    // still one block to publish the scalars
+    const unsigned int grid = n_grid + fblocks;
     CommK ck;
     std::memset(&ck, 0, sizeof(ck));
+    const FusedEntry e = fused_entry(m->cfg, nullptr, 0, fblocks, n_grid, 0, k.n_cv);
     switch (m->cfg.n_cv)
         {
-        case 1: k_fused_force<float4, 1, true, 1, false, false><<<grid, FF_THREADS, 0, s>>>(k, nullptr, out, 0, 0.0, m->cfg, dep, n_grid, ck); break;
-        case 2: k_fused_force<float4, 2, true, 1, false, false><<<grid, FF_THREADS, 0, s>>>(k, nullptr, out, 0, 0.0, m->cfg, dep, n_grid, ck); break;
-        default: k_fused_force<float4, 3, true, 1, false, false><<<grid, FF_THREADS, 0, s>>>(k, nullptr, out, 0, 0.0, m->cfg, dep, n_grid, ck); break;
+        case 1: k_fused_force<float4, 1, true, 1, false, false><<<grid, FF_THREADS, 0, s>>>(e, k, out, 0.0, m->cfg, dep, ck); break;
+        case 2: k_fused_force<float4, 2, true, 1, false, false><<<grid, FF_THREADS, 0, s>>>(e, k, out, 0.0, m->cfg, dep, ck); break;
+        default: k_fused_force<float4, 3, true, 1, false, false><<<grid, FF_THREADS, 0, s>>>(e, k, out, 0.0, m->cfg, dep, ck); break;
         }
     MTD_LAUNCH_CHECK();
     m->pending_apply = dep;

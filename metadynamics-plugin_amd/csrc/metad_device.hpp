@@ -9,6 +9,8 @@
 #include "comm_device.hpp"
 #include "exact_div.hpp"
 
+#include <cstddef>
+
 #ifndef MTD_STAMP
 #define MTD_STAMP(slot, cond) do { } while (0)
 #endif
@@ -485,7 +487,106 @@ template<int NCH> struct ChainPre
     int patch_ok;
     };
 
+// Where the chain's partial sums lie, RESOLVED: a source that is off (beyond the grid's n_cv, or a value the host provides) is
+// (&st->zero, 0, 0, 0).  chain_preload forms its addresses from these alone.
+struct ChainSums
+    {
+    const double *ptr[CHAIN_MAX_CV];
+    unsigned int cnt[CHAIN_MAX_CV], str[CHAIN_MAX_CV], off[CHAIN_MAX_CV];
+    };
+
+// FIRST kernel argument of launch B of the fused step (k_fused_force, k_fused_force_general: fused.hip): every scalar a wave
+// needs before its first vector load, filled by the host at the launch site (fused_entry, metad_host.hpp) and read once at kernel
+// entry — adjacent wide scalar loads in one batch, one round trip.  Fetched field by field from LamKArgs / MetadCfg / the scalar
+// arguments behind the role branches they were up to seven dependent round trips of ~0.14 us each in front of the first load.
+struct alignas(64) FusedEntry
+    {
+    const void *postype;
+    MetadState *st;
+    unsigned int N;
+    unsigned int n_particle_blocks;            // force blocks, behind the passengers
+    unsigned int n_passenger_blocks;           // grid blocks: blockIdx.x < n_passenger_blocks
+    unsigned int n_modes, n_cv;                // of the lamellar set
+    unsigned int _pad;
+    ChainSums sums;
+    };
+static_assert(sizeof(FusedEntry) <= 128 && alignof(FusedEntry) == 64, "one aligned batch of scalar loads");
+// fused_entry_read names every field by hand: a field added to (or taken from) the struct must be added to (taken from) its operands
+static_assert(CHAIN_MAX_CV == 3 && sizeof(ChainSums) == 64 && offsetof(FusedEntry, sums) == 40, "fused_entry_read names every field");
+
+// "Read once at kernel entry": returns n_passenger_blocks — the operand of the role branch, which every wave evaluates first —
+// through a one-instruction asm statement that ALSO takes the other fields as scalar operands.  The compiler must then hold them all
+// in registers in front of the role branch and fetches them with adjacent wide scalar loads in one batch; left alone it sinks each
+// load into the branch that uses the field, a wait per branch level (gfx950 ISA: two batches in front of the chain's loads).
+// Not `volatile` (it lives through its result): a volatile statement counts as a write to memory, behind which the compiler no
+// longer turns uniform loads from global memory into scalar loads.  This rests on how the compiler schedules scalar loads, not on
+// anything the language promises: profiles/r17/force_entry_isa.txt is the check, to be repeated with a new compiler.
+// (n_cv is carried for completeness of "what a wave needs at entry"; no kernel reads it from here yet.)
+// _head: the fields in front of the chain's sums only (k_fused_force_general, whose sums the whole block adds up).
+__device__ __forceinline__ unsigned int fused_entry_read_head(const FusedEntry &e)
+    {
+    unsigned int npb;
+    asm("s_mov_b32 %0, %1" : "=s"(npb) : "s"(e.n_passenger_blocks), "s"(e.postype), "s"(e.st), "s"(e.N), "s"(e.n_particle_blocks),
+        "s"(e.n_modes), "s"(e.n_cv));
+    return npb;
+    }
+__device__ __forceinline__ unsigned int fused_entry_read(const FusedEntry &e)
+    {
+    unsigned int npb;
+    asm("s_mov_b32 %0, %1" : "=s"(npb) : "s"(e.n_passenger_blocks), "s"(e.postype), "s"(e.st), "s"(e.N), "s"(e.n_particle_blocks),
+        "s"(e.n_modes), "s"(e.n_cv), "s"(e.sums.ptr[0]), "s"(e.sums.ptr[1]), "s"(e.sums.ptr[2]), "s"(e.sums.cnt[0]), "s"(e.sums.cnt[1]),
+        "s"(e.sums.cnt[2]), "s"(e.sums.str[0]), "s"(e.sums.str[1]), "s"(e.sums.str[2]), "s"(e.sums.off[0]), "s"(e.sums.off[1]),
+        "s"(e.sums.off[2]));
+    return npb;
+    }
+
+// the resolved form from the grid's configuration, as chain_preload(MetadCfg) below selects it on the device (host: fused_entry)
+inline ChainSums chain_sums_of(const MetadCfg &c)
+    {
+    ChainSums s;
+    const double *safe = &c.st->zero;                              // (an address, not an access: fine on the host)
+#pragma unroll
+    for (int i = 0; i < CHAIN_MAX_CV; ++i)
+        {
+        const bool on = i < (int)c.n_cv && c.src[i].partials != nullptr;
+        s.ptr[i] = on ? c.src[i].partials : safe;
+        s.cnt[i] = on ? c.src[i].n_partials : 0u;
+        s.str[i] = on ? c.src[i].stride : 0u;
+        s.off[i] = on ? c.src[i].offset : 0u;
+        }
+    return s;
+    }
+
+// the vector loads of chain_preload: branch-free, from clamped addresses
+template<int NCH, bool SUMS>
+__device__ __forceinline__ void chain_preload_sums(const ChainSums &s, const double *safe, ChainPre<NCH> &p)
+    {
+    const unsigned int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            {
+            // (a lane without a partial sum reads the 0.0 of MetadState::zero: nothing behind the load has to wait for it)
+            const unsigned int b = lane + j * MTD_WAVE;
+            const double *q = (SUMS && b < s.cnt[i]) ? s.ptr[i] + ((size_t)b * s.str[i] + s.off[i]) : safe;
+            p.x[i][j] = SUMS ? *q : 0.0;
+            }
+    }
+template<int NCH>
+__device__ __forceinline__ void chain_preload_patch(const MetadState *st, ChainPre<NCH> &p)
+    {
+    const unsigned int lane = threadIdx.x & 63;
+    p.patch.v[0] = st->patch_v[lane];                                // 36 slots (two variables) sit in the first 64
+#pragma unroll
+    for (int r = 1; r < 4; ++r) p.patch.v[r] = NCH == 3 ? st->patch_v[min(lane + 64 * r, 215u)] : 0.0;
+    }
+
 // SUMS = false: the grid patch only (sharded step: the sums come out of the mailbox)
+// (the launches of mesh.hip, steinhardt.hip and fused_step.hip, which carry MetadCfg alone; statement for statement what it was
+// before the fused launches got their own form below, so that those kernels stay the code they were: built from
+// chain_preload_sums / chain_preload_patch above, k_tile_forces_chain came out one instruction longer.  TWO COPIES of the address
+// rule and of the patch's slot layout — a change to either goes into both)
 template<int NCH, bool SUMS = true>
 __device__ __forceinline__ void chain_preload(const MetadCfg &c, ChainPre<NCH> &p)
     {
@@ -524,6 +625,29 @@ __device__ __forceinline__ void chain_preload(const MetadCfg &c, ChainPre<NCH> &
     p.patch.v[0] = c.st->patch_v[lane];                              // 36 slots (two variables) sit in the first 64
 #pragma unroll
     for (int r = 1; r < 4; ++r) p.patch.v[r] = NCH == 3 ? c.st->patch_v[min(lane + 64 * r, 215u)] : 0.0;
+    }
+
+// The same from the entry block of a fused launch: NO scalar load at all.  The patch's validity flag and origin (four
+// consecutive ints of MetadState, consumed only in stage 3 of chain_wave) travel as ONE vector load by lanes 0 .. 3 in the same
+// batch as the sums and the patch values — through st they were a dependent scalar round trip in front of every vector load here.
+// chain_preload_resolve hands them out (v_readlane: wave-uniform, as the scalar loads left them) once the chain's wave gets to
+// its work.
+template<int NCH, bool SUMS = true>
+__device__ __forceinline__ int chain_preload(const FusedEntry &e, ChainPre<NCH> &p)
+    {
+    const unsigned int lane = threadIdx.x & 63;
+    chain_preload_sums<NCH, SUMS>(e.sums, &e.st->zero, p);
+    static_assert(offsetof(MetadState, patch_org) == offsetof(MetadState, patch_valid) + sizeof(int), "one run of four ints");
+    const int meta = (&e.st->patch_valid)[min(lane, 3u)];
+    chain_preload_patch<NCH>(e.st, p);
+    return meta;
+    }
+template<int NCH>
+__device__ __forceinline__ void chain_preload_resolve(const int meta, ChainPre<NCH> &p)
+    {
+    p.patch_ok = wave_read(meta, 0);
+#pragma unroll
+    for (int i = 0; i < CHAIN_MAX_CV; ++i) p.patch.org[i] = wave_read(meta, 1 + i);
     }
 
 // a / (the divisor whose reciprocal is y), correctly rounded (exact_div.hpp) when the grid qualifies, else the division

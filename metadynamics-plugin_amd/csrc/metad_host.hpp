@@ -36,6 +36,23 @@ namespace mtd
 {
 // does this step deposit a hill? (IntegratorMetaDynamics.cc:368)
 inline int deposit_due(const mtd_metad *m, unsigned int timestep) { return (m->add_bias && (timestep % m->stride == 0)) ? 1 : 0; }
+// the entry block of a fused launch (FusedEntry, metad_device.hpp), filled where the launch is issued: the particle array, the
+// launch's two block counts, the set's counts and the chain's partial sums in their resolved form
+inline FusedEntry fused_entry(const MetadCfg &c, const void *postype, unsigned int N, unsigned int n_particle_blocks,
+                              unsigned int n_passenger_blocks, unsigned int n_modes, unsigned int n_cv)
+    {
+    FusedEntry e;
+    e.postype = postype;
+    e.st = c.st;
+    e.N = N;
+    e.n_particle_blocks = n_particle_blocks;
+    e.n_passenger_blocks = n_passenger_blocks;
+    e.n_modes = n_modes;
+    e.n_cv = n_cv;
+    e._pad = 0;
+    e.sums = chain_sums_of(c);
+    return e;
+    }
 // Blocks of `kernel` the current device holds at one time (occupancy x compute units; 0 if the query fails), cached per device
 // and kernel (fused.hip).  A launch whose blocks wait for each other is only issued when its whole grid is resident at once.
 unsigned int resident_capacity(const void *kernel, int threads);
