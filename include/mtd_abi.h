@@ -331,8 +331,9 @@ int mtd_comm_create(mtd_comm **out, unsigned int rank, unsigned int world, unsig
 int mtd_comm_handle(mtd_comm *c, void *out_handle);
 /* handles: world * MTD_COMM_HANDLE_BYTES bytes in rank order (the own entry is ignored).  world == 1 needs no connect. */
 int mtd_comm_connect(mtd_comm *c, const void *handles);
-/* d_values[0..n) <- sum over ranks, added up in rank order (the same bits on every rank).  Every rank must issue the
- * same sequence of exchanges (this call and the fused step's) on its comm. */
+/* d_values[0..n) <- sum over ranks, added up in rank order starting from +0.0 (the same bits on every rank).  Every rank must
+ * issue the same sequence of exchanges (this call and the fused step's) on its comm.  A message of more than 60000 / (8 world)
+ * doubles is refused (MTD_ERR_UNSUPPORTED); a refused call takes no exchange number, so the communicator stays usable. */
 int mtd_comm_allreduce_small(mtd_comm *c, double *d_values, unsigned int n, mtd_stream_t stream);
 /* number of timed-out waits so far; SYNCHRONISES the stream */
 int mtd_comm_status(mtd_comm *c, unsigned int *timeouts, mtd_stream_t stream);
@@ -352,7 +353,12 @@ int mtd_comm_open(mtd_comm *c, unsigned int slot, const void *handles, void **pe
  * all-gather); two mailbox exchanges are the barriers.  Same bits on every rank; an expired wait poisons the whole result (NaN)
  * and the communicator (MTD_ERR_COMM_TIMEOUT from then on).
  * Set-up: two buffers of mtd_comm_pull_bytes(max_doubles) bytes per rank from mtd_comm_share, opened by every rank
- * (mtd_comm_open), handed over once with mtd_comm_pull_attach (in_peers / out_peers: rank r's buffer as mapped here). */
+ * (mtd_comm_open), handed over once with mtd_comm_pull_attach (in_peers / out_peers: rank r's buffer as mapped here).
+ * Layout: slices of roundup32(ceil(count / world)) doubles, rank r owns [r chunk, min((r + 1) chunk, count)) — possibly nothing.
+ * count may be anything from 1 to the attached max_doubles (more, or no attach: MTD_ERR_INVALID_ARGUMENT, nothing is launched);
+ * world == 1 returns MTD_SUCCESS without looking at the buffer.  The order of the additions, the layout, back-to-back re-use of the
+ * buffers, the poison and the cap of MTD_COMM_MAX_SHARED slots are pinned bit for bit by tests/test_gpu_comm_pull.py.
+ * Known limitation: slots are released only by mtd_comm_destroy, so a larger capacity needs a new communicator. */
 size_t mtd_comm_pull_bytes(size_t max_doubles);
 int mtd_comm_pull_attach(mtd_comm *c, size_t max_doubles, void *const *in_peers, void *const *out_peers);
 int mtd_comm_allreduce_pull(mtd_comm *c, double *d_buffer, size_t count, mtd_stream_t stream);

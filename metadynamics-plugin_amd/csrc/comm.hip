@@ -361,11 +361,13 @@ int mtd_comm_open(mtd_comm *c, unsigned int slot, const void *handles, void **pe
 int mtd_comm_allreduce_small(mtd_comm *c, double *d_values, unsigned int n, mtd_stream_t stream)
     {
     if (!c || !d_values || n == 0 || n > c->max_doubles) return MTD_ERR_INVALID_ARGUMENT;
+    // every refusal comes BEFORE comm_next: a refused call must not take an exchange number — a skipped number would break the
+    // alternation of slot parities that the double-buffering rests on (comm_device.hpp)
+    const size_t lds = sizeof(unsigned int) * 2 * n * c->k.world;
+    if (lds > 60000) return MTD_ERR_UNSUPPORTED;
     CommK k;
     int rc = comm_next(c, k);
     if (rc) return rc;
-    const size_t lds = sizeof(unsigned int) * 2 * n * k.world;
-    if (lds > 60000) return MTD_ERR_UNSUPPORTED;
     k_comm_allreduce<<<1, AR_THREADS, lds, (hipStream_t)stream>>>(k, d_values, n);
     MTD_LAUNCH_CHECK();
     return MTD_SUCCESS;
