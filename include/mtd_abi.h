@@ -616,8 +616,9 @@ int mtd_ql_forces_virial(unsigned int n_particles, const void *d_postype, void *
  * Not square-rooted, divided by N_global: the conventions of the global variable, with the square taken per particle.
  * Preconditions: the list is FULL and symmetric for same-type pairs within r_cut ((i, j) listed <=> (j, i) listed: what HOOMD and
  * mtd_nlist_build produce — the force pass gathers both roles of a particle from its own row), holds no duplicate and indexes no
- * ghost particle; entries j >= n_particles and self entries are skipped.  Known limits: a pair exactly on the z axis gives NaN in
- * the force, as in mtd_ql_forces; c_i jumps from 0 to the one-neighbour value when a first neighbour enters an empty shell.
+ * ghost particle; entries j >= n_particles and self entries are skipped.  A pair exactly on the z axis of the box (a column of a
+ * cubic crystal) has a finite force, here and in mtd_ql_forces, where the reference gives NaN (tests/test_gpu_ql_axis.py).  Known
+ * limit: c_i jumps from 0 to the one-neighbour value when a first neighbour enters an empty shell.
  * Arguments are checked before a device is touched: MTD_ERR_INVALID_ARGUMENT for null pointers, r_cut <= 0, r_on < 0,
  * r_on >= r_cut, n_global == 0, an unknown dtype or a d_scratch that is not 16-byte aligned; MTD_ERR_UNSUPPORTED for lmax > 12.
  *

@@ -25,10 +25,10 @@
 //                     variable: value -> scalar chain -> first grid pass in one launch (mtd_ql_finalize_update_bias); the
 //                     engine's deferred pass then rides in the force pass of the same step
 //   k_ql_forces       the spherical-basis gradient of :287-321 contracted BEFORE it is expanded: with Z_lm = h^m q_lm
-//                     (q_lm = nrm w_l conj(Q_lm) in LDS) the pair force is -(alpha U + beta V + gamma W) with three scalars
-//                     U = sum P Re Z, V = cot sum m P Re Z + sin sum d_lm p_m+1,l-m-1 Re Z, W = -sum m P Im Z and three real
-//                     vectors alpha = d f'/r, beta = (f/r) e_theta, gamma = (f/rho) e_phi; m < 0 terms equal their m > 0
-//                     partners (weight 2), degrees with Ql_ref[l] = 0 are skipped as a whole.  Per-particle sums over the
+//                     (q_lm = nrm w_l conj(Q_lm) in LDS) the pair force is -(f'/r U d + f/r g) with U = sum P Re Z and g the sum
+//                     of P' Re Z (e_z - ct e_r) + m P Re(h^(m-1) q (e_x + i e_y - h e_r)): a polynomial in d / r, no 1 / tan(theta)
+//                     and no 1 / rho, finite for a pair on the z axis where the reference is NaN (ql_pair_force); m < 0 terms equal
+//                     their m > 0 partners (weight 2), degrees with Ql_ref[l] = 0 are skipped as a whole.  Per-particle sums over the
 //                     pairs of a unit in a fixed order through LDS (deterministic, no atomics for full lists).
 //                     VIR (mtd_ql_forces_virial): the pair vectors go through LDS beside the pair forces and the summing
 //                     threads form virial_k[ab] = 1/2 sum_j d_kj,a fp_kj,b in the same order
@@ -678,8 +678,8 @@ __global__ __launch_bounds__(256) void k_ql_finalize_chain(const QlArgs<LMAX> a,
 // — and added with integer atomics: the sums are exact, so they cannot depend on the order, and a last pass converts them to
 // the caller's force array (one rounding per component).  Range: |x| < 2^72 per contribution, bits below 2^-120 are dropped
 // (forces of order 1: 1e-36 relative); 15 bits of headroom per bin = 32768 contributions at the top of a bin.  Non-finite
-// contributions (theta = 0, Q_l = 0: the reference produces inf / NaN there too) set flags that the conversion turns back into
-// what IEEE addition in any order would have given.
+// contributions (non-finite input; a pair on the z axis gives none since ql_pair_force divides by no rho) set flags
+// that the conversion turns back into what IEEE addition in any order would have given.
 constexpr int QL_BINS = 4;
 constexpr int QL_BIN_BITS = 48;
 constexpr int QL_BIN_LOW = -120;

@@ -202,10 +202,14 @@ __device__ __forceinline__ void smoothing_tab(const QlArgs<LMAX> &a, const doubl
 // the pair force of one list entry (SteinhardtQl.cc:287-333 contracted as the header describes), in the monic amplitudes:
 // with h = sin(theta) e^{i phi} = (dx + i dy) / r, P = p_m,l-m(cos theta) and Z_lm = h^m q_lm (q_lm = nrm(l, m) w_l conj(Q_lm)
 // from the weight source),
-//   U = sum P Re Z,   V = cot(theta) sum m P Re Z + sin(theta) sum_{m < l} d(l, m) p_m+1,l-m-1 Re Z,   W = -sum m P Im Z
-// and the force is -(f'/r U d + f/r V e_theta + f/rho W e_phi).  Degrees with Ql_ref[l] = 0 are skipped as a whole (one scalar
-// branch per degree); per order m the sums over l are kept apart (U_m, W_m) so that the factor m is applied once.
-// On the z axis 1/rho is infinite and the force comes out NaN, as from the reference's 0 * (1 / tan(0)).
+//   U = sum P Re Z,   and per term   grad[P Re Z] = { P' Re Z (e_z - ct e_r) + m P Re(h^(m-1) q (e_x + i e_y - h e_r)) } / r
+// with P' = dP/d(cos theta) = -d(l, m) p_m+1,l-m-1: a polynomial in d / r, the spherical components (1 / tan(theta), 1 / rho) never
+// formed.  The sums are taken over Y_lm = h^(m-1) q_lm (m >= 1), the last factor h applied once at the end:
+//   A + i B = sum m P Y,   VA = Re(h (A + i B)),   D = sum d(l, m) p_m+1,l-m-1 Re Z
+// and the force is -(f'/r U d + f/r {(A, -B, 0) + (D ct - VA) (ex, ey, 0) - (VA ct + D sin^2) e_z}).  Degrees with Ql_ref[l] = 0
+// are skipped as a whole (one scalar branch per degree); per order m the sums over l are kept apart (A_m, B_m) so that the
+// factor m is applied once.  A pair on the z axis (dx = dy = 0) gets the finite limit, where the reference's 0 * (1 / tan(0)) is
+// NaN (SteinhardtQl.cc:305, :314); tests/test_gpu_ql_axis.py holds every entry point to a rotated-frame restatement there.
 // The weights q_lm come from a source object, `qsrc(l, m, idx)` with idx = l (l + 1) / 2 + m: one table per launch in LDS for the
 // global variable (QlWeightsLds), the sum of two per-particle table rows for the local one (steinhardt_local.hip).
 struct QlWeightsLds
@@ -227,8 +231,6 @@ __device__ __forceinline__ void ql_pair_force(const QlArgs<LMAX> &a, const doubl
     {
     typedef QlTab<LMAX> T;
     const double inv_r = rsqrt(rsq);
-    const double rho2 = dx * dx + dy * dy;
-    const double inv_rho = rsqrt(rho2);
     const double ct = dz * inv_r, ex = dx * inv_r, ey = dy * inv_r;
     double f, fprime_divr;
     smoothing_tab<LMAX>(a, tab, rsq, inv_r, f, fprime_divr);
@@ -242,15 +244,15 @@ __device__ __forceinline__ void ql_pair_force(const QlArgs<LMAX> &a, const doubl
 #pragma unroll
         for (int n = 2; m + n <= LMAX; ++n) p[m][n] = ct * p[m][n - 1] - tab[T::beta(m, n)] * p[m][n - 2];
         }
-    // h^m
+    // h^(m - 1), m = 1 ... LMAX
     cplx h[LMAX + 1];
     h[0] = {1.0, 0.0};
-    if (LMAX >= 1) h[1] = {ex, ey};
+    if (LMAX >= 2) h[1] = {ex, ey};
 #pragma unroll
-    for (int m = 2; m <= LMAX; ++m) h[m] = cmul(h[m - 1], {ex, ey});
-    double Um[LMAX + 1], Wm[LMAX + 1], VB = 0.0;
+    for (int m = 2; m < LMAX; ++m) h[m] = cmul(h[m - 1], {ex, ey});
+    double Am[LMAX + 1], Bm[LMAX + 1], U0 = 0.0, D0 = 0.0, Dre = 0.0, Dim = 0.0;
 #pragma unroll
-    for (int m = 0; m <= LMAX; ++m) Um[m] = Wm[m] = 0.0;
+    for (int m = 0; m <= LMAX; ++m) Am[m] = Bm[m] = 0.0;
 #pragma unroll
     for (int l = 0; l <= LMAX; ++l)
         {
@@ -261,43 +263,56 @@ __device__ __forceinline__ void ql_pair_force(const QlArgs<LMAX> &a, const doubl
                 {
                 const int idx = l * (l + 1) / 2 + m;
                 const cplx q = qsrc(l, m, idx);
-                const cplx Z = m == 0 ? q : cmul(h[m], q);
-                if (m == l)
-                    Um[m] += Z.re;
-                else
-                    Um[m] += p[m][l - m] * Z.re;
-                if (m > 0)
+                if (m == 0)
                     {
-                    if (m == l)
-                        Wm[m] += Z.im;
+                    if (l == 0)
+                        U0 += q.re;
                     else
-                        Wm[m] += p[m][l - m] * Z.im;
+                        {
+                        U0 += p[0][l] * q.re;
+                        if (l == 1)
+                            D0 += tab[T::d(l, 0)] * q.re;
+                        else
+                            D0 += (tab[T::d(l, 0)] * p[1][l - 1]) * q.re;
+                        }
                     }
-                if (m < l)
+                else
                     {
-                    if (l - m - 1 == 0)
-                        VB += tab[T::d(l, m)] * Z.re;
+                    const cplx Y = m == 1 ? q : cmul(h[m - 1], q);
+                    if (m == l)
+                        {
+                        Am[m] += Y.re;
+                        Bm[m] += Y.im;
+                        }
                     else
-                        VB += (tab[T::d(l, m)] * p[m + 1][l - m - 1]) * Z.re;
+                        {
+                        Am[m] += p[m][l - m] * Y.re;
+                        Bm[m] += p[m][l - m] * Y.im;
+                        const double c = l - m - 1 == 0 ? tab[T::d(l, m)] : tab[T::d(l, m)] * p[m + 1][l - m - 1];
+                        Dre += c * Y.re;
+                        Dim += c * Y.im;
+                        }
                     }
                 }
             }
         }
-    double U = Um[0], VA = 0.0, W = 0.0;
+    double A0 = 0.0, B0 = 0.0, A1 = 0.0, B1 = 0.0;
 #pragma unroll
     for (int m = 1; m <= LMAX; ++m)
         {
-        U += Um[m];
-        VA += (double)m * Um[m];
-        W -= (double)m * Wm[m];
+        A0 += Am[m];
+        B0 += Bm[m];
+        A1 += (double)m * Am[m];
+        B1 += (double)m * Bm[m];
         }
-    const double st = rho2 * inv_rho * inv_r, cot = dz * inv_rho;      // sin(theta) = rho / r, 1 / tan(theta)
-    const double cp = dx * inv_rho, sp = dy * inv_rho;
-    const double V = cot * VA + st * VB;
-    const double fa = fprime_divr * U, fb = f * inv_r * V, fc = f * inv_rho * W;   // 1/(r sin theta) = 1/rho
-    fpx = -(fa * dx + fb * (ct * cp) - fc * sp);                                  // e_theta = (ct cp, ct sp, -st), e_phi = (-sp, cp, 0)  (:288)
-    fpy = -(fa * dy + fb * (ct * sp) + fc * cp);
-    fpz = -(fa * dz - fb * st);
+    const double U = U0 + (ex * A0 - ey * B0);
+    const double VA = ex * A1 - ey * B1;                     // sum m P Re(h^m q)
+    const double D = D0 + (ex * Dre - ey * Dim);             // -sum P' Re(h^m q)
+    const double fa = fprime_divr * U, fr = f * inv_r;
+    const double k = D * ct - VA;
+    fpx = -(fa * dx + fr * (A1 + k * ex));
+    fpy = -(fa * dy + fr * (k * ey - B1));
+    fpz = -(fa * dz - fr * (VA * ct + D * (ex * ex + ey * ey)));
     }
 
 template<int LMAX>

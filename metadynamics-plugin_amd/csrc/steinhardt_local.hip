@@ -25,9 +25,10 @@
 // the last term rides in the (0, 0) slot of the table.
 //
 // Preconditions: the list is full and symmetric for same-type pairs within r_cut (what HOOMD and nlist.hip build), holds no
-// duplicate and indexes no ghost particle (entries j >= N and self entries are skipped).  Known limits: a pair exactly on the z axis
-// gives NaN in the force, as in mtd_ql_forces; c_i jumps from 0 to the one-neighbour value when a first neighbour enters an empty
-// shell (inherent in the normalised definition; irrelevant at liquid or solid density).
+// duplicate and indexes no ghost particle (entries j >= N and self entries are skipped).  A pair on the z axis of the box (a column of a cubic
+// crystal: dx = dy = 0 exactly) has a finite force, here and in mtd_ql_forces: ql_pair_force forms the gradient without 1 / rho
+// (tests/test_gpu_ql_axis.py, every entry point, on and next to the axis).  Known limit: c_i jumps from 0 to the one-neighbour value
+// when a first neighbour enters an empty shell (inherent in the normalised definition; irrelevant at liquid or solid density).
 //
 // MI355X design.  Two launches per step, both walk chunks of 64 consecutive central particles per block and round:
 //   lanes            FOUR lanes (a quad) per central particle; lane q takes entries q, q + 4, ... of the particle's row, so the

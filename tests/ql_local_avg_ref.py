@@ -9,6 +9,8 @@ pairs of the list, with an ANALYTIC gradient in the scatter form (every ordered 
     switch:   h(c) = x^p / (1 + x^p), x = max(c, 0) / c0                              (else h(c) = c)
     gate:     g(n) = 3 t^2 - 2 t^3, t = clip((n - n_lo) / (n_hi - n_lo), 0, 1)        (else g = 1)
     v_i = g(n_i) h(c_i),  s = sum_i v_i / N_global,  F = -bias ds/dr
+
+`frame`: a rotation the angular part is done in, the gradient rotated back (see ql_local_ref); None: the lab frame.
 """
 import numpy as np
 from scipy.special import sph_harm_y
@@ -43,7 +45,7 @@ def gate_fn(n, gate):
 
 
 def compute(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, n_global=None, tilt=None, gradient=True,
-            average=False, switch=None, gate=None):
+            average=False, switch=None, gate=None, frame=None):
     """returns dict(s, c, v, n, grad): c_i (averaged when `average`), v_i = g h, n_i for every particle, grad = ds/dr (N, 3)"""
     pos = np.asarray(pos, dtype=np.float64)
     types = np.asarray(types)
@@ -51,6 +53,7 @@ def compute(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, n_global=None
     n_global = N if n_global is None else n_global
     Ql_ref = np.asarray(Ql_ref, dtype=np.float64)
     i, j, d = ql_local_ref.pairs(pos, types, nl, type_id, r_cut, tilt=tilt, L=L)
+    d = ql_local_ref.to_frame(d, frame)
     r = np.sqrt((d * d).sum(axis=1))
     f, df = ql_local_ref.smoothing(r, r_on, r_cut)
     theta = np.arccos(np.clip(d[:, 2] / r, -1.0, 1.0))
@@ -111,6 +114,7 @@ def compute(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, n_global=None
             tht = (W * dY_dtheta).real * f / r
             ph = (W * dY_dphi).real * f / (r * st)
             G += rad[:, None] * rhat + tht[:, None] * e_theta + ph[:, None] * e_phi
+        G = ql_local_ref.from_frame(G, frame)
         grad = np.zeros((N, 3))
         for k in range(3):
             grad[:, k] = np.bincount(i, weights=G[:, k], minlength=N) - np.bincount(j, weights=G[:, k], minlength=N)

@@ -10,6 +10,9 @@ ql_local_virial_ref.entry_gradients.
     sigma   = 3 t^2 - 2 t^3, t = clip((d - d_lo) / (d_hi - d_lo), 0, 1)
     b_i     = sum_j f_ij sigma(d_ij),  v_i = g(n_i) h(b_i),  s = sum_i v_i / N_global
 bonds = None: v_i = g(n_i) h(c_i), the variable of ql_local_avg_ref without the average.
+
+`frame`: a rotation the angular part is done in (see ql_local_ref); the per-entry gradients come back in the lab frame, where the virial
+is formed with the lab-frame pair vectors (the tensor of the frame carried back, Q^T V Q).  None: the lab frame.
 """
 import numpy as np
 from scipy.special import sph_harm_y
@@ -27,7 +30,8 @@ def ramp_fn(d, bonds):
     return t * t * (3.0 - 2.0 * t), 6.0 * t * (1.0 - t) / (d_hi - d_lo)
 
 
-def entry_gradients(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, tilt=None, switch=None, gate=None, bonds=None, gradient=True):
+def entry_gradients(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, tilt=None, switch=None, gate=None, bonds=None, gradient=True,
+                    frame=None):
     """dict(i, j, d: the list entries that take part and their pair vectors; G: the gradient of N_global s with respect to d per entry
     (None without `gradient`); c, n, v, b per particle; dent: d_ij per entry (b and dent None without bonds)).
     N_global ds/dr_k = sum_{i = k} G - sum_{j = k} G."""
@@ -37,7 +41,8 @@ def entry_gradients(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, tilt=
     Ql_ref = np.asarray(Ql_ref, dtype=np.float64)
     if bonds is not None and (Ql_ref < 0).any():
         raise ValueError("bonds need Ql_ref >= 0")
-    i, j, d = ql_local_ref.pairs(pos, types, nl, type_id, r_cut, tilt=tilt, L=L)
+    i, j, d_lab = ql_local_ref.pairs(pos, types, nl, type_id, r_cut, tilt=tilt, L=L)
+    d = ql_local_ref.to_frame(d_lab, frame)
     r = np.sqrt((d * d).sum(axis=1))
     f, df = ql_local_ref.smoothing(r, r_on, r_cut)
     theta = np.arccos(np.clip(d[:, 2] / r, -1.0, 1.0))
@@ -75,7 +80,7 @@ def entry_gradients(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, tilt=
         b = np.bincount(i, weights=f * sg, minlength=N)
         h, dh = ql_local_avg_ref.switch_fn(b, switch)
     v = g * h
-    out = dict(i=i, j=j, d=d, G=None, c=c, n=n, v=v, b=b, dent=dent)
+    out = dict(i=i, j=j, d=d_lab, G=None, c=c, n=n, v=v, b=b, dent=dent)
     if not gradient:
         return out
     beta = g * dh
@@ -112,18 +117,18 @@ def entry_gradients(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, tilt=
         tht = (W * dY_dtheta).real * f / r
         ph = (W * dY_dphi).real * f / (r * st)
         G += rad[:, None] * rhat + tht[:, None] * e_theta + ph[:, None] * e_phi
-    out["G"] = G
+    out["G"] = ql_local_ref.from_frame(G, frame)
     return out
 
 
 def compute(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, n_global=None, tilt=None, gradient=True, switch=None, gate=None,
-            bonds=None, bias=None):
+            bonds=None, bias=None, frame=None):
     """returns dict(s, c, v, n, b, dent, i, j, grad (N, 3)); with `bias` also virial (N, 6), W (6,) = its sums and tensor (3, 3) =
     sum over the entries of d_a F_b, as ql_local_virial_ref.compute"""
     N = len(pos)
     n_global = N if n_global is None else n_global
     e = entry_gradients(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, tilt=tilt, switch=switch, gate=gate, bonds=bonds,
-                        gradient=gradient)
+                        gradient=gradient, frame=frame)
     out = {k: e[k] for k in ("c", "v", "n", "b", "dent", "i", "j")}
     out["s"] = e["v"].sum() / n_global
     out["grad"] = None

@@ -4,6 +4,11 @@ its neighbour) — independent of the gather form the GPU pass uses.  Harmonics:
 
     n_i = sum_j f,  A_lm(i) = sum_j f Y_lm(d_ij),  q_l^2(i) = 4 pi/(2l+1) sum_m |A_lm(i)|^2 / n_i^2,
     c_i = sum_l Ql_ref[l] q_l^2(i),  s = sum_i c_i / N_global,  F = -bias ds/dr
+
+`frame` (a proper rotation Q, util.random_rotation): the pair vectors are rotated after the minimum image (d @ Q.T), everything angular is
+done in that frame and the per-pair gradients are rotated back (G @ Q).  The variable is rotation invariant, so nothing changes — but
+the spherical components below divide by sin(theta), and a bond on the z axis of the box (a column of a cubic crystal) is generic in
+the rotated frame.  frame=None is the lab frame, with its NaN on the axis.
 """
 import numpy as np
 from scipy.special import sph_harm_y
@@ -58,7 +63,17 @@ def pairs(pos, types, nl, type_id, r_cut, tilt=None, L=None, rows=None):
     return i[keep], j[keep], d[keep]
 
 
-def compute(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, n_global=None, tilt=None, gradient=True, rows=None):
+def to_frame(d, frame):
+    """the pair vectors in the frame Q (None: as they are)"""
+    return d if frame is None else d @ np.asarray(frame, dtype=np.float64).T
+
+
+def from_frame(G, frame):
+    """per-pair vectors of the frame Q back in the lab frame"""
+    return G if frame is None else G @ np.asarray(frame, dtype=np.float64)
+
+
+def compute(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, n_global=None, tilt=None, gradient=True, rows=None, frame=None):
     """returns dict(s, c, n, grad): c_i, n_i for every particle, grad = ds/dr (N, 3) (None when gradient=False).
     rows: restrict the CENTRAL particles to these (values of the others are 0; the gradient is then that of the partial sum)."""
     pos = np.asarray(pos, dtype=np.float64)
@@ -67,6 +82,7 @@ def compute(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, n_global=None
     n_global = N if n_global is None else n_global
     Ql_ref = np.asarray(Ql_ref, dtype=np.float64)
     i, j, d = pairs(pos, types, nl, type_id, r_cut, tilt=tilt, L=L, rows=rows)
+    d = to_frame(d, frame)
     r = np.sqrt((d * d).sum(axis=1))
     f, df = smoothing(r, r_on, r_cut)
     theta = np.arccos(np.clip(d[:, 2] / r, -1.0, 1.0))
@@ -110,6 +126,7 @@ def compute(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, n_global=None
                 tht = (W * dY_dtheta).real * f / r
                 ph = (W * dY_dphi).real * f / (r * st)
                 G += rad[:, None] * rhat + tht[:, None] * e_theta + ph[:, None] * e_phi
+        G = from_frame(G, frame)
         grad = np.zeros((N, 3))
         for k in range(3):
             grad[:, k] = np.bincount(i, weights=G[:, k], minlength=N) - np.bincount(j, weights=G[:, k], minlength=N)
@@ -117,9 +134,9 @@ def compute(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, n_global=None
     return {"s": s, "c": c, "n": n, "grad": grad}
 
 
-def forces(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, bias, n_global=None, tilt=None):
+def forces(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, bias, n_global=None, tilt=None, frame=None):
     """(N, 4): F = -bias ds/dr, w = 0"""
-    out = compute(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, n_global=n_global, tilt=tilt)
+    out = compute(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, n_global=n_global, tilt=tilt, frame=frame)
     F = np.zeros((len(pos), 4))
     F[:, :3] = -bias * out["grad"]
     return F

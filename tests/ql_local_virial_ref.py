@@ -8,6 +8,9 @@ for the six components xx, xy, xz, yy, yz, zz (HOOMD's order).  Independent of t
 pair force per entry of a row.  Pairs, smoothing, switch and gate are those of ql_local_ref / ql_local_avg_ref; the per-entry gradient G,
 which those keep internal, is restated here (the value and the gradient it returns are compared with theirs in
 tests/test_ql_local_virial_ref.py).
+
+`frame`: a rotation the angular part is done in (see ql_local_ref); G comes back in the lab frame and the virial is formed there with the
+lab-frame pair vectors, which is the tensor of the frame carried back (Q^T V Q).  None: the lab frame.
 """
 import numpy as np
 from scipy.special import sph_harm_y
@@ -18,14 +21,16 @@ import ql_local_ref
 COMPONENTS = [(0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2)]        # xx, xy, xz, yy, yz, zz
 
 
-def entry_gradients(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, tilt=None, average=False, switch=None, gate=None):
+def entry_gradients(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, tilt=None, average=False, switch=None, gate=None,
+                    frame=None):
     """(i, j, d, G, v): the list entries that take part, their pair vectors and G_ij = d v_i-and-beyond / d d_ij (before 1 / N_global),
     and v_i = g(n_i) h(c_i) per particle.  N_global ds/dr_k = sum_{i = k} G - sum_{j = k} G."""
     pos = np.asarray(pos, dtype=np.float64)
     types = np.asarray(types)
     N = len(pos)
     Ql_ref = np.asarray(Ql_ref, dtype=np.float64)
-    i, j, d = ql_local_ref.pairs(pos, types, nl, type_id, r_cut, tilt=tilt, L=L)
+    i, j, d_lab = ql_local_ref.pairs(pos, types, nl, type_id, r_cut, tilt=tilt, L=L)
+    d = ql_local_ref.to_frame(d_lab, frame)
     r = np.sqrt((d * d).sum(axis=1))
     f, df = ql_local_ref.smoothing(r, r_on, r_cut)
     theta = np.arccos(np.clip(d[:, 2] / r, -1.0, 1.0))
@@ -75,15 +80,16 @@ def entry_gradients(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, tilt=
         tht = (W * dY_dtheta).real * f / r
         ph = (W * dY_dphi).real * f / (r * st)
         G += rad[:, None] * rhat + tht[:, None] * e_theta + ph[:, None] * e_phi
-    return i, j, d, G, g * h, n
+    return i, j, d_lab, ql_local_ref.from_frame(G, frame), g * h, n
 
 
-def compute(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, bias, n_global=None, tilt=None, average=False, switch=None, gate=None):
+def compute(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, bias, n_global=None, tilt=None, average=False, switch=None, gate=None,
+            frame=None):
     """returns dict(virial (N, 6), W (6,) = its sums, tensor (3, 3) = sum over entries of d_a F_b with all nine (a, b), s, n, grad (N, 3))"""
     N = len(pos)
     n_global = N if n_global is None else n_global
     i, j, d, G, v, n = entry_gradients(pos, types, L, nl, r_cut, r_on, lmax, type_id, Ql_ref, tilt=tilt, average=average, switch=switch,
-                                       gate=gate)
+                                       gate=gate, frame=frame)
     Fp = -bias * G / n_global                                        # the force of the entry on its centre i; -Fp on its neighbour j
     virial = np.zeros((N, 6))
     for c, (a, b) in enumerate(COMPONENTS):
