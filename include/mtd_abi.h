@@ -808,6 +808,87 @@ int mtd_pe_forces(unsigned int n_particles, const void *d_postype, void *d_force
                   unsigned int virial_pitch);
 
 /* ================================================================================================
+ * Environment similarity (cv.environment_similarity) — no reference counterpart.  The template-matching crystallinity of Piaggi and
+ * Parrinello (J. Chem. Phys. 150, 244119; PLUMED's ENVIRONMENTSIMILARITY): every particle's neighbourhood is compared, in a FIXED
+ * orientation, with one or more template environments, each a short list of lattice vectors.  It selects one polymorph (fcc against bcc
+ * or hcp, cubic against hexagonal ice) and one orientation, which neither the Steinhardt variables nor the pair entropy can.
+ * Parameters: a particle type t; E environments (1 <= E <= MTD_ES_MAX_ENV), environment e with M_e template vectors T^e_m
+ * (1 <= M_e <= 32, sum_e M_e <= MTD_ES_MAX_VEC, every vector finite with 0 < |T| < r_cut); sigma_env > 0; 0 <= r_on < r_cut; lambda > 0,
+ * read only when E > 1; an optional switch with c0 > 0 and integer p >= 1.
+ * Entries (i, j) of a FULL list take part when i and j are both of type t, j != i and r = |d| <= r_cut, with
+ * d = minImage(r_j - r_i): the vector FROM the central particle TO the neighbour, in the lab frame.  The central particles are the
+ * n_particles local ones; entries may address ghost particles stored behind them.  f(r) is the cosine window of the Steinhardt passes
+ * between r_on and r_cut (SteinhardtQl.cc:36-60).
+ *     phi(x) = exp(-|x|^2 / (4 sigma_env^2))
+ *     k^e_i  = (1 / M_e) sum_{j in row i} f(r_ij) sum_m phi(d_ij - T^e_m)          (~1 on the perfect lattice, ~0.1 in a liquid)
+ *     k_i    = k^1_i                                          for E = 1
+ *     k_i    = (1 / lambda) ln sum_e exp(lambda k^e_i)        for E > 1: PLUMED's smooth maximum, formed as max + log-sum-exp of the differences
+ *     w^e_i  = exp(lambda k^e_i) / sum_e' exp(lambda k^e'_i)  (1 for E = 1)
+ *     v_i    = h(k_i),  h(k) = x^p / (1 + x^p), x = k / c0    (h(k) = k without a switch; the switch of mtd_ql_local_options)
+ *     s      = (1 / N_global) sum_i v_i                       (particles of another type: k^e = k = v = 0)
+ * Gradient: with beta^e_i = h'(k_i) w^e_i, an entry has
+ *     g_ij = sum_e (beta^e_i / M_e) [ f'(r) (d / r) sum_m phi_m - f(r) sum_m phi_m (d - T^e_m) / (2 sigma_env^2) ]      (= d(N s) / d d_ij)
+ * and gives +g_ij to d(N s)/dr_j and -g_ij to d(N s)/dr_i.  As a gather over row k of a symmetric list:
+ *     N ds/dr_k = sum_{j in row k} [ -g_kj(d_kj) + g_jk(-d_kj) ]          (the second term needs beta_j),       F = -bias ds/dr.
+ * The pair term is not parallel to d: the variable is not rotation invariant; sum_k F_k = 0 still holds on a single domain.  An
+ * environment that holds -T for every T (fcc, bcc, sc; detected by exact comparison of the vectors) has g_jk(-d) = -(beta^e_j / beta^e_k)
+ * g_kj(d): one evaluation per entry serves both terms.  Diamond's two environments are each other's inverse, not closed themselves:
+ * two evaluations per entry.
+ * Virial (only with a virial pointer).  The templates stay FIXED in the lab frame under strain.  The six stored components (a, b),
+ * a <= b, in HOOMD's order xx, xy, xz, yy, yz, zz are the derivatives under the cell deformations a HOOMD box can make,
+ * x_a -> x_a + eps x_b of positions and box:
+ *     sum_k virial_k[ab] = -bias ds/d eps_ab = -(bias / N_global) sum_entries g_a d_b
+ * The tensor is NOT symmetric (yx, zx, zy differ from xy, xz, yz); the three stored off-diagonals are xy, xz, yz, those of the upper
+ * triangular deformations.  Per particle half of every entry goes to each of its ends; in the gather
+ *     virial_k[ab] = -(bias / N_global) 1/2 sum_{j in row k} [ g_kj,a d_kj,b + g_jk,a d_jk,b ]
+ * Layout, scalar type and pitch rule of mtd_ql_local_forces_virial (virial[c * pitch + k], six components); every row [0, n_particles)
+ * is written at every call, [n_particles, pitch) is left alone.
+ * A step is _accumulate then _forces with the same arguments and scratch.  Fixed summation orders, no atomics: two identical calls give
+ * identical bits.  Arguments are checked before a device is touched: MTD_ERR_INVALID_ARGUMENT for null pointers, an unknown dtype, a
+ * d_scratch that is not 16-byte aligned, n_global == 0, a virial pitch below n_particles, non-finite or out-of-range parameters,
+ * n_env == 0 or an n_vec[e] == 0, a template vector that is non-finite, zero or not shorter than r_cut; MTD_ERR_UNSUPPORTED for
+ * n_env > 4, an n_vec[e] > 32, a total above 64, and for n_ghost > 0 together with E > 1 or a switch (beta of a ghost would have to be
+ * exchanged; with E = 1 and no switch beta = 1, the table is never read for a neighbour, and ghosts work).
+ * ============================================================================================== */
+
+#define MTD_ES_MAX_ENV 4
+#define MTD_ES_MAX_VEC 64
+
+typedef struct
+    {
+    unsigned int n_env;                    /* E */
+    unsigned int n_vec[MTD_ES_MAX_ENV];    /* M_e */
+    double vec[MTD_ES_MAX_VEC][3];         /* the template vectors, packed environment after environment */
+    double sigma_env, r_on, r_cut;
+    double lambda;                         /* read when n_env > 1 */
+    int switch_on;                         /* c0, p are read when switch_on != 0 */
+    double c0;
+    unsigned int p;
+    } mtd_es_params;
+
+/* device doubles the two calls share: per particle k^e_i [4], beta^e_i [4], k_i, v_i; block sums; and nine gradient sums per particle,
+ * which the first pass fills when beta = 1 everywhere and the environment is closed (the second pass then only scales them) */
+size_t mtd_es_scratch_doubles(unsigned int n_particles);
+
+/* First pass.  On return *d_partials points at *n_partials block sums of v_i (consume with
+ * mtd_metad_set_cv_source(engine, slot, *d_partials, *n_partials, 1, 0, 1.0 / N_global, 0.0) or mtd_reduce_partials), *d_k at
+ * k_i[n_particles], *d_ke at k^e_i as [n_particles][4] (columns e >= n_env are 0) and *d_v at v_i[n_particles] (d_k, d_ke, d_v may be
+ * NULL), all inside d_scratch.  n_ghost: the particles stored behind the n_particles local ones that entries may address. */
+int mtd_es_accumulate(unsigned int n_particles, unsigned int n_ghost, const void *d_postype, int dtype, const mtd_box *box,
+                      const unsigned int *d_head_list, const unsigned int *d_n_neigh, const unsigned int *d_nlist, unsigned int type,
+                      const mtd_es_params *params, unsigned int n_global, double *d_scratch, const double **d_partials, unsigned int *n_partials,
+                      const double **d_k, const double **d_ke, const double **d_v, mtd_stream_t stream);
+
+/* Second pass, with the beta^e_i the last mtd_es_accumulate (same arguments) left in d_scratch: writes d_force[0..n_particles) (w
+ * component 0; 0 for particles of another type); bias = *d_bias when d_bias != NULL, else bias_host.  d_virial == NULL: no virial, the
+ * kernel without the sums; the force array is the same, bit for bit, either way.  n_particles == 0 is success.  No atomics: bitwise
+ * reproducible. */
+int mtd_es_forces(unsigned int n_particles, unsigned int n_ghost, const void *d_postype, void *d_force, int dtype, const mtd_box *box,
+                  const unsigned int *d_head_list, const unsigned int *d_n_neigh, const unsigned int *d_nlist, unsigned int type,
+                  const mtd_es_params *params, unsigned int n_global, const double *d_scratch, const double *d_bias, double bias_host,
+                  mtd_stream_t stream, void *d_virial, unsigned int virial_pitch);
+
+/* ================================================================================================
  * Neighbour list of the stand-alone path (cell list, built on the device)
  * no reference counterpart: HOOMD's md::NeighborList is HOOMD core.  Produces the three arrays SteinhardtQl.cc:80-85 reads, in
  * HOOMD's layout: the neighbours of particle i are d_nlist[d_head_list[i] .. d_head_list[i] + d_n_neigh[i]).

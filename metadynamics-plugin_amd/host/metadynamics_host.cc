@@ -1054,6 +1054,186 @@ double PairEntropy::getLogValue(const std::string &quantity, unsigned int timest
     }
 
 // ------------------------------------------------------------------------------------------------
+// EnvironmentSimilarity
+// ------------------------------------------------------------------------------------------------
+
+EnvironmentSimilarity::EnvironmentSimilarity(std::shared_ptr<SystemDefinition> sysdef, const std::vector<std::vector<std::vector<double>>> &templates,
+                                             double sigma_env, double r_cut, double r_on, double lambda, std::shared_ptr<NeighborList> nlist,
+                                             unsigned int type, const std::string &log_suffix)
+    : CollectiveVariable(sysdef, "environment_similarity" + log_suffix), m_par(), m_nlist(nlist), m_type(type), m_cv_last_updated(0),
+      m_have_computed(false), m_d_partials(nullptr), m_d_k(nullptr), m_d_ke(nullptr), m_d_v(nullptr), m_n_partials(0)
+    {
+    if (!nlist) throw std::runtime_error("cv.environment_similarity: a neighbour list is required");
+    if (templates.empty() || templates.size() > MTD_ES_MAX_ENV)
+        throw std::runtime_error("cv.environment_similarity: between 1 and 4 template environments in this build");
+    if (!(sigma_env > 0.0) || !std::isfinite(sigma_env)) throw std::runtime_error("cv.environment_similarity: sigma_env > 0 is required");
+    if (!(r_on >= 0.0) || !(r_on < r_cut) || !std::isfinite(r_cut)) throw std::runtime_error("cv.environment_similarity: 0 <= r_on < r_cut is required");
+    if (templates.size() > 1 && (!(lambda > 0.0) || !std::isfinite(lambda)))
+        throw std::runtime_error("cv.environment_similarity: lambda > 0 is required with several environments");
+    m_par.n_env = (unsigned int)templates.size();
+    unsigned int k = 0;
+    for (unsigned int e = 0; e < m_par.n_env; ++e)
+        {
+        if (templates[e].empty() || templates[e].size() > 32 || k + templates[e].size() > MTD_ES_MAX_VEC)
+            throw std::runtime_error("cv.environment_similarity: 1 to 32 vectors per environment and 64 in all in this build");
+        m_par.n_vec[e] = (unsigned int)templates[e].size();
+        for (const std::vector<double> &t : templates[e])
+            {
+            if (t.size() != 3) throw std::runtime_error("cv.environment_similarity: a template vector has three components");
+            const double len2 = t[0] * t[0] + t[1] * t[1] + t[2] * t[2];
+            if (!std::isfinite(len2) || !(len2 > 0.0) || !(len2 < r_cut * r_cut))
+                throw std::runtime_error("cv.environment_similarity: every template vector must be finite with 0 < |T| < r_cut");
+            for (int c = 0; c < 3; ++c) m_par.vec[k][c] = t[c];
+            ++k;
+            }
+        }
+    m_par.sigma_env = sigma_env;
+    m_par.r_on = r_on;
+    m_par.r_cut = r_cut;
+    m_par.lambda = lambda;
+    m_scratch.resize(sizeof(double) * mtd_es_scratch_doubles(m_pdata->getN()));
+    m_sum.resize(sizeof(double));
+    }
+
+void EnvironmentSimilarity::setSwitch(double c0, unsigned int p)
+    {
+    if (!(c0 > 0.0) || !std::isfinite(c0) || p == 0) throw std::runtime_error("cv.environment_similarity: a switch needs c0 > 0 and an integer p >= 1");
+    m_par.switch_on = 1;
+    m_par.c0 = c0;
+    m_par.p = p;
+    m_have_computed = false;                                         // beta in the scratch belongs to the old switch
+    }
+
+void EnvironmentSimilarity::clearSwitch()
+    {
+    m_par.switch_on = 0;
+    m_par.c0 = 0.0;
+    m_par.p = 0;
+    m_have_computed = false;
+    }
+
+void EnvironmentSimilarity::computeCV(unsigned int timestep)
+    {
+    ProfRange prof_range("CV");
+    if (m_cv_last_updated == timestep && m_have_computed) return;
+    // the force pass gathers both roles of a particle from its own row
+    if (m_nlist->getStorageMode() == NeighborList::half)
+        throw std::runtime_error("cv.environment_similarity: a full neighbour list is required (the force pass gathers both roles of a "
+                                 "particle from its own row)");
+    if (distributed() && (m_par.n_env > 1 || m_par.switch_on))
+        throw std::runtime_error("cv.environment_similarity: domain-decomposed runs are not supported with several environments or a switch "
+                                 "(beta of a ghost neighbour would have to be exchanged)");
+    if (m_nlist->isDeviceBuild() && m_nlist->getRCut() < getRCut())
+        throw std::runtime_error("cv.environment_similarity: the neighbour list must reach r_cut");
+    m_nlist->compute(timestep);
+    const mtd_box box = m_pdata->getBox().toMtd();
+    const size_t need = sizeof(double) * mtd_es_scratch_doubles(m_pdata->getN());
+    if (need > m_scratch.bytes()) m_scratch.resize(need);
+    mtd_check(mtd_es_accumulate(m_pdata->getN(), m_pdata->getNGhosts(), m_pdata->positionsPtr(), m_pdata->getDtype(), &box,
+                                (const unsigned int *)m_nlist->getHeadList().data(), (const unsigned int *)m_nlist->getNNeighArray().data(),
+                                (const unsigned int *)m_nlist->getNListArray().data(), m_type, &m_par, m_pdata->getNGlobal(),
+                                (double *)m_scratch.data(), &m_d_partials, &m_n_partials, &m_d_k, &m_d_ke, &m_d_v, m_exec_conf->getStream()),
+              "mtd_es_accumulate");
+    // the ranks of a domain-decomposed run add their sums of v_i: one double, the same bits everywhere afterwards
+    if (distributed())
+        {
+        hipStream_t s = m_exec_conf->getStream();
+        mtd_check(mtd_reduce_partials(m_d_partials, m_n_partials, 1, 1, 1.0 / (double)m_pdata->getNGlobal(), 0.0, (double *)m_sum.data(), s),
+                  "mtd_reduce_partials");
+        m_exec_conf->allreduceSmall((double *)m_sum.data(), 1, s);
+        }
+    m_have_computed = true;
+    m_cv_last_updated = timestep;
+    }
+
+void EnvironmentSimilarity::enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot)
+    {
+    computeCV(timestep);
+    if (distributed())
+        mtd_check(mtd_metad_set_cv_source(engine, slot, (const double *)m_sum.data(), 1, 1, 0, 1.0, 0.0), "mtd_metad_set_cv_source");
+    else
+        mtd_check(mtd_metad_set_cv_source(engine, slot, m_d_partials, m_n_partials, 1, 0, 1.0 / (double)m_pdata->getNGlobal(), 0.0),
+                  "mtd_metad_set_cv_source");
+    }
+
+double EnvironmentSimilarity::getCurrentValue(unsigned int timestep)
+    {
+    computeCV(timestep);
+    if (!distributed())
+        mtd_check(mtd_reduce_partials(m_d_partials, m_n_partials, 1, 1, 1.0 / (double)m_pdata->getNGlobal(), 0.0, (double *)m_sum.data(),
+                                      m_exec_conf->getStream()),
+                  "mtd_reduce_partials");
+    m_exec_conf->sync();
+    double value = 0.0;
+    hip_check(hipMemcpy(&value, m_sum.data(), sizeof(double), hipMemcpyDeviceToHost), "cv read-back");
+    return value;
+    }
+
+void EnvironmentSimilarity::computeBiasForces(unsigned int timestep)
+    {
+    ProfRange prof_range("Force");
+    if (!m_have_computed || m_cv_last_updated != timestep) computeCV(timestep);      // beta of THIS step's positions
+    m_nlist->compute(timestep);
+    const mtd_box box = m_pdata->getBox().toMtd();
+    // constant pressure: the per-particle virial of the bias force beside it (include/mtd_abi.h).  Without the flag the plain call; a
+    // virial array somebody has allocated earlier is zeroed then, so that a stale virial is never read (as SteinhardtLocal)
+    void *virial = nullptr;
+    if (m_pdata->getPressureFlag())
+        virial = getVirialArray().data();
+    else if (m_virial.bytes())
+        hip_check(hipMemsetAsync(m_virial.data(), 0, m_virial.bytes(), m_exec_conf->getStream()), "virial reset");
+    mtd_check(mtd_es_forces(m_pdata->getN(), m_pdata->getNGhosts(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &box,
+                            (const unsigned int *)m_nlist->getHeadList().data(), (const unsigned int *)m_nlist->getNNeighArray().data(),
+                            (const unsigned int *)m_nlist->getNListArray().data(), m_type, &m_par, m_pdata->getNGlobal(),
+                            (const double *)m_scratch.data(), m_bias_device, m_bias, m_exec_conf->getStream(), virial, getVirialPitch()),
+              "mtd_es_forces");
+    }
+
+std::vector<double> EnvironmentSimilarity::readBack(const double *d_src, size_t n, const char *what, unsigned int timestep)
+    {
+    computeCV(timestep);
+    m_exec_conf->sync();
+    std::vector<double> out(n);
+    if (!out.empty()) hip_check(hipMemcpy(out.data(), d_src, sizeof(double) * n, hipMemcpyDeviceToHost), what);
+    return out;
+    }
+
+std::vector<double> EnvironmentSimilarity::getLocalValues(unsigned int timestep)
+    {
+    computeCV(timestep);
+    return readBack(m_d_k, m_pdata->getN(), "k_i read-back", timestep);
+    }
+
+std::vector<double> EnvironmentSimilarity::getSwitchedValues(unsigned int timestep)
+    {
+    computeCV(timestep);
+    return readBack(m_d_v, m_pdata->getN(), "v_i read-back", timestep);
+    }
+
+std::vector<double> EnvironmentSimilarity::getEnvironmentValues(unsigned int timestep)
+    {
+    computeCV(timestep);
+    const std::vector<double> all = readBack(m_d_ke, (size_t)MTD_ES_MAX_ENV * m_pdata->getN(), "k^e_i read-back", timestep);
+    std::vector<double> out((size_t)m_par.n_env * m_pdata->getN());
+    for (size_t i = 0; i < m_pdata->getN(); ++i)
+        for (unsigned int e = 0; e < m_par.n_env; ++e) out[i * m_par.n_env + e] = all[i * MTD_ES_MAX_ENV + e];
+    return out;
+    }
+
+std::vector<std::string> EnvironmentSimilarity::getProvidedLogQuantities()
+    {
+    auto list = CollectiveVariable::getProvidedLogQuantities();
+    list.push_back("cv_" + m_cv_name);
+    return list;
+    }
+
+double EnvironmentSimilarity::getLogValue(const std::string &quantity, unsigned int timestep)
+    {
+    if (quantity == "cv_" + m_cv_name) return getCurrentValue(timestep);
+    return CollectiveVariable::getLogValue(quantity, timestep);
+    }
+
+// ------------------------------------------------------------------------------------------------
 // AspectRatio, Density
 // ------------------------------------------------------------------------------------------------
 

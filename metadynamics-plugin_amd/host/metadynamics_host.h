@@ -388,6 +388,44 @@ class PairEntropy : public CollectiveVariable
         const double *m_d_value, *m_d_g;
     };
 
+//! Environment similarity (no reference counterpart; include/mtd_abi.h "Environment similarity"): every particle's neighbourhood compared
+//! with template environments in a fixed orientation, s = (1/N_global) sum_i h(k_i).  Domain-decomposed runs: the plain variable (one
+//! environment, no switch) only — beta of a ghost neighbour would have to be exchanged otherwise.
+class EnvironmentSimilarity : public CollectiveVariable
+    {
+    public:
+        //! templates: the environments, each a list of 3-vectors
+        EnvironmentSimilarity(std::shared_ptr<SystemDefinition> sysdef, const std::vector<std::vector<std::vector<double>>> &templates,
+                              double sigma_env, double r_cut, double r_on, double lambda, std::shared_ptr<NeighborList> nlist,
+                              unsigned int type, const std::string &log_suffix = "");
+        double getCurrentValue(unsigned int timestep) override;
+        //! device-resident: the block sums of v_i become the engine's source of this variable, no host synchronisation
+        void enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot) override;
+        void computeBiasForces(unsigned int timestep) override;
+        std::vector<std::string> getProvidedLogQuantities() override;
+        double getLogValue(const std::string &quantity, unsigned int timestep) override;
+        std::vector<double> getLocalValues(unsigned int timestep);         //!< k_i of every local particle (0 for other types)
+        std::vector<double> getEnvironmentValues(unsigned int timestep);   //!< k^e_i, N x E row-major
+        std::vector<double> getSwitchedValues(unsigned int timestep);      //!< v_i = h(k_i)
+        unsigned int getNumEnvironments() const { return m_par.n_env; }
+        double getRCut() const { return m_par.r_cut; }                     //!< what the neighbour list must reach
+        //! h(k) = x^p / (1 + x^p), x = k / c0; every change invalidates the cached step
+        void setSwitch(double c0, unsigned int p);
+        void clearSwitch();
+
+    private:
+        void computeCV(unsigned int timestep);
+        std::vector<double> readBack(const double *d_src, size_t n, const char *what, unsigned int timestep);
+        mtd_es_params m_par;
+        std::shared_ptr<NeighborList> m_nlist;
+        unsigned int m_type;
+        unsigned int m_cv_last_updated;
+        bool m_have_computed;
+        DeviceBuffer m_scratch, m_sum;
+        const double *m_d_partials, *m_d_k, *m_d_ke, *m_d_v;
+        unsigned int m_n_partials;
+    };
+
 //! AspectRatio.h / AspectRatio.cc:5-130 — box-shape CV, external virial only
 class AspectRatio : public CollectiveVariable
     {

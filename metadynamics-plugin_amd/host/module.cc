@@ -361,6 +361,28 @@ PYBIND11_MODULE(_metadynamics, m)
             return py::array_t<double>((ssize_t)v.size(), v.data());
         });
 
+    // no reference counterpart: the environment similarity against template environments
+    py::class_<EnvironmentSimilarity, CollectiveVariable, std::shared_ptr<EnvironmentSimilarity>>(m, "EnvironmentSimilarity")
+        .def(py::init<std::shared_ptr<SystemDefinition>, const std::vector<std::vector<std::vector<double>>> &, double, double, double, double,
+                      std::shared_ptr<NeighborList>, unsigned int, const std::string &>())
+        .def("getRCut", &EnvironmentSimilarity::getRCut)
+        .def("getNumEnvironments", &EnvironmentSimilarity::getNumEnvironments)
+        .def("setSwitch", &EnvironmentSimilarity::setSwitch)
+        .def("clearSwitch", &EnvironmentSimilarity::clearSwitch)
+        .def("getLocalValues", [](EnvironmentSimilarity &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getLocalValues(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        })
+        .def("getSwitchedValues", [](EnvironmentSimilarity &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getSwitchedValues(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        })
+        .def("getEnvironmentValues", [](EnvironmentSimilarity &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getEnvironmentValues(timestep);
+            const ssize_t E = (ssize_t)cv.getNumEnvironments();
+            return py::array_t<double>({(ssize_t)v.size() / E, E}, v.data());
+        });
+
     py::class_<WellTemperedEnsemble, CollectiveVariable, std::shared_ptr<WellTemperedEnsemble>>(m, "WellTemperedEnsemble")
         .def(py::init<std::shared_ptr<SystemDefinition>, const std::string &>());
 

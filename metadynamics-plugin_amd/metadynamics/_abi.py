@@ -114,6 +114,35 @@ class QlLocalBonds(C.Structure):
         return o
 
 
+MTD_ES_MAX_ENV, MTD_ES_MAX_VEC = 4, 64
+
+
+class EsParams(C.Structure):
+    """mtd_es_params: the template environments (packed one after the other), sigma_env, the window, lambda and the optional switch"""
+    _fields_ = [("n_env", C.c_uint), ("n_vec", C.c_uint * MTD_ES_MAX_ENV), ("vec", (C.c_double * 3) * MTD_ES_MAX_VEC),
+                ("sigma_env", C.c_double), ("r_on", C.c_double), ("r_cut", C.c_double), ("lam", C.c_double),
+                ("switch_on", C.c_int), ("c0", C.c_double), ("p", C.c_uint)]
+
+    @classmethod
+    def make(cls, templates, sigma_env, r_on, r_cut, lam=100.0, switch=None):
+        """templates: a list of environments, each a list of 3-vectors; switch: (c0, p) or None.  Nothing is checked here beyond the
+        capacity of the arrays: the entry points refuse what they do not take"""
+        o = cls()
+        o.n_env = len(templates)
+        k = 0
+        for e, env in enumerate(templates):
+            if e < MTD_ES_MAX_ENV:
+                o.n_vec[e] = len(env)
+            for t in env:
+                if e < MTD_ES_MAX_ENV and k < MTD_ES_MAX_VEC:
+                    o.vec[k][:] = [float(x) for x in t]
+                k += 1
+        o.sigma_env, o.r_on, o.r_cut, o.lam = float(sigma_env), float(r_on), float(r_cut), float(lam)
+        if switch is not None:
+            o.switch_on, o.c0, o.p = 1, float(switch[0]), int(switch[1])
+        return o
+
+
 _vp = C.c_void_p
 _dp = C.POINTER(C.c_double)
 _up = C.POINTER(C.c_uint)
@@ -259,6 +288,11 @@ _SIGNATURES = {
     "mtd_pe_finalize": (C.c_int, [C.POINTER(Box), C.c_double, C.c_double, C.c_uint, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp]),
     "mtd_pe_forces": (C.c_int, [C.c_uint, _vp, _vp, C.c_int, C.POINTER(Box), _vp, _vp, _vp, C.c_double, C.c_double, C.c_uint, C.c_uint, _vp, _vp,
                                  C.c_double, _vp, _vp, C.c_uint]),
+    "mtd_es_scratch_doubles": (C.c_size_t, [C.c_uint]),
+    "mtd_es_accumulate": (C.c_int, [C.c_uint, C.c_uint, _vp, C.c_int, C.POINTER(Box), _vp, _vp, _vp, C.c_uint, C.POINTER(EsParams), C.c_uint, _vp,
+                                     C.POINTER(_vp), _up, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    "mtd_es_forces": (C.c_int, [C.c_uint, C.c_uint, _vp, _vp, C.c_int, C.POINTER(Box), _vp, _vp, _vp, C.c_uint, C.POINTER(EsParams), C.c_uint, _vp,
+                                 _vp, C.c_double, _vp, _vp, C.c_uint]),
     "mtd_nlist_create": (C.c_int, [C.POINTER(_vp)]),
     "mtd_nlist_destroy": (C.c_int, [_vp]),
     "mtd_nlist_build": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp, C.c_int, C.POINTER(Box), C.c_double, C.c_int, C.c_int,

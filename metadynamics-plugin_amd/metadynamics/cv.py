@@ -399,6 +399,148 @@ class pair_entropy(_collective_variable):
         return v.copy() if per_particle else v.sum(axis=1)
 
 
+def environment_templates(structure, a):
+    """the template environments of a cubic lattice with the conventional lattice constant ``a``, for ``cv.environment_similarity``:
+    ``"fcc"`` 12 vectors of length a / sqrt(2), ``"bcc"`` 14 vectors (the 8 nearest of length a sqrt(3) / 2 and the 6 second neighbours of
+    length a, as PLUMED), ``"sc"`` 6 vectors of length a: one list of 3-vectors each; ``"diamond"``: a list of TWO environments of 4
+    vectors of length a sqrt(3) / 4, (1, 1, 1)-type and its inverse, one per sublattice"""
+    a = float(a)
+    if not 0.0 < a < float("inf"):
+        raise RuntimeError("cv.environment_templates: the lattice constant must be positive")
+
+    def family(v):
+        out = []
+        for p in ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0)):
+            for sx in (1.0, -1.0):
+                for sy in (1.0, -1.0):
+                    for sz in (1.0, -1.0):
+                        t = (sx * v[p[0]] * a + 0.0, sy * v[p[1]] * a + 0.0, sz * v[p[2]] * a + 0.0)
+                        if t not in out:
+                            out.append(t)
+        return [list(t) for t in out]
+
+    if structure == "fcc":
+        return family((0.5, 0.5, 0.0))
+    if structure == "bcc":
+        return family((0.5, 0.5, 0.5)) + family((1.0, 0.0, 0.0))
+    if structure == "sc":
+        return family((1.0, 0.0, 0.0))
+    if structure == "diamond":
+        first = [[s[0] * a / 4.0, s[1] * a / 4.0, s[2] * a / 4.0] for s in ((1, 1, 1), (1, -1, -1), (-1, 1, -1), (-1, -1, 1))]
+        return [first, [[-x + 0.0 for x in t] for t in first]]
+    raise RuntimeError("cv.environment_templates: structure must be 'fcc', 'bcc', 'sc' or 'diamond'")
+
+
+class environment_similarity(_collective_variable):
+    """this build (no reference counterpart; include/mtd_abi.h "Environment similarity"): the environment similarity kernel of Piaggi and
+    Parrinello (J. Chem. Phys. 150, 244119; PLUMED's ENVIRONMENTSIMILARITY).  Every particle's neighbourhood is compared with one or more
+    template environments, each a list of lattice vectors in the LAB frame (``cv.environment_templates``):
+    k^e_i = (1 / M_e) sum_j f(r_ij) sum_m exp(-|d_ij - T^e_m|^2 / 4 sigma_env^2), d_ij the vector from i to j, f the cosine window between
+    ``r_on`` and ``r_cut``; k_i is k^1_i or, with several environments, their smooth maximum (1 / lam) ln sum_e exp(lam k^e_i);
+    CV = (1 / N) sum_i h(k_i) with h(k) = k or, with ``switch=dict(c0=..., p=...)``, x^p / (1 + x^p), x = k / c0 — CV * N is then the
+    smooth number of particles in the template's structure AND orientation.  ``templates``: a list of 3-vectors (one environment) or a list
+    of such lists (at most 4 environments, 32 vectors each, 64 in all, every vector shorter than ``r_cut``).  Needs a full list that
+    reaches ``r_cut``.  Domain-decomposed runs: one environment without a switch only."""
+
+    def __init__(self, templates, sigma_env, r_cut, r_on, nlist, type, lam=100.0, switch=None, name=None, sigma=1.0):
+        suffix = ""
+        if name is not None:
+            suffix = "_" + name
+        _collective_variable.__init__(self, sigma, name)
+        try:
+            type_list = context.current.type_names
+            sigma_env, r_cut, r_on, lam = float(sigma_env), float(r_cut), float(r_on), float(lam)
+            envs = [[[float(x) for x in t] for t in env] for env in self._environments(templates)]
+            if type not in type_list or not 1 <= len(envs) <= 4 or sum(len(env) for env in envs) > 64 \
+                    or not 0.0 < sigma_env < float("inf") or not 0.0 <= r_on < r_cut < float("inf") or not 0.0 < lam < float("inf") \
+                    or float(nlist.r_cut) < r_cut:
+                raise ValueError
+            for env in envs:
+                if not 1 <= len(env) <= 32:
+                    raise ValueError
+                for t in env:
+                    if len(t) != 3 or not 0.0 < t[0] * t[0] + t[1] * t[1] + t[2] * t[2] < r_cut * r_cut:
+                        raise ValueError
+            sw = self._switch(switch)
+            self.type = type
+            self.nlist = nlist
+            self.templates, self.sigma_env, self.r_cut, self.r_on, self.lam = envs, sigma_env, r_cut, r_on, lam
+            self.nlist.cpp_nlist.setStorageMode(_metadynamics.NeighborList.storageMode.full)
+            self.cpp_force = _metadynamics.EnvironmentSimilarity(context.current.system_definition, envs, sigma_env, r_cut, r_on, lam,
+                                                                 nlist.cpp_nlist, type_list.index(type), suffix)
+            if sw is not None:
+                self.cpp_force.setSwitch(*sw)
+        except (TypeError, ValueError, KeyError, IndexError, AttributeError, RuntimeError):
+            context.current.forces.remove(self)                      # refused: the run must not find a half-made variable
+            raise RuntimeError("Error creating collective variable.")
+        if getattr(nlist, "device", False):
+            nlist._attach(type_list.index(type))      # a device-built list only needs the pairs of this CV's type
+
+    @staticmethod
+    def _environments(templates):
+        """a list of 3-vectors is one environment, a list of such lists several"""
+        templates = [t for t in templates]
+        if len(templates) == 0:
+            raise ValueError
+        first = [x for x in templates[0]]
+        if len(first) == 0:
+            raise ValueError
+        if hasattr(first[0], "__len__"):
+            return [[list(t) for t in env] for env in templates]
+        return [[list(t) for t in templates]]
+
+    @staticmethod
+    def _switch(switch):
+        if switch is None:
+            return None
+        sw = (float(switch["c0"]), int(switch["p"]))
+        if set(switch.keys()) != {"c0", "p"} or int(switch["p"]) != switch["p"] or not 0.0 < sw[0] < float("inf") or sw[1] < 1:
+            raise ValueError
+        return sw
+
+    def get_rcut(self):
+        """the cut-off this CV asks of the neighbour list, by type pair — only (type, type) interacts"""
+        names = context.current.type_names
+        return {(a, b): (self.r_cut if a == b == self.type else -1.0) for i, a in enumerate(names) for b in names[i:]}
+
+    def get_local(self):
+        """k_i of every particle at the current time step (0 for particles of another type)"""
+        return self.cpp_force.getLocalValues(context.current.system.getCurrentTimeStep())
+
+    def get_environments(self):
+        """k^e_i of every particle and environment at the current time step, shape (N, E)"""
+        return self.cpp_force.getEnvironmentValues(context.current.system.getCurrentTimeStep())
+
+    def get_switched(self):
+        """v_i = h(k_i) of every particle at the current time step: what the CV averages (k_i itself without a switch)"""
+        return self.cpp_force.getSwitchedValues(context.current.system.getCurrentTimeStep())
+
+    def set_switch(self, switch):
+        """``dict(c0=..., p=...)`` or ``None`` (no switch); takes effect with the next step"""
+        try:
+            sw = self._switch(switch)
+            if sw is None:
+                self.cpp_force.clearSwitch()
+            else:
+                self.cpp_force.setSwitch(*sw)
+        except (TypeError, KeyError, ValueError, AttributeError, RuntimeError):
+            raise RuntimeError("Error creating collective variable.")
+
+    def get_virial(self, per_particle=False):
+        """the virial of the bias force the last step wrote (include/mtd_abi.h, mtd_es_forces): the six sums xx, xy, xz, yy, yz, zz as
+        float64, or with ``per_particle=True`` the (6, N) array, half of every entry at each of its ends.  The sums are -bias * dCV/d(eps_ab)
+        under x_a += eps x_b of positions and box with the templates held fixed: the tensor is NOT symmetric, and xy, xz, yz are the
+        off-diagonals a HOOMD box can deform along.  It is formed only while the pressure flag of the particle data is set; without the flag
+        this raises."""
+        pdata = context.current.system_definition.getParticleData()
+        if not pdata.getPressureFlag():
+            raise RuntimeError("cv.environment_similarity: the virial is computed only while the pressure flag is set")
+        import numpy as np
+        n = pdata.getN()
+        v = np.asarray(self.cpp_force.getVirial(), dtype=np.float64)[:, :n]
+        return v.copy() if per_particle else v.sum(axis=1)
+
+
 class nlist_cell(object):
     """Stand-in for ``hoomd.md.nlist.cell``: HOOMD's NeighborList is not part of the plugin.
 
