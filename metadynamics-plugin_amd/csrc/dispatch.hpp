@@ -8,6 +8,7 @@
 #include "mtd_abi.h"
 
 #include <cassert>
+#include <cstdint>
 #include <type_traits>
 
 namespace mtd
@@ -47,5 +48,19 @@ template<typename F> auto dispatch_lmax(unsigned int lmax, F &&f)
     if (lmax <= 6) return f(std::integral_constant<int, 6>{});
     if (lmax <= 8) return f(std::integral_constant<int, 8>{});
     return f(std::integral_constant<int, 12>{});
+    }
+
+// What every entry point that walks a neighbour list over an S4 array refuses before a device is touched: a missing array while there
+// are particles (`pointers`: the caller's conjunction of the ones it needs), an unknown dtype, a scratch that is not 16-byte aligned, a
+// virial array with a pitch below n_particles.  All four give MTD_ERR_INVALID_ARGUMENT, so their order among themselves cannot be seen
+// from outside; WHERE the caller asks, before or after its own MTD_ERR_UNSUPPORTED refusals, can, and stays the caller's business.
+inline int refuse_row_arrays(unsigned int n_particles, bool pointers, int dtype, const void *d_scratch, const void *d_virial,
+                             unsigned int virial_pitch)
+    {
+    if (n_particles && !pointers) return MTD_ERR_INVALID_ARGUMENT;
+    if (dtype != MTD_F32 && dtype != MTD_F64) return MTD_ERR_INVALID_ARGUMENT;
+    if (((uintptr_t)d_scratch & 15u) != 0) return MTD_ERR_INVALID_ARGUMENT;
+    if (d_virial && virial_pitch < n_particles) return MTD_ERR_INVALID_ARGUMENT;
+    return MTD_SUCCESS;
     }
 }

@@ -8,13 +8,14 @@
 //     B_e(d) = f' (d / r) S_e - f (S_e d - V_e) / (2 sigma_env^2),   S_e = sum_m phi_m,  V_e = sum_m phi_m T^e_m
 //     G_kj = sum_e [ -beta^e_k B_e(d_kj) + beta^e_j B_e(-d_kj) ] / M_e,   N_global ds/dr_k = sum_{j in row k} G_kj
 // with f the cosine window of steinhardt_device.hpp between r_on and r_cut.  Smoothing, minimum image, particle loads and the type test are
-// those of the Steinhardt units (QlArgs<4>, smoothing_tab, min_image); launches go through dispatch.hpp.
+// those of the Steinhardt units (QlArgs<4>, smoothing_tab, min_image); the walk over a row, its centre, the group's sum and the store of
+// force and virial are those of row_walk.hpp; launches and the shared refusals go through dispatch.hpp.
 //
 // MI355X design.  Two launches per step, fp64 arithmetic over fp32 or fp64 arrays, ONE walk over the rows for the plain
 // variable with a closed environment and two otherwise:
 //   lanes            FOUR lanes (a DPP quad) per central particle, 64 central particles per block and round; lane q takes entries q, q + 4,
 //                    ... of the row (rows hold ~17 entries at r_cut 1.5: 5 trips per lane, 85 % of the lanes' trips used where eight lanes
-//                    use 71 %), list entry two trips and neighbour position one trip ahead of the arithmetic, as the walk of pair_entropy.hip
+//                    use 71 %), list entry two trips and neighbour position one trip ahead of the arithmetic: row_walk of row_walk.hpp
 //   the table        (T_x, T_y, T_z, |T|^2) of the <= 64 template vectors arrives in the kernel arguments and is copied to LDS once per
 //                    block (2 KB); the loop over m has the same trip count in every lane and reads one vector as one 32-byte broadcast:
 //                    |d - T|^2 = r^2 + |T|^2 - 2 d.T is three FMAs and an add
@@ -31,7 +32,7 @@
 //                    (CONSTB; ghost neighbours then need no table).  Fixed summation order, no atomics; the four lanes' sums are added by
 //                    two DPP moves.  VIR adds the six sums -1/2 G_a d_b; VIR = false is the kernel without them
 #include "mtd_device.hpp"
-#include "steinhardt_device.hpp"
+#include "row_walk.hpp"
 #include "dispatch.hpp"
 
 #include <cmath>
@@ -47,7 +48,6 @@ constexpr int ES_G = 4;                                    // lanes per central 
 constexpr int ES_PPB = ES_THREADS / ES_G;                  // central particles per block and round
 constexpr unsigned int ES_MAX_BLOCKS = 1024;               // block sums in the scratch
 constexpr unsigned int ES_MAX_PER_ENV = 32;
-constexpr unsigned int ES_NONE = 0xffffffffu;
 
 // the scratch, in doubles, with n = n_particles rounded up to even:
 //     k^e_i [n][4] | beta^e_i [n][4] | k_i [n] | v_i [n] | block sums [ES_MAX_BLOCKS] | FUSED: sum_j G_kj and sum_j G_a d_b [9][n]
@@ -70,96 +70,6 @@ struct EsTable
     {
     double4 t[MTD_ES_MAX_VEC];                             // (T_x, T_y, T_z, |T|^2)
     };
-
-template<typename S4> __device__ __forceinline__ S4 es_zero();
-template<> __device__ __forceinline__ float4 es_zero<float4>() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-template<> __device__ __forceinline__ double4 es_zero<double4>() { return make_double4(0.0, 0.0, 0.0, 0.0); }
-
-// a wave-uniform constant moved into a vector register (pair_entropy.hip: the pair passes run out of scalar registers, not of vector ones)
-__device__ __forceinline__ double in_vgpr(double v)
-    {
-    asm volatile("" : "+v"(v));
-    return v;
-    }
-
-__device__ __forceinline__ QlArgs<4> in_vgpr(QlArgs<4> a)
-    {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) a.L[k] = in_vgpr(a.L[k]), a.Linv[k] = in_vgpr(a.Linv[k]);
-    a.xy = in_vgpr(a.xy), a.xz = in_vgpr(a.xz), a.yz = in_vgpr(a.yz);
-    a.rcutsq = in_vgpr(a.rcutsq), a.ronsq = in_vgpr(a.ronsq), a.r_on = in_vgpr(a.r_on), a.inv_width = in_vgpr(a.inv_width);
-    return a;
-    }
-
-// sum over the four lanes of a particle (a DPP quad), the same bits in all four
-__device__ __forceinline__ double quad_sum(double v)
-    {
-    v += dpp_move<MTD_DPP_QUAD_XOR1>(v);
-    v += dpp_move<MTD_DPP_QUAD_XOR2>(v);
-    return v;
-    }
-
-// the central particle of a lane group: its row is empty for i >= N and for a particle of another type
-struct EsCentre
-    {
-    unsigned int i;
-    Particle p;
-    unsigned int start, cnt;
-    };
-
-template<typename S4>
-__device__ __forceinline__ EsCentre es_centre(const QlArgs<4> &a, const S4 *postype, const unsigned int *head_list, const unsigned int *n_neigh,
-                                              const unsigned int i)
-    {
-    Particle p = {0.0, 0.0, 0.0, -1};
-    unsigned int start = 0, cnt = 0;
-    if (i < a.N)
-        {
-        p = scalar4_traits<S4>::load(postype, i);
-        if ((unsigned int)p.type == a.type)
-            {
-            start = head_list[i];
-            cnt = n_neigh[i];
-            }
-        }
-    return {i, p, start, cnt};
-    }
-
-// The walk over one row: calls body(tab, j, dx, dy, dz, rsq), d = minImage(r_j - r_i), for every entry of lane q that takes part.
-// Neighbour indices are NOT compared with N: entries may address ghost particles stored behind the local ones; only the particle itself
-// is skipped.  The smoothing table is handed on behind a zero the compiler cannot see through (pair_entropy.hip: its coefficients are
-// then loaded where the window is evaluated, not held in scalar registers across the walk).
-template<typename S4, typename F>
-__device__ __forceinline__ void es_row(const QlArgs<4> &a, const S4 *__restrict__ postype, const unsigned int *__restrict__ nlist,
-                                       const double *__restrict__ tab, const EsCentre &c, const unsigned int q, F &&body)
-    {
-    unsigned int e = q;
-    unsigned int j0 = e < c.cnt ? nlist[c.start + e] : ES_NONE;
-    unsigned int j1 = e + ES_G < c.cnt ? nlist[c.start + e + ES_G] : ES_NONE;
-    S4 pos0 = es_zero<S4>();
-    if (j0 != ES_NONE) pos0 = postype[j0];
-#pragma unroll 1
-    for (; e < c.cnt; e += ES_G)
-        {
-        unsigned int tab_shift = 0;
-        asm volatile("" : "+s"(tab_shift));
-        const double *__restrict__ tab_k = tab + tab_shift;
-        const unsigned int j2 = e + 2 * ES_G < c.cnt ? nlist[c.start + e + 2 * ES_G] : ES_NONE;
-        S4 pos1 = es_zero<S4>();
-        if (j1 != ES_NONE) pos1 = postype[j1];
-        if (j0 != c.i)
-            {
-            const Particle pj = scalar4_traits<S4>::unpack(pos0);
-            double dx = pj.x - c.p.x, dy = pj.y - c.p.y, dz = pj.z - c.p.z;
-            min_image(a, dx, dy, dz);
-            const double rsq = dx * dx + dy * dy + dz * dz;
-            if ((unsigned int)pj.type == a.type && rsq <= a.rcutsq) body(tab_k, j0, dx, dy, dz, rsq);
-            }
-        j0 = j1;
-        j1 = j2;
-        pos0 = pos1;
-        }
-    }
 
 // x^n for a wave-uniform n (binary powering: at most 32 trips of a scalar loop)
 __device__ __forceinline__ double es_powi(double x, unsigned int n)
@@ -242,7 +152,7 @@ __global__ __launch_bounds__(ES_THREADS) void k_es_accumulate(const QlArgs<4> a_
     {
     __shared__ double4 s_t[MTD_ES_MAX_VEC];
     __shared__ double s_red[16];
-    const QlArgs<4> a = in_vgpr(a_in);
+    const QlArgs<4> a = in_vgpr_window(a_in);
     const double neg_inv4s2 = in_vgpr(p.neg_inv4s2), cs = in_vgpr(p.c);
     const unsigned int tid = threadIdx.x, g = tid / ES_G, q = tid % ES_G;
     const unsigned int n_chunks = (a.N + ES_PPB - 1) / ES_PPB;
@@ -257,10 +167,10 @@ __global__ __launch_bounds__(ES_THREADS) void k_es_accumulate(const QlArgs<4> a_
     // the literals of its logarithm and exponentials are not held in scalar registers across the walk (they spilled)
     for (unsigned int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
         {
-        const EsCentre c = es_centre(a, postype, head_list, n_neigh, chunk * ES_PPB + g);
+        const RowCentre c = row_centre(a, postype, head_list, n_neigh, chunk * ES_PPB + g);
         double ke[MTD_ES_MAX_ENV] = {0.0, 0.0, 0.0, 0.0};
         double gs[ES_N_GSUMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};     // FUSED: G_x G_y G_z and G_a d_b for xx xy xz yy yz zz
-        es_row(a, postype, nlist, tab, c, q, [&](const double *tab_k, const unsigned int, const double dx, const double dy, const double dz,
+        row_walk<ES_G, false>(a, postype, nlist, tab, c, q, [&](const double *tab_k, const unsigned int, const double dx, const double dy, const double dz,
                                                  const double rsq)
             {
             const double inv_r = rsqrt(rsq);
@@ -290,7 +200,7 @@ __global__ __launch_bounds__(ES_THREADS) void k_es_accumulate(const QlArgs<4> a_
                 }
             });
 #pragma unroll
-        for (int u = 0; u < MTD_ES_MAX_ENV; ++u) ke[u] = quad_sum(ke[u]) * p.inv_m[u];             // (1 / M_e is 0 for e >= E)
+        for (int u = 0; u < MTD_ES_MAX_ENV; ++u) ke[u] = group_sum<ES_G>(ke[u]) * p.inv_m[u];             // (1 / M_e is 0 for e >= E)
         if (q == 0 && c.i < a.N)
             {
 #pragma unroll
@@ -299,7 +209,7 @@ __global__ __launch_bounds__(ES_THREADS) void k_es_accumulate(const QlArgs<4> a_
         if constexpr (FUSED)
             {
 #pragma unroll
-            for (int u = 0; u < ES_N_GSUMS; ++u) gs[u] = quad_sum(gs[u]);
+            for (int u = 0; u < ES_N_GSUMS; ++u) gs[u] = group_sum<ES_G>(gs[u]);
             if (q == 0 && c.i < a.N)
                 {
 #pragma unroll
@@ -390,7 +300,7 @@ __global__ __launch_bounds__(ES_THREADS) void k_es_forces(const QlArgs<4> a_in, 
     {
     typedef typename scalar4_traits<S4>::scalar scalar;
     __shared__ double4 s_t[MTD_ES_MAX_VEC];
-    const QlArgs<4> a = in_vgpr(a_in);
+    const QlArgs<4> a = in_vgpr_window(a_in);
     const double neg_inv4s2 = in_vgpr(p.neg_inv4s2), cs = in_vgpr(p.c);
     const unsigned int tid = threadIdx.x, g = tid / ES_G, q = tid % ES_G;
     const unsigned int n_chunks = (a.N + ES_PPB - 1) / ES_PPB;
@@ -403,7 +313,7 @@ __global__ __launch_bounds__(ES_THREADS) void k_es_forces(const QlArgs<4> a_in, 
     if constexpr (VIR) asm volatile("" : "+v"(virial));
     for (unsigned int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
         {
-        const EsCentre c = es_centre(a, postype, head_list, n_neigh, chunk * ES_PPB + g);
+        const RowCentre c = row_centre(a, postype, head_list, n_neigh, chunk * ES_PPB + g);
         double bk[MTD_ES_MAX_ENV] = {1.0, 1.0, 1.0, 1.0};
         if constexpr (!CONSTB)
             {
@@ -415,7 +325,7 @@ __global__ __launch_bounds__(ES_THREADS) void k_es_forces(const QlArgs<4> a_in, 
             }
         double Fx = 0.0, Fy = 0.0, Fz = 0.0;
         double vxx = 0.0, vxy = 0.0, vxz = 0.0, vyy = 0.0, vyz = 0.0, vzz = 0.0;
-        es_row(a, postype, nlist, tab, c, q, [&](const double *tab_k, const unsigned int j, const double dx, const double dy, const double dz,
+        row_walk<ES_G, false>(a, postype, nlist, tab, c, q, [&](const double *tab_k, const unsigned int j, const double dx, const double dy, const double dz,
                                                  const double rsq)
             {
             const double inv_r = rsqrt(rsq);
@@ -443,32 +353,23 @@ __global__ __launch_bounds__(ES_THREADS) void k_es_forces(const QlArgs<4> a_in, 
                 vyy += gy * dy, vyz += gy * dz, vzz += gz * dz;
                 }
             });
-        Fx = quad_sum(Fx);
-        Fy = quad_sum(Fy);
-        Fz = quad_sum(Fz);
+        Fx = group_sum<ES_G>(Fx);
+        Fy = group_sum<ES_G>(Fy);
+        Fz = group_sum<ES_G>(Fz);
         if (q == 0 && c.i < a.N)
             nt_store(scalar4_traits<S4>::make((scalar)(Fx * scale), (scalar)(Fy * scale), (scalar)(Fz * scale), (scalar)0), force + c.i);
         if constexpr (VIR)
             {
-            vxx = quad_sum(vxx), vxy = quad_sum(vxy), vxz = quad_sum(vxz);
-            vyy = quad_sum(vyy), vyz = quad_sum(vyz), vzz = quad_sum(vzz);
-            if (q == 0 && c.i < a.N)
-                {
-                const double h = -0.5 * scale;
-                scalar *v = virial + c.i;
-                nt_store((scalar)(vxx * h), v);
-                nt_store((scalar)(vxy * h), v + virial_pitch);
-                nt_store((scalar)(vxz * h), v + 2 * (size_t)virial_pitch);
-                nt_store((scalar)(vyy * h), v + 3 * (size_t)virial_pitch);
-                nt_store((scalar)(vyz * h), v + 4 * (size_t)virial_pitch);
-                nt_store((scalar)(vzz * h), v + 5 * (size_t)virial_pitch);
-                }
+            vxx = group_sum<ES_G>(vxx), vxy = group_sum<ES_G>(vxy), vxz = group_sum<ES_G>(vxz);
+            vyy = group_sum<ES_G>(vyy), vyz = group_sum<ES_G>(vyz), vzz = group_sum<ES_G>(vzz);
+            if (q == 0 && c.i < a.N) row_store_virial<false>(virial + c.i, virial_pitch, vxx, vxy, vxz, vyy, vyz, vzz, -0.5 * scale, 0.0);
             }
         }
     }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
-// what both entry points check before a device is touched, and the kernel arguments they share
+// what both entry points check before a device is touched, after refuse_row_arrays (dtype, arrays, alignment of the scratch, virial pitch:
+// all invalid arguments, as everything here ahead of the first unsupported one), and the kernel arguments they share
 struct EsSetup
     {
     QlArgs<4> a;
@@ -477,12 +378,10 @@ struct EsSetup
     bool closed, const_beta;
     };
 
-int es_setup(EsSetup &s, unsigned int n_particles, unsigned int n_ghost, int dtype, const mtd_box *box, unsigned int type,
+int es_setup(EsSetup &s, unsigned int n_particles, unsigned int n_ghost, const mtd_box *box, unsigned int type,
              const mtd_es_params *par, unsigned int n_global, const double *d_scratch)
     {
     if (!box || !par || !d_scratch) return MTD_ERR_INVALID_ARGUMENT;
-    if (dtype != MTD_F32 && dtype != MTD_F64) return MTD_ERR_INVALID_ARGUMENT;
-    if (((uintptr_t)d_scratch & 15u) != 0) return MTD_ERR_INVALID_ARGUMENT;
     if (n_global == 0) return MTD_ERR_INVALID_ARGUMENT;
     if (par->n_env == 0) return MTD_ERR_INVALID_ARGUMENT;
     if (par->n_env > MTD_ES_MAX_ENV) return MTD_ERR_UNSUPPORTED;
@@ -543,13 +442,6 @@ int es_setup(EsSetup &s, unsigned int n_particles, unsigned int n_ghost, int dty
     return MTD_SUCCESS;
     }
 
-unsigned int es_blocks(const unsigned int N)
-    {
-    unsigned int b = (N + ES_PPB - 1) / ES_PPB;
-    if (b < 1) b = 1;
-    return b > ES_MAX_BLOCKS ? ES_MAX_BLOCKS : b;
-    }
-
 } // namespace
 
 extern "C" {
@@ -565,14 +457,15 @@ int mtd_es_accumulate(unsigned int n_particles, unsigned int n_ghost, const void
                       const double **d_k, const double **d_ke, const double **d_v, mtd_stream_t stream)
     {
     if (!d_partials || !n_partials) return MTD_ERR_INVALID_ARGUMENT;
-    if (n_particles && (!d_postype || !d_head_list || !d_n_neigh)) return MTD_ERR_INVALID_ARGUMENT;
+    int rc = refuse_row_arrays(n_particles, d_postype && d_head_list && d_n_neigh, dtype, d_scratch, nullptr, 0);
+    if (rc) return rc;
     EsSetup su;
-    int rc = es_setup(su, n_particles, n_ghost, dtype, box, type, params, n_global, d_scratch);
+    rc = es_setup(su, n_particles, n_ghost, box, type, params, n_global, d_scratch);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const double *tab = ql_device_table<4>(s, rc);
     if (rc) return rc;
-    const unsigned int blocks = es_blocks(n_particles);
+    const unsigned int blocks = row_blocks(n_particles, ES_PPB, ES_MAX_BLOCKS);
     // beta = 1 everywhere and the environment closed: the walk of this pass also forms the gradient sums (FUSED)
     dispatch_s4(dtype, [&](auto t)
         {
@@ -599,16 +492,16 @@ int mtd_es_forces(unsigned int n_particles, unsigned int n_ghost, const void *d_
                   const mtd_es_params *params, unsigned int n_global, const double *d_scratch, const double *d_bias, double bias_host,
                   mtd_stream_t stream, void *d_virial, unsigned int virial_pitch)
     {
-    if (n_particles && (!d_postype || !d_head_list || !d_n_neigh || !d_force)) return MTD_ERR_INVALID_ARGUMENT;
-    if (d_virial && virial_pitch < n_particles) return MTD_ERR_INVALID_ARGUMENT;
+    int rc = refuse_row_arrays(n_particles, d_postype && d_head_list && d_n_neigh && d_force, dtype, d_scratch, d_virial, virial_pitch);
+    if (rc) return rc;
     EsSetup su;
-    int rc = es_setup(su, n_particles, n_ghost, dtype, box, type, params, n_global, d_scratch);
+    rc = es_setup(su, n_particles, n_ghost, box, type, params, n_global, d_scratch);
     if (rc) return rc;
     if (n_particles == 0) return MTD_SUCCESS;
     hipStream_t s = (hipStream_t)stream;
     const double *tab = ql_device_table<4>(s, rc);
     if (rc) return rc;
-    const unsigned int blocks = es_blocks(n_particles);
+    const unsigned int blocks = row_blocks(n_particles, ES_PPB, ES_MAX_BLOCKS);
     dispatch_s4(dtype, [&](auto t)
         {
         return dispatch_bool(d_virial != nullptr, [&](auto vir)

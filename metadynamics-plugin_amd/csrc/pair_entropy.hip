@@ -7,12 +7,13 @@
 //     g_b = H_b / (4 pi N_t rho r_b^2),   S = -2 pi rho Delta sum_b r_b^2 (g ln g - g + 1)        (g < 1e-10: the bin counts as 1)
 //     W_b = dS/dH_b = -Delta ln g_b / (2 N_t),   u = sum_b W_b K_b [f' + f (r_b - r) / sigma^2],   dS/dr_k = 2 sum_{j in row k} u d / r
 // with f the cosine window of steinhardt_device.hpp between r_max + 3 sigma and r_cut.  Smoothing, minimum image, particle loads and the
-// type test are those of the Steinhardt units (QlArgs<4>, smoothing_tab, min_image); launches go through dispatch.hpp.
+// type test are those of the Steinhardt units (QlArgs<4>, smoothing_tab, min_image); the walk over a row, its centre, the group's sum and
+// the store of force and virial are those of row_walk.hpp; launches and the shared refusals go through dispatch.hpp.
 //
 // MI355X design.  Four launches per step, all in fp64 arithmetic over fp32 or fp64 arrays:
 //   lanes            EIGHT lanes (half a DPP row) per central particle, 32 central particles per block and round; lane q takes entries
 //                    q, q + 8, ... of the row (rows hold ~80-100 entries: 10-13 trips per lane), list entry two trips and neighbour
-//                    position one trip ahead of the arithmetic, as the walk of steinhardt_local.hip
+//                    position one trip ahead of the arithmetic: row_walk of row_walk.hpp
 //   the window       two exponentials per entry, K_c = K(r_c - r) at the centre bin c and e = exp(-(r_c - r) Delta / sigma^2); then
 //                    K_{b+1} = K_b q_b, q_{b+1} = q_b s^2 upwards from q_c = e s and K_{b-1} = K_b p_b, p_{b-1} = p_b s^2 downwards from
 //                    p_c = s / e, s = exp(-Delta^2 / 2 sigma^2): every factor is <= 1, the recurrence never amplifies.  Both chains advance
@@ -35,7 +36,7 @@
 // (E_blk <= 4000, K(0) = 4 .. 8, n <= 216) that is below 1e-8 absolute on H of 1e3 .. 1e5: under 1e-11 relative.  Two identical calls
 // give identical bits: integer adds inside a block, fixed orders everywhere else.
 #include "mtd_device.hpp"
-#include "steinhardt_device.hpp"
+#include "row_walk.hpp"
 #include "dispatch.hpp"
 
 #include <cmath>
@@ -51,7 +52,6 @@ constexpr int PE_G = 8;                                    // lanes per central 
 constexpr int PE_PPB = PE_THREADS / PE_G;                  // central particles per block and round
 constexpr unsigned int PE_MAX_BINS = 256;
 constexpr unsigned int PE_MAX_BLOCKS = 1024;               // columns of block sums in the scratch
-constexpr unsigned int PE_NONE = 0xffffffffu;
 constexpr double PE_G_MIN = 1e-10;
 
 // the scratch, in doubles: sums [258] | value, explicit volume derivative, N_t, (pad) [4] | g [256] | (W_b, W_b r_b) [256][2] | block sums [257][PE_MAX_BLOCKS]
@@ -69,103 +69,12 @@ struct PeArgs
     unsigned int trips, _pad;                              // min(w, the largest centre bin + 1): beyond it both chains are off the table
     };
 
-template<typename S4> __device__ __forceinline__ S4 pe_zero();
-template<> __device__ __forceinline__ float4 pe_zero<float4>() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-template<> __device__ __forceinline__ double4 pe_zero<double4>() { return make_double4(0.0, 0.0, 0.0, 0.0); }
-
-// A wave-uniform constant moved into a vector register: the pair passes hold the box, the window, the bin constants, nine pointers, the
-// literals of two exponentials and the masks of four nested branches — more than the 102 scalar registers of a wave, and the surplus was
-// spilled.  Vector registers are not short here; what the per-bin loop multiplies with lives there.
-__device__ __forceinline__ double in_vgpr(double v)
-    {
-    asm volatile("" : "+v"(v));
-    return v;
-    }
-
-__device__ __forceinline__ PeArgs in_vgpr(PeArgs p)
+// the bin constants beside the box (row_walk.hpp, in_vgpr): what the per-bin loop multiplies with lives in vector registers
+__device__ __forceinline__ PeArgs pe_in_vgpr(PeArgs p)
     {
     p.delta = in_vgpr(p.delta), p.inv_delta = in_vgpr(p.inv_delta), p.inv_s2 = in_vgpr(p.inv_s2), p.neg_half_inv_s2 = in_vgpr(p.neg_half_inv_s2);
     p.k0 = in_vgpr(p.k0), p.s = in_vgpr(p.s), p.s2 = in_vgpr(p.s2);
     return p;
-    }
-
-__device__ __forceinline__ QlArgs<4> in_vgpr(QlArgs<4> a)
-    {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) a.L[k] = in_vgpr(a.L[k]), a.Linv[k] = in_vgpr(a.Linv[k]);
-    a.xy = in_vgpr(a.xy), a.xz = in_vgpr(a.xz), a.yz = in_vgpr(a.yz);
-    return a;
-    }
-
-// sum over the eight lanes of a particle (half a DPP row), the same bits in all eight
-__device__ __forceinline__ double oct_sum(double v)
-    {
-    v += dpp_move<MTD_DPP_QUAD_XOR1>(v);
-    v += dpp_move<MTD_DPP_QUAD_XOR2>(v);
-    v += dpp_move<MTD_DPP_ROW_HALF_MIRROR>(v);
-    return v;
-    }
-
-// the central particle of a lane group: its row is empty for i >= N and for a particle of another type
-struct PeCentre
-    {
-    unsigned int i;
-    Particle p;
-    unsigned int start, cnt;
-    };
-
-template<typename S4>
-__device__ __forceinline__ PeCentre pe_centre(const QlArgs<4> &a, const S4 *postype, const unsigned int *head_list, const unsigned int *n_neigh,
-                                              const unsigned int i)
-    {
-    Particle p = {0.0, 0.0, 0.0, -1};
-    unsigned int start = 0, cnt = 0;
-    if (i < a.N)
-        {
-        p = scalar4_traits<S4>::load(postype, i);
-        if ((unsigned int)p.type == a.type)
-            {
-            start = head_list[i];
-            cnt = n_neigh[i];
-            }
-        }
-    return {i, p, start, cnt};
-    }
-
-// The walk over one row: calls body(tab, dx, dy, dz, rsq) for every entry of lane q that takes part.  Neighbour indices are NOT compared
-// with N: entries may address ghost particles stored behind the local ones (mtd_ql_accumulate_local); only the particle itself is skipped.
-// The table of the smoothing polynomial is handed on with a zero added that the compiler cannot see through, so that its twenty
-// coefficients are loaded where the window is evaluated and not held in scalar registers across the walk (they spilled).
-template<typename S4, typename F>
-__device__ __forceinline__ void pe_row(const QlArgs<4> &a, const S4 *__restrict__ postype, const unsigned int *__restrict__ nlist,
-                                       const double *__restrict__ tab, const PeCentre &c, const unsigned int q, F &&body)
-    {
-    unsigned int e = q;
-    unsigned int j0 = e < c.cnt ? nlist[c.start + e] : PE_NONE;
-    unsigned int j1 = e + PE_G < c.cnt ? nlist[c.start + e + PE_G] : PE_NONE;
-    S4 pos0 = pe_zero<S4>();
-    if (j0 != PE_NONE) pos0 = postype[j0];
-#pragma unroll 1
-    for (; e < c.cnt; e += PE_G)
-        {
-        unsigned int tab_shift = 0;
-        asm volatile("" : "+s"(tab_shift));
-        const double *__restrict__ tab_k = tab + tab_shift;
-        const unsigned int j2 = e + 2 * PE_G < c.cnt ? nlist[c.start + e + 2 * PE_G] : PE_NONE;
-        S4 pos1 = pe_zero<S4>();
-        if (j1 != PE_NONE) pos1 = postype[j1];
-        if (j0 != c.i)
-            {
-            const Particle pj = scalar4_traits<S4>::unpack(pos0);
-            double dx = c.p.x - pj.x, dy = c.p.y - pj.y, dz = c.p.z - pj.z;
-            min_image(a, dx, dy, dz);
-            const double rsq = dx * dx + dy * dy + dz * dz;
-            if ((unsigned int)pj.type == a.type && rsq <= a.rcutsq) body(tab_k, dx, dy, dz, rsq);
-            }
-        j0 = j1;
-        j1 = j2;
-        pos0 = pos1;
-        }
     }
 
 // The window of one entry at distance r: calls bin(b, K_b) for the centre bin c, then for c + t and c - t, t = 1 .. trips, both chains of
@@ -201,7 +110,7 @@ __global__ __launch_bounds__(PE_THREADS) void k_pe_accumulate(const QlArgs<4> a_
     __shared__ unsigned long long s_h[PE_MAX_BINS + 1];
     __shared__ double s_red[16];
     const QlArgs<4> a = in_vgpr(a_in);
-    const PeArgs p = in_vgpr(p_in);
+    const PeArgs p = pe_in_vgpr(p_in);
     const unsigned int tid = threadIdx.x, g = tid / PE_G, q = tid % PE_G;
     const unsigned int n_chunks = (a.N + PE_PPB - 1) / PE_PPB;
     for (unsigned int b = tid; b <= PE_MAX_BINS; b += PE_THREADS) s_h[b] = 0ull;
@@ -218,9 +127,9 @@ __global__ __launch_bounds__(PE_THREADS) void k_pe_accumulate(const QlArgs<4> a_
     const double scale = ldexp(1.0, 62 - ex), inv_scale = ldexp(1.0, ex - 62);
     for (unsigned int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
         {
-        const PeCentre c = pe_centre(a, postype, head_list, n_neigh, chunk * PE_PPB + g);
+        const RowCentre c = row_centre(a, postype, head_list, n_neigh, chunk * PE_PPB + g);
         if (q == 0 && c.i < a.N && (unsigned int)c.p.type == a.type) atomicAdd(&s_h[p.B], 1ull);
-        pe_row(a, postype, nlist, tab, c, q, [&](const double *tab_k, const double, const double, const double, const double rsq)
+        row_walk<PE_G, true>(a, postype, nlist, tab, c, q, [&](const double *tab_k, const unsigned int, const double, const double, const double, const double rsq)
             {
             const double inv_r = rsqrt(rsq);
             double f, fprime_divr;
@@ -300,7 +209,7 @@ __global__ __launch_bounds__(PE_THREADS) void k_pe_forces(const QlArgs<4> a_in, 
     typedef typename scalar4_traits<S4>::scalar scalar;
     __shared__ double2 s_w[PE_MAX_BINS + 2];                  // (W_b, W_b r_b) at [b + 1]; [0] and [B + 1] are zero: where a bin off the table is read
     const QlArgs<4> a = in_vgpr(a_in);
-    const PeArgs p = in_vgpr(p_in);
+    const PeArgs p = pe_in_vgpr(p_in);
     const unsigned int tid = threadIdx.x, g = tid / PE_G, q = tid % PE_G;
     const unsigned int n_chunks = (a.N + PE_PPB - 1) / PE_PPB;
     for (unsigned int b = tid; b < PE_MAX_BINS + 2; b += PE_THREADS)
@@ -312,10 +221,10 @@ __global__ __launch_bounds__(PE_THREADS) void k_pe_forces(const QlArgs<4> a_in, 
     __syncthreads();
     for (unsigned int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
         {
-        const PeCentre c = pe_centre(a, postype, head_list, n_neigh, chunk * PE_PPB + g);
+        const RowCentre c = row_centre(a, postype, head_list, n_neigh, chunk * PE_PPB + g);
         double Fx = 0.0, Fy = 0.0, Fz = 0.0;
         double vxx = 0.0, vxy = 0.0, vxz = 0.0, vyy = 0.0, vyz = 0.0, vzz = 0.0;
-        pe_row(a, postype, nlist, tab, c, q, [&](const double *tab_k, const double dx, const double dy, const double dz, const double rsq)
+        row_walk<PE_G, true>(a, postype, nlist, tab, c, q, [&](const double *tab_k, const unsigned int, const double dx, const double dy, const double dz, const double rsq)
             {
             const double inv_r = rsqrt(rsq), r = rsq * inv_r;
             double f, fprime_divr;
@@ -340,33 +249,26 @@ __global__ __launch_bounds__(PE_THREADS) void k_pe_forces(const QlArgs<4> a_in, 
                 vyy += dy * gy, vyz += dy * gz, vzz += dz * gz;
                 }
             });
-        Fx = oct_sum(Fx);
-        Fy = oct_sum(Fy);
-        Fz = oct_sum(Fz);
+        Fx = group_sum<PE_G>(Fx);
+        Fy = group_sum<PE_G>(Fy);
+        Fz = group_sum<PE_G>(Fz);
         if (q == 0 && c.i < a.N)
             nt_store(scalar4_traits<S4>::make((scalar)(Fx * scale), (scalar)(Fy * scale), (scalar)(Fz * scale), (scalar)0), force + c.i);
         if constexpr (VIR)
             {
-            vxx = oct_sum(vxx), vxy = oct_sum(vxy), vxz = oct_sum(vxz);
-            vyy = oct_sum(vyy), vyz = oct_sum(vyz), vzz = oct_sum(vzz);
-            if (q == 0 && c.i < a.N)
-                {
-                const double h = 0.5 * scale;
-                const double d = (unsigned int)c.p.type == a.type ? scale * diag : 0.0;
-                scalar *v = virial + c.i;
-                nt_store((scalar)(vxx * h + d), v);
-                nt_store((scalar)(vxy * h), v + virial_pitch);
-                nt_store((scalar)(vxz * h), v + 2 * (size_t)virial_pitch);
-                nt_store((scalar)(vyy * h + d), v + 3 * (size_t)virial_pitch);
-                nt_store((scalar)(vyz * h), v + 4 * (size_t)virial_pitch);
-                nt_store((scalar)(vzz * h + d), v + 5 * (size_t)virial_pitch);
-                }
+            vxx = group_sum<PE_G>(vxx), vxy = group_sum<PE_G>(vxy), vxz = group_sum<PE_G>(vxz);
+            vyy = group_sum<PE_G>(vyy), vyz = group_sum<PE_G>(vyz), vzz = group_sum<PE_G>(vzz);
+            if (q == 0 && c.i < a.N)                             // (the explicit diagonal term: a particle of the type)
+                row_store_virial<true>(virial + c.i, virial_pitch, vxx, vxy, vxz, vyy, vyz, vzz, 0.5 * scale,
+                                       (unsigned int)c.p.type == a.type ? scale * diag : 0.0);
             }
         }
     }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
-// the checks every entry point shares, before a device is touched
+// The checks every entry point shares, before a device is touched.  The alignment of the scratch is refused HERE, ahead of the bin count
+// (mtd_pe_finalize has no arrays to check, and a misaligned scratch with too many bins is an invalid argument, not an unsupported one);
+// refuse_row_arrays, which the two passes over the list call afterwards, finds it aligned.
 int pe_check(const mtd_box *box, double r_max, double sigma_r, unsigned int n_bins, const double *d_scratch)
     {
     if (!box || !d_scratch) return MTD_ERR_INVALID_ARGUMENT;
@@ -402,13 +304,6 @@ int pe_ql_args(QlArgs<4> &a, unsigned int N, const mtd_box *box, double r_max, d
     return fill_args<4>(a, N, box, r_max + 4.0 * sigma_r, r_max + 3.0 * sigma_r, 0, type, no_ref, 1, 0);
     }
 
-unsigned int pe_blocks(const unsigned int N)
-    {
-    unsigned int b = (N + PE_PPB - 1) / PE_PPB;
-    if (b < 1) b = 1;
-    return b > PE_MAX_BLOCKS ? PE_MAX_BLOCKS : b;
-    }
-
 } // namespace
 
 extern "C" {
@@ -426,8 +321,8 @@ int mtd_pe_accumulate(unsigned int n_particles, const void *d_postype, int dtype
     if (!d_sums || !n_sums) return MTD_ERR_INVALID_ARGUMENT;
     int rc = pe_check(box, r_max, sigma_r, n_bins, d_scratch);
     if (rc) return rc;
-    if (n_particles && (!d_postype || !d_head_list || !d_n_neigh)) return MTD_ERR_INVALID_ARGUMENT;
-    if (dtype != MTD_F32 && dtype != MTD_F64) return MTD_ERR_INVALID_ARGUMENT;
+    rc = refuse_row_arrays(n_particles, d_postype && d_head_list && d_n_neigh, dtype, d_scratch, nullptr, 0);
+    if (rc) return rc;
     QlArgs<4> a;
     rc = pe_ql_args(a, n_particles, box, r_max, sigma_r, type);
     if (rc) return rc;
@@ -435,7 +330,7 @@ int mtd_pe_accumulate(unsigned int n_particles, const void *d_postype, int dtype
     hipStream_t s = (hipStream_t)stream;
     const double *tab = ql_device_table<4>(s, rc);
     if (rc) return rc;
-    const unsigned int blocks = pe_blocks(n_particles);
+    const unsigned int blocks = row_blocks(n_particles, PE_PPB, PE_MAX_BLOCKS);
     double *part = d_scratch + PE_OFF_PART;
     dispatch_s4(dtype, [&](auto t)
         {
@@ -472,9 +367,8 @@ int mtd_pe_forces(unsigned int n_particles, const void *d_postype, void *d_force
     {
     int rc = pe_check(box, r_max, sigma_r, n_bins, d_scratch);
     if (rc) return rc;
-    if (n_particles && (!d_postype || !d_head_list || !d_n_neigh || !d_force)) return MTD_ERR_INVALID_ARGUMENT;
-    if (dtype != MTD_F32 && dtype != MTD_F64) return MTD_ERR_INVALID_ARGUMENT;
-    if (d_virial && virial_pitch < n_particles) return MTD_ERR_INVALID_ARGUMENT;
+    rc = refuse_row_arrays(n_particles, d_postype && d_head_list && d_n_neigh && d_force, dtype, d_scratch, d_virial, virial_pitch);
+    if (rc) return rc;
     QlArgs<4> a;
     rc = pe_ql_args(a, n_particles, box, r_max, sigma_r, type);
     if (rc) return rc;
@@ -483,7 +377,7 @@ int mtd_pe_forces(unsigned int n_particles, const void *d_postype, void *d_force
     hipStream_t s = (hipStream_t)stream;
     const double *tab = ql_device_table<4>(s, rc);
     if (rc) return rc;
-    const unsigned int blocks = pe_blocks(n_particles);
+    const unsigned int blocks = row_blocks(n_particles, PE_PPB, PE_MAX_BLOCKS);
     dispatch_s4(dtype, [&](auto t)
         {
         return dispatch_bool(d_virial != nullptr, [&](auto vir)

@@ -35,8 +35,9 @@
 //                    per-particle sums stay in registers: no LDS atomics.  The quad's sums are added with two DPP quad_perm moves
 //                    ((q0 + q1) + (q2 + q3), the same bits in all four lanes)
 //   memory trips     list entry two iterations ahead, neighbour position one iteration ahead of the arithmetic
-//   one walk         the centre of a quad (QllCentre / qll_centre) and the zero that keeps the table loads in the loop
-//                    (qll_loop_table) are written once for all seven kernels; the look-ahead and the pair test once (QllWalker) for the
+//   one walk         the centre of a quad (RowCentre / row_centre), the quad's sum (group_sum<4>) and the zero that keeps the table loads
+//                    in the loop (loop_table) come from row_walk.hpp, which pair_entropy.hip and env_similarity.hip share, and serve all
+//                    seven kernels; the look-ahead and the pair test are written once (QllWalker) for the
 //                    four gather passes of the options, which share their whole frame (below).  accumulate, forces (per lane) and
 //                    forces_tile (per wave) keep the walk written out: see the note above QllWalker
 //   one gather frame k_qll_average, k_qll_backprop, k_qll_bonds and k_qll_bonds_backprop are one frame with four bodies: the window of a
@@ -77,7 +78,7 @@
 //                    and beta_j: the table row and E_kj = (beta_k + beta_j) sigma(d_kj) per list entry), then the AVG force pass as it is.
 //                    See the block above k_qll_bonds.
 #include "mtd_device.hpp"
-#include "steinhardt_device.hpp"
+#include "row_walk.hpp"
 #include "dispatch.hpp"
 
 namespace
@@ -100,17 +101,6 @@ struct QllLayout
     unsigned int off[13];
     };
 
-template<typename S4> __device__ __forceinline__ S4 qll_zero();
-template<> __device__ __forceinline__ float4 qll_zero<float4>() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-template<> __device__ __forceinline__ double4 qll_zero<double4>() { return make_double4(0.0, 0.0, 0.0, 0.0); }
-
-__device__ __forceinline__ double quad_sum(double v)
-    {
-    v += dpp_move<MTD_DPP_QUAD_XOR1>(v);
-    v += dpp_move<MTD_DPP_QUAD_XOR2>(v);
-    return v;
-    }
-
 // The chunk's sum of a per-particle value, added to the block's running sum: every lane brings the value of its quad's particle (0
 // past the end), wave 0 adds the 64 in the fixed order of wave_sum.  Every lane of the block is here: the chunk loop is uniform.
 __device__ __forceinline__ void qll_chunk_sum(double (&s_c)[QLL_PPB], const unsigned int tid, const double v, double &block_sum)
@@ -128,65 +118,42 @@ template<int U> __device__ __forceinline__ unsigned int quad_bcast(const unsigne
     return (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, U * 0x55, 0xf, 0xf, false);
     }
 
-// ---- the walk over a row: a quad's central particle (all seven kernels) and its lane's share of the row ----------------------------
-// the central particle of a quad: particle i of the chunk, its row of the list (empty for i >= N and for a particle of another type)
-struct QllCentre
-    {
-    unsigned int i;
-    Particle p;
-    unsigned int start, cnt;
-    __device__ __forceinline__ unsigned int row(const unsigned int N) const { return i < N ? i : 0; }   // a table row that is safe to address
-    __device__ __forceinline__ double own(const unsigned int N, const double *of) const { return i < N ? of[i] : 0.0; }   // its per-particle value
-    };
-
-template<typename S4, int LMAX>
-__device__ __forceinline__ QllCentre qll_centre(const QlArgs<LMAX> &a, const S4 *postype, const unsigned int *head_list, const unsigned int *n_neigh,
-                                                const unsigned int i)
-    {
-    Particle p = {0.0, 0.0, 0.0, -1};
-    unsigned int start = 0, cnt = 0;
-    if (i < a.N)
-        {
-        p = scalar4_traits<S4>::load(postype, i);
-        if ((unsigned int)p.type == a.type)
-            {
-            start = head_list[i];
-            cnt = n_neigh[i];
-            }
-        }
-    return {i, p, start, cnt};
-    }
-
+// ---- the walk over a row: its lane's share of the row (the quad's central particle, all seven kernels: RowCentre of row_walk.hpp) ------
 // Lane q of the quad takes entries q, q + 4, ... of the row.  The walker owns the look-ahead: the list entry is asked for two
 // iterations, the neighbour's position one iteration ahead of the arithmetic on (j0, pos0).  A loop is
 //     w.begin(..); while (its own condition on w.e) { w.ahead(..); w.pair(.., what to do with the pair); w.step(); }
 // Used by the four gather passes, through qll_entries.  k_qll_accumulate, k_qll_forces and k_qll_forces_tile keep the same walk written out:
-// through the walker their bits or their speed did not stay the parent's (profiles/r10/README.md).  A change to the look-ahead, the
-// list format or the skip rule is made here AND in those three loops.  The walker holds the look-ahead only; what it reads from is
-// handed to begin and ahead.
+// through the walker their bits or their speed did not stay the parent's (profiles/r10/README.md).  The walk therefore lives in these
+// places, and a change to the look-ahead, the list format or the skip rule is made in ALL of them:
+//     QllWalker (here)                                       the four gather passes
+//     the loops of k_qll_accumulate, k_qll_forces and k_qll_forces_tile, written out below
+//     row_walk of row_walk.hpp                               both passes of pair_entropy.hip and of env_similarity.hip
+// The walks of this unit skip an entry j >= N (position, listed: a ghost has no table row); row_walk walks ghosts and tests j against
+// "no entry" alone.  That difference is meant (row_walk.hpp).  The walker holds the look-ahead only; what it reads from is handed to
+// begin and ahead.
 template<typename S4> struct QllWalker
     {
     unsigned int e, j0, j1, j2;                            // the entry in hand and its index; the indices one and two entries on
     S4 pos0, pos1;                                         // the positions of j0 and j1
 
-    static __device__ __forceinline__ unsigned int entry(const unsigned int *nlist, const QllCentre &c, const unsigned int k)
+    static __device__ __forceinline__ unsigned int entry(const unsigned int *nlist, const RowCentre &c, const unsigned int k)
         {
         return k < c.cnt ? nlist[c.start + k] : QLL_NONE;
         }
     static __device__ __forceinline__ S4 position(const unsigned int N, const S4 *postype, const unsigned int j)
         {
-        S4 pos = qll_zero<S4>();
+        S4 pos = row_zero<S4>();
         if (j < N) pos = postype[j];
         return pos;
         }
-    __device__ __forceinline__ void begin(const unsigned int N, const S4 *postype, const unsigned int *nlist, const QllCentre &c, const unsigned int q)
+    __device__ __forceinline__ void begin(const unsigned int N, const S4 *postype, const unsigned int *nlist, const RowCentre &c, const unsigned int q)
         {
         e = q;
         j0 = entry(nlist, c, e);
         j1 = entry(nlist, c, e + QLL_G);
         pos0 = position(N, postype, j0);
         }
-    __device__ __forceinline__ void ahead(const unsigned int N, const S4 *postype, const unsigned int *nlist, const QllCentre &c)
+    __device__ __forceinline__ void ahead(const unsigned int N, const S4 *postype, const unsigned int *nlist, const RowCentre &c)
         {
         j2 = entry(nlist, c, e + 2 * QLL_G);
         pos1 = position(N, postype, j1);
@@ -202,9 +169,9 @@ template<typename S4> struct QllWalker
     // of the row) and the particle itself are skipped.  near: d = minImage(r_c - r_j0), and whether j0 has the type and lies within the
     // cut-off.  pair: calls f(dx, dy, dz, rsq) for an entry that passes both, the geometry formed for listed entries only.  The pair's
     // arithmetic is handed in, not a flag handed out: d then lives where the hand-written loops declared it.
-    __device__ __forceinline__ bool listed(const unsigned int N, const QllCentre &c) const { return j0 < N && j0 != c.i; }
+    __device__ __forceinline__ bool listed(const unsigned int N, const RowCentre &c) const { return j0 < N && j0 != c.i; }
     template<int LMAX>
-    __device__ __forceinline__ bool near(const QlArgs<LMAX> &a, const QllCentre &c, double &dx, double &dy, double &dz, double &rsq) const
+    __device__ __forceinline__ bool near(const QlArgs<LMAX> &a, const RowCentre &c, double &dx, double &dy, double &dz, double &rsq) const
         {
         const Particle pj = scalar4_traits<S4>::unpack(pos0);
         dx = c.p.x - pj.x, dy = c.p.y - pj.y, dz = c.p.z - pj.z;
@@ -212,7 +179,7 @@ template<typename S4> struct QllWalker
         rsq = dx * dx + dy * dy + dz * dz;
         return (unsigned int)pj.type == a.type && rsq <= a.rcutsq;
         }
-    template<int LMAX, typename F> __device__ __forceinline__ void pair(const QlArgs<LMAX> &a, const QllCentre &c, F &&f) const
+    template<int LMAX, typename F> __device__ __forceinline__ void pair(const QlArgs<LMAX> &a, const RowCentre &c, F &&f) const
         {
         if (listed(a.N, c))
             {
@@ -221,14 +188,6 @@ template<typename S4> struct QllWalker
             }
         }
     };
-
-// the table with a zero added that the compiler cannot see through: called inside a loop, it keeps the table loads in the loop
-__device__ __forceinline__ const double *qll_loop_table(const double *tab)
-    {
-    unsigned int tab_shift = 0;
-    asm volatile("" : "+s"(tab_shift));
-    return tab + tab_shift;
-    }
 
 // ---- the per-particle transforms of the options: v_i = g(n_i) h(c_i) ------------------------------------------------------------
 struct QllOpt
@@ -310,7 +269,7 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_accumulate(const QlArgs<LMA
     double block_c = 0.0;
     for (unsigned int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
         {
-        const QllCentre ci = qll_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
+        const RowCentre ci = row_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
         const unsigned int i = ci.i, start = ci.start, cnt = ci.cnt;
         const Particle pi = ci.p;
         cplx S[LMAX + 1][LMAX + 1];                                                // [m][l], l >= m
@@ -322,14 +281,14 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_accumulate(const QlArgs<LMA
         unsigned int e = q;
         unsigned int j0 = e < cnt ? nlist[start + e] : QLL_NONE;
         unsigned int j1 = e + QLL_G < cnt ? nlist[start + e + QLL_G] : QLL_NONE;
-        S4 pos0 = qll_zero<S4>();
+        S4 pos0 = row_zero<S4>();
         if (j0 < a.N) pos0 = postype[j0];
 #pragma unroll 1
         for (; e < cnt; e += QLL_G)
             {
-            const double *__restrict__ tab_k = qll_loop_table(tab);
+            const double *__restrict__ tab_k = loop_table(tab);
             const unsigned int j2 = e + 2 * QLL_G < cnt ? nlist[start + e + 2 * QLL_G] : QLL_NONE;
-            S4 pos1 = qll_zero<S4>();
+            S4 pos1 = row_zero<S4>();
             if (j1 < a.N) pos1 = postype[j1];
             if (j0 < a.N && j0 != i)
                 {
@@ -380,7 +339,7 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_accumulate(const QlArgs<LMA
             pos0 = pos1;
             }
         // the quad's sums (every lane of the wave is here: the chunk loop is uniform), then the particle's value and table row
-        nsum = quad_sum(nsum);
+        nsum = group_sum<QLL_G>(nsum);
         const double inv_n = nsum > 0.0 ? 1.0 / nsum : 0.0;
         const double inv_n2 = inv_n * inv_n;
         const bool write = q == 0 && i < a.N;
@@ -394,8 +353,8 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_accumulate(const QlArgs<LMA
 #pragma unroll
                 for (int m = 0; m <= l; ++m)
                     {
-                    S[m][l].re = quad_sum(S[m][l].re);
-                    if (m > 0) S[m][l].im = quad_sum(S[m][l].im);
+                    S[m][l].re = group_sum<QLL_G>(S[m][l].re);
+                    if (m > 0) S[m][l].im = group_sum<QLL_G>(S[m][l].im);
                     }
                 if (lay.act & (1u << l))
                     {
@@ -439,8 +398,8 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_accumulate(const QlArgs<LMA
 #pragma unroll
                     for (int m = 0; m <= l; ++m)
                         {
-                        S[m][l].re = quad_sum(S[m][l].re);
-                        if (m > 0) S[m][l].im = quad_sum(S[m][l].im);
+                        S[m][l].re = group_sum<QLL_G>(S[m][l].re);
+                        if (m > 0) S[m][l].im = group_sum<QLL_G>(S[m][l].im);
                         const double nr = tab[T::nrm(l, m)];
                         sq += ((m > 0 ? 2.0 : 1.0) * (nr * nr)) * (S[m][l].re * S[m][l].re + S[m][l].im * S[m][l].im);
                         }
@@ -499,8 +458,8 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_accumulate(const QlArgs<LMA
 #pragma unroll
                     for (int m = 0; m <= l; ++m)
                         {
-                        S[m][l].re = quad_sum(S[m][l].re);
-                        if (m > 0) S[m][l].im = quad_sum(S[m][l].im);
+                        S[m][l].re = group_sum<QLL_G>(S[m][l].re);
+                        if (m > 0) S[m][l].im = group_sum<QLL_G>(S[m][l].im);
                         const double nr = tab[T::nrm(l, m)];
                         const double w = (m > 0 ? 2.0 : 1.0) * (nr * nr);
                         sq += w * (S[m][l].re * S[m][l].re + S[m][l].im * S[m][l].im);
@@ -563,8 +522,8 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_accumulate(const QlArgs<LMA
 #pragma unroll
                     for (int m = 0; m <= l; ++m)
                         {
-                        S[m][l].re = quad_sum(S[m][l].re);
-                        if (m > 0) S[m][l].im = quad_sum(S[m][l].im);
+                        S[m][l].re = group_sum<QLL_G>(S[m][l].re);
+                        if (m > 0) S[m][l].im = group_sum<QLL_G>(S[m][l].im);
                         if (write)
                             {
                             row[2 * (lay.off[l] + m)] = S[m][l].re * inv_n;
@@ -627,8 +586,8 @@ struct QllVirial
     template<typename scalar> __device__ __forceinline__ void store(scalar *virial, const unsigned int pitch, const unsigned int k, const unsigned int q,
                                                                      const unsigned int N, const double scale)
         {
-        xx = quad_sum(xx), xy = quad_sum(xy), xz = quad_sum(xz);
-        yy = quad_sum(yy), yz = quad_sum(yz), zz = quad_sum(zz);
+        xx = group_sum<QLL_G>(xx), xy = group_sum<QLL_G>(xy), xz = group_sum<QLL_G>(xz);
+        yy = group_sum<QLL_G>(yy), yz = group_sum<QLL_G>(yz), zz = group_sum<QLL_G>(zz);
         if (q == 0 && k < N)
             {
             const double h = 0.5 * scale;
@@ -659,7 +618,7 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
     const unsigned int act = __builtin_amdgcn_readfirstlane(lay.act | 1u);         // slot (0, 0) carries the -2 (c_k/n_k + c_j/n_j) grad f term
     for (unsigned int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
         {
-        const QllCentre ck = qll_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
+        const RowCentre ck = row_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
         const unsigned int k = ck.i, start = ck.start, cnt = ck.cnt;
         const Particle pk = ck.p;
         const double *__restrict__ rk = rows + (size_t)ck.row(a.N) * lay.row_doubles;
@@ -668,16 +627,16 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
         unsigned int e = q;
         unsigned int j0 = e < cnt ? nlist[start + e] : QLL_NONE;
         unsigned int j1 = e + QLL_G < cnt ? nlist[start + e + QLL_G] : QLL_NONE;
-        S4 pos0 = qll_zero<S4>();
+        S4 pos0 = row_zero<S4>();
         if (j0 < a.N) pos0 = postype[j0];
         double e0 = 0.0;                                     // E of the entry in hand; the next one travels with the next position
         if (AVG && e < cnt) e0 = epair[start + e];
 #pragma unroll 1
         for (; e < cnt; e += QLL_G)
             {
-            const double *__restrict__ tab_k = qll_loop_table(tab);
+            const double *__restrict__ tab_k = loop_table(tab);
             const unsigned int j2 = e + 2 * QLL_G < cnt ? nlist[start + e + 2 * QLL_G] : QLL_NONE;
-            S4 pos1 = qll_zero<S4>();
+            S4 pos1 = row_zero<S4>();
             if (j1 < a.N) pos1 = postype[j1];
             double e1 = 0.0;
             if (AVG && e + QLL_G < cnt) e1 = epair[start + e + QLL_G];
@@ -702,9 +661,9 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
             pos0 = pos1;
             if (AVG) e0 = e1;
             }
-        Fx = quad_sum(Fx);
-        Fy = quad_sum(Fy);
-        Fz = quad_sum(Fz);
+        Fx = group_sum<QLL_G>(Fx);
+        Fy = group_sum<QLL_G>(Fy);
+        Fz = group_sum<QLL_G>(Fz);
         if (q == 0 && k < a.N)
             nt_store(scalar4_traits<S4>::make((scalar)(Fx * scale), (scalar)(Fy * scale), (scalar)(Fz * scale), (scalar)0), force + k);
         if constexpr (VIR) W.store(virial, virial_pitch, k, q, a.N, scale);
@@ -752,7 +711,7 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
     const unsigned int act = __builtin_amdgcn_readfirstlane(lay.act | 1u);
     for (unsigned int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
         {
-        const QllCentre ck = qll_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
+        const RowCentre ck = row_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
         const unsigned int k = ck.i, start = ck.start, cnt = ck.cnt;
         const Particle pk = ck.p;
         qll_wave_sync();                                    // the last chunk's reads of the tiles are done
@@ -770,16 +729,16 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
         unsigned int e = q;
         unsigned int j0 = e < cnt ? nlist[start + e] : QLL_NONE;
         unsigned int j1 = e + QLL_G < cnt ? nlist[start + e + QLL_G] : QLL_NONE;
-        S4 pos0 = qll_zero<S4>();
+        S4 pos0 = row_zero<S4>();
         if (j0 < a.N) pos0 = postype[j0];
         double e0 = 0.0;                                     // E of the entry in hand; the next one travels with the next position
         if (AVG && e < cnt) e0 = epair[start + e];
 #pragma unroll 1
         while (__ballot(e < cnt) != 0ull)
             {
-            const double *__restrict__ tab_k = qll_loop_table(tab);
+            const double *__restrict__ tab_k = loop_table(tab);
             const unsigned int j2 = e + 2 * QLL_G < cnt ? nlist[start + e + 2 * QLL_G] : QLL_NONE;
-            S4 pos1 = qll_zero<S4>();
+            S4 pos1 = row_zero<S4>();
             if (j1 < a.N) pos1 = postype[j1];
             double e1 = 0.0;
             if (AVG && e + QLL_G < cnt) e1 = epair[start + e + QLL_G];
@@ -832,9 +791,9 @@ __global__ __launch_bounds__(QLL_THREADS, (qll_force_waves<LMAX>())) void k_qll_
             if (AVG) e0 = e1;
             e += QLL_G;
             }
-        Fx = quad_sum(Fx);
-        Fy = quad_sum(Fy);
-        Fz = quad_sum(Fz);
+        Fx = group_sum<QLL_G>(Fx);
+        Fy = group_sum<QLL_G>(Fy);
+        Fz = group_sum<QLL_G>(Fz);
         if (q == 0 && k < a.N)
             nt_store(scalar4_traits<S4>::make((scalar)(Fx * scale), (scalar)(Fy * scale), (scalar)(Fz * scale), (scalar)0), force + k);
         if constexpr (VIR) W.store(virial, virial_pitch, k, q, a.N, scale);
@@ -882,7 +841,7 @@ struct QllEntry
 
 // the entries of the quad's row, four per round: body(QllEntry) for the entry of this lane, every lane of the quad in every round
 template<typename S4, typename F>
-__device__ __forceinline__ void qll_entries(const QlArgs<12> &a, const S4 *postype, const unsigned int *nlist, const QllCentre &c,
+__device__ __forceinline__ void qll_entries(const QlArgs<12> &a, const S4 *postype, const unsigned int *nlist, const RowCentre &c,
                                             const unsigned int q, const double *tab, F &&body)
     {
     QllWalker<S4> w;
@@ -890,7 +849,7 @@ __device__ __forceinline__ void qll_entries(const QlArgs<12> &a, const S4 *posty
 #pragma unroll 1
     for (unsigned int eb = 0; eb < c.cnt; eb += QLL_G, w.step())                    // cnt is the quad's: its four lanes stay together
         {
-        const double *__restrict__ tab_k = qll_loop_table(tab);
+        const double *__restrict__ tab_k = loop_table(tab);
         w.ahead(a.N, postype, nlist, c);
         QllEntry en = {0.0, c.row(a.N), false, w.e, c.start, c.cnt};
         w.pair(a, c, [&](double, double, double, const double rsq)
@@ -936,7 +895,7 @@ template<typename F> __device__ __forceinline__ double quad_keep(const unsigned 
 #pragma unroll
     for (unsigned int u = 0; u < QLL_G; ++u)
         {
-        const double sum = quad_sum(share(u));
+        const double sum = group_sum<QLL_G>(share(u));
         if (q == u) mine = sum;
         }
     return mine;
@@ -972,7 +931,7 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_average(const QlArgs<12> a,
     double block_v = 0.0;
     for (unsigned int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
         {
-        const QllCentre ci = qll_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
+        const RowCentre ci = row_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
         const unsigned int i = ci.i, ii = ci.row(a.N);
         const double ni = ci.own(a.N, n_in);
         const double inv_1n = 1.0 / (1.0 + ni);
@@ -1003,7 +962,7 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_average(const QlArgs<12> a,
                     if (i < a.N) brows[(size_t)i * rs16 + c] = make_double2(2.0 * w * inv_1n * qx, -(2.0 * w * inv_1n * qy));
                     }
             }
-        const double c = quad_sum(csum);
+        const double c = group_sum<QLL_G>(csum);
         double h, dh, g, dg;
         qll_transform(o, c, ni, h, dh, g, dg);
         const double gh = g * dh;
@@ -1036,7 +995,7 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_backprop(const QlArgs<12> a
     const unsigned int n_chunks = (a.N + QLL_PPB - 1) / QLL_PPB;
     for (unsigned int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
         {
-        const QllCentre ck = qll_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
+        const RowCentre ck = row_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
         const unsigned int k = ck.i, kk = ck.row(a.N);
         const double nk = ck.own(a.N, n_in), a0 = ck.own(a.N, a0_in);
         const double inv_n = nk > 0.0 ? 1.0 / nk : 0.0;
@@ -1088,7 +1047,7 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_backprop(const QlArgs<12> a
                         rows[(size_t)k * rs16 + c] = make_double2(acc[v].x * inv_n, acc[v].y * inv_n);
                     }
             }
-        cq = quad_sum(cq);
+        cq = group_sum<QLL_G>(cq);
         if (q == 0 && k < a.N) rows[(size_t)k * rs16] = make_double2(r00 + (a0 - cq * inv_n), 0.0);
         }
     }
@@ -1121,7 +1080,7 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_bonds(const QlArgs<12> a, c
     double block_v = 0.0;
     for (unsigned int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
         {
-        const QllCentre ci = qll_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
+        const RowCentre ci = row_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
         const unsigned int i = ci.i, ii = ci.row(a.N);
         const double ni = ci.own(a.N, n_in);
         double bsum = 0.0;
@@ -1165,7 +1124,7 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_bonds(const QlArgs<12> a, c
                     }
                 });
             }
-        const double b = quad_sum(bsum);
+        const double b = group_sum<QLL_G>(bsum);
         double h, dh, g, dg;
         qll_transform(o, b, ni, h, dh, g, dg);
         if (q == 0 && i < a.N)
@@ -1193,7 +1152,7 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_bonds_backprop(const QlArgs
     const unsigned int n_chunks = (a.N + QLL_PPB - 1) / QLL_PPB;
     for (unsigned int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
         {
-        const QllCentre ck = qll_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
+        const RowCentre ck = row_centre(a, postype, head_list, n_neigh, chunk * QLL_PPB + p);
         const unsigned int k = ck.i, kk = ck.row(a.N);
         const bool there = k < a.N;
         const double nk = ck.own(a.N, n_in), a0 = ck.own(a.N, a0_in), c_k = ck.own(a.N, c_in), beta_k = ck.own(a.N, beta_in);
@@ -1224,7 +1183,7 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_bonds_backprop(const QlArgs
                 if (en.mine() && last) epair[en.at()] = en.counts ? bsum * sg : 0.0;   // E replaces d once no window needs d again
                 qll_add_rows(acc, urows, rs16, cs, en.j, t);
                 });
-            td = quad_sum(td);
+            td = group_sum<QLL_G>(td);
             // Bm of this window: its share of sum Re Bm qm, and the row of the force pass
 #pragma unroll
             for (unsigned int v = 0; v < QLL_GV; ++v)
@@ -1240,7 +1199,7 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_bonds_backprop(const QlArgs
                         rows[(size_t)k * rs16 + c] = make_double2(bx * inv_n, by * inv_n);
                     }
             }
-        cq = quad_sum(cq);
+        cq = group_sum<QLL_G>(cq);
         if (q == 0 && there) rows[(size_t)k * rs16] = make_double2(r00 + (a0 - cq * inv_n), 0.0);
         }
     }
@@ -1318,13 +1277,6 @@ QllScratch qll_scratch(double *scratch, const size_t n, const unsigned int lmax,
     return s;
     }
 
-unsigned int qll_blocks(const unsigned int N)
-    {
-    unsigned int b = (N + QLL_PPB - 1) / QLL_PPB;
-    if (b < 1) b = 1;
-    return b > QLL_MAX_BLOCKS ? QLL_MAX_BLOCKS : b;
-    }
-
 QllOpt qll_opt(const mtd_ql_local_options *opt)
     {
     QllOpt o;
@@ -1391,7 +1343,7 @@ int qll_prepare(QllCall &k, unsigned int n_particles, const void *d_postype, int
     const int mode = qll_mode(opt, bonds);
     k = {n_particles, d_postype, dtype, box, d_head, d_nneigh, d_nlist, rcut, ron, lmax, type, ql_ref, n_global, (hipStream_t)stream, mode,
          qll_layout(lmax, ql_ref), qll_opt(opt), ramp, qll_scratch(const_cast<double *>(d_scratch), n_particles, lmax, 0, mode),
-         qll_blocks(n_particles)};
+         row_blocks(n_particles, QLL_PPB, QLL_MAX_BLOCKS)};
     return MTD_SUCCESS;
     }
 

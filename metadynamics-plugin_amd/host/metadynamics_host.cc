@@ -73,6 +73,13 @@ void CollectiveVariable::computeForces(unsigned int timestep)
     }
 
 // CollectiveVariable.cc:68-106
+void *CollectiveVariable::virialTarget()
+    {
+    if (m_pdata->getPressureFlag()) return getVirialArray().data();
+    if (m_virial.bytes()) hip_check(hipMemsetAsync(m_virial.data(), 0, m_virial.bytes(), m_exec_conf->getStream()), "virial reset");
+    return nullptr;
+    }
+
 double CollectiveVariable::getUmbrellaPotential(unsigned int timestep)
     {
     if (m_umbrella != no_umbrella)
@@ -712,20 +719,13 @@ void SteinhardtQl::computeBiasForces(unsigned int timestep)
     if (!m_have_computed) computeCV(timestep);
     const mtd_box box = m_pdata->getBox().toMtd();
     const Lists l = lists();
-    // constant pressure: the per-particle virial of the bias force beside it (include/mtd_abi.h).  Without the flag today's call; a
-    // virial array somebody has allocated earlier is zeroed then, so that a stale virial is never read (as SteinhardtLocal).  A half
-    // list reaches this point as its symmetric full list (mode 2); the third-law pass (kept by the diagnostic MTD_QL_HALF_THIRD_LAW, or
-    // for a half list that indexes ghost particles) forms no virial
-    void *virial = nullptr;
-    if (m_pdata->getPressureFlag())
-        {
-        if (l.mode == 1)
-            throw std::runtime_error("cv.steinhardt: the third-law pass of a half neighbour list (MTD_QL_HALF_THIRD_LAW, or a half list "
-                                     "with ghost particles) forms no virial: unset the variable or use a full list in a constant-pressure run");
-        virial = getVirialArray().data();
-        }
-    else if (m_virial.bytes())
-        hip_check(hipMemsetAsync(m_virial.data(), 0, m_virial.bytes(), m_exec_conf->getStream()), "virial reset");
+    // constant pressure: the per-particle virial of the bias force beside it (include/mtd_abi.h, virialTarget).  A half list reaches
+    // this point as its symmetric full list (mode 2); the third-law pass (kept by the diagnostic MTD_QL_HALF_THIRD_LAW, or for a half
+    // list that indexes ghost particles) forms no virial
+    if (l.mode == 1 && m_pdata->getPressureFlag())
+        throw std::runtime_error("cv.steinhardt: the third-law pass of a half neighbour list (MTD_QL_HALF_THIRD_LAW, or a half list "
+                                 "with ghost particles) forms no virial: unset the variable or use a full list in a constant-pressure run");
+    void *virial = virialTarget();
     mtd_check(mtd_ql_forces_virial(m_pdata->getN(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &box, l.head, l.n_neigh, l.nlist,
                                    l.mode, m_rcut, m_ron, m_lmax, m_type, m_Ql_ref.data(), m_pdata->getNGlobal(), (const double *)m_scratch.data(),
                                    m_bias_device, m_bias, m_exec_conf->getStream(), virial, getVirialPitch()),
@@ -753,14 +753,79 @@ double SteinhardtQl::getLogValue(const std::string &quantity, unsigned int times
     }
 
 // ------------------------------------------------------------------------------------------------
+// NeighbourVariable: what SteinhardtLocal, PairEntropy and EnvironmentSimilarity share
+// ------------------------------------------------------------------------------------------------
+
+NeighbourVariable::NeighbourVariable(std::shared_ptr<SystemDefinition> sysdef, const char *kind, const std::string &log_suffix,
+                                     std::shared_ptr<NeighborList> nlist, unsigned int type)
+    : CollectiveVariable(sysdef, kind + log_suffix), m_prefix(std::string("cv.") + kind + ": "), m_nlist(nlist), m_type(type),
+      m_cv_last_updated(0), m_have_computed(false)
+    {
+    }
+
+void NeighbourVariable::requireFullList() const
+    {
+    // the force pass gathers both roles of a particle from its own row
+    if (m_nlist->getStorageMode() == NeighborList::half)
+        throw std::runtime_error(m_prefix + "a full neighbour list is required (the force pass gathers both roles of a particle from its own row)");
+    }
+
+void NeighbourVariable::requireReach(double r_cut, const char *what) const
+    {
+    if (m_nlist->isDeviceBuild() && m_nlist->getRCut() < r_cut) throw std::runtime_error(m_prefix + "the neighbour list must reach " + what);
+    }
+
+NeighbourVariable::Lists NeighbourVariable::lists() const
+    {
+    return {(const unsigned int *)m_nlist->getHeadList().data(), (const unsigned int *)m_nlist->getNNeighArray().data(),
+            (const unsigned int *)m_nlist->getNListArray().data()};
+    }
+
+std::vector<double> NeighbourVariable::readBack(const double *d_src, size_t n, const char *what, unsigned int timestep)
+    {
+    computeCV(timestep);
+    m_exec_conf->sync();
+    std::vector<double> out(n);
+    if (!out.empty()) hip_check(hipMemcpy(out.data(), d_src, sizeof(double) * n, hipMemcpyDeviceToHost), what);
+    return out;
+    }
+
+double NeighbourVariable::readValue(const double *d_src, unsigned int timestep)
+    {
+    return readBack(d_src, 1, "cv read-back", timestep)[0];
+    }
+
+double NeighbourVariable::readPartials(const double *d_partials, unsigned int n_partials, unsigned int timestep)
+    {
+    computeCV(timestep);
+    mtd_check(mtd_reduce_partials(d_partials, n_partials, 1, 1, 1.0 / (double)m_pdata->getNGlobal(), 0.0, (double *)m_sum.data(),
+                                  m_exec_conf->getStream()),
+              "mtd_reduce_partials");
+    return readValue((const double *)m_sum.data(), timestep);
+    }
+
+std::vector<std::string> NeighbourVariable::getProvidedLogQuantities()
+    {
+    auto list = CollectiveVariable::getProvidedLogQuantities();
+    list.push_back("cv_" + m_cv_name);
+    return list;
+    }
+
+double NeighbourVariable::getLogValue(const std::string &quantity, unsigned int timestep)
+    {
+    if (quantity == "cv_" + m_cv_name) return getCurrentValue(timestep);
+    return CollectiveVariable::getLogValue(quantity, timestep);
+    }
+
+// ------------------------------------------------------------------------------------------------
 // SteinhardtLocal
 // ------------------------------------------------------------------------------------------------
 
 SteinhardtLocal::SteinhardtLocal(std::shared_ptr<SystemDefinition> sysdef, double rcut, double ron, unsigned int lmax,
                                  std::shared_ptr<NeighborList> nlist, unsigned int type, const std::vector<double> &Ql_ref,
                                  const std::string &log_suffix)
-    : CollectiveVariable(sysdef, "steinhardt_local" + log_suffix), m_rcut(rcut), m_ron(ron), m_lmax(lmax), m_nlist(nlist), m_type(type),
-      m_Ql_ref(Ql_ref), m_cv_last_updated(0), m_have_computed(false), m_d_partials(nullptr), m_d_c(nullptr), m_d_n(nullptr), m_d_v(nullptr),
+    : NeighbourVariable(sysdef, "steinhardt_local", log_suffix, nlist, type), m_rcut(rcut), m_ron(ron), m_lmax(lmax), m_Ql_ref(Ql_ref),
+      m_d_partials(nullptr), m_d_c(nullptr), m_d_n(nullptr), m_d_v(nullptr),
       m_d_b(nullptr), m_n_partials(0), m_opt(), m_bonds()
     {
     if (Ql_ref.size() != lmax + 1) throw std::runtime_error("Error setting up local Steinhardt CV");
@@ -774,12 +839,10 @@ SteinhardtLocal::SteinhardtLocal(std::shared_ptr<SystemDefinition> sysdef, doubl
 void SteinhardtLocal::computeCV(unsigned int timestep)
     {
     ProfRange prof_range("CV");
-    if (m_cv_last_updated == timestep && m_have_computed) return;
+    if (fresh(timestep)) return;
     // the force pass gathers a neighbour's table row: both roles of a particle must be in its own row, and the row of a ghost
     // would have to be exchanged between the ranks
-    if (m_nlist->getStorageMode() == NeighborList::half)
-        throw std::runtime_error("cv.steinhardt_local: a full neighbour list is required (the force pass gathers both roles of a "
-                                 "particle from its own row)");
+    requireFullList();
     if (distributed())
         throw std::runtime_error("cv.steinhardt_local: domain-decomposed runs are not supported (the table row of a ghost "
                                  "neighbour would have to be exchanged)");
@@ -790,26 +853,21 @@ void SteinhardtLocal::computeCV(unsigned int timestep)
     const size_t need = sizeof(double) * mtd_ql_local_scratch_doubles_bonds(m_pdata->getN(), m_lmax,
                                                                             m_nlist->getNListArray().bytes() / sizeof(unsigned int), &m_opt, &m_bonds);
     if (need > m_scratch.bytes()) m_scratch.resize(need);
-    mtd_check(mtd_ql_local_accumulate_bonds(m_pdata->getN(), m_pdata->positionsPtr(), m_pdata->getDtype(), &box,
-                                            (const unsigned int *)m_nlist->getHeadList().data(), (const unsigned int *)m_nlist->getNNeighArray().data(),
-                                            (const unsigned int *)m_nlist->getNListArray().data(), m_rcut, m_ron, m_lmax, m_type, m_Ql_ref.data(),
-                                            m_pdata->getNGlobal(), (double *)m_scratch.data(), &m_d_partials, &m_n_partials, &m_d_c, &m_d_n,
-                                            m_exec_conf->getStream(), &m_opt, &m_d_v, &m_bonds, &m_d_b),
+    const Lists l = lists();
+    mtd_check(mtd_ql_local_accumulate_bonds(m_pdata->getN(), m_pdata->positionsPtr(), m_pdata->getDtype(), &box, l.head, l.n_neigh, l.nlist, m_rcut,
+                                            m_ron, m_lmax, m_type, m_Ql_ref.data(), m_pdata->getNGlobal(), (double *)m_scratch.data(), &m_d_partials,
+                                            &m_n_partials, &m_d_c, &m_d_n, m_exec_conf->getStream(), &m_opt, &m_d_v, &m_bonds, &m_d_b),
               "mtd_ql_local_accumulate_bonds");
-    m_have_computed = true;
-    m_cv_last_updated = timestep;
+    computed(timestep);
     }
 
-void SteinhardtLocal::optionsChanged()
-    {
-    m_have_computed = false;                                         // the table in the scratch belongs to the old options
-    }
+// the setters below end with invalidate(): the table in the scratch belongs to the old options
 
 void SteinhardtLocal::setAverage(bool on)
     {
     if (on && m_bonds.on) throw std::runtime_error("cv.steinhardt_local: the bond count is not available on the averaged vectors");
     m_opt.average = on ? 1 : 0;
-    optionsChanged();
+    invalidate();
     }
 
 void SteinhardtLocal::setSwitch(double c0, unsigned int p)
@@ -818,7 +876,7 @@ void SteinhardtLocal::setSwitch(double c0, unsigned int p)
     m_opt.switch_on = 1;
     m_opt.c0 = c0;
     m_opt.p = p;
-    optionsChanged();
+    invalidate();
     }
 
 void SteinhardtLocal::clearSwitch()
@@ -826,7 +884,7 @@ void SteinhardtLocal::clearSwitch()
     m_opt.switch_on = 0;
     m_opt.c0 = 0.0;
     m_opt.p = 0;
-    optionsChanged();
+    invalidate();
     }
 
 void SteinhardtLocal::setGate(double n_lo, double n_hi)
@@ -835,14 +893,14 @@ void SteinhardtLocal::setGate(double n_lo, double n_hi)
     m_opt.gate_on = 1;
     m_opt.n_lo = n_lo;
     m_opt.n_hi = n_hi;
-    optionsChanged();
+    invalidate();
     }
 
 void SteinhardtLocal::clearGate()
     {
     m_opt.gate_on = 0;
     m_opt.n_lo = m_opt.n_hi = 0.0;
-    optionsChanged();
+    invalidate();
     }
 
 void SteinhardtLocal::setBonds(double d_lo, double d_hi)
@@ -854,14 +912,14 @@ void SteinhardtLocal::setBonds(double d_lo, double d_hi)
     m_bonds.on = 1;
     m_bonds.d_lo = d_lo;
     m_bonds.d_hi = d_hi;
-    optionsChanged();
+    invalidate();
     }
 
 void SteinhardtLocal::clearBonds()
     {
     m_bonds.on = 0;
     m_bonds.d_lo = m_bonds.d_hi = 0.0;
-    optionsChanged();
+    invalidate();
     }
 
 void SteinhardtLocal::enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot)
@@ -873,34 +931,22 @@ void SteinhardtLocal::enqueueCurrentValue(unsigned int timestep, mtd_metad *engi
 
 double SteinhardtLocal::getCurrentValue(unsigned int timestep)
     {
-    computeCV(timestep);
-    mtd_check(mtd_reduce_partials(m_d_partials, m_n_partials, 1, 1, 1.0 / (double)m_pdata->getNGlobal(), 0.0, (double *)m_sum.data(),
-                                  m_exec_conf->getStream()),
-              "mtd_reduce_partials");
-    m_exec_conf->sync();
-    double value = 0.0;
-    hip_check(hipMemcpy(&value, m_sum.data(), sizeof(double), hipMemcpyDeviceToHost), "cv read-back");
-    return value;
+    computeCV(timestep);                                             // (sets the pointers: before they are handed on, here and below)
+    return readPartials(m_d_partials, m_n_partials, timestep);
     }
 
 void SteinhardtLocal::computeBiasForces(unsigned int timestep)
     {
     ProfRange prof_range("Force");
-    if (!m_have_computed || m_cv_last_updated != timestep) computeCV(timestep);      // the table of THIS step's positions
+    if (!fresh(timestep)) computeCV(timestep);                       // the table of THIS step's positions
     m_nlist->compute(timestep);
     const mtd_box box = m_pdata->getBox().toMtd();
-    // constant pressure: the per-particle virial of the bias force beside it (include/mtd_abi.h).  Without the flag today's call; a
-    // virial array somebody has allocated earlier is zeroed then, so that a stale virial is never read (as the mesh's external virial)
-    void *virial = nullptr;
-    if (m_pdata->getPressureFlag())
-        virial = getVirialArray().data();
-    else if (m_virial.bytes())
-        hip_check(hipMemsetAsync(m_virial.data(), 0, m_virial.bytes(), m_exec_conf->getStream()), "virial reset");
-    mtd_check(mtd_ql_local_forces_bonds(m_pdata->getN(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &box,
-                                        (const unsigned int *)m_nlist->getHeadList().data(), (const unsigned int *)m_nlist->getNNeighArray().data(),
-                                        (const unsigned int *)m_nlist->getNListArray().data(), m_rcut, m_ron, m_lmax, m_type, m_Ql_ref.data(),
-                                        m_pdata->getNGlobal(), (const double *)m_scratch.data(), m_bias_device, m_bias, m_exec_conf->getStream(),
-                                        &m_opt, virial, getVirialPitch(), &m_bonds),
+    const Lists l = lists();
+    void *virial = virialTarget();                                   // constant pressure: the per-particle virial of the bias force beside it
+    mtd_check(mtd_ql_local_forces_bonds(m_pdata->getN(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &box, l.head, l.n_neigh,
+                                        l.nlist, m_rcut, m_ron, m_lmax, m_type, m_Ql_ref.data(), m_pdata->getNGlobal(),
+                                        (const double *)m_scratch.data(), m_bias_device, m_bias, m_exec_conf->getStream(), &m_opt, virial,
+                                        getVirialPitch(), &m_bonds),
               "mtd_ql_local_forces_bonds");
     }
 
@@ -908,50 +954,25 @@ std::vector<double> SteinhardtLocal::getBondCounts(unsigned int timestep)
     {
     if (!m_bonds.on) throw std::runtime_error("cv.steinhardt_local: no bond count without the bonds option");
     computeCV(timestep);
-    m_exec_conf->sync();
-    std::vector<double> out(m_pdata->getN());
-    if (!out.empty()) hip_check(hipMemcpy(out.data(), m_d_b, sizeof(double) * out.size(), hipMemcpyDeviceToHost), "b_i read-back");
-    return out;
+    return readBack(m_d_b, m_pdata->getN(), "b_i read-back", timestep);
     }
 
 std::vector<double> SteinhardtLocal::getSwitchedValues(unsigned int timestep)
     {
     computeCV(timestep);
-    m_exec_conf->sync();
-    std::vector<double> out(m_pdata->getN());
-    if (!out.empty()) hip_check(hipMemcpy(out.data(), m_d_v, sizeof(double) * out.size(), hipMemcpyDeviceToHost), "v_i read-back");
-    return out;
+    return readBack(m_d_v, m_pdata->getN(), "v_i read-back", timestep);
     }
 
 std::vector<double> SteinhardtLocal::getLocalValues(unsigned int timestep)
     {
     computeCV(timestep);
-    m_exec_conf->sync();
-    std::vector<double> out(m_pdata->getN());
-    if (!out.empty()) hip_check(hipMemcpy(out.data(), m_d_c, sizeof(double) * out.size(), hipMemcpyDeviceToHost), "c_i read-back");
-    return out;
+    return readBack(m_d_c, m_pdata->getN(), "c_i read-back", timestep);
     }
 
 std::vector<double> SteinhardtLocal::getCoordination(unsigned int timestep)
     {
     computeCV(timestep);
-    m_exec_conf->sync();
-    std::vector<double> out(m_pdata->getN());
-    if (!out.empty()) hip_check(hipMemcpy(out.data(), m_d_n, sizeof(double) * out.size(), hipMemcpyDeviceToHost), "n_i read-back");
-    return out;
-    }
-
-std::vector<std::string> SteinhardtLocal::getProvidedLogQuantities()
-    {
-    auto list = CollectiveVariable::getProvidedLogQuantities();
-    list.push_back("cv_" + m_cv_name);
-    return list;
-    }
-
-double SteinhardtLocal::getLogValue(const std::string &quantity, unsigned int timestep)
-    {
-    if (quantity == "cv_" + m_cv_name) return getCurrentValue(timestep);
-    return CollectiveVariable::getLogValue(quantity, timestep);
+    return readBack(m_d_n, m_pdata->getN(), "n_i read-back", timestep);
     }
 
 // ------------------------------------------------------------------------------------------------
@@ -960,8 +981,8 @@ double SteinhardtLocal::getLogValue(const std::string &quantity, unsigned int ti
 
 PairEntropy::PairEntropy(std::shared_ptr<SystemDefinition> sysdef, double r_max, double sigma_r, unsigned int n_bins,
                          std::shared_ptr<NeighborList> nlist, unsigned int type, const std::string &log_suffix)
-    : CollectiveVariable(sysdef, "pair_entropy" + log_suffix), m_r_max(r_max), m_sigma_r(sigma_r), m_n_bins(n_bins), m_nlist(nlist), m_type(type),
-      m_cv_last_updated(0), m_have_computed(false), m_d_value(nullptr), m_d_g(nullptr)
+    : NeighbourVariable(sysdef, "pair_entropy", log_suffix, nlist, type), m_r_max(r_max), m_sigma_r(sigma_r), m_n_bins(n_bins), m_d_value(nullptr),
+      m_d_g(nullptr)
     {
     if (!nlist) throw std::runtime_error("cv.pair_entropy: a neighbour list is required");
     if (!(r_max > 0.0) || !std::isfinite(r_max) || !(sigma_r > 0.0) || !std::isfinite(sigma_r))
@@ -973,27 +994,22 @@ PairEntropy::PairEntropy(std::shared_ptr<SystemDefinition> sysdef, double r_max,
 void PairEntropy::computeCV(unsigned int timestep)
     {
     ProfRange prof_range("CV");
-    if (m_cv_last_updated == timestep && m_have_computed) return;
-    // the force pass gathers both roles of a particle from its own row
-    if (m_nlist->getStorageMode() == NeighborList::half)
-        throw std::runtime_error("cv.pair_entropy: a full neighbour list is required (the force pass gathers both roles of a particle "
-                                 "from its own row)");
-    if (m_nlist->isDeviceBuild() && m_nlist->getRCut() < getRCut())
-        throw std::runtime_error("cv.pair_entropy: the neighbour list must reach r_max + 4 sigma_r");
+    if (fresh(timestep)) return;
+    requireFullList();
+    requireReach(getRCut(), "r_max + 4 sigma_r");
     m_nlist->compute(timestep);
     const mtd_box box = m_pdata->getBox().toMtd();
     hipStream_t s = m_exec_conf->getStream();
     double *d_sums = nullptr;
     unsigned int n_sums = 0;
-    mtd_check(mtd_pe_accumulate(m_pdata->getN(), m_pdata->positionsPtr(), m_pdata->getDtype(), &box, (const unsigned int *)m_nlist->getHeadList().data(),
-                                (const unsigned int *)m_nlist->getNNeighArray().data(), (const unsigned int *)m_nlist->getNListArray().data(), m_r_max,
-                                m_sigma_r, m_n_bins, m_type, (double *)m_scratch.data(), &d_sums, &n_sums, s),
+    const Lists l = lists();
+    mtd_check(mtd_pe_accumulate(m_pdata->getN(), m_pdata->positionsPtr(), m_pdata->getDtype(), &box, l.head, l.n_neigh, l.nlist, m_r_max, m_sigma_r,
+                                m_n_bins, m_type, (double *)m_scratch.data(), &d_sums, &n_sums, s),
               "mtd_pe_accumulate");
     // H_b and N_t over the ranks: the central particles of a rank are its local ones, their neighbours may be ghosts
     if (distributed()) m_exec_conf->allreduceSmall(d_sums, n_sums, s);
     mtd_check(mtd_pe_finalize(&box, m_r_max, m_sigma_r, m_n_bins, (double *)m_scratch.data(), &m_d_value, &m_d_g, s), "mtd_pe_finalize");
-    m_have_computed = true;
-    m_cv_last_updated = timestep;
+    computed(timestep);
     }
 
 void PairEntropy::enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot)
@@ -1005,52 +1021,27 @@ void PairEntropy::enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, 
 double PairEntropy::getCurrentValue(unsigned int timestep)
     {
     computeCV(timestep);
-    m_exec_conf->sync();
-    double value = 0.0;
-    hip_check(hipMemcpy(&value, m_d_value, sizeof(double), hipMemcpyDeviceToHost), "cv read-back");
-    return value;
+    return readValue(m_d_value, timestep);
     }
 
 std::vector<double> PairEntropy::getGr(unsigned int timestep)
     {
     computeCV(timestep);
-    m_exec_conf->sync();
-    std::vector<double> out(m_n_bins);
-    hip_check(hipMemcpy(out.data(), m_d_g, sizeof(double) * out.size(), hipMemcpyDeviceToHost), "g(r) read-back");
-    return out;
+    return readBack(m_d_g, m_n_bins, "g(r) read-back", timestep);
     }
 
 void PairEntropy::computeBiasForces(unsigned int timestep)
     {
     ProfRange prof_range("Force");
-    if (!m_have_computed || m_cv_last_updated != timestep) computeCV(timestep);      // the W_b of THIS step's positions
+    if (!fresh(timestep)) computeCV(timestep);                       // the W_b of THIS step's positions
     m_nlist->compute(timestep);
     const mtd_box box = m_pdata->getBox().toMtd();
-    // constant pressure: the per-particle virial of the bias force beside it (include/mtd_abi.h).  Without the flag the plain call; a
-    // virial array somebody has allocated earlier is zeroed then, so that a stale virial is never read (as SteinhardtQl)
-    void *virial = nullptr;
-    if (m_pdata->getPressureFlag())
-        virial = getVirialArray().data();
-    else if (m_virial.bytes())
-        hip_check(hipMemsetAsync(m_virial.data(), 0, m_virial.bytes(), m_exec_conf->getStream()), "virial reset");
-    mtd_check(mtd_pe_forces(m_pdata->getN(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &box,
-                            (const unsigned int *)m_nlist->getHeadList().data(), (const unsigned int *)m_nlist->getNNeighArray().data(),
-                            (const unsigned int *)m_nlist->getNListArray().data(), m_r_max, m_sigma_r, m_n_bins, m_type,
-                            (const double *)m_scratch.data(), m_bias_device, m_bias, m_exec_conf->getStream(), virial, getVirialPitch()),
+    const Lists l = lists();
+    void *virial = virialTarget();                                   // constant pressure: the per-particle virial of the bias force beside it
+    mtd_check(mtd_pe_forces(m_pdata->getN(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &box, l.head, l.n_neigh, l.nlist, m_r_max,
+                            m_sigma_r, m_n_bins, m_type, (const double *)m_scratch.data(), m_bias_device, m_bias, m_exec_conf->getStream(), virial,
+                            getVirialPitch()),
               "mtd_pe_forces");
-    }
-
-std::vector<std::string> PairEntropy::getProvidedLogQuantities()
-    {
-    auto list = CollectiveVariable::getProvidedLogQuantities();
-    list.push_back("cv_" + m_cv_name);
-    return list;
-    }
-
-double PairEntropy::getLogValue(const std::string &quantity, unsigned int timestep)
-    {
-    if (quantity == "cv_" + m_cv_name) return getCurrentValue(timestep);
-    return CollectiveVariable::getLogValue(quantity, timestep);
     }
 
 // ------------------------------------------------------------------------------------------------
@@ -1060,8 +1051,7 @@ double PairEntropy::getLogValue(const std::string &quantity, unsigned int timest
 EnvironmentSimilarity::EnvironmentSimilarity(std::shared_ptr<SystemDefinition> sysdef, const std::vector<std::vector<std::vector<double>>> &templates,
                                              double sigma_env, double r_cut, double r_on, double lambda, std::shared_ptr<NeighborList> nlist,
                                              unsigned int type, const std::string &log_suffix)
-    : CollectiveVariable(sysdef, "environment_similarity" + log_suffix), m_par(), m_nlist(nlist), m_type(type), m_cv_last_updated(0),
-      m_have_computed(false), m_d_partials(nullptr), m_d_k(nullptr), m_d_ke(nullptr), m_d_v(nullptr), m_n_partials(0)
+    : NeighbourVariable(sysdef, "environment_similarity", log_suffix, nlist, type), m_par(), m_d_partials(nullptr), m_d_k(nullptr), m_d_ke(nullptr), m_d_v(nullptr), m_n_partials(0)
     {
     if (!nlist) throw std::runtime_error("cv.environment_similarity: a neighbour list is required");
     if (templates.empty() || templates.size() > MTD_ES_MAX_ENV)
@@ -1101,7 +1091,7 @@ void EnvironmentSimilarity::setSwitch(double c0, unsigned int p)
     m_par.switch_on = 1;
     m_par.c0 = c0;
     m_par.p = p;
-    m_have_computed = false;                                         // beta in the scratch belongs to the old switch
+    invalidate();                                                    // beta in the scratch belongs to the old switch
     }
 
 void EnvironmentSimilarity::clearSwitch()
@@ -1109,30 +1099,25 @@ void EnvironmentSimilarity::clearSwitch()
     m_par.switch_on = 0;
     m_par.c0 = 0.0;
     m_par.p = 0;
-    m_have_computed = false;
+    invalidate();
     }
 
 void EnvironmentSimilarity::computeCV(unsigned int timestep)
     {
     ProfRange prof_range("CV");
-    if (m_cv_last_updated == timestep && m_have_computed) return;
-    // the force pass gathers both roles of a particle from its own row
-    if (m_nlist->getStorageMode() == NeighborList::half)
-        throw std::runtime_error("cv.environment_similarity: a full neighbour list is required (the force pass gathers both roles of a "
-                                 "particle from its own row)");
+    if (fresh(timestep)) return;
+    requireFullList();
     if (distributed() && (m_par.n_env > 1 || m_par.switch_on))
         throw std::runtime_error("cv.environment_similarity: domain-decomposed runs are not supported with several environments or a switch "
                                  "(beta of a ghost neighbour would have to be exchanged)");
-    if (m_nlist->isDeviceBuild() && m_nlist->getRCut() < getRCut())
-        throw std::runtime_error("cv.environment_similarity: the neighbour list must reach r_cut");
+    requireReach(getRCut(), "r_cut");
     m_nlist->compute(timestep);
     const mtd_box box = m_pdata->getBox().toMtd();
     const size_t need = sizeof(double) * mtd_es_scratch_doubles(m_pdata->getN());
     if (need > m_scratch.bytes()) m_scratch.resize(need);
-    mtd_check(mtd_es_accumulate(m_pdata->getN(), m_pdata->getNGhosts(), m_pdata->positionsPtr(), m_pdata->getDtype(), &box,
-                                (const unsigned int *)m_nlist->getHeadList().data(), (const unsigned int *)m_nlist->getNNeighArray().data(),
-                                (const unsigned int *)m_nlist->getNListArray().data(), m_type, &m_par, m_pdata->getNGlobal(),
-                                (double *)m_scratch.data(), &m_d_partials, &m_n_partials, &m_d_k, &m_d_ke, &m_d_v, m_exec_conf->getStream()),
+    const Lists l = lists();
+    mtd_check(mtd_es_accumulate(m_pdata->getN(), m_pdata->getNGhosts(), m_pdata->positionsPtr(), m_pdata->getDtype(), &box, l.head, l.n_neigh,
+                                l.nlist, m_type, &m_par, m_pdata->getNGlobal(), (double *)m_scratch.data(), &m_d_partials, &m_n_partials, &m_d_k, &m_d_ke, &m_d_v, m_exec_conf->getStream()),
               "mtd_es_accumulate");
     // the ranks of a domain-decomposed run add their sums of v_i: one double, the same bits everywhere afterwards
     if (distributed())
@@ -1142,8 +1127,7 @@ void EnvironmentSimilarity::computeCV(unsigned int timestep)
                   "mtd_reduce_partials");
         m_exec_conf->allreduceSmall((double *)m_sum.data(), 1, s);
         }
-    m_have_computed = true;
-    m_cv_last_updated = timestep;
+    computed(timestep);
     }
 
 void EnvironmentSimilarity::enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot)
@@ -1159,43 +1143,21 @@ void EnvironmentSimilarity::enqueueCurrentValue(unsigned int timestep, mtd_metad
 double EnvironmentSimilarity::getCurrentValue(unsigned int timestep)
     {
     computeCV(timestep);
-    if (!distributed())
-        mtd_check(mtd_reduce_partials(m_d_partials, m_n_partials, 1, 1, 1.0 / (double)m_pdata->getNGlobal(), 0.0, (double *)m_sum.data(),
-                                      m_exec_conf->getStream()),
-                  "mtd_reduce_partials");
-    m_exec_conf->sync();
-    double value = 0.0;
-    hip_check(hipMemcpy(&value, m_sum.data(), sizeof(double), hipMemcpyDeviceToHost), "cv read-back");
-    return value;
+    if (!distributed()) return readPartials(m_d_partials, m_n_partials, timestep);
+    return readValue((const double *)m_sum.data(), timestep);       // computeCV has left the sum over the ranks there
     }
 
 void EnvironmentSimilarity::computeBiasForces(unsigned int timestep)
     {
     ProfRange prof_range("Force");
-    if (!m_have_computed || m_cv_last_updated != timestep) computeCV(timestep);      // beta of THIS step's positions
+    if (!fresh(timestep)) computeCV(timestep);                       // beta of THIS step's positions
     m_nlist->compute(timestep);
     const mtd_box box = m_pdata->getBox().toMtd();
-    // constant pressure: the per-particle virial of the bias force beside it (include/mtd_abi.h).  Without the flag the plain call; a
-    // virial array somebody has allocated earlier is zeroed then, so that a stale virial is never read (as SteinhardtLocal)
-    void *virial = nullptr;
-    if (m_pdata->getPressureFlag())
-        virial = getVirialArray().data();
-    else if (m_virial.bytes())
-        hip_check(hipMemsetAsync(m_virial.data(), 0, m_virial.bytes(), m_exec_conf->getStream()), "virial reset");
-    mtd_check(mtd_es_forces(m_pdata->getN(), m_pdata->getNGhosts(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &box,
-                            (const unsigned int *)m_nlist->getHeadList().data(), (const unsigned int *)m_nlist->getNNeighArray().data(),
-                            (const unsigned int *)m_nlist->getNListArray().data(), m_type, &m_par, m_pdata->getNGlobal(),
-                            (const double *)m_scratch.data(), m_bias_device, m_bias, m_exec_conf->getStream(), virial, getVirialPitch()),
+    const Lists l = lists();
+    void *virial = virialTarget();                                   // constant pressure: the per-particle virial of the bias force beside it
+    mtd_check(mtd_es_forces(m_pdata->getN(), m_pdata->getNGhosts(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &box, l.head,
+                            l.n_neigh, l.nlist, m_type, &m_par, m_pdata->getNGlobal(), (const double *)m_scratch.data(), m_bias_device, m_bias, m_exec_conf->getStream(), virial, getVirialPitch()),
               "mtd_es_forces");
-    }
-
-std::vector<double> EnvironmentSimilarity::readBack(const double *d_src, size_t n, const char *what, unsigned int timestep)
-    {
-    computeCV(timestep);
-    m_exec_conf->sync();
-    std::vector<double> out(n);
-    if (!out.empty()) hip_check(hipMemcpy(out.data(), d_src, sizeof(double) * n, hipMemcpyDeviceToHost), what);
-    return out;
     }
 
 std::vector<double> EnvironmentSimilarity::getLocalValues(unsigned int timestep)
@@ -1218,19 +1180,6 @@ std::vector<double> EnvironmentSimilarity::getEnvironmentValues(unsigned int tim
     for (size_t i = 0; i < m_pdata->getN(); ++i)
         for (unsigned int e = 0; e < m_par.n_env; ++e) out[i * m_par.n_env + e] = all[i * MTD_ES_MAX_ENV + e];
     return out;
-    }
-
-std::vector<std::string> EnvironmentSimilarity::getProvidedLogQuantities()
-    {
-    auto list = CollectiveVariable::getProvidedLogQuantities();
-    list.push_back("cv_" + m_cv_name);
-    return list;
-    }
-
-double EnvironmentSimilarity::getLogValue(const std::string &quantity, unsigned int timestep)
-    {
-    if (quantity == "cv_" + m_cv_name) return getCurrentValue(timestep);
-    return CollectiveVariable::getLogValue(quantity, timestep);
     }
 
 // ------------------------------------------------------------------------------------------------

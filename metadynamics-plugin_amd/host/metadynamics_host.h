@@ -96,6 +96,9 @@ class CollectiveVariable : public ForceCompute
     protected:
         void computeForces(unsigned int timestep) override;            // CollectiveVariable.cc:22-66
         virtual void computeBiasForces(unsigned int timestep) {}
+        //! Where a force pass writes the per-particle virial of the bias force: the virial array in a constant-pressure run (the pressure
+        //! flag), nullptr otherwise — and a virial array somebody has allocated earlier is then zeroed, so that a stale virial is never read
+        void *virialTarget();
 
         double m_bias;
         const double *m_bias_device;
@@ -315,9 +318,56 @@ class SteinhardtQl : public CollectiveVariable
         bool m_sym_ok;
     };
 
+//! What the variables that walk the rows of a FULL neighbour list share (SteinhardtLocal, PairEntropy, EnvironmentSimilarity): the list,
+//! the particle type, the scratch the passes leave their results in, "this step is computed already", the refusals of a list that does
+//! not fit, the synchronising read-backs and the cv_<name> log quantity.  A subclass supplies computeCV (its checks in its own order:
+//! full list, distributed, reach, then the list's compute) and the force pass.  SteinhardtQl stays outside: its lists have a mode and
+//! a symmetrised copy.
+class NeighbourVariable : public CollectiveVariable
+    {
+    public:
+        std::vector<std::string> getProvidedLogQuantities() override;  //!< the umbrella's and cv_<name>
+        double getLogValue(const std::string &quantity, unsigned int timestep) override;
+
+    protected:
+        //! `kind` ("pair_entropy"): the variable is called kind + log_suffix and its messages begin with "cv.<kind>: "
+        NeighbourVariable(std::shared_ptr<SystemDefinition> sysdef, const char *kind, const std::string &log_suffix,
+                          std::shared_ptr<NeighborList> nlist, unsigned int type);
+        virtual void computeCV(unsigned int timestep) = 0;
+        //! the results in the scratch are those of `timestep` / now are / are no longer anybody's (an option has changed)
+        bool fresh(unsigned int timestep) const { return m_have_computed && m_cv_last_updated == timestep; }
+        void computed(unsigned int timestep)
+            {
+            m_have_computed = true;
+            m_cv_last_updated = timestep;
+            }
+        void invalidate() { m_have_computed = false; }
+        void requireFullList() const;                                  //!< throws for a half list
+        void requireReach(double r_cut, const char *what) const;       //!< throws when a device-built list is shorter than r_cut (`what` names it)
+        struct Lists
+            {
+            const unsigned int *head, *n_neigh, *nlist;
+            };
+        Lists lists() const;
+        //! computeCV, then synchronising copies: n doubles at d_src; one double; the sum of the block sums times 1 / N_global (through m_sum).
+        //! A caller that hands on a pointer computeCV sets calls computeCV itself first
+        std::vector<double> readBack(const double *d_src, size_t n, const char *what, unsigned int timestep);
+        double readValue(const double *d_src, unsigned int timestep);
+        double readPartials(const double *d_partials, unsigned int n_partials, unsigned int timestep);
+
+        std::string m_prefix;                                          // "cv.<kind>: "
+        std::shared_ptr<NeighborList> m_nlist;
+        unsigned int m_type;
+        DeviceBuffer m_scratch, m_sum;                                 // (m_sum: one double, sized by the variables that reduce block sums)
+
+    private:
+        unsigned int m_cv_last_updated;
+        bool m_have_computed;
+    };
+
 //! Local Steinhardt bond order (no reference counterpart; include/mtd_abi.h "Local Steinhardt bond order"): the harmonics summed
 //! over one particle's own neighbours, squared per particle, averaged over the particles: s = (1/N_global) sum_i sum_l Ql_ref[l] q_l^2(i)
-class SteinhardtLocal : public CollectiveVariable
+class SteinhardtLocal : public NeighbourVariable
     {
     public:
         SteinhardtLocal(std::shared_ptr<SystemDefinition> sysdef, double rcut, double ron, unsigned int lmax,
@@ -327,8 +377,6 @@ class SteinhardtLocal : public CollectiveVariable
         //! device-resident: the block sums of c_i become the engine's source of this variable, no host synchronisation
         void enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot) override;
         void computeBiasForces(unsigned int timestep) override;
-        std::vector<std::string> getProvidedLogQuantities() override;
-        double getLogValue(const std::string &quantity, unsigned int timestep) override;
         std::vector<double> getLocalValues(unsigned int timestep);     //!< c_i of every local particle (0 for other types)
         std::vector<double> getCoordination(unsigned int timestep);    //!< n_i = sum_j f(r_ij)
         //! the options of mtd_ql_local_options; every change invalidates the cached step
@@ -344,16 +392,10 @@ class SteinhardtLocal : public CollectiveVariable
         std::vector<double> getBondCounts(unsigned int timestep);      //!< b_i of every local particle; throws without bonds
 
     private:
-        void computeCV(unsigned int timestep);
-        void optionsChanged();
+        void computeCV(unsigned int timestep) override;
         double m_rcut, m_ron;
         unsigned int m_lmax;
-        std::shared_ptr<NeighborList> m_nlist;
-        unsigned int m_type;
         std::vector<double> m_Ql_ref;
-        unsigned int m_cv_last_updated;
-        bool m_have_computed;
-        DeviceBuffer m_scratch, m_sum;
         const double *m_d_partials, *m_d_c, *m_d_n, *m_d_v, *m_d_b;
         unsigned int m_n_partials;
         mtd_ql_local_options m_opt;
@@ -362,7 +404,7 @@ class SteinhardtLocal : public CollectiveVariable
 
 //! Pair entropy (no reference counterpart; include/mtd_abi.h "Pair entropy"): S2 from a Gaussian-smoothed g(r) of one particle type.
 //! Works domain-decomposed: the only exchange is one allreduceSmall of the n_bins + 1 sums.
-class PairEntropy : public CollectiveVariable
+class PairEntropy : public NeighbourVariable
     {
     public:
         PairEntropy(std::shared_ptr<SystemDefinition> sysdef, double r_max, double sigma_r, unsigned int n_bins,
@@ -371,27 +413,20 @@ class PairEntropy : public CollectiveVariable
         //! device-resident: the value in the scratch becomes the engine's source of this variable, no host synchronisation
         void enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot) override;
         void computeBiasForces(unsigned int timestep) override;
-        std::vector<std::string> getProvidedLogQuantities() override;
-        double getLogValue(const std::string &quantity, unsigned int timestep) override;
         std::vector<double> getGr(unsigned int timestep);              //!< g_b of the n_bins bins (r_b = (b + 1/2) r_max / n_bins)
         double getRCut() const { return m_r_max + 4.0 * m_sigma_r; }   //!< what the neighbour list must reach
 
     private:
-        void computeCV(unsigned int timestep);
+        void computeCV(unsigned int timestep) override;
         double m_r_max, m_sigma_r;
         unsigned int m_n_bins;
-        std::shared_ptr<NeighborList> m_nlist;
-        unsigned int m_type;
-        unsigned int m_cv_last_updated;
-        bool m_have_computed;
-        DeviceBuffer m_scratch;
         const double *m_d_value, *m_d_g;
     };
 
 //! Environment similarity (no reference counterpart; include/mtd_abi.h "Environment similarity"): every particle's neighbourhood compared
 //! with template environments in a fixed orientation, s = (1/N_global) sum_i h(k_i).  Domain-decomposed runs: the plain variable (one
 //! environment, no switch) only — beta of a ghost neighbour would have to be exchanged otherwise.
-class EnvironmentSimilarity : public CollectiveVariable
+class EnvironmentSimilarity : public NeighbourVariable
     {
     public:
         //! templates: the environments, each a list of 3-vectors
@@ -402,8 +437,6 @@ class EnvironmentSimilarity : public CollectiveVariable
         //! device-resident: the block sums of v_i become the engine's source of this variable, no host synchronisation
         void enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot) override;
         void computeBiasForces(unsigned int timestep) override;
-        std::vector<std::string> getProvidedLogQuantities() override;
-        double getLogValue(const std::string &quantity, unsigned int timestep) override;
         std::vector<double> getLocalValues(unsigned int timestep);         //!< k_i of every local particle (0 for other types)
         std::vector<double> getEnvironmentValues(unsigned int timestep);   //!< k^e_i, N x E row-major
         std::vector<double> getSwitchedValues(unsigned int timestep);      //!< v_i = h(k_i)
@@ -414,14 +447,8 @@ class EnvironmentSimilarity : public CollectiveVariable
         void clearSwitch();
 
     private:
-        void computeCV(unsigned int timestep);
-        std::vector<double> readBack(const double *d_src, size_t n, const char *what, unsigned int timestep);
+        void computeCV(unsigned int timestep) override;
         mtd_es_params m_par;
-        std::shared_ptr<NeighborList> m_nlist;
-        unsigned int m_type;
-        unsigned int m_cv_last_updated;
-        bool m_have_computed;
-        DeviceBuffer m_scratch, m_sum;
         const double *m_d_partials, *m_d_k, *m_d_ke, *m_d_v;
         unsigned int m_n_partials;
     };

@@ -186,48 +186,67 @@ class mesh(_collective_variable):
         self.cpp_force.setTable(Ktable, dKtable, kmin, kmax)
 
 
-class steinhardt(_collective_variable):
-    """Steinhardt Ql (cv.py:540-617): CV = sum_l Ql_ref[l] * Q_l over particles of one type within r_cut."""
+class _neighbour_variable(_collective_variable):
+    """What the variables over the rows of a neighbour list share (steinhardt, steinhardt_local, pair_entropy, environment_similarity):
+    the frame of their constructors, ``get_rcut`` and ``get_virial``.  A subclass sets ``self.type``, ``self.nlist`` and ``self.r_cut``
+    (what the list must reach) and names itself in ``_cv`` for the error texts."""
 
-    def __init__(self, r_cut, r_on, lmax, Ql_ref, nlist, type, name=None, sigma=1.0):
-        suffix = ""
-        if name is not None:
-            suffix = "_" + name
+    _cv = None
+
+    def _begin(self, sigma, name):
+        """registers the variable; returns the suffix of its log quantities"""
         _collective_variable.__init__(self, sigma, name)
-        self.type = type
-        self.nlist = nlist
-        self.r_cut = r_cut
+        return "" if name is None else "_" + name
+
+    def _full_list(self):
         # cv.py:584-585: the reference forces full storage when HOOMD runs on the GPU — this build always does
         self.nlist.cpp_nlist.setStorageMode(_metadynamics.NeighborList.storageMode.full)
-        type_list = context.current.type_names
-        if type not in type_list:
-            raise RuntimeError("Error creating collective variable.")     # cv.py:591-593
-        self.cpp_force = _metadynamics.SteinhardtQl(context.current.system_definition, float(r_cut), float(r_on), int(lmax),
-                                                    nlist.cpp_nlist, type_list.index(type), [float(q) for q in Ql_ref], suffix)
-        if getattr(nlist, "device", False):
-            nlist._attach(type_list.index(type))      # a device-built list only needs the pairs of this CV's type (get_rcut)
+
+    def _attach(self, type_id):
+        if getattr(self.nlist, "device", False):
+            self.nlist._attach(type_id)               # a device-built list only needs the pairs of this CV's type (get_rcut)
 
     def get_rcut(self):
-        """cv.py:603-617: the cut-off this CV asks of the neighbour list, by type pair — only (type, type) interacts.
-        (The reference body refers to an undefined ``nl``; this returns the plain dict it was building.)"""
+        """the cut-off this CV asks of the neighbour list, by type pair — only (type, type) interacts, up to ``r_cut`` (pair_entropy:
+        r_max + 4 sigma_r).  (cv.py:603-617; the reference body refers to an undefined ``nl``; this returns the plain dict it was
+        building.)"""
         names = context.current.type_names
         return {(a, b): (self.r_cut if a == b == self.type else -1.0) for i, a in enumerate(names) for b in names[i:]}
 
     def get_virial(self, per_particle=False):
-        """the virial of the bias force the last step wrote (include/mtd_abi.h, mtd_ql_forces_virial): the six sums xx, xy, xz, yy, yz,
-        zz as float64, or with ``per_particle=True`` the (6, N) array, half of every pair at each of its ends.  It is the virial of the
-        force that is applied: the full-list force keeps only the central terms of the gradient (as the reference's), so the sums are
-        -1/2 * bias * ds/d(strain), not -bias * ds/d(strain).  In a domain-decomposed run every rank holds the rows of its local
-        particles.  It is formed only while the pressure flag of the particle data is set (a constant-pressure run); without the flag
-        this raises."""
+        """the virial of the bias force the last step wrote (include/mtd_abi.h): the six sums xx, xy, xz, yy, yz, zz as float64, or with
+        ``per_particle=True`` the (6, N) array, half of every pair at each of its ends.  What the sums are the derivative of is said
+        under "Virial" in the variable's own docstring.  In a domain-decomposed run every rank holds the rows of its local particles.
+        It is formed only while the pressure flag of the particle data is set (a constant-pressure run); without the flag this raises."""
         pdata = context.current.system_definition.getParticleData()
         if not pdata.getPressureFlag():
-            raise RuntimeError("cv.steinhardt: the virial is computed only while the pressure flag is set")
+            raise RuntimeError("%s: the virial is computed only while the pressure flag is set" % self._cv)
         import numpy as np
         n = pdata.getN()
         v = np.asarray(self.cpp_force.getVirial(), dtype=np.float64)[:, :n]
         return v.copy() if per_particle else v.sum(axis=1)
 
+
+class steinhardt(_neighbour_variable):
+    """Steinhardt Ql (cv.py:540-617): CV = sum_l Ql_ref[l] * Q_l over particles of one type within r_cut.
+
+    Virial (``get_virial``; mtd_ql_forces_virial): it is the virial of the force that is applied: the full-list force keeps only the
+    central terms of the gradient (as the reference's), so the sums are -1/2 * bias * ds/d(strain), not -bias * ds/d(strain)."""
+
+    _cv = "cv.steinhardt"
+
+    def __init__(self, r_cut, r_on, lmax, Ql_ref, nlist, type, name=None, sigma=1.0):
+        suffix = self._begin(sigma, name)
+        self.type = type
+        self.nlist = nlist
+        self.r_cut = r_cut
+        self._full_list()
+        type_list = context.current.type_names
+        if type not in type_list:
+            raise RuntimeError("Error creating collective variable.")     # cv.py:591-593
+        self.cpp_force = _metadynamics.SteinhardtQl(context.current.system_definition, float(r_cut), float(r_on), int(lmax),
+                                                    nlist.cpp_nlist, type_list.index(type), [float(q) for q in Ql_ref], suffix)
+        self._attach(type_list.index(type))
 
 class _local_options(type):
     """``cv.steinhardt_local(..., average=False, switch=None, gate=None, bonds=None)``: the options are keyword arguments of the CALL.  They
@@ -246,7 +265,7 @@ class _local_options(type):
         return obj
 
 
-class steinhardt_local(_collective_variable, metaclass=_local_options):
+class steinhardt_local(_neighbour_variable, metaclass=_local_options):
     """this build (no reference counterpart): the LOCAL Steinhardt order parameter.  The harmonics are summed over one particle's own
     neighbours, turned into the rotational invariant per particle and averaged:
     CV = (1 / N) sum_i sum_l Ql_ref[l] * q_l^2(i),  q_l^2(i) = 4 pi / (2l + 1) sum_m |sum_j f(r_ij) Y_lm(r_ij)|^2 / (sum_j f(r_ij))^2
@@ -261,29 +280,24 @@ class steinhardt_local(_collective_variable, metaclass=_local_options):
     of the q vectors of i and j (weights Ql_ref[l] 4 pi / (2l + 1), all >= 0), a bond counts with the smoothstep sigma of d_ij from d_lo to
     d_hi (-1 <= d_lo < d_hi <= 1), b_i = sum_j f(r_ij) sigma(d_ij), and switch and gate act on it: CV = (1 / N) sum_i g(n_i) h(b_i).
     With ``Ql_ref = e_6``, ``bonds=dict(d_lo=0.5, d_hi=0.7)`` and ``switch=dict(c0=6.5, p=12)``, CV * N is the smooth number of solid
-    particles of the literature.  Not together with ``average``."""
+    particles of the literature.  Not together with ``average``.
+
+    Virial: ``get_virial`` (mtd_ql_local_forces_virial)."""
+
+    _cv = "cv.steinhardt_local"
 
     def __init__(self, r_cut, r_on, lmax, Ql_ref, nlist, type, name=None, sigma=1.0):
-        suffix = ""
-        if name is not None:
-            suffix = "_" + name
-        _collective_variable.__init__(self, sigma, name)
+        suffix = self._begin(sigma, name)
         self.type = type
         self.nlist = nlist
         self.r_cut = r_cut
-        self.nlist.cpp_nlist.setStorageMode(_metadynamics.NeighborList.storageMode.full)
+        self._full_list()
         type_list = context.current.type_names
         if type not in type_list:
             raise RuntimeError("Error creating collective variable.")
         self.cpp_force = _metadynamics.SteinhardtLocal(context.current.system_definition, float(r_cut), float(r_on), int(lmax),
                                                        nlist.cpp_nlist, type_list.index(type), [float(q) for q in Ql_ref], suffix)
-        if getattr(nlist, "device", False):
-            nlist._attach(type_list.index(type))      # a device-built list only needs the pairs of this CV's type
-
-    def get_rcut(self):
-        """the cut-off this CV asks of the neighbour list, by type pair — only (type, type) interacts"""
-        names = context.current.type_names
-        return {(a, b): (self.r_cut if a == b == self.type else -1.0) for i, a in enumerate(names) for b in names[i:]}
+        self._attach(type_list.index(type))
 
     def get_local(self):
         """c_i = sum_l Ql_ref[l] q_l^2(i) of every particle at the current time step (0 for particles of another type)"""
@@ -301,18 +315,6 @@ class steinhardt_local(_collective_variable, metaclass=_local_options):
     def get_bonds(self):
         """b_i = sum_j f(r_ij) sigma(d_ij): the smooth number of solid bonds of every particle at the current time step (needs ``bonds``)"""
         return self.cpp_force.getBondCounts(context.current.system.getCurrentTimeStep())
-
-    def get_virial(self, per_particle=False):
-        """the virial of the bias force the last step wrote (include/mtd_abi.h, mtd_ql_local_forces_virial): the six sums xx, xy, xz, yy,
-        yz, zz as float64, or with ``per_particle=True`` the (6, N) array, half of every pair at each of its ends.  It is formed only
-        while the pressure flag of the particle data is set (a constant-pressure run); without the flag this raises."""
-        pdata = context.current.system_definition.getParticleData()
-        if not pdata.getPressureFlag():
-            raise RuntimeError("cv.steinhardt_local: the virial is computed only while the pressure flag is set")
-        import numpy as np
-        n = pdata.getN()
-        v = np.asarray(self.cpp_force.getVirial(), dtype=np.float64)[:, :n]
-        return v.copy() if per_particle else v.sum(axis=1)
 
     def set_options(self, average=False, switch=None, gate=None, bonds=None):
         """set all four options (the defaults switch them off); takes effect with the next step"""
@@ -342,18 +344,20 @@ class steinhardt_local(_collective_variable, metaclass=_local_options):
             raise RuntimeError("Error creating collective variable.")
 
 
-class pair_entropy(_collective_variable):
+class pair_entropy(_neighbour_variable):
     """this build (no reference counterpart; include/mtd_abi.h "Pair entropy"): the two-body excess entropy of the particles of one type
     from a Gaussian-smoothed radial distribution function (Piaggi, Valsson and Parrinello, PRL 119, 015701; PLUMED's PAIRENTROPY),
     CV = -2 pi rho int_0^r_max [g ln g - g + 1] r^2 dr in units of k_B, on ``n_bins`` midpoints with Gaussians of width ``sigma_r``.
     It needs no knowledge of the target structure and is normally biased together with ``cv.potential_energy`` on a 2-d grid.
-    Needs a full list that reaches ``r_max + 4 * sigma_r`` (``get_rcut``); works in domain-decomposed runs; n_bins <= 256."""
+    Needs a full list that reaches ``r_max + 4 * sigma_r`` (``get_rcut``); works in domain-decomposed runs; n_bins <= 256.
+
+    Virial (``get_virial``; mtd_pe_forces): half of every pair at each of its ends, and the explicit volume term spread evenly over the
+    particles of the type.  The sums are -bias * dS/d(strain)."""
+
+    _cv = "cv.pair_entropy"
 
     def __init__(self, r_max, sigma_r, n_bins, nlist, type, name=None, sigma=1.0):
-        suffix = ""
-        if name is not None:
-            suffix = "_" + name
-        _collective_variable.__init__(self, sigma, name)
+        suffix = self._begin(sigma, name)
         try:
             type_list = context.current.type_names
             r_max, sigma_r = float(r_max), float(sigma_r)
@@ -364,40 +368,19 @@ class pair_entropy(_collective_variable):
             self.nlist = nlist
             self.r_max, self.sigma_r, self.n_bins = r_max, sigma_r, int(n_bins)
             self.r_cut = r_max + 4.0 * sigma_r
-            self.nlist.cpp_nlist.setStorageMode(_metadynamics.NeighborList.storageMode.full)
+            self._full_list()
             self.cpp_force = _metadynamics.PairEntropy(context.current.system_definition, r_max, sigma_r, int(n_bins), nlist.cpp_nlist,
                                                        type_list.index(type), suffix)
         except (TypeError, ValueError, AttributeError, RuntimeError):
             context.current.forces.remove(self)                      # refused: the run must not find a half-made variable
             raise RuntimeError("Error creating collective variable.")
-        if getattr(nlist, "device", False):
-            nlist._attach(type_list.index(type))      # a device-built list only needs the pairs of this CV's type
-
-    def get_rcut(self):
-        """the cut-off this CV asks of the neighbour list, by type pair — only (type, type) interacts, up to r_max + 4 sigma_r"""
-        names = context.current.type_names
-        return {(a, b): (self.r_cut if a == b == self.type else -1.0) for i, a in enumerate(names) for b in names[i:]}
+        self._attach(type_list.index(type))
 
     def get_gr(self):
         """(r_b, g_b): the bin midpoints and the smoothed radial distribution function of the current time step"""
         import numpy as np
         r_b = (np.arange(self.n_bins) + 0.5) * (self.r_max / self.n_bins)
         return r_b, np.asarray(self.cpp_force.getGr(context.current.system.getCurrentTimeStep()))
-
-    def get_virial(self, per_particle=False):
-        """the virial of the bias force the last step wrote (include/mtd_abi.h, mtd_pe_forces): the six sums xx, xy, xz, yy, yz, zz as
-        float64, or with ``per_particle=True`` the (6, N) array: half of every pair at each of its ends, and the explicit volume term
-        spread evenly over the particles of the type.  The sums are -bias * dS/d(strain); in a domain-decomposed run every rank holds the
-        rows of its local particles.  It is formed only while the pressure flag of the particle data is set; without the flag this
-        raises."""
-        pdata = context.current.system_definition.getParticleData()
-        if not pdata.getPressureFlag():
-            raise RuntimeError("cv.pair_entropy: the virial is computed only while the pressure flag is set")
-        import numpy as np
-        n = pdata.getN()
-        v = np.asarray(self.cpp_force.getVirial(), dtype=np.float64)[:, :n]
-        return v.copy() if per_particle else v.sum(axis=1)
-
 
 def environment_templates(structure, a):
     """the template environments of a cubic lattice with the conventional lattice constant ``a``, for ``cv.environment_similarity``:
@@ -431,7 +414,7 @@ def environment_templates(structure, a):
     raise RuntimeError("cv.environment_templates: structure must be 'fcc', 'bcc', 'sc' or 'diamond'")
 
 
-class environment_similarity(_collective_variable):
+class environment_similarity(_neighbour_variable):
     """this build (no reference counterpart; include/mtd_abi.h "Environment similarity"): the environment similarity kernel of Piaggi and
     Parrinello (J. Chem. Phys. 150, 244119; PLUMED's ENVIRONMENTSIMILARITY).  Every particle's neighbourhood is compared with one or more
     template environments, each a list of lattice vectors in the LAB frame (``cv.environment_templates``):
@@ -440,13 +423,16 @@ class environment_similarity(_collective_variable):
     CV = (1 / N) sum_i h(k_i) with h(k) = k or, with ``switch=dict(c0=..., p=...)``, x^p / (1 + x^p), x = k / c0 — CV * N is then the
     smooth number of particles in the template's structure AND orientation.  ``templates``: a list of 3-vectors (one environment) or a list
     of such lists (at most 4 environments, 32 vectors each, 64 in all, every vector shorter than ``r_cut``).  Needs a full list that
-    reaches ``r_cut``.  Domain-decomposed runs: one environment without a switch only."""
+    reaches ``r_cut``.  Domain-decomposed runs: one environment without a switch only.
+
+    Virial (``get_virial``; mtd_es_forces): half of every entry at each of its ends.  The sums are -bias * dCV/d(eps_ab) under
+    x_a += eps x_b of positions and box with the templates held fixed: the tensor is NOT symmetric, and xy, xz, yz are the off-diagonals a
+    HOOMD box can deform along."""
+
+    _cv = "cv.environment_similarity"
 
     def __init__(self, templates, sigma_env, r_cut, r_on, nlist, type, lam=100.0, switch=None, name=None, sigma=1.0):
-        suffix = ""
-        if name is not None:
-            suffix = "_" + name
-        _collective_variable.__init__(self, sigma, name)
+        suffix = self._begin(sigma, name)
         try:
             type_list = context.current.type_names
             sigma_env, r_cut, r_on, lam = float(sigma_env), float(r_cut), float(r_on), float(lam)
@@ -465,7 +451,7 @@ class environment_similarity(_collective_variable):
             self.type = type
             self.nlist = nlist
             self.templates, self.sigma_env, self.r_cut, self.r_on, self.lam = envs, sigma_env, r_cut, r_on, lam
-            self.nlist.cpp_nlist.setStorageMode(_metadynamics.NeighborList.storageMode.full)
+            self._full_list()
             self.cpp_force = _metadynamics.EnvironmentSimilarity(context.current.system_definition, envs, sigma_env, r_cut, r_on, lam,
                                                                  nlist.cpp_nlist, type_list.index(type), suffix)
             if sw is not None:
@@ -473,8 +459,7 @@ class environment_similarity(_collective_variable):
         except (TypeError, ValueError, KeyError, IndexError, AttributeError, RuntimeError):
             context.current.forces.remove(self)                      # refused: the run must not find a half-made variable
             raise RuntimeError("Error creating collective variable.")
-        if getattr(nlist, "device", False):
-            nlist._attach(type_list.index(type))      # a device-built list only needs the pairs of this CV's type
+        self._attach(type_list.index(type))
 
     @staticmethod
     def _environments(templates):
@@ -498,11 +483,6 @@ class environment_similarity(_collective_variable):
             raise ValueError
         return sw
 
-    def get_rcut(self):
-        """the cut-off this CV asks of the neighbour list, by type pair — only (type, type) interacts"""
-        names = context.current.type_names
-        return {(a, b): (self.r_cut if a == b == self.type else -1.0) for i, a in enumerate(names) for b in names[i:]}
-
     def get_local(self):
         """k_i of every particle at the current time step (0 for particles of another type)"""
         return self.cpp_force.getLocalValues(context.current.system.getCurrentTimeStep())
@@ -525,20 +505,6 @@ class environment_similarity(_collective_variable):
                 self.cpp_force.setSwitch(*sw)
         except (TypeError, KeyError, ValueError, AttributeError, RuntimeError):
             raise RuntimeError("Error creating collective variable.")
-
-    def get_virial(self, per_particle=False):
-        """the virial of the bias force the last step wrote (include/mtd_abi.h, mtd_es_forces): the six sums xx, xy, xz, yy, yz, zz as
-        float64, or with ``per_particle=True`` the (6, N) array, half of every entry at each of its ends.  The sums are -bias * dCV/d(eps_ab)
-        under x_a += eps x_b of positions and box with the templates held fixed: the tensor is NOT symmetric, and xy, xz, yz are the
-        off-diagonals a HOOMD box can deform along.  It is formed only while the pressure flag of the particle data is set; without the flag
-        this raises."""
-        pdata = context.current.system_definition.getParticleData()
-        if not pdata.getPressureFlag():
-            raise RuntimeError("cv.environment_similarity: the virial is computed only while the pressure flag is set")
-        import numpy as np
-        n = pdata.getN()
-        v = np.asarray(self.cpp_force.getVirial(), dtype=np.float64)[:, :n]
-        return v.copy() if per_particle else v.sum(axis=1)
 
 
 class nlist_cell(object):
