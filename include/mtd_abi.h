@@ -756,6 +756,63 @@ int mtd_ql_local_forces_bonds(unsigned int n_particles, const void *d_postype, v
                               unsigned int virial_pitch, const mtd_ql_local_bonds *bonds);
 
 /* ================================================================================================
+ * Clusters — no reference counterpart.  Connected components of the "solid" particles over a neighbour list, and the mask of the
+ * largest one: what nucleation studies bias is the size of the largest connected cluster of solid particles (ten Wolde, Ruiz-Montero
+ * and Frenkel; PLUMED's DFSCLUSTERING followed by CLUSTER_NATOMS or CLUSTER_PROPERTIES ... SUM).  The unit stands alone: d_v is any
+ * per-particle value (the v_i of mtd_ql_local_accumulate_bonds, the k_i of the environment similarity, ...).
+ *     nodes   particles i < n_particles with type(i) == type and d_v[i] >= v_min (NaN is not a node)
+ *     edges   list entries (i, j), j in row i, with both ends nodes, j != i, j < n_particles and
+ *             |minImage(r_i - r_j)|^2 <= r_link^2
+ * The list need not be symmetric for this pass: an edge seen from either end unites.  Ghost entries (j >= n_particles) are skipped, so a
+ * cluster that crosses a domain boundary is cut there: single-domain runs only.
+ * Outputs, all inside d_scratch (mtd_cluster_scratch_bytes(n_particles) bytes, 16-byte aligned), stream-ordered, nothing synchronised:
+ *     label[i]   the smallest particle index of i's component; MTD_CLUSTER_NONE for a particle that is not a node
+ *     size[r]    the member count at every root r (label[r] == r), 0 elsewhere
+ *     summary    { root of the largest cluster, its member count, number of clusters, number of nodes }; largest = most members, a tie
+ *                goes to the smaller root; without any node the root is MTD_CLUSTER_NONE and the count 0
+ *     w[i]       1.0 for the members of the largest cluster, 0.0 for everybody else
+ * Every output is a function of the input alone: only integer atomics are used, two calls give the same bits.  Any of the four output
+ * pointers may be NULL.
+ * MTD_ERR_INVALID_ARGUMENT, before a device is touched, for a null box, scratch or (with particles) array, an unknown dtype, a scratch
+ * that is not 16-byte aligned, r_link <= 0 or not finite, v_min not finite, and for p == NULL or p->on == 0: "off" is the caller's
+ * business (mtd_ql_local_accumulate_cluster).  r_link is not compared with the reach of the list, which is unknown here.
+ * ============================================================================================== */
+typedef struct
+    {
+    int on;
+    double v_min, r_link;
+    } mtd_cluster_params;                                                      /* all-zero = off */
+#define MTD_CLUSTER_NONE 0xffffffffu
+
+size_t mtd_cluster_scratch_bytes(unsigned int n_particles);
+int mtd_cluster_largest(unsigned int n_particles, const void *d_postype, int dtype, const mtd_box *box, const unsigned int *d_head_list,
+                        const unsigned int *d_n_neigh, const unsigned int *d_nlist, unsigned int type, const double *d_v,
+                        const mtd_cluster_params *p, void *d_scratch, const unsigned int **d_label, const unsigned int **d_size,
+                        const double **d_w, const unsigned int **d_summary, mtd_stream_t stream);
+
+/* The local Steinhardt variable restricted to the largest cluster of solid particles:
+ *     s = (1 / N_global) sum_{i in the largest cluster} v_i = (1 / N_global) sum_i w_i v_i
+ * with the clusters of mtd_cluster_largest built from the v_i of this call (v_i >= v_min, linked within r_link).  With the bond count
+ * and a switch, s N_global is the smooth SIZE OF THE LARGEST NUCLEUS.  Membership is piecewise constant, so the gradient is the one
+ * above with v_i -> w_i v_i (PLUMED's treatment); the variable jumps when clusters merge or split.  The mask enters linearly and is
+ * applied between the launches of the passes above: plain / switch / gate — the table row of i times w_i; bonds — beta_i and a0_i times
+ * w_i before the back-propagation.  mtd_ql_local_forces_bonds (and its virial) then runs unchanged on the masked table, with the same
+ * opt and bonds: there is no force entry point of its own.  *d_partials: the block sums of w_i v_i; *d_v stays the UNMASKED v_i, the
+ * solid-ness the clusters were built from.  d_cluster_scratch: mtd_cluster_scratch_bytes(n_particles) bytes, separate from d_scratch,
+ * whose layout and size do not change; *d_w, *d_label, *d_summary (each may be NULL) point into it as mtd_cluster_largest leaves them.
+ * cluster == NULL or on == 0: mtd_ql_local_accumulate_bonds, bit for bit (that entry point forwards here); the three pointers are set
+ * to NULL.  Refused before a device is touched: what mtd_cluster_largest refuses (MTD_ERR_INVALID_ARGUMENT), and `average` together with a
+ * cluster (MTD_ERR_UNSUPPORTED: its B rows and the extra a_k term would need the mask too). */
+int mtd_ql_local_accumulate_cluster(unsigned int n_particles, const void *d_postype, int dtype, const mtd_box *box,
+                                    const unsigned int *d_head_list, const unsigned int *d_n_neigh, const unsigned int *d_nlist, double rcut,
+                                    double ron, unsigned int lmax, unsigned int type, const double *Ql_ref, unsigned int n_global,
+                                    double *d_scratch, const double **d_partials, unsigned int *n_partials, const double **d_c,
+                                    const double **d_n, mtd_stream_t stream, const mtd_ql_local_options *opt, const double **d_v,
+                                    const mtd_ql_local_bonds *bonds, const double **d_b, const mtd_cluster_params *cluster,
+                                    void *d_cluster_scratch, const double **d_w, const unsigned int **d_label,
+                                    const unsigned int **d_summary);
+
+/* ================================================================================================
  * Pair entropy (cv.pair_entropy) — no reference counterpart.  The two-body excess entropy S2 from a Gaussian-smoothed g(r) (Piaggi,
  * Valsson and Parrinello, PRL 119, 015701; PLUMED's PAIRENTROPY): a bias variable for nucleation that needs no knowledge of the target
  * structure.  Parameters r_max > 0, sigma_r > 0, n_bins = B (1 .. 256) and a particle type t.

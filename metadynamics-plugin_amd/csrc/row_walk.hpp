@@ -9,7 +9,8 @@
 // (profiles/r20/README.md compares them kernel by kernel).
 //
 // The walk lives in THREE forms, and a change to the look-ahead, the list format or the skip rule is made in all of them:
-//   row_walk                   here: both passes of pair_entropy.hip and of env_similarity.hip
+//   row_walk                   here: both passes of pair_entropy.hip and of env_similarity.hip; as row_walk_entries<.., GHOSTS = false>
+//                              the link pass of cluster.hip (local entries only: the rule of QllWalker, switched at compile time)
 //   QllWalker                  steinhardt_local.hip: its four gather passes, through qll_entries
 //   three loops written out    k_qll_accumulate, k_qll_forces and k_qll_forces_tile of steinhardt_local.hip (through a walker their bits
 //                              or their speed did not stay the parent's: profiles/r10/README.md)
@@ -110,23 +111,26 @@ __device__ __forceinline__ const double *loop_table(const double *tab)
 // arithmetic.  j is NOT compared with N (header: ghosts are walked).  FROM_CENTRE says which way d points, d = minImage(r_i - r_j) (true:
 // pair_entropy.hip) or minImage(r_j - r_i) (false: env_similarity.hip); each unit's subtraction is the one it always made, nothing is
 // negated afterwards.
-template<int G, bool FROM_CENTRE, typename S4, typename F>
-__device__ __forceinline__ void row_walk(const QlArgs<4> &a, const S4 *__restrict__ postype, const unsigned int *__restrict__ nlist,
-                                         const double *__restrict__ tab, const RowCentre &c, const unsigned int q, F &&body)
+// GHOSTS = false (cluster.hip, whose per-particle arrays end at N like the Steinhardt tables): an entry j >= a.N is skipped and its
+// position is not loaded, the rule of QllWalker.  It is a compile-time switch: row_walk, below, is the walk with ghosts, as it always was.
+template<int G, bool FROM_CENTRE, bool GHOSTS, typename S4, typename F>
+__device__ __forceinline__ void row_walk_entries(const QlArgs<4> &a, const S4 *__restrict__ postype, const unsigned int *__restrict__ nlist,
+                                                 const double *__restrict__ tab, const RowCentre &c, const unsigned int q, F &&body)
     {
+    const auto held = [&](const unsigned int j) { return GHOSTS ? j != ROW_NONE : j < a.N; };      // its position may be loaded
     unsigned int e = q;
     unsigned int j0 = e < c.cnt ? nlist[c.start + e] : ROW_NONE;
     unsigned int j1 = e + G < c.cnt ? nlist[c.start + e + G] : ROW_NONE;
     S4 pos0 = row_zero<S4>();
-    if (j0 != ROW_NONE) pos0 = postype[j0];
+    if (held(j0)) pos0 = postype[j0];
 #pragma unroll 1
     for (; e < c.cnt; e += G)
         {
         const double *__restrict__ tab_k = loop_table(tab);
         const unsigned int j2 = e + 2 * G < c.cnt ? nlist[c.start + e + 2 * G] : ROW_NONE;
         S4 pos1 = row_zero<S4>();
-        if (j1 != ROW_NONE) pos1 = postype[j1];
-        if (j0 != c.i)
+        if (held(j1)) pos1 = postype[j1];
+        if (GHOSTS ? j0 != c.i : j0 != c.i && j0 < a.N)
             {
             const Particle pj = scalar4_traits<S4>::unpack(pos0);
             double dx, dy, dz;
@@ -142,6 +146,13 @@ __device__ __forceinline__ void row_walk(const QlArgs<4> &a, const S4 *__restric
         j1 = j2;
         pos0 = pos1;
         }
+    }
+
+template<int G, bool FROM_CENTRE, typename S4, typename F>
+__device__ __forceinline__ void row_walk(const QlArgs<4> &a, const S4 *__restrict__ postype, const unsigned int *__restrict__ nlist,
+                                         const double *__restrict__ tab, const RowCentre &c, const unsigned int q, F &&body)
+    {
+    row_walk_entries<G, FROM_CENTRE, true>(a, postype, nlist, tab, c, q, body);
     }
 
 // The virial of a force pass, stored by lane 0 of the group of a particle i < N (the caller's test): the six sums times `h`, the diagonal

@@ -77,9 +77,15 @@
 //                    q(i) / sqrt(c_i)), k_qll_bonds (gathers u(j): d per list entry, b_i, v_i, beta_i), k_qll_bonds_backprop (gathers u(j)
 //                    and beta_j: the table row and E_kj = (beta_k + beta_j) sigma(d_kj) per list entry), then the AVG force pass as it is.
 //                    See the block above k_qll_bonds.
+//   cluster          (mtd_cluster_params, mtd_ql_local_accumulate_cluster) the sum restricted to the largest connected cluster of particles with
+//                    v_i >= v_min: s = (1 / N) sum_i w_i v_i with the 0 / 1 mask w of cluster.hip.  The mask enters linearly, so it is applied
+//                    BETWEEN the launches above by k_qll_cluster_apply (rows, or beta_i and a0_i, of the non-members zeroed; the block sums
+//                    replaced by those of w_i v_i); the force kernels and the virial run unchanged on the masked table.  Not with the
+//                    average.  See the block above k_qll_cluster_apply.
 #include "mtd_device.hpp"
 #include "row_walk.hpp"
 #include "dispatch.hpp"
+#include "cluster_host.hpp"
 
 namespace
 {
@@ -1204,6 +1210,44 @@ __global__ __launch_bounds__(QLL_THREADS) void k_qll_bonds_backprop(const QlArgs
         }
     }
 
+// ---- the largest cluster: the mask w_i of cluster.hip applied between the launches above ------------------------------------------
+// The variable restricted to the largest cluster is sum_i w_i v_i with w piecewise constant: the mask enters every sum above linearly.
+//   ROWS = true   (plain, switch, gate; after k_qll_accumulate) the table row R(i) times w_i — the (0, 0) slot with a_i folded in is part
+//                 of the row; lane q of the quad takes slots q, q + 4, ...
+//   ROWS = false  (bonds; between k_qll_bonds and k_qll_bonds_backprop) beta_i and a0_i times w_i: t_kj, E_kj and the rows then come out
+//                 masked by themselves
+// Both overwrite the block sums with those of w_i v_i, chunks and blocks in the order of the other passes, summed by qll_chunk_sum: no
+// atomics, the same bits at every call.  v_i itself stays unmasked: it is what the clusters were built from.
+template<bool ROWS>
+__global__ __launch_bounds__(QLL_THREADS) void k_qll_cluster_apply(const unsigned int N, const unsigned int rs16, const double *__restrict__ w,
+                                                                   const double *__restrict__ v, double2 *__restrict__ rows,
+                                                                   double *__restrict__ beta, double *__restrict__ a0,
+                                                                   double *__restrict__ partials)
+    {
+    __shared__ double s_c[QLL_PPB];
+    const unsigned int tid = threadIdx.x, p = tid / QLL_G, q = tid % QLL_G;
+    const unsigned int n_chunks = (N + QLL_PPB - 1) / QLL_PPB;
+    double block_v = 0.0;
+    for (unsigned int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x)
+        {
+        const unsigned int i = chunk * QLL_PPB + p;
+        const bool there = i < N;
+        const double wi = there ? w[i] : 0.0;
+        if constexpr (ROWS)
+            {
+            if (there && wi == 0.0)                                                  // w is 0 or 1: a member's row stays as it is
+                for (unsigned int c = q; c < rs16; c += QLL_G) rows[(size_t)i * rs16 + c] = make_double2(0.0, 0.0);
+            }
+        else if (there && q == 0 && wi == 0.0)
+            {
+            beta[i] = 0.0;
+            a0[i] = 0.0;
+            }
+        qll_chunk_sum(s_c, tid, there && wi != 0.0 ? v[i] : 0.0, block_v);
+        }
+    if (tid == 0) partials[blockIdx.x] = block_v;
+    }
+
 // ---- host side ------------------------------------------------------------------------------------------------------------
 QllLayout qll_layout(const unsigned int lmax, const double *ql_ref)
     {
@@ -1352,7 +1396,27 @@ template<int LMAX> int qll_args(QlArgs<LMAX> &a, const QllCall &k)
     return fill_args<LMAX>(a, k.N, k.box, k.rcut, k.ron, k.lmax, k.type, k.ql_ref, k.n_global, 0);
     }
 
-template<typename S4, int LMAX> int qll_accumulate_impl(const QllCall &k)
+// the cluster pass of a call: the mask of the largest cluster of the v_i just formed (cluster.hip), then k_qll_cluster_apply
+struct QllCluster
+    {
+    const mtd_cluster_params *p;                           // NULL: off
+    void *scratch;
+    const double *w;
+    const unsigned int *label, *summary;
+    };
+
+template<bool ROWS> int qll_cluster_pass(const QllCall &k, QllCluster &cl)
+    {
+    const int rc = mtd_cluster_largest(k.N, k.postype, k.dtype, k.box, k.head, k.nneigh, k.nlist, k.type, k.sc.v, cl.p, cl.scratch, &cl.label,
+                                       nullptr, &cl.w, &cl.summary, (mtd_stream_t)k.s);
+    if (rc) return rc;
+    k_qll_cluster_apply<ROWS><<<k.blocks, QLL_THREADS, 0, k.s>>>(k.N, k.lay.row_doubles / 2, cl.w, k.sc.v, (double2 *)k.sc.rows, k.sc.beta, k.sc.a0,
+                                                                  k.sc.partials);
+    MTD_LAUNCH_CHECK();
+    return MTD_SUCCESS;
+    }
+
+template<typename S4, int LMAX> int qll_accumulate_impl(const QllCall &k, QllCluster &cl)
     {
     QlArgs<LMAX> a;
     int rc = qll_args(a, k);
@@ -1379,6 +1443,7 @@ template<typename S4, int LMAX> int qll_accumulate_impl(const QllCall &k)
         k_qll_bonds<S4><<<k.blocks, QLL_THREADS, 0, k.s>>>(a12, k.opt, k.ramp, rs16, postype, k.head, k.nneigh, k.nlist, sc.n, (const double2 *)sc.qrows,
                                                             sc.wtab, sc.epair, sc.b, sc.v, sc.beta, sc.a0, sc.partials, tab);
         MTD_LAUNCH_CHECK();
+        if (cl.p && (rc = qll_cluster_pass<false>(k, cl)) != 0) return rc;         // v_i, beta_i and a0_i of every particle are complete
         k_qll_bonds_backprop<S4><<<k.blocks, QLL_THREADS, 0, k.s>>>(a12, k.ramp, rs16, postype, k.head, k.nneigh, k.nlist, sc.n, sc.c, sc.beta, sc.a0,
                                                                      (const double2 *)sc.qrows, sc.wtab, (double2 *)sc.rows, sc.epair, tab);
         MTD_LAUNCH_CHECK();
@@ -1392,6 +1457,7 @@ template<typename S4, int LMAX> int qll_accumulate_impl(const QllCall &k)
                                                                (const double2 *)sc.brows, (double2 *)sc.rows, sc.epair, tab);
         MTD_LAUNCH_CHECK();
         }
+    if (cl.p && (k.mode == QLL_PLAIN || k.mode == QLL_TRANSFORM)) return qll_cluster_pass<true>(k, cl);
     return MTD_SUCCESS;
     }
 
@@ -1470,16 +1536,42 @@ int mtd_ql_local_accumulate_bonds(unsigned int n_particles, const void *d_postyp
                                   unsigned int *n_partials, const double **d_c, const double **d_n, mtd_stream_t stream,
                                   const mtd_ql_local_options *opt, const double **d_v, const mtd_ql_local_bonds *bonds, const double **d_b)
     {
+    return mtd_ql_local_accumulate_cluster(n_particles, d_postype, dtype, box, d_head_list, d_n_neigh, d_nlist, rcut, ron, lmax, type, Ql_ref,
+                                           n_global, d_scratch, d_partials, n_partials, d_c, d_n, stream, opt, d_v, bonds, d_b, nullptr, nullptr,
+                                           nullptr, nullptr, nullptr);
+    }
+
+int mtd_ql_local_accumulate_cluster(unsigned int n_particles, const void *d_postype, int dtype, const mtd_box *box,
+                                    const unsigned int *d_head_list, const unsigned int *d_n_neigh, const unsigned int *d_nlist, double rcut,
+                                    double ron, unsigned int lmax, unsigned int type, const double *Ql_ref, unsigned int n_global,
+                                    double *d_scratch, const double **d_partials, unsigned int *n_partials, const double **d_c,
+                                    const double **d_n, mtd_stream_t stream, const mtd_ql_local_options *opt, const double **d_v,
+                                    const mtd_ql_local_bonds *bonds, const double **d_b, const mtd_cluster_params *cluster,
+                                    void *d_cluster_scratch, const double **d_w, const unsigned int **d_label,
+                                    const unsigned int **d_summary)
+    {
     if (!d_partials || !n_partials) return MTD_ERR_INVALID_ARGUMENT;
     QllCall k;
     int rc = qll_prepare(k, n_particles, d_postype, dtype, box, d_head_list, d_n_neigh, d_nlist, rcut, ron, lmax, type, Ql_ref, n_global, d_scratch,
                          stream, opt, bonds);
     if (rc) return rc;
+    QllCluster cl = {nullptr, d_cluster_scratch, nullptr, nullptr, nullptr};
+    if (cluster_on(cluster))
+        {
+        // what mtd_cluster_largest would refuse, refused here: before the first launch of this call
+        if ((rc = cluster_refuse(cluster)) != 0) return rc;
+        if (!d_cluster_scratch || ((uintptr_t)d_cluster_scratch & 15u) != 0 || (n_particles && !d_nlist)) return MTD_ERR_INVALID_ARGUMENT;
+        if (k.mode == QLL_AVERAGE) return MTD_ERR_UNSUPPORTED;
+        cl.p = cluster;
+        }
     rc = dispatch_lmax(lmax, [&](auto lm)
         {
-        return dispatch_s4(dtype, [&](auto t) { return qll_accumulate_impl<typename decltype(t)::type, decltype(lm)::value>(k); });
+        return dispatch_s4(dtype, [&](auto t) { return qll_accumulate_impl<typename decltype(t)::type, decltype(lm)::value>(k, cl); });
         });
     if (rc) return rc;
+    if (d_w) *d_w = cl.w;
+    if (d_label) *d_label = cl.label;
+    if (d_summary) *d_summary = cl.summary;
     *d_partials = k.sc.partials;
     *n_partials = k.blocks;
     if (d_c) *d_c = k.sc.c;

@@ -826,7 +826,7 @@ SteinhardtLocal::SteinhardtLocal(std::shared_ptr<SystemDefinition> sysdef, doubl
                                  const std::string &log_suffix)
     : NeighbourVariable(sysdef, "steinhardt_local", log_suffix, nlist, type), m_rcut(rcut), m_ron(ron), m_lmax(lmax), m_Ql_ref(Ql_ref),
       m_d_partials(nullptr), m_d_c(nullptr), m_d_n(nullptr), m_d_v(nullptr),
-      m_d_b(nullptr), m_n_partials(0), m_opt(), m_bonds()
+      m_d_b(nullptr), m_n_partials(0), m_opt(), m_bonds(), m_cluster(), m_d_w(nullptr), m_d_label(nullptr), m_d_summary(nullptr)
     {
     if (Ql_ref.size() != lmax + 1) throw std::runtime_error("Error setting up local Steinhardt CV");
     if (lmax > 12) throw std::runtime_error("cv.steinhardt_local: lmax <= 12 in this build");
@@ -853,11 +853,19 @@ void SteinhardtLocal::computeCV(unsigned int timestep)
     const size_t need = sizeof(double) * mtd_ql_local_scratch_doubles_bonds(m_pdata->getN(), m_lmax,
                                                                             m_nlist->getNListArray().bytes() / sizeof(unsigned int), &m_opt, &m_bonds);
     if (need > m_scratch.bytes()) m_scratch.resize(need);
+    if (m_cluster.on)
+        {
+        requireReach(m_cluster.r_link, "r_link");
+        const size_t need_cluster = mtd_cluster_scratch_bytes(m_pdata->getN());
+        if (need_cluster > m_cluster_scratch.bytes()) m_cluster_scratch.resize(need_cluster);
+        }
     const Lists l = lists();
-    mtd_check(mtd_ql_local_accumulate_bonds(m_pdata->getN(), m_pdata->positionsPtr(), m_pdata->getDtype(), &box, l.head, l.n_neigh, l.nlist, m_rcut,
-                                            m_ron, m_lmax, m_type, m_Ql_ref.data(), m_pdata->getNGlobal(), (double *)m_scratch.data(), &m_d_partials,
-                                            &m_n_partials, &m_d_c, &m_d_n, m_exec_conf->getStream(), &m_opt, &m_d_v, &m_bonds, &m_d_b),
-              "mtd_ql_local_accumulate_bonds");
+    mtd_check(mtd_ql_local_accumulate_cluster(m_pdata->getN(), m_pdata->positionsPtr(), m_pdata->getDtype(), &box, l.head, l.n_neigh, l.nlist, m_rcut,
+                                              m_ron, m_lmax, m_type, m_Ql_ref.data(), m_pdata->getNGlobal(), (double *)m_scratch.data(),
+                                              &m_d_partials, &m_n_partials, &m_d_c, &m_d_n, m_exec_conf->getStream(), &m_opt, &m_d_v, &m_bonds,
+                                              &m_d_b, &m_cluster, m_cluster.on ? m_cluster_scratch.data() : nullptr, &m_d_w, &m_d_label,
+                                              &m_d_summary),
+              "mtd_ql_local_accumulate_cluster");
     computed(timestep);
     }
 
@@ -866,6 +874,7 @@ void SteinhardtLocal::computeCV(unsigned int timestep)
 void SteinhardtLocal::setAverage(bool on)
     {
     if (on && m_bonds.on) throw std::runtime_error("cv.steinhardt_local: the bond count is not available on the averaged vectors");
+    if (on && m_cluster.on) throw std::runtime_error("cv.steinhardt_local: the largest cluster is not available on the averaged vectors");
     m_opt.average = on ? 1 : 0;
     invalidate();
     }
@@ -922,6 +931,25 @@ void SteinhardtLocal::clearBonds()
     invalidate();
     }
 
+void SteinhardtLocal::setCluster(double v_min, double r_link)
+    {
+    if (!std::isfinite(v_min) || !(r_link > 0.0) || !std::isfinite(r_link))
+        throw std::runtime_error("cv.steinhardt_local: a cluster needs a finite v_min and r_link > 0");
+    if (m_opt.average) throw std::runtime_error("cv.steinhardt_local: the largest cluster is not available on the averaged vectors");
+    requireReach(r_link, "r_link");
+    m_cluster.on = 1;
+    m_cluster.v_min = v_min;
+    m_cluster.r_link = r_link;
+    invalidate();
+    }
+
+void SteinhardtLocal::clearCluster()
+    {
+    m_cluster.on = 0;
+    m_cluster.v_min = m_cluster.r_link = 0.0;
+    invalidate();
+    }
+
 void SteinhardtLocal::enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot)
     {
     computeCV(timestep);
@@ -955,6 +983,37 @@ std::vector<double> SteinhardtLocal::getBondCounts(unsigned int timestep)
     if (!m_bonds.on) throw std::runtime_error("cv.steinhardt_local: no bond count without the bonds option");
     computeCV(timestep);
     return readBack(m_d_b, m_pdata->getN(), "b_i read-back", timestep);
+    }
+
+std::vector<unsigned int> SteinhardtLocal::readBackWords(const unsigned int *d_src, size_t n, const char *what, unsigned int timestep)
+    {
+    if (!m_cluster.on) throw std::runtime_error("cv.steinhardt_local: no clusters without the cluster option");
+    computeCV(timestep);
+    m_exec_conf->sync();
+    std::vector<unsigned int> out(n);
+    if (!out.empty()) hip_check(hipMemcpy(out.data(), d_src, sizeof(unsigned int) * n, hipMemcpyDeviceToHost), what);
+    return out;
+    }
+
+std::vector<unsigned int> SteinhardtLocal::getClusterLabels(unsigned int timestep)
+    {
+    if (!m_cluster.on) throw std::runtime_error("cv.steinhardt_local: no clusters without the cluster option");
+    computeCV(timestep);                                             // (sets the pointers: before they are handed on)
+    return readBackWords(m_d_label, m_pdata->getN(), "cluster label read-back", timestep);
+    }
+
+std::vector<unsigned int> SteinhardtLocal::getLargestCluster(unsigned int timestep)
+    {
+    if (!m_cluster.on) throw std::runtime_error("cv.steinhardt_local: no clusters without the cluster option");
+    computeCV(timestep);
+    return readBackWords(m_d_summary, 4, "cluster summary read-back", timestep);
+    }
+
+std::vector<double> SteinhardtLocal::getClusterMask(unsigned int timestep)
+    {
+    if (!m_cluster.on) throw std::runtime_error("cv.steinhardt_local: no clusters without the cluster option");
+    computeCV(timestep);
+    return readBack(m_d_w, m_pdata->getN(), "cluster mask read-back", timestep);
     }
 
 std::vector<double> SteinhardtLocal::getSwitchedValues(unsigned int timestep)

@@ -390,9 +390,18 @@ class SteinhardtLocal : public NeighbourVariable
         void setBonds(double d_lo, double d_hi);                       //!< sigma = smoothstep of d_ij from d_lo to d_hi, -1 <= d_lo < d_hi <= 1
         void clearBonds();
         std::vector<double> getBondCounts(unsigned int timestep);      //!< b_i of every local particle; throws without bonds
+        //! the largest cluster of mtd_cluster_params (include/mtd_abi.h "Clusters"): the variable becomes (1/N) sum of v_i over the largest
+        //! connected cluster of particles with v_i >= v_min, linked within r_link; not with the average.  getSwitchedValues stays unmasked
+        void setCluster(double v_min, double r_link);                  //!< v_min finite, r_link > 0 and within the reach of a device-built list
+        void clearCluster();
+        //! the only places that read the cluster pass back; all three throw without the option
+        std::vector<unsigned int> getClusterLabels(unsigned int timestep);   //!< smallest index of i's cluster, MTD_CLUSTER_NONE for a non-node
+        std::vector<double> getClusterMask(unsigned int timestep);           //!< w_i: 1 for the members of the largest cluster, else 0
+        std::vector<unsigned int> getLargestCluster(unsigned int timestep);  //!< {root, members, number of clusters, number of nodes}
 
     private:
         void computeCV(unsigned int timestep) override;
+        std::vector<unsigned int> readBackWords(const unsigned int *d_src, size_t n, const char *what, unsigned int timestep);
         double m_rcut, m_ron;
         unsigned int m_lmax;
         std::vector<double> m_Ql_ref;
@@ -400,6 +409,10 @@ class SteinhardtLocal : public NeighbourVariable
         unsigned int m_n_partials;
         mtd_ql_local_options m_opt;
         mtd_ql_local_bonds m_bonds;
+        mtd_cluster_params m_cluster;
+        DeviceBuffer m_cluster_scratch;                                // grown like m_scratch, never shrinks
+        const double *m_d_w;
+        const unsigned int *m_d_label, *m_d_summary;
     };
 
 //! Pair entropy (no reference counterpart; include/mtd_abi.h "Pair entropy"): S2 from a Gaussian-smoothed g(r) of one particle type.

@@ -349,6 +349,20 @@ PYBIND11_MODULE(_metadynamics, m)
         .def("getBondCounts", [](SteinhardtLocal &cv, unsigned int timestep) {
             const std::vector<double> v = cv.getBondCounts(timestep);
             return py::array_t<double>((ssize_t)v.size(), v.data());
+        })
+        .def("setCluster", &SteinhardtLocal::setCluster)
+        .def("clearCluster", &SteinhardtLocal::clearCluster)
+        .def("getClusterLabels", [](SteinhardtLocal &cv, unsigned int timestep) {
+            const std::vector<unsigned int> v = cv.getClusterLabels(timestep);
+            return py::array_t<unsigned int>((ssize_t)v.size(), v.data());
+        })
+        .def("getClusterMask", [](SteinhardtLocal &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getClusterMask(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        })
+        .def("getLargestCluster", [](SteinhardtLocal &cv, unsigned int timestep) {
+            const std::vector<unsigned int> v = cv.getLargestCluster(timestep);
+            return py::make_tuple(v[0], v[1], v[2], v[3]);
         });
 
     // no reference counterpart: the pair entropy from a smoothed g(r)

@@ -114,6 +114,20 @@ class QlLocalBonds(C.Structure):
         return o
 
 
+class ClusterParams(C.Structure):
+    """mtd_cluster_params: all-zero is off; nodes are the particles with v >= v_min, linked within r_link"""
+    _fields_ = [("on", C.c_int), ("v_min", C.c_double), ("r_link", C.c_double)]
+
+    @classmethod
+    def make(cls, cluster=None):
+        """cluster: (v_min, r_link) or None"""
+        o = cls()
+        if cluster is not None:
+            o.on, o.v_min, o.r_link = 1, float(cluster[0]), float(cluster[1])
+        return o
+
+
+MTD_CLUSTER_NONE = 0xffffffff
 MTD_ES_MAX_ENV, MTD_ES_MAX_VEC = 4, 64
 
 
@@ -282,6 +296,13 @@ _SIGNATURES = {
     "mtd_ql_local_forces_bonds": (C.c_int, [C.c_uint, _vp, _vp, C.c_int, C.POINTER(Box), _vp, _vp, _vp, C.c_double, C.c_double, C.c_uint, C.c_uint,
                                              _dp, C.c_uint, _vp, _vp, C.c_double, _vp, C.POINTER(QlLocalOptions), _vp, C.c_uint,
                                              C.POINTER(QlLocalBonds)]),
+    "mtd_cluster_scratch_bytes": (C.c_size_t, [C.c_uint]),
+    "mtd_cluster_largest": (C.c_int, [C.c_uint, _vp, C.c_int, C.POINTER(Box), _vp, _vp, _vp, C.c_uint, _vp, C.POINTER(ClusterParams), _vp,
+                                       C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    "mtd_ql_local_accumulate_cluster": (C.c_int, [C.c_uint, _vp, C.c_int, C.POINTER(Box), _vp, _vp, _vp, C.c_double, C.c_double, C.c_uint, C.c_uint,
+                                                   _dp, C.c_uint, _vp, C.POINTER(_vp), _up, C.POINTER(_vp), C.POINTER(_vp), _vp,
+                                                   C.POINTER(QlLocalOptions), C.POINTER(_vp), C.POINTER(QlLocalBonds), C.POINTER(_vp),
+                                                   C.POINTER(ClusterParams), _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "mtd_pe_scratch_doubles": (C.c_size_t, [C.c_uint]),
     "mtd_pe_accumulate": (C.c_int, [C.c_uint, _vp, C.c_int, C.POINTER(Box), _vp, _vp, _vp, C.c_double, C.c_double, C.c_uint, C.c_uint, _vp,
                                      C.POINTER(_vp), _up, _vp]),

@@ -249,20 +249,41 @@ class steinhardt(_neighbour_variable):
         self._attach(type_list.index(type))
 
 class _local_options(type):
-    """``cv.steinhardt_local(..., average=False, switch=None, gate=None, bonds=None)``: the options are keyword arguments of the CALL.  They
+    """``cv.steinhardt_local(..., average=False, switch=None, gate=None, bonds=None, cluster=None)``: the options are keyword arguments of the CALL.  They
     are taken off here and applied to the finished object, so that ``__init__`` keeps the argument list of the variable without options,
     which tests/test_ql_local_abi.py pins.  The price: ``inspect.signature(cv.steinhardt_local)`` and ``help()`` do not show the
     options, and subclasses inherit this metaclass.  Once that test may change, move the keywords into ``__init__`` (ending with a
     call of ``set_options``) and delete this class."""
 
-    def __call__(cls, *args, average=False, switch=None, gate=None, bonds=None, **kwargs):
+    def __call__(cls, *args, average=False, switch=None, gate=None, bonds=None, cluster=None, **kwargs):
         obj = super().__call__(*args, **kwargs)
         try:
-            obj.set_options(average=average, switch=switch, gate=gate, bonds=bonds)
+            obj.set_options(average=average, switch=switch, gate=gate, bonds=bonds, cluster=cluster)
         except RuntimeError:
             context.current.forces.remove(obj)                       # refused: the run must not find a half-made variable
             raise
         return obj
+
+
+def _with_cluster(set_options):
+    """``set_options(..., cluster=None)``: the fifth option, taken off in front of the four that tests/test_ql_local_bonds_ref.py pins as
+    the parameter list of ``set_options`` (``inspect.signature`` follows ``__wrapped__`` to the function below and shows those four) and
+    applied behind them.  Once that test may change, make ``cluster`` a fifth parameter of ``set_options`` and delete this decorator."""
+    import functools
+
+    @functools.wraps(set_options)
+    def with_cluster(self, *args, cluster=None, **kwargs):
+        try:
+            cl = None if cluster is None else (float(cluster["v_min"]), float(cluster["r_link"]))
+            if cl is not None and (set(cluster.keys()) != {"v_min", "r_link"} or not abs(cl[0]) < float("inf") or not 0.0 < cl[1] < float("inf")):
+                raise ValueError
+            self.cpp_force.clearCluster()
+            set_options(self, *args, **kwargs)
+            if cl is not None:
+                self.cpp_force.setCluster(*cl)         # refuses the average and an r_link beyond the reach of a device-built list
+        except (TypeError, KeyError, ValueError, AttributeError, RuntimeError):
+            raise RuntimeError("Error creating collective variable.")
+    return with_cluster
 
 
 class steinhardt_local(_neighbour_variable, metaclass=_local_options):
@@ -281,6 +302,16 @@ class steinhardt_local(_neighbour_variable, metaclass=_local_options):
     d_hi (-1 <= d_lo < d_hi <= 1), b_i = sum_j f(r_ij) sigma(d_ij), and switch and gate act on it: CV = (1 / N) sum_i g(n_i) h(b_i).
     With ``Ql_ref = e_6``, ``bonds=dict(d_lo=0.5, d_hi=0.7)`` and ``switch=dict(c0=6.5, p=12)``, CV * N is the smooth number of solid
     particles of the literature.  Not together with ``average``.
+    ``cluster=dict(v_min=..., r_link=...)``: the LARGEST CLUSTER of solid particles, what seeding and umbrella studies of nucleation bias
+    (ten Wolde, Ruiz-Montero and Frenkel; PLUMED's DFSCLUSTERING followed by CLUSTER_NATOMS or CLUSTER_PROPERTIES ... SUM).  Nodes are the
+    particles of the type with v_i >= v_min, two nodes are linked when one lists the other within r_link (minimum image), the clusters are
+    the connected components, the largest is the one with most members (a tie goes to the one that holds the smallest particle index),
+    and CV = (1 / N) sum_{i in the largest cluster} v_i.  With the bond count and the switch above CV * N is the smooth size of the largest
+    nucleus.  Membership is piecewise constant, so the force is the gradient of the v_i of the members alone (PLUMED's treatment): the
+    variable JUMPS when clusters merge or split, by the size of the smaller one.  Single-domain runs only: a cluster would be cut at a domain
+    boundary.  ``get_switched()`` stays unmasked — it is the solid-ness the clusters are built from; ``get_cluster_mask()``,
+    ``get_cluster_labels()`` and ``get_largest_cluster()`` give the rest.  r_link must lie within the reach of a device-built list.  Not
+    together with ``average``.
 
     Virial: ``get_virial`` (mtd_ql_local_forces_virial)."""
 
@@ -316,8 +347,23 @@ class steinhardt_local(_neighbour_variable, metaclass=_local_options):
         """b_i = sum_j f(r_ij) sigma(d_ij): the smooth number of solid bonds of every particle at the current time step (needs ``bonds``)"""
         return self.cpp_force.getBondCounts(context.current.system.getCurrentTimeStep())
 
+    def get_cluster_labels(self):
+        """uint32 per particle: the smallest particle index of its cluster, 0xffffffff for a particle that is not solid (needs ``cluster``)"""
+        return self.cpp_force.getClusterLabels(context.current.system.getCurrentTimeStep())
+
+    def get_cluster_mask(self):
+        """w_i: 1.0 for the members of the largest cluster, 0.0 for everybody else (needs ``cluster``)"""
+        return self.cpp_force.getClusterMask(context.current.system.getCurrentTimeStep())
+
+    def get_largest_cluster(self):
+        """(root, members, n_clusters, n_nodes): the smallest particle index of the largest cluster and its member count, the number of
+        clusters and of solid particles; root is 0xffffffff and members 0 when nothing is solid (needs ``cluster``)"""
+        return self.cpp_force.getLargestCluster(context.current.system.getCurrentTimeStep())
+
+    @_with_cluster
     def set_options(self, average=False, switch=None, gate=None, bonds=None):
-        """set all four options (the defaults switch them off); takes effect with the next step"""
+        """set all options (the defaults switch them off), ``cluster=dict(v_min=..., r_link=...)`` among them as a keyword; takes effect
+        with the next step"""
         try:
             sw = None if switch is None else (float(switch["c0"]), int(switch["p"]))
             gt = None if gate is None else (float(gate["n_lo"]), float(gate["n_hi"]))

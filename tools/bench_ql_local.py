@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Developer tool: the config 5 snapshot of tools/bench_ql.py (256 000-particle noisy fcc crystal, lmax 6, degrees 4 and 6,
 r_cut 1.4, 512-point grid) with cv.steinhardt_local instead of the global variable; prints us/step.
-usage: tools/bench_ql_local.py [steps] [f32|f64] [--device-nlist] [--average] [--switch c0,p] [--gate lo,hi] [--bonds lo,hi] [--lmax L --ql-ref a,b,...] [--pressure]
+usage: tools/bench_ql_local.py [steps] [f32|f64] [--device-nlist] [--average] [--switch c0,p] [--gate lo,hi] [--bonds lo,hi] [--cluster v_min,r_link] [--lmax L --ql-ref a,b,...] [--pressure]
 (--pressure: sets the pressure flag before the run, as a barostat would: the force pass also writes the per-particle virial;
 --device-nlist: cv.nlist_cell(device=True), r_buff 0.4; the next four: the options of cv.steinhardt_local, e.g. --average --switch 0.12,3,
-or the solid-bond count --bonds 0.5,0.7 --switch 6.5,12 --ql-ref 0,0,0,0,0,0,1;
+or the solid-bond count --bonds 0.5,0.7 --switch 6.5,12 --ql-ref 0,0,0,0,0,0,1, and with --cluster 0.5,1.2 its largest cluster;
 --lmax 12 --ql-ref 0,0,0,0,1,0,1,0,0,0,0.5,0.3,0.25: table rows of 784 bytes, which take the direct force pass instead of the LDS tiles)
 Run under rocprofv3 --kernel-trace --stats for the per-kernel table."""
 import os, sys, time
@@ -16,7 +16,7 @@ from metadynamics import context, cv, integrate
 argv = sys.argv[1:]
 options = {}
 for flag, keys, kinds in (("--switch", ("c0", "p"), (float, int)), ("--gate", ("n_lo", "n_hi"), (float, float)),
-                          ("--bonds", ("d_lo", "d_hi"), (float, float))):
+                          ("--bonds", ("d_lo", "d_hi"), (float, float)), ("--cluster", ("v_min", "r_link"), (float, float))):
     if flag in argv:
         k = argv.index(flag)
         options[flag[2:]] = {key: kind(v) for key, kind, v in zip(keys, kinds, argv[k + 1].split(","))}
@@ -83,5 +83,7 @@ if options:
     print("options %s: mean v_i %.6f" % (options, st.get_switched().mean()))
 if "bonds" in options:
     print("mean b_i %.6f" % st.get_bonds().mean())
+if "cluster" in options:
+    print("largest cluster (root, members, clusters, nodes): %s" % (st.get_largest_cluster(),))
 print("config 5 local (%s%s%s): %.1f us/step  (%.3e particle-CV-evals/s, %.3e list entries/s incl. CV + force pass)"
       % (np.dtype(dtype).name + (", virial" if pressure else ""), ", device list" if device_nlist else "", "" if lmax == 6 else ", lmax %d" % lmax, 1e6 * dt / steps, N * steps / dt, 2 * entries * steps / dt))
