@@ -93,10 +93,11 @@ def liquid(N, seed, density=0.8, r_list=1.5):
 _cases = {}
 
 
-def liquid_case(N):
-    if N not in _cases:
-        _cases[N] = liquid(N, seed=N)
-    return _cases[N]
+def liquid_case(N, seed=None):
+    seed = N if seed is None else seed
+    if (N, seed) not in _cases:
+        _cases[N, seed] = liquid(N, seed=seed)
+    return _cases[N, seed]
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -128,6 +129,50 @@ def test_liquid_with_v_min_at_the_median(abi, dtype, N):
     """several blocks and a ragged last chunk (4099 = 64 * 64 + 3); about half the particles are nodes; twice: the same bytes"""
     g, r = check(abi, liquid_case(N), dtype, calls=2)
     assert 0.4 * N < r["summary"][3] < 0.6 * N and r["summary"][2] > 10
+
+
+# ---- the loops behind the block caps: init, flatten and mask run 1024 blocks of 256 lanes (one trip up to N = 262 144), link 4096 blocks
+# of 64 rows (the same N), pick 256 blocks of 256 lanes (N = 65 536) ------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_chunk_loop_liquid_past_every_cap(abi, dtype):
+    """270 001 particles: 1055 chunks of 256 on 1024 blocks (flatten takes two rounds, in every lane), 4219 chunks of 64 rows on 4096
+    blocks, 1055 chunks on the 256 blocks of the pick (four or five trips); about half the particles are nodes; twice: the same bytes"""
+    N = 270_001
+    assert (N + 255) // 256 > 1024 and (N + 63) // 64 > 4096
+    g, r = check(abi, liquid_case(N, seed=3), dtype, calls=2)
+    assert 0.4 * N < r["summary"][3] < 0.6 * N and r["summary"][2] > 10_000
+    assert r["summary"].tolist() == [316, 100, 46090, 133917]
+    assert (r["label"][262_144:] != NONE).sum() > 1000                  # nodes among the particles of the second round
+
+
+def test_chunk_loop_of_the_pick_alone(abi):
+    """70 001 particles: 274 chunks of 256, so only k_cluster_pick (256 blocks) takes a second trip, in blocks 0 - 17; clusters rooted at
+    i >= 65 536 are counted there, by nothing else"""
+    N = 70_001
+    assert 256 < (N + 255) // 256 <= 1024 and (N + 63) // 64 <= 4096
+    g, r = check(abi, liquid_case(N), np.float64, calls=2)
+    assert 0.4 * N < r["summary"][3] < 0.6 * N and r["summary"][2] > 10_000
+    assert (r["label"][65_536:] == np.arange(65_536, N)).sum() > 100     # roots that the second trip counts
+
+
+@pytest.mark.parametrize("order", ["lattice", "permuted"])
+def test_chunk_loop_one_cluster_spanning_the_box(abi, order):
+    """simple cubic 65^3 (N = 274 625), every particle a node, linked to its six neighbours: one cluster with root 0.  4292 chunks of 64
+    rows on 4096 blocks and 1073 chunks of 256 on 1024: every atomic of the link pass falls on one tree, the flatten pass counts all
+    members on one word over two rounds.  In lattice order and with the indices permuted at random (deep trees, as the chain above)"""
+    n = 65
+    axis = np.arange(n) - 0.5 * (n - 1)
+    pos = np.stack(np.meshgrid(axis, axis, axis, indexing="ij"), -1).reshape(-1, 3)
+    N = len(pos)
+    assert N == 274_625 and (N + 255) // 256 > 1024 and (N + 63) // 64 > 4096
+    if order == "permuted":
+        pos = pos[np.random.default_rng(8).permutation(N)]
+    nl = util.build_nlist(pos, float(n), 1.3)
+    assert len(nl[2]) == 6 * N
+    case = dict(pos=pos, types=np.zeros(N, dtype=np.int32), L=float(n), nl=nl, v=np.ones(N), cluster=(0.5, 1.1))
+    g, r = check(abi, case, np.float64, calls=2)
+    assert g["summary"].tolist() == [0, N, 1, N]
+    assert not g["label"].any() and g["size"][0] == N and not g["size"][1:].any() and (g["w"] == 1.0).all()
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

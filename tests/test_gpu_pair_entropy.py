@@ -8,6 +8,12 @@ fixed-point accumulation's worst case at these shapes is below 1e-11 of H (heade
 Measured on an MI355X (every figure is printed before it is asserted): fp64 arrays g_b <= 1.2e-14 of max g (H_b <= 1.4e-14), S <= 2.8e-14
 relative, forces <= 2.7e-14 of max|F|, per-particle virial <= 2e-14 of max|virial_i|, the six sums <= 8e-14; fp32 arrays forces <= 4.6e-8,
 per-particle virial <= 5.5e-8, sums <= 3.6e-8.  No bound had to move.
+
+test_chunk_loop (N = 37 044, 1158 chunks of 32 on the 1024 blocks the launches are capped at).  The header's bound at this shape: a block
+walks one or two chunks, E_blk <= 1121 entries, sum_blocks E_blk^2 K(0) 2^-62 = 3.8e-10 absolute, and 1024 blocks added in doubles give
+1.1e-13 relative, on H up to 1.4e6: below 4e-13 relative, the bound of 1e-10 is not a small-shape accident.  Measured on an MI355X: fp64
+arrays g_b <= 4.7e-15 of max g (H_b <= 3.7e-15), S <= 3e-15 relative, forces <= 3.6e-15 of max|F|, per-particle virial <= 5.9e-15, the six
+sums <= 7.1e-15; fp32 arrays forces 3.8e-8, per-particle virial 3.6e-8, sums 4e-10.  No bound had to move here either.
 """
 import ctypes as C
 
@@ -242,6 +248,40 @@ def test_pair_entropy_many_blocks(abi):
     compare(g, r, 0.9, np.float64)
     fs = np.abs(g["F"]).max()
     assert np.abs(g["F"][:, :3].sum(axis=0)).max() <= 1e-12 * fs * len(pos)      # translation invariance: the forces add up to zero
+
+
+@pytest.mark.parametrize("dtype,two_types", [(np.float64, False), (np.float32, False), (np.float64, True)])
+def test_chunk_loop(abi, dtype, two_types):
+    """fcc 21 (N = 37 044): 1158 chunks of 32 on 1024 blocks, so blocks 0 - 133 walk two chunks in both passes and take their fixed-point
+    scale from the entries of two chunks, the others from one.  The list reaches r_cut = 1.5 only (~17 entries per row): the restatement
+    stays cheap.  With a second type on ~30 % of the particles the type test decides in second-trip chunks too"""
+    pos, L = noisy_fcc(21, sigma=0.05, seed=1)
+    N = len(pos)
+    n_chunks = (N + 31) // 32
+    assert N == 37044 and n_chunks > 1024 and n_chunks < 2 * 1024
+    pos = pos.astype(dtype).astype(np.float64)                          # the snapshot is the rounded array
+    types = (np.random.default_rng(4).random(N) < 0.3).astype(np.int32) if two_types else np.zeros(N, dtype=np.int32)
+    par = (1.1, 0.1, 22)
+    assert pe.constants(*par)["r_cut"] <= 1.5 + 1e-12
+    nl = util.build_nlist(pos, L, 1.5)
+    assert 15 < len(nl[2]) / N < 20
+    g = run_gpu(abi, pos, types, L, nl, *par, 0, dtype, virial=True)
+    r = pe.compute(pos, types, L, nl, *par, 0, bias=0.9)
+    if two_types:
+        assert 0.6 * N < r["n_t"] < 0.8 * N and (types[1024 * 32:] == 1).sum() > 100      # the other type inside the second-trip chunks
+    else:
+        assert r["S"] == pytest.approx(-1.74991, abs=1e-5) and (r["g"] >= pe.G_MIN).sum() == 20
+    compare(g, r, 0.9, dtype, types=types if two_types else None)
+    again = run_gpu(abi, pos, types, L, nl, *par, 0, dtype, virial=True)
+    for key in ("g", "sums", "F", "virial"):
+        assert np.array_equal(g[key], again[key]), key                  # two identical calls: identical bits
+    assert g["S"] == again["S"]
+    # translation invariance: the forces add up to zero, as in test_pair_entropy_many_blocks (fp32 arrays: every stored component errs
+    # by half a unit in the last place, 2^-25 of itself, at most)
+    fs = np.abs(g["F"]).max()
+    total = np.abs(g["F"][:, :3].sum(axis=0)).max()
+    print("sum of the forces: %.3e of N max |F|" % (total / (fs * N)))
+    assert total <= (1e-12 + (0.0 if dtype == np.float64 else 2.0 ** -25)) * fs * N
 
 
 def test_pair_entropy_bias_from_device_and_host(abi, snapshots):

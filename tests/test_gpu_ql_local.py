@@ -216,7 +216,7 @@ def test_ql_local_perfect_lattice(abi, dtype):
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_ql_local_config5_size(abi, dtype):
     """256 000 particles (40^3 fcc cells), lmax 6, r_cut 1.4, r_on 1.2, Ql_ref [0,0,0,0,1,0,1]: s and every c_i against the
-    restatement, forces on the first 30 000 rows, stated tolerance 1e-5 of max|F|"""
+    restatement, forces on the first and on the last 30 000 rows (a block's first and last chunks), stated tolerance 1e-5 of max|F|"""
     pos, L = noisy_fcc(40)
     N = len(pos)
     assert N == 256000
@@ -236,6 +236,14 @@ def test_ql_local_config5_size(abi, dtype):
     assert fs > 0
     err = np.abs(g["F"][:n_sl, :3] - F_ref).max() / fs
     print("forces on the first %d rows: %.3e of max |F|" % (n_sl, err))
+    assert err <= 1e-5, err
+    # the first rows all lie in a block's first chunk (i < 1024 * 64): the last ones are written on a later trip of the chunk loop
+    assert N - n_sl >= 1024 * 64 and len(r["grad"]) == N
+    F_last = -0.9 * r["grad"][N - n_sl:]
+    fs_last = np.abs(F_last).max()
+    assert fs_last > 0
+    err = np.abs(g["F"][N - n_sl:, :3] - F_last).max() / fs_last
+    print("forces on the last %d rows: %.3e of max |F|" % (n_sl, err))
     assert err <= 1e-5, err
     assert np.isfinite(g["F"]).all() and np.all(g["F"][:, 3] == 0.0)
     # translation invariance of s: the forces add up to zero
