@@ -504,6 +504,15 @@ int mtd_mesh_slab_compute_cv(mtd_mesh *m, unsigned int n_particles, const void *
  * them) and indexes no ghost particle: the CV pass then visits every pair once, from its lower index — Y_lm(-d) = (-1)^l
  * Y_lm(d), so the reference's two visits add up to twice the even degrees and cancel in the odd ones, the scaling of :173-179;
  * the force pass treats 2 like 0.  Not for mtd_ql_accumulate_local with ghost particles.
+ *
+ * The row layout, for every entry point of this header that takes (d_head_list, d_n_neigh, d_nlist) — mtd_ql_*,
+ * mtd_ql_symmetrize_half_list*, mtd_ql_local_*, mtd_cluster_largest, mtd_pe_*, mtd_es_*: the neighbours of i are
+ * d_nlist[d_head_list[i] .. d_head_list[i] + d_n_neigh[i]), and nothing else is assumed.  As in a HOOMD list with a fixed capacity per
+ * row, the rows may lie anywhere in d_nlist, in any order (d_head_list need not ascend, start at 0 or be the prefix sum of d_n_neigh),
+ * with unused slots before, between and behind them whose contents are never read.  Results do not depend on where a row lies: the
+ * same rows stored differently give the same bits (tests/test_gpu_list_layouts.py).  Where a size `n_list_entries` is asked for (the
+ * `average` mode and the bond count of the local variable) it is the largest d_head_list[i] + d_n_neigh[i], the length of d_nlist up
+ * to the end of its last row — not the number of listed pairs, sum_i d_n_neigh[i].
  * ============================================================================================== */
 
 /* device doubles the two calls share (block partial sums, Q_lm tables, Q_l, CV value) */
@@ -672,8 +681,9 @@ int mtd_ql_local_forces(unsigned int n_particles, const void *d_postype, void *d
                         const double *d_bias, double bias_host, mtd_stream_t stream);
 
 /* The same three with options; opt == NULL or an all-zero struct is the plain variable, bit for bit (the three above forward here).
- * n_list_entries: the length of d_nlist (the largest d_head_list[i] + d_n_neigh[i]) — with `average` the scratch keeps one double per
- * list entry, and the two calls cannot see the size of either array: size the scratch again whenever the list grows.
+ * n_list_entries: the length of d_nlist (the largest d_head_list[i] + d_n_neigh[i], NOT the number of listed pairs: rows with slack
+ * between them count with their slack, "The row layout" above) — with `average` the scratch keeps one double per slot of the list,
+ * indexed like d_nlist itself, and the two calls cannot see the size of either array: size the scratch again whenever the list grows.
  * *d_partials: block sums of v_i (consumed as above); *d_c: c_i, averaged when `average` is set; *d_v (may be NULL): v_i.
  * The same opt goes to both passes.  MTD_ERR_INVALID_ARGUMENT, before a device is touched, for a switch with c0 <= 0 or p == 0
  * and for a gate without 0 <= n_lo < n_hi.  A scratch that is too small for the list is NOT detected (no size is passed): with `average`

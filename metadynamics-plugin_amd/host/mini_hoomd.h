@@ -442,7 +442,13 @@ class NeighborList
         void setLists(const unsigned int *head, const unsigned int *n_neigh, size_t n, const unsigned int *nlist, size_t n_list)
             {
             if (n != m_N) throw std::runtime_error("NeighborList::setLists: head_list / n_neigh must have N entries");
-            m_device_build = false;          // a list handed in replaces the device build
+            // rows may lie anywhere in nlist, in any order, with unused slots between them: every row must end inside the array,
+            // checked before anything is replaced or uploaded (the symmetry check below reads nlist[head[i] + k] on the host)
+            for (size_t i = 0; i < n; ++i)
+                if ((size_t)head[i] + (size_t)n_neigh[i] > n_list)
+                    throw std::runtime_error("NeighborList::setLists: row " + std::to_string(i) + " ends beyond the nlist array (head_list + n_neigh = "
+                                             + std::to_string((size_t)head[i] + (size_t)n_neigh[i]) + " > " + std::to_string(n_list) + ")");
+            m_device_build = false;         // a list handed in replaces the device build
             m_head.resize(sizeof(unsigned int) * n);
             m_nneigh.resize(sizeof(unsigned int) * n);
             m_nlist.resize(sizeof(unsigned int) * (n_list ? n_list : 1));

@@ -26,14 +26,15 @@ UNSUPPORTED = -2
 ARGS = (cr.ARGS["r_cut"], cr.ARGS["r_on"], cr.ARGS["lmax"], cr.ARGS["type_id"], cr.ARGS["Ql_ref"])
 
 
-def run_gpu(abi, pos, types, L, nl, dtype, opt=None, cluster=None, entry="cluster", bias=BIAS, expect=0):
+def run_gpu(abi, pos, types, L, nl, dtype, opt=None, cluster=None, entry="cluster", bias=BIAS, expect=0, args=ARGS):
     """pass 1 through mtd_ql_local_accumulate_cluster, then mtd_ql_local_forces_bonds without and with a virial array on the same table.
     opt: dict(switch=, gate=, bonds=, average=); cluster: (v_min, r_link) or None; entry = "null": cluster == NULL, "zero": an all-zero
-    struct.  Both scratches start as garbage.  Returns dict(s, c, n, v, b, F, F_vir, raw, partials, w, label, summary)."""
+    struct; args: (r_cut, r_on, lmax, type_id, Ql_ref).  Both scratches start as garbage.  Returns dict(s, c, n, v, b, F, F_vir, raw,
+    partials, w, label, summary)."""
     lib = abi.load()
     opt = dict(opt or {})
     bonds = opt.pop("bonds", None)
-    r_cut, r_on, lmax, type_id, Ql_ref = ARGS
+    r_cut, r_on, lmax, type_id, Ql_ref = args
     N = len(pos)
     box = abi.Box.make(L)
     dt = abi.MTD_F32 if dtype == np.float32 else abi.MTD_F64
