@@ -211,7 +211,7 @@ int mtd_metad_get_state(mtd_metad *m, double *cv, double *bias, double *bias_pot
 double mtd_metad_sigma_determinant(const mtd_metad *m); /* sigmaDeterminant .cc:1296-1313 */
 unsigned int mtd_metad_num_elements(const mtd_metad *m);
 
-/* raw grid arrays for writeGrid / readGrid (.cc:831-1000); SYNCHRONISE.  which: 0 grid, 1 grid_delta,
+/* raw grid arrays and the hill count for writeGrid / readGrid (.cc:831-1000); all three SYNCHRONISE the stream.  which: 0 grid, 1 grid_delta,
  * 2 reweighted, 3 weight, 4 sigma_grid, 5 sigma_grid_delta (double[G]); 6 hist, 7 hist_delta,
  * 8 hist_gauss, 9 hist_gauss_delta (uint32[G]) */
 int mtd_metad_get_array(mtd_metad *m, int which, void *host_out, mtd_stream_t stream);
@@ -221,7 +221,9 @@ int mtd_metad_set_num_gaussians(mtd_metad *m, unsigned int n, mtd_stream_t strea
  * the pointer must say so after every such write, on the stream the write ran on, with mtd_metad_grid_touched: the engine keeps
  * a small patch of grid values around the last CV values (the scalar chain's preload) which is then rewritten from the grid
  * before its next use.  Fetching the pointer for which = 0 invalidates the patch once, on the NULL stream (kept for callers
- * that write before their next update on that stream); returns NULL when that fails. */
+ * that write before their next update on that stream); returns NULL when that fails.  That one invalidation is NOT ordered with
+ * work on a non-blocking stream: an update still queued there validates the patch again when it runs.  A caller with a stream of
+ * its own must not rely on it: mtd_metad_grid_touched after every write is what tells the engine. */
 void *mtd_metad_device_array(mtd_metad *m, int which);
 int mtd_metad_grid_touched(mtd_metad *m, mtd_stream_t stream);
 
@@ -388,7 +390,9 @@ typedef struct mtd_mesh mtd_mesh; /* opaque; owns the meshes, the cell list and 
 int mtd_mesh_create(mtd_mesh **out, unsigned int nx, unsigned int ny, unsigned int nz, const double *mode,
                     unsigned int n_types, unsigned int max_particles);
 int mtd_mesh_destroy(mtd_mesh *m);
-/* 1 (default): interpolation function with the reference's unsigned integer division; 0: as intended */
+/* 1 (default): interpolation function with the reference's unsigned integer division; 0: as intended.
+ * SYNCHRONISES THE DEVICE (the call has no stream): it waits for everything queued on any stream, rewrites the tables and waits
+ * again, so evaluations queued before it use the old tables and everything queued after it the new ones. */
 int mtd_mesh_set_bug_compat(mtd_mesh *m, int on);
 /* The normalised Fourier mesh f = FFT(mesh) / N (fourier_mesh of the reference, OrderParameterMesh.cc:697-712) is only read by
  * mtd_mesh_qmax, mtd_mesh_virial and mtd_mesh_get_array(1): the spectral step writes it when `on` (default 1; 18.9 MB per
@@ -464,7 +468,9 @@ int mtd_mesh_forces(mtd_mesh *m, unsigned int n_particles, const void *d_postype
                     const mtd_box *box, unsigned int n_global, const double *d_bias, double bias_host, mtd_stream_t stream);
 
 /* setTable (OrderParameterMesh.cc:148-189): convolution kernel K(k) and its derivative on n equidistant points of
- * [k_min, k_max].  Like the reference, K itself is stored and never applied to the mesh; K' enters the virial. */
+ * [k_min, k_max].  Like the reference, K itself is stored and never applied to the mesh; K' enters the virial.
+ * SYNCHRONISES THE DEVICE (the call has no stream): it waits for everything queued on any stream before the old table is freed,
+ * and the new one is in place when it returns. */
 int mtd_mesh_set_table(mtd_mesh *m, const double *K, const double *d_K, unsigned int n, double k_min, double k_max);
 int mtd_mesh_set_use_table(mtd_mesh *m, int use_table);
 

@@ -551,23 +551,25 @@ __global__ __launch_bounds__(FS_THREADS, 1) void k_fused_step(const LamKArgs a, 
         }
     }
 
-int step_buffers(mtd_metad *m)
+// The buffers of the one-launch step, allocated at an engine's first such step and cleared ON THE STEP'S STREAM: the launch that
+// follows on the same stream sees the zeros, and the call waits for nobody (mtd_abi.h: no entry point synchronises the device unless
+// its comment says so).
+int step_buffers(mtd_metad *m, hipStream_t s)
     {
     if (m->d_ll) return MTD_SUCCESS;
     void *ll = nullptr, *err = nullptr;
     unsigned int *h = nullptr, *dh = nullptr;
     const size_t ll_bytes = sizeof(unsigned long long) * FS_LL_REPLICAS * FS_LL_REPLICA_WORDS;
     hipError_t e = hipMalloc(&ll, ll_bytes);
-    if (e == hipSuccess) e = hipMemset(ll, 0, ll_bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(ll, 0, ll_bytes, s);
     if (e == hipSuccess) e = hipMalloc(&err, 64);
-    if (e == hipSuccess) e = hipMemset(err, 0, 64);
+    if (e == hipSuccess) e = hipMemsetAsync(err, 0, 64, s);
     if (e == hipSuccess) e = hipHostMalloc((void **)&h, sizeof(unsigned int), hipHostMallocMapped);
     if (e == hipSuccess)
         {
         *h = 0;
         e = hipHostGetDevicePointer((void **)&dh, h, 0);
         }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess)
         {
         (void)hipGetLastError();
@@ -671,7 +673,7 @@ int mtd_fused_step(mtd_metad *m, const mtd_lamellar_set *set, unsigned int n_par
 
     rc = metad_flush(m, s);                                     // (a deposit of the two-launch form may still be pending)
     if (rc) return rc;
-    rc = step_buffers(m);
+    rc = step_buffers(m, s);
     if (rc) return rc;
     CommK lk, ck;
     std::memset(&lk, 0, sizeof(lk));

@@ -4308,6 +4308,8 @@ int mtd_mesh_set_keep_fourier(mtd_mesh *m, int on)
 int mtd_mesh_set_bug_compat(mtd_mesh *m, int on)
     {
     if (!m) return MTD_ERR_INVALID_ARGUMENT;
+    // the setter has no stream: evaluations still queued on a non-blocking stream of the caller's must read the old tables
+    MTD_HIP_TRY(hipDeviceSynchronize());
     m->bug_compat = on ? 1 : 0;
     k_interp_tables<<<(m->nx + m->ny + m->nz + 255) / 256, 256>>>(m->nx, m->ny, m->nz, m->bug_compat, m->d_itab);
     MTD_LAUNCH_CHECK();
@@ -4666,6 +4668,8 @@ int mtd_mesh_set_table(mtd_mesh *m, const double *K, const double *d_K, unsigned
     {
     if (!m || !K || !d_K || n < 2) return MTD_ERR_INVALID_ARGUMENT;
     if (k_min < 0 || k_max < 0 || k_max <= k_min) return MTD_ERR_INVALID_ARGUMENT;       // :153-158
+    // the setter has no stream: nothing queued on a stream of the caller's may still read the table that is freed here
+    MTD_HIP_TRY(hipDeviceSynchronize());
     if (m->d_table) MTD_HIP_TRY(hipFree(m->d_table));
     m->d_table = nullptr;
     MTD_HIP_TRY(hipMalloc((void **)&m->d_table, sizeof(double) * 2 * n));

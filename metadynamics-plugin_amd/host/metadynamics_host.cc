@@ -39,6 +39,7 @@ void CollectiveVariable::computeForces(unsigned int timestep)
         if (m_bias_device)
             {
             double b = 0.0;
+            m_exec_conf->sync();                                       // the factor was written on the caller's stream
             hip_check(hipMemcpy(&b, m_bias_device, sizeof(double), hipMemcpyDeviceToHost), "bias read-back");
             setBiasFactor(b);
             }
@@ -268,7 +269,11 @@ void WellTemperedEnsemble::computeBiasForces(unsigned int)
     if (any_virial)
         {
         double bias = m_bias;
-        if (m_bias_device) hip_check(hipMemcpy(&bias, m_bias_device, sizeof(double), hipMemcpyDeviceToHost), "bias read-back");
+        if (m_bias_device)
+            {
+            m_exec_conf->sync();                                       // the factor was written on the caller's stream
+            hip_check(hipMemcpy(&bias, m_bias_device, sizeof(double), hipMemcpyDeviceToHost), "bias read-back");
+            }
         const double fac = 1.0 + bias;
         for (unsigned int i = 0; i < 6; ++i) m_pdata->setExternalVirial(i, fac * m_pdata->getExternalVirial(i));   // :180-184
         }
@@ -1271,16 +1276,20 @@ double AspectRatio::getCurrentValue(unsigned int)
     return length1 / length2;
     }
 
-static double host_bias(double bias, const double *d_bias)
+static double host_bias(double bias, const double *d_bias, const ExecutionConfiguration &exec_conf)
     {
-    if (d_bias) hip_check(hipMemcpy(&bias, d_bias, sizeof(double), hipMemcpyDeviceToHost), "bias read-back");
+    if (d_bias)
+        {
+        exec_conf.sync();                                              // the factor was written on the caller's stream
+        hip_check(hipMemcpy(&bias, d_bias, sizeof(double), hipMemcpyDeviceToHost), "bias read-back");
+        }
     return bias;
     }
 
 // AspectRatio.cc:59-130
 void AspectRatio::computeBiasForces(unsigned int)
     {
-    const double bias = host_bias(m_bias, m_bias_device);
+    const double bias = host_bias(m_bias, m_bias_device, *m_exec_conf);
     const BoxDim &box = m_pdata->getGlobalBox();
     const auto L = box.getL();
     double d_l_x = 0.0, d_l_y = 0.0, d_l_z = 0.0;
@@ -1321,7 +1330,7 @@ double Density::getCurrentValue(unsigned int)
 
 void Density::computeBiasForces(unsigned int)
     {
-    const double bias = host_bias(m_bias, m_bias_device);
+    const double bias = host_bias(m_bias, m_bias_device, *m_exec_conf);
     const double V = m_pdata->getGlobalBox().getVolume();
     const double fac = -(double)m_pdata->getNGlobal() / (V * V);       // Density.cc:44
     const auto L = m_pdata->getGlobalBox().getL();

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import ql_local_cluster_ref as cr
+import stream_gate
 import util
 
 torch = pytest.importorskip("torch")
@@ -19,32 +20,37 @@ NONE = cr.NONE
 DTYPES = [np.float64, np.float32]
 
 
-def run_gpu(abi, pos, types, L, nl, type_id, v, cluster, dtype, tilt=None, calls=1):
-    """`calls` calls on the same scratch; returns the list of dict(label, size, w, summary) read back after each"""
+def run_gpu(abi, pos, types, L, nl, type_id, v, cluster, dtype, tilt=None, calls=1, gate=None):
+    """`calls` calls on the same scratch; returns the list of dict(label, size, w, summary) read back after each.  gate: the stream the
+    calls run on and how their inputs arrive (tests/stream_gate.py; None: the NULL stream)"""
     lib = abi.load()
+    gate = gate or stream_gate.Plain()
     N = len(pos)
     box = abi.Box.make(L, **(tilt or {}))
     dt = abi.MTD_F32 if dtype == np.float32 else abi.MTD_F64
-    d_pos = torch.from_numpy(util.pack_postype(np.asarray(pos).astype(dtype), types, dtype)).cuda()
+    d_pos = gate.inp(util.pack_postype(np.asarray(pos).astype(dtype), types, dtype))
     lists = [np.asarray(x).astype(np.int64).astype(np.uint32).view(np.int32) for x in nl]
     lists[2] = np.concatenate([lists[2], np.zeros(1, dtype=np.int32)])           # never empty: a device pointer to hand over
-    d_head, d_nn, d_nl = (torch.from_numpy(x).cuda() for x in lists)
-    d_v = torch.from_numpy(np.asarray(v, dtype=np.float64)).cuda()
+    d_head, d_nn, d_nl = (gate.inp(x) for x in lists)
+    d_v = gate.inp(np.asarray(v, dtype=np.float64))
     p = abi.ClusterParams.make(cluster)
     n_bytes = lib.mtd_cluster_scratch_bytes(N)
     scratch = torch.full((n_bytes,), 0xA5, dtype=torch.uint8, device="cuda")
     out = []
+    stream = gate.arm()
     for _ in range(calls):
         ptrs = [C.c_void_p() for _ in range(4)]
         abi.check(lib.mtd_cluster_largest(N, abi.ptr(d_pos), dt, C.byref(box), abi.ptr(d_head), abi.ptr(d_nn), abi.ptr(d_nl), type_id,
-                                          abi.ptr(d_v), C.byref(p), abi.ptr(scratch), *[C.byref(x) for x in ptrs], None))
-        torch.cuda.synchronize()
-        raw = scratch.cpu().numpy()
-        at = [x.value - scratch.data_ptr() for x in ptrs]
-        assert all(0 <= a and a % 16 == 0 for a in at) and max(at) < n_bytes
-        take = lambda a, n, t: raw[a:a + n * np.dtype(t).itemsize].view(t).copy()
-        out.append(dict(label=take(at[0], N, np.uint32), size=take(at[1], N, np.uint32), w=take(at[2], N, np.float64),
-                        summary=take(at[3], 4, np.uint32)))
+                                          abi.ptr(d_v), C.byref(p), abi.ptr(scratch), *[C.byref(x) for x in ptrs], stream))
+
+        def read():
+            raw = scratch.cpu().numpy()
+            at = [x.value - scratch.data_ptr() for x in ptrs]
+            assert all(0 <= a and a % 16 == 0 for a in at) and max(at) < n_bytes
+            take = lambda a, n, t: raw[a:a + n * np.dtype(t).itemsize].view(t).copy()
+            return dict(label=take(at[0], N, np.uint32), size=take(at[1], N, np.uint32), w=take(at[2], N, np.float64),
+                        summary=take(at[3], 4, np.uint32))
+        out.append(gate.done(read))
     return out
 
 

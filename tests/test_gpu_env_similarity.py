@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import env_similarity_ref as es
+import stream_gate
 import util
 from pair_entropy_ref import brute_nlist
 
@@ -42,9 +43,11 @@ VARIANTS = {"fcc": (FCC, 100.0, None, True), "two": (TWO, 20.0, None, True), "tw
 
 
 def run_gpu(abi, pos, types, L, nl, templates, dtype, sigma_env=SIGMA_ENV, r_on=R_ON, r_cut=R_CUT, type_id=0, lam=100.0, sw=None, bias=0.9,
-            tilt=None, bias_on_device=True, virial=False, n_rows=None, n_ghost=0, expect=0):
-    """returns dict(s, sum_v, ke, k, v, F, virial, n_part); n_rows: the first n_rows particles are the central ones, the others ghosts"""
+            tilt=None, bias_on_device=True, virial=False, n_rows=None, n_ghost=0, expect=0, gate=None):
+    """returns dict(s, sum_v, ke, k, v, F, virial, n_part); n_rows: the first n_rows particles are the central ones, the others ghosts;
+    gate: the stream the calls run on and how their inputs arrive (tests/stream_gate.py; None: the NULL stream)"""
     lib = abi.load()
+    gate = gate or stream_gate.Plain()
     envs = es.as_environments(templates)
     E = len(envs)
     N = len(nl[0]) if n_rows is None else n_rows
@@ -53,42 +56,45 @@ def run_gpu(abi, pos, types, L, nl, templates, dtype, sigma_env=SIGMA_ENV, r_on=
     par = abi.EsParams.make(envs, sigma_env, r_on, r_cut, lam, sw)
     dt = abi.MTD_F32 if dtype == np.float32 else abi.MTD_F64
     tdt = torch.float32 if dtype == np.float32 else torch.float64
-    d_pos = torch.from_numpy(util.pack_postype(pos.astype(dtype), types, dtype)).cuda()
-    d_head, d_nn, d_nl = (torch.from_numpy(np.asarray(x).astype(np.int32)).cuda() for x in nl)
+    d_pos = gate.inp(util.pack_postype(pos.astype(dtype), types, dtype))
+    d_head, d_nn, d_nl = (gate.inp(np.asarray(x).astype(np.int32)) for x in nl)
     if len(nl[2]) == 0:
         d_nl = torch.zeros(1, dtype=torch.int32, device="cuda")
+    d_bias = gate.inp(np.array([bias], dtype=np.float64))
     scratch = torch.zeros(lib.mtd_es_scratch_doubles(N), dtype=torch.float64, device="cuda")
-    p_part, p_k, p_ke, p_v = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
-    n_part = C.c_uint()
-    lists = (abi.ptr(d_head), abi.ptr(d_nn), abi.ptr(d_nl))
-    rc = lib.mtd_es_accumulate(N, n_ghost, abi.ptr(d_pos), dt, C.byref(box), *lists, type_id, C.byref(par), n_global, abi.ptr(scratch),
-                               C.byref(p_part), C.byref(n_part), C.byref(p_k), C.byref(p_ke), C.byref(p_v), None)
     force = torch.full((N, 4), 3.0, dtype=tdt, device="cuda")
     pitch = N + 3
     vir = torch.full((6, pitch), 7.0, dtype=tdt, device="cuda") if virial else None
-    d_bias = torch.tensor([bias], dtype=torch.float64, device="cuda")
+    p_part, p_k, p_ke, p_v = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+    n_part = C.c_uint()
+    lists = (abi.ptr(d_head), abi.ptr(d_nn), abi.ptr(d_nl))
+    stream = gate.arm()
+    rc = lib.mtd_es_accumulate(N, n_ghost, abi.ptr(d_pos), dt, C.byref(box), *lists, type_id, C.byref(par), n_global, abi.ptr(scratch),
+                               C.byref(p_part), C.byref(n_part), C.byref(p_k), C.byref(p_ke), C.byref(p_v), stream)
     rc2 = lib.mtd_es_forces(N, n_ghost, abi.ptr(d_pos), abi.ptr(force), dt, C.byref(box), *lists, type_id, C.byref(par), n_global, abi.ptr(scratch),
-                            abi.ptr(d_bias) if bias_on_device else None, 0.0 if bias_on_device else bias, None,
+                            abi.ptr(d_bias) if bias_on_device else None, 0.0 if bias_on_device else bias, stream,
                             abi.ptr(vir) if virial else None, pitch if virial else 0)
     if expect:
         assert rc == expect and rc2 == expect
         return None
     abi.check(rc)
     abi.check(rc2)
-    torch.cuda.synchronize()
-    s = scratch.cpu().numpy()
-    off = lambda p: (p.value - scratch.data_ptr()) // 8
-    assert 1 <= n_part.value <= 1024
-    sum_v = float(s[off(p_part):off(p_part) + n_part.value].sum())
-    ke = s[off(p_ke):off(p_ke) + 4 * N].reshape(N, 4)
-    assert np.all(ke[:, E:] == 0.0)
-    out = dict(sum_v=sum_v, s=sum_v / n_global, ke=ke[:, :E].copy(), k=s[off(p_k):off(p_k) + N].copy(), v=s[off(p_v):off(p_v) + N].copy(),
-               F=force.cpu().numpy().astype(np.float64), virial=None, n_part=n_part.value)
-    if virial:
-        v = vir.cpu().numpy().astype(np.float64)
-        assert np.all(v[:, N:] == 7.0)                                  # [n_particles, pitch) is left alone
-        out["virial"] = v[:, :N].T.copy()
-    return out
+
+    def read():
+        s = scratch.cpu().numpy()
+        off = lambda p: (p.value - scratch.data_ptr()) // 8
+        assert 1 <= n_part.value <= 1024
+        sum_v = float(s[off(p_part):off(p_part) + n_part.value].sum())
+        ke = s[off(p_ke):off(p_ke) + 4 * N].reshape(N, 4)
+        assert np.all(ke[:, E:] == 0.0)
+        out = dict(sum_v=sum_v, s=sum_v / n_global, ke=ke[:, :E].copy(), k=s[off(p_k):off(p_k) + N].copy(), v=s[off(p_v):off(p_v) + N].copy(),
+                   F=force.cpu().numpy().astype(np.float64), virial=None, n_part=n_part.value)
+        if virial:
+            v = vir.cpu().numpy().astype(np.float64)
+            assert np.all(v[:, N:] == 7.0)                                  # [n_particles, pitch) is left alone
+            out["virial"] = v[:, :N].T.copy()
+        return out
+    return gate.done(read)
 
 
 def compare(g, r, bias, dtype, types=None, type_id=0, zero_sum=True):

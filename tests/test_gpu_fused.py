@@ -37,10 +37,11 @@ def make_traj(N, L, steps, dtype=np.float32):
 
 class Fused:
     """one bias step through the C ABI: the two-launch form (mtd_fused_cv_pass + mtd_fused_force_pass) or the one-launch
-    persistent kernel (mtd_fused_step)"""
+    persistent kernel (mtd_fused_step); stream: the HIP stream of every call (None: the NULL stream)"""
 
-    def __init__(self, abi, g, N, dtype, one_launch=False, cvs=None):
+    def __init__(self, abi, g, N, dtype, one_launch=False, cvs=None, stream=None):
         self.abi, self.g, self.N = abi, g, N
+        self.stream = stream
         self.lib = abi.load()
         self.cvs = cvs or CVS
         self.n_cv = len(self.cvs)
@@ -58,19 +59,19 @@ class Fused:
         if self.one_launch:
             abi.check(lib.mtd_fused_step_set_mode(self.g.h, 1))
             abi.check(lib.mtd_fused_step(self.g.h, C.byref(self.lset), self.N, abi.ptr(d_pos) if self.N else None, self.fptr, self.dt,
-                                         n_global or self.N, C.byref(box), abi.ptr(self.scratch), t, None))
+                                         n_global or self.N, C.byref(box), abi.ptr(self.scratch), t, self.stream))
             assert lib.mtd_fused_step_launches(self.g.h) == 1
             return
         n_part = C.c_uint()
         abi.check(lib.mtd_fused_cv_pass(self.g.h, C.byref(self.lset), self.N, abi.ptr(d_pos), self.dt, C.byref(box),
-                                        abi.ptr(self.scratch), C.byref(n_part), None))
+                                        abi.ptr(self.scratch), C.byref(n_part), self.stream))
         if not self.registered:
             for c in range(self.n_cv):
                 abi.check(lib.mtd_metad_set_cv_source(self.g.h, c, abi.ptr(self.scratch), n_part.value, self.n_cv, c,
                                                       1.0 / (n_global or self.N), 0.0))
             self.registered = True
         abi.check(lib.mtd_fused_force_pass(self.g.h, C.byref(self.lset), self.N, abi.ptr(d_pos), self.fptr, self.dt,
-                                           n_global or self.N, C.byref(box), t, None))
+                                           n_global or self.N, C.byref(box), t, self.stream))
 
 
 @pytest.mark.parametrize("one_launch", [False, True], ids=["two_launches", "one_launch"])

@@ -14,8 +14,12 @@ pytestmark = pytest.mark.gpu
 
 
 class GpuMesh:
-    def __init__(self, abi, dims, mode, max_particles):
+    """stream: the HIP stream every call of the mesh is handed (None: the NULL stream).  enqueue_cv / enqueue_forces only queue work and
+    return device tensors; cv / forces are those followed by a synchronise and a download, for the NULL stream"""
+
+    def __init__(self, abi, dims, mode, max_particles, stream=None):
         self.abi, self.lib = abi, abi.load()
+        self.stream = stream
         self.dims = dims
         self.h = C.c_void_p()
         abi.check(self.lib.mtd_mesh_create(C.byref(self.h), dims[0], dims[1], dims[2], util.dbl_array(mode), len(mode), max_particles))
@@ -26,20 +30,30 @@ class GpuMesh:
             self.abi.check(self.lib.mtd_mesh_destroy(self.h))
             self.h = None
 
-    def cv(self, d_pos, dt, box, n_global):
+    def enqueue_cv(self, d_pos, dt, box, n_global, out):
+        """mtd_mesh_compute_cv + mtd_reduce_partials into the device double `out`"""
         parts, n = C.c_void_p(), C.c_uint()
         self.abi.check(self.lib.mtd_mesh_compute_cv(self.h, d_pos.shape[0], self.abi.ptr(d_pos), dt, C.byref(box), n_global,
-                                                    C.byref(parts), C.byref(n), None))
+                                                    C.byref(parts), C.byref(n), self.stream))
+        self.abi.check(self.lib.mtd_reduce_partials(parts.value, n.value, 1, 1, 0.5, 0.0, self.abi.ptr(out), self.stream))
+
+    def cv(self, d_pos, dt, box, n_global):
+        assert self.stream is None
         out = torch.zeros(1, dtype=torch.float64, device="cuda")
-        self.abi.check(self.lib.mtd_reduce_partials(parts.value, n.value, 1, 1, 0.5, 0.0, self.abi.ptr(out), None))
+        self.enqueue_cv(d_pos, dt, box, n_global, out)
         torch.cuda.synchronize()
         return out.item()
 
+    def enqueue_forces(self, d_pos, dt, box, n_global, f, d_bias, bias_host=0.0):
+        """mtd_mesh_forces into f, the bias factor from the device double d_bias (None: bias_host)"""
+        self.abi.check(self.lib.mtd_mesh_forces(self.h, d_pos.shape[0], self.abi.ptr(d_pos), self.abi.ptr(f), dt, C.byref(box),
+                                                n_global, self.abi.ptr(d_bias), bias_host, self.stream))
+
     def forces(self, d_pos, dt, box, n_global, bias, device_bias=True):
+        assert self.stream is None
         f = torch.zeros_like(d_pos)
         d_bias = torch.tensor([bias], dtype=torch.float64, device="cuda")
-        self.abi.check(self.lib.mtd_mesh_forces(self.h, d_pos.shape[0], self.abi.ptr(d_pos), self.abi.ptr(f), dt, C.byref(box),
-                                                n_global, self.abi.ptr(d_bias) if device_bias else None, bias, None))
+        self.enqueue_forces(d_pos, dt, box, n_global, f, d_bias if device_bias else None, bias)
         torch.cuda.synchronize()
         return f.cpu().numpy().astype(np.float64)
 
@@ -51,7 +65,7 @@ class GpuMesh:
             out = np.zeros(1)
         else:
             out = np.zeros(2 * self.M)
-        self.abi.check(self.lib.mtd_mesh_get_array(self.h, which, out.ctypes.data, None))
+        self.abi.check(self.lib.mtd_mesh_get_array(self.h, which, out.ctypes.data, self.stream))
         if which in (0, 3):
             return out.reshape(nz, ny, nx)
         if which == 7:
@@ -62,7 +76,7 @@ class GpuMesh:
 def assign_info(abi, g):
     """(pipeline, particles through the overflow list) of the mesh's last assignment: mtd_mesh_assign_info"""
     pl, ovf = C.c_int(-1), C.c_uint(0)
-    abi.check(abi.load().mtd_mesh_assign_info(g.h, C.byref(pl), C.byref(ovf), None))
+    abi.check(abi.load().mtd_mesh_assign_info(g.h, C.byref(pl), C.byref(ovf), g.stream))
     return pl.value, ovf.value
 
 

@@ -20,9 +20,12 @@ RTOL = 1e-11
 
 
 class GpuMetad:
+    """stream: the HIP stream every call of the engine is handed (None: the NULL stream); may be set between calls"""
+
     def __init__(self, abi, sigma, cv_min, cv_max, num_points, W=1.0, T_shift=1.0, T=1.0, stride=1,
-                 mode="standard", add_bias=True):
+                 mode="standard", add_bias=True, stream=None):
         self.abi = abi
+        self.stream = stream
         self.lib = abi.load()
         self.n_cv = len(sigma)
         h = C.c_void_p()
@@ -41,7 +44,7 @@ class GpuMetad:
     def step(self, t, vals):
         for c, v in enumerate(vals):
             self.abi.check(self.lib.mtd_metad_set_cv_value(self.h, c, float(v)))
-        self.abi.check(self.lib.mtd_metad_update_bias(self.h, t, None))
+        self.abi.check(self.lib.mtd_metad_update_bias(self.h, t, self.stream))
 
     def state(self):
         cv = (C.c_double * self.n_cv)()
@@ -49,14 +52,14 @@ class GpuMetad:
         V, w = C.c_double(), C.c_double()
         ng, oob = C.c_uint(), C.c_uint()
         self.abi.check(self.lib.mtd_metad_get_state(self.h, cv, bias, C.byref(V), C.byref(w), C.byref(ng),
-                                                    C.byref(oob), None))
+                                                    C.byref(oob), self.stream))
         return dict(cv=np.array(cv[:]), bias=np.array(bias[:]), V=V.value, w=w.value, num_gaussians=ng.value,
                     oob=oob.value)
 
     def array(self, name):
         which = self.abi.ARRAY_NAMES.index(name)
         out = np.zeros(self.len, dtype=np.float64 if which < 6 else np.uint32)
-        self.abi.check(self.lib.mtd_metad_get_array(self.h, which, out.ctypes.data, None))
+        self.abi.check(self.lib.mtd_metad_get_array(self.h, which, out.ctypes.data, self.stream))
         return out
 
 

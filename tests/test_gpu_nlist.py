@@ -27,8 +27,12 @@ def _download_uints(ptr, count):
 
 
 class Handle:
-    def __init__(self, abi):
+    """stream: the HIP stream of mtd_nlist_build / mtd_nlist_check (None: the NULL stream).  The fill of a build is only stream-ordered:
+    the download waits for the device on the NULL stream and for `wait` (the caller's torch stream) otherwise"""
+
+    def __init__(self, abi, stream=None, wait=None):
         self.abi, self.lib = abi, abi.load()
+        self.stream, self.wait = stream, wait
         self.h = C.c_void_p()
         abi.check(self.lib.mtd_nlist_create(C.byref(self.h)))
 
@@ -36,12 +40,22 @@ class Handle:
         """(status, lists); postype: packed Scalar4 array (fp32 or fp64) of locals followed by ghosts"""
         dt = self.abi.MTD_F32 if postype.dtype == np.float32 else self.abi.MTD_F64
         self.d_pos = torch.from_numpy(np.ascontiguousarray(postype)).cuda() if len(postype) else None
+        return self.build_device(self.d_pos, dt, len(postype), n_local, box, r_list, half, type)
+
+    def build_device(self, d_pos, dt, n_total, n_local, box, r_list, half=False, type=-1, after_build=None):
+        """the same on a position array that is on the device already; after_build(): called when mtd_nlist_build has returned"""
+        self.d_pos = d_pos
         head, nn, nl, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
-        rc = self.lib.mtd_nlist_build(self.h, n_local, len(postype) - n_local, self.abi.ptr(self.d_pos), dt, C.byref(box), float(r_list),
-                                      int(half), int(type), C.byref(head), C.byref(nn), C.byref(nl), C.byref(n), None)
+        rc = self.lib.mtd_nlist_build(self.h, n_local, n_total - n_local, self.abi.ptr(self.d_pos), dt, C.byref(box), float(r_list),
+                                      int(half), int(type), C.byref(head), C.byref(nn), C.byref(nl), C.byref(n), self.stream)
+        if after_build is not None:
+            after_build()
         if rc != 0:
             return rc, None
-        torch.cuda.synchronize()
+        if self.stream is None:
+            torch.cuda.synchronize()
+        else:
+            self.wait.synchronize()
         return rc, (_download_uints(head.value, n_local), _download_uints(nn.value, n_local), _download_uints(nl.value, n.value))
 
     def build(self, *a, **k):
@@ -51,9 +65,11 @@ class Handle:
 
     def check(self, postype, box, r_buff):
         dt = self.abi.MTD_F32 if postype.dtype == np.float32 else self.abi.MTD_F64
-        d = torch.from_numpy(np.ascontiguousarray(postype)).cuda()
+        return self.check_device(torch.from_numpy(np.ascontiguousarray(postype)).cuda(), dt, box, r_buff)
+
+    def check_device(self, d, dt, box, r_buff):
         needs = C.c_int(-1)
-        self.abi.check(self.lib.mtd_nlist_check(self.h, self.abi.ptr(d), dt, C.byref(box), float(r_buff), C.byref(needs), None))
+        self.abi.check(self.lib.mtd_nlist_check(self.h, self.abi.ptr(d), dt, C.byref(box), float(r_buff), C.byref(needs), self.stream))
         return needs.value
 
     def cells(self):

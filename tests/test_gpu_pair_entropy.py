@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import pair_entropy_ref as pe
+import stream_gate
 import util
 from test_gpu_ql_local import brute_nlist
 
@@ -29,42 +30,48 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 
-def run_gpu(abi, pos, types, L, nl, r_max, sigma_r, n_bins, type_id, dtype, bias=0.9, tilt=None, bias_on_device=True, virial=False, n_rows=None):
-    """returns dict(S, g, sums, F, virial); n_rows: the first n_rows particles are the central ones, the others ghosts"""
+def run_gpu(abi, pos, types, L, nl, r_max, sigma_r, n_bins, type_id, dtype, bias=0.9, tilt=None, bias_on_device=True, virial=False, n_rows=None,
+            gate=None):
+    """returns dict(S, g, sums, F, virial); n_rows: the first n_rows particles are the central ones, the others ghosts; gate: the
+    stream the calls run on and how their inputs arrive (tests/stream_gate.py; None: the NULL stream)"""
     lib = abi.load()
+    gate = gate or stream_gate.Plain()
     N = len(nl[0]) if n_rows is None else n_rows
     box = abi.Box.make(L, **(tilt or {}))
     dt = abi.MTD_F32 if dtype == np.float32 else abi.MTD_F64
     tdt = torch.float32 if dtype == np.float32 else torch.float64
-    d_pos = torch.from_numpy(util.pack_postype(pos.astype(dtype), types, dtype)).cuda()
-    d_head, d_nn, d_nl = (torch.from_numpy(np.asarray(x).astype(np.int32)).cuda() for x in nl)
+    d_pos = gate.inp(util.pack_postype(pos.astype(dtype), types, dtype))
+    d_head, d_nn, d_nl = (gate.inp(np.asarray(x).astype(np.int32)) for x in nl)
     if len(nl[2]) == 0:
         d_nl = torch.zeros(1, dtype=torch.int32, device="cuda")
+    d_bias = gate.inp(np.array([bias], dtype=np.float64))
     scratch = torch.zeros(lib.mtd_pe_scratch_doubles(n_bins), dtype=torch.float64, device="cuda")
-    p_sums, p_value, p_g = C.c_void_p(), C.c_void_p(), C.c_void_p()
-    n_sums = C.c_uint()
-    lists = (abi.ptr(d_head), abi.ptr(d_nn), abi.ptr(d_nl))
-    abi.check(lib.mtd_pe_accumulate(N, abi.ptr(d_pos), dt, C.byref(box), *lists, r_max, sigma_r, n_bins, type_id, abi.ptr(scratch),
-                                    C.byref(p_sums), C.byref(n_sums), None))
-    assert n_sums.value == n_bins + 1
-    abi.check(lib.mtd_pe_finalize(C.byref(box), r_max, sigma_r, n_bins, abi.ptr(scratch), C.byref(p_value), C.byref(p_g), None))
     force = torch.full((N, 4), 3.0, dtype=tdt, device="cuda")
     pitch = N + 3
     vir = torch.full((6, pitch), 7.0, dtype=tdt, device="cuda") if virial else None
-    d_bias = torch.tensor([bias], dtype=torch.float64, device="cuda")
+    p_sums, p_value, p_g = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    n_sums = C.c_uint()
+    lists = (abi.ptr(d_head), abi.ptr(d_nn), abi.ptr(d_nl))
+    stream = gate.arm()
+    abi.check(lib.mtd_pe_accumulate(N, abi.ptr(d_pos), dt, C.byref(box), *lists, r_max, sigma_r, n_bins, type_id, abi.ptr(scratch),
+                                    C.byref(p_sums), C.byref(n_sums), stream))
+    assert n_sums.value == n_bins + 1
+    abi.check(lib.mtd_pe_finalize(C.byref(box), r_max, sigma_r, n_bins, abi.ptr(scratch), C.byref(p_value), C.byref(p_g), stream))
     abi.check(lib.mtd_pe_forces(N, abi.ptr(d_pos), abi.ptr(force), dt, C.byref(box), *lists, r_max, sigma_r, n_bins, type_id, abi.ptr(scratch),
-                                abi.ptr(d_bias) if bias_on_device else None, 0.0 if bias_on_device else bias, None,
+                                abi.ptr(d_bias) if bias_on_device else None, 0.0 if bias_on_device else bias, stream,
                                 abi.ptr(vir) if virial else None, pitch if virial else 0))
-    torch.cuda.synchronize()
-    s = scratch.cpu().numpy()
-    off = lambda p: (p.value - scratch.data_ptr()) // 8
-    out = dict(S=float(s[off(p_value)]), g=s[off(p_g):off(p_g) + n_bins].copy(), sums=s[off(p_sums):off(p_sums) + n_bins + 1].copy(),
-               F=force.cpu().numpy().astype(np.float64), virial=None)
-    if virial:
-        v = vir.cpu().numpy().astype(np.float64)
-        assert np.all(v[:, N:] == 7.0)                                  # [n_particles, pitch) is left alone
-        out["virial"] = v[:, :N].T.copy()
-    return out
+
+    def read():
+        s = scratch.cpu().numpy()
+        off = lambda p: (p.value - scratch.data_ptr()) // 8
+        out = dict(S=float(s[off(p_value)]), g=s[off(p_g):off(p_g) + n_bins].copy(), sums=s[off(p_sums):off(p_sums) + n_bins + 1].copy(),
+                   F=force.cpu().numpy().astype(np.float64), virial=None)
+        if virial:
+            v = vir.cpu().numpy().astype(np.float64)
+            assert np.all(v[:, N:] == 7.0)                                  # [n_particles, pitch) is left alone
+            out["virial"] = v[:, :N].T.copy()
+        return out
+    return gate.done(read)
 
 
 def noisy_fcc(n, sigma=0.05, seed=777):

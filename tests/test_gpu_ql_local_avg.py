@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import ql_local_avg_ref as avg_ref
+import stream_gate
 import util
 
 torch = pytest.importorskip("torch")
@@ -20,17 +21,19 @@ QL_46 = [0, 0, 0, 0, 1, 0, 1]
 
 
 def run_gpu(abi, pos, types, L, nl, rcut, ron, lmax, type_id, Ql_ref, dtype, opt=None, n_global=None, bias=0.9, tilt=None, bias_on_device=True,
-            entry="opt"):
+            entry="opt", gate=None):
     """opt: dict(average=, switch=, gate=) -> the _opt entry points with that struct; entry = "null": the _opt entry points with
     opt == NULL; "zero": with an all-zero struct; "old": the entry points without options.  Returns dict(s, c, n, v, F, partials).
-    The scratch starts as NaN: whatever the passes read they must have written."""
+    The scratch starts as NaN: whatever the passes read they must have written.  gate: the stream the calls run on and how their inputs
+    arrive (tests/stream_gate.py; None: the NULL stream)."""
     lib = abi.load()
+    gate = gate or stream_gate.Plain()
     N = len(pos)
     n_global = N if n_global is None else n_global
     box = abi.Box.make(L, **(tilt or {}))
     dt = abi.MTD_F32 if dtype == np.float32 else abi.MTD_F64
-    d_pos = torch.from_numpy(util.pack_postype(pos.astype(dtype), types, dtype)).cuda()
-    d_head, d_nn, d_nl = (torch.from_numpy(np.asarray(x).astype(np.int32)).cuda() for x in nl)
+    d_pos = gate.inp(util.pack_postype(pos.astype(dtype), types, dtype))
+    d_head, d_nn, d_nl = (gate.inp(np.asarray(x).astype(np.int32)) for x in nl)
     assert int(np.asarray(nl[0]).astype(np.int64)[-1] + np.asarray(nl[1]).astype(np.int64)[-1]) <= len(nl[2])
     o = abi.QlLocalOptions.make(**(opt or {}))
     p_opt = None if entry in ("null", "old") else C.byref(o)
@@ -39,24 +42,27 @@ def run_gpu(abi, pos, types, L, nl, rcut, ron, lmax, type_id, Ql_ref, dtype, opt
     p_part, p_c, p_n, p_v = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
     n_part = C.c_uint()
     force = torch.full((N, 4), 3.0, dtype=torch.float32 if dtype == np.float32 else torch.float64, device="cuda")
-    d_bias = torch.tensor([bias], dtype=torch.float64, device="cuda")
+    d_bias = gate.inp(np.array([bias], dtype=np.float64))
     common = (abi.ptr(d_head), abi.ptr(d_nn), abi.ptr(d_nl), rcut, ron, lmax, type_id, util.dbl_array(Ql_ref), n_global, abi.ptr(scratch))
-    b_args = (abi.ptr(d_bias) if bias_on_device else None, 0.0 if bias_on_device else bias, None)
+    stream = gate.arm()
+    b_args = (abi.ptr(d_bias) if bias_on_device else None, 0.0 if bias_on_device else bias, stream)
     if entry == "old":
         abi.check(lib.mtd_ql_local_accumulate(N, abi.ptr(d_pos), dt, C.byref(box), *common, C.byref(p_part), C.byref(n_part), C.byref(p_c),
-                                              C.byref(p_n), None))
+                                              C.byref(p_n), stream))
         abi.check(lib.mtd_ql_local_forces(N, abi.ptr(d_pos), abi.ptr(force), dt, C.byref(box), *common, *b_args))
         p_v = p_c
     else:
         abi.check(lib.mtd_ql_local_accumulate_opt(N, abi.ptr(d_pos), dt, C.byref(box), *common, C.byref(p_part), C.byref(n_part), C.byref(p_c),
-                                                  C.byref(p_n), None, p_opt, C.byref(p_v)))
+                                                  C.byref(p_n), stream, p_opt, C.byref(p_v)))
         abi.check(lib.mtd_ql_local_forces_opt(N, abi.ptr(d_pos), abi.ptr(force), dt, C.byref(box), *common, *b_args, p_opt))
-    torch.cuda.synchronize()
-    s = scratch.cpu().numpy()
-    off = lambda p: (p.value - scratch.data_ptr()) // 8
-    partials = s[off(p_part):off(p_part) + n_part.value].copy()
-    take = lambda p: s[off(p):off(p) + N].copy()
-    return dict(s=partials.sum() / n_global, c=take(p_c), n=take(p_n), v=take(p_v), F=force.cpu().numpy().astype(np.float64), partials=partials)
+
+    def read():
+        s = scratch.cpu().numpy()
+        off = lambda p: (p.value - scratch.data_ptr()) // 8
+        partials = s[off(p_part):off(p_part) + n_part.value].copy()
+        take = lambda p: s[off(p):off(p) + N].copy()
+        return dict(s=partials.sum() / n_global, c=take(p_c), n=take(p_n), v=take(p_v), F=force.cpu().numpy().astype(np.float64), partials=partials)
+    return gate.done(read)
 
 
 def noisy_fcc(n, sigma=0.05, seed=777):

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import ql_local_bonds_ref as bonds_ref
+import stream_gate
 import util
 from test_gpu_ql_local_avg import brute_nlist, cluster_case
 from test_gpu_ql_local_avg import run_gpu as run_gpu_opt
@@ -35,11 +36,13 @@ BIAS = 0.9
 
 
 def run_gpu(abi, pos, types, L, nl, rcut, ron, lmax, type_id, Ql_ref, dtype, opt=None, n_global=None, bias=BIAS, tilt=None, bias_on_device=True,
-            entry="bonds"):
+            entry="bonds", gate=None):
     """opt: dict(switch=, gate=, bonds=, average=); pass 1 through mtd_ql_local_accumulate_bonds, then mtd_ql_local_forces_bonds without
     and with a virial array on the same table.  entry = "null": bonds == NULL, "zero": an all-zero struct.  Returns dict(s, c, n, v, b,
-    F, F_vir, raw, partials); b is None with bonds off.  The scratch starts as NaN: whatever the passes read they must have written."""
+    F, F_vir, raw, partials); b is None with bonds off.  The scratch starts as NaN: whatever the passes read they must have written.
+    gate: the stream the calls run on and how their inputs arrive (tests/stream_gate.py; None: the NULL stream)."""
     lib = abi.load()
+    gate = gate or stream_gate.Plain()
     opt = dict(opt or {})
     bonds = opt.pop("bonds", None)
     N = len(pos)
@@ -47,8 +50,8 @@ def run_gpu(abi, pos, types, L, nl, rcut, ron, lmax, type_id, Ql_ref, dtype, opt
     box = abi.Box.make(L, **(tilt or {}))
     dt = abi.MTD_F32 if dtype == np.float32 else abi.MTD_F64
     tdt = torch.float32 if dtype == np.float32 else torch.float64
-    d_pos = torch.from_numpy(util.pack_postype(pos.astype(dtype), types, dtype)).cuda()
-    d_head, d_nn, d_nl = (torch.from_numpy(np.asarray(x).astype(np.int32)).cuda() for x in nl)
+    d_pos = gate.inp(util.pack_postype(pos.astype(dtype), types, dtype))
+    d_head, d_nn, d_nl = (gate.inp(np.asarray(x).astype(np.int32)) for x in nl)
     assert int(np.asarray(nl[0]).astype(np.int64)[-1] + np.asarray(nl[1]).astype(np.int64)[-1]) <= len(nl[2])
     o = abi.QlLocalOptions.make(**opt)
     bd = abi.QlLocalBonds.make(bonds if entry == "bonds" else None)
@@ -57,25 +60,29 @@ def run_gpu(abi, pos, types, L, nl, rcut, ron, lmax, type_id, Ql_ref, dtype, opt
     scratch = torch.full((n_doubles,), float("nan"), dtype=torch.float64, device="cuda")
     p_part, p_c, p_n, p_v, p_b = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
     n_part = C.c_uint()
-    d_bias = torch.tensor([bias], dtype=torch.float64, device="cuda")
+    d_bias = gate.inp(np.array([bias], dtype=np.float64))
     common = (abi.ptr(d_head), abi.ptr(d_nn), abi.ptr(d_nl), rcut, ron, lmax, type_id, util.dbl_array(Ql_ref), n_global, abi.ptr(scratch))
-    b_args = (abi.ptr(d_bias) if bias_on_device else None, 0.0 if bias_on_device else bias, None)
-    abi.check(lib.mtd_ql_local_accumulate_bonds(N, abi.ptr(d_pos), dt, C.byref(box), *common, C.byref(p_part), C.byref(n_part), C.byref(p_c),
-                                                C.byref(p_n), None, C.byref(o), C.byref(p_v), p_bd, C.byref(p_b)))
     force = torch.full((N, 4), 3.0, dtype=tdt, device="cuda")
     f_vir = torch.full((N, 4), 5.0, dtype=tdt, device="cuda")
     virial = torch.full((6, N + 3), SENTINEL, dtype=tdt, device="cuda")
+    stream = gate.arm()
+    b_args = (abi.ptr(d_bias) if bias_on_device else None, 0.0 if bias_on_device else bias, stream)
+    abi.check(lib.mtd_ql_local_accumulate_bonds(N, abi.ptr(d_pos), dt, C.byref(box), *common, C.byref(p_part), C.byref(n_part), C.byref(p_c),
+                                                C.byref(p_n), stream, C.byref(o), C.byref(p_v), p_bd, C.byref(p_b)))
     abi.check(lib.mtd_ql_local_forces_bonds(N, abi.ptr(d_pos), abi.ptr(force), dt, C.byref(box), *common, *b_args, C.byref(o), None, 0, p_bd))
     abi.check(lib.mtd_ql_local_forces_bonds(N, abi.ptr(d_pos), abi.ptr(f_vir), dt, C.byref(box), *common, *b_args, C.byref(o), abi.ptr(virial),
                                             N + 3, p_bd))
-    torch.cuda.synchronize()
-    s = scratch.cpu().numpy()
-    off = lambda p: (p.value - scratch.data_ptr()) // 8
-    partials = s[off(p_part):off(p_part) + n_part.value].copy()
-    take = lambda p: s[off(p):off(p) + N].copy()
-    assert (p_b.value is None) == (bonds is None or entry != "bonds")
-    return dict(s=partials.sum() / n_global, c=take(p_c), n=take(p_n), v=take(p_v), b=take(p_b) if p_b.value else None,
-                F=force.cpu().numpy().astype(np.float64), F_vir=f_vir.cpu().numpy().astype(np.float64), raw=virial.cpu().numpy(), partials=partials)
+
+    def read():
+        s = scratch.cpu().numpy()
+        off = lambda p: (p.value - scratch.data_ptr()) // 8
+        partials = s[off(p_part):off(p_part) + n_part.value].copy()
+        take = lambda p: s[off(p):off(p) + N].copy()
+        assert (p_b.value is None) == (bonds is None or entry != "bonds")
+        return dict(s=partials.sum() / n_global, c=take(p_c), n=take(p_n), v=take(p_v), b=take(p_b) if p_b.value else None,
+                    F=force.cpu().numpy().astype(np.float64), F_vir=f_vir.cpu().numpy().astype(np.float64), raw=virial.cpu().numpy(),
+                    partials=partials)
+    return gate.done(read)
 
 
 def compare(g, r, bias, dtype, types=None, type_id=0):

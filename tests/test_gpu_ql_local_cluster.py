@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import ql_local_cluster_ref as cr
+import stream_gate
 import util
 from test_gpu_ql_local_bonds import API_TOL, SENTINEL, _oracle_bias
 from test_gpu_ql_local_bonds import run_gpu as run_gpu_bonds
@@ -26,12 +27,14 @@ UNSUPPORTED = -2
 ARGS = (cr.ARGS["r_cut"], cr.ARGS["r_on"], cr.ARGS["lmax"], cr.ARGS["type_id"], cr.ARGS["Ql_ref"])
 
 
-def run_gpu(abi, pos, types, L, nl, dtype, opt=None, cluster=None, entry="cluster", bias=BIAS, expect=0, args=ARGS):
+def run_gpu(abi, pos, types, L, nl, dtype, opt=None, cluster=None, entry="cluster", bias=BIAS, expect=0, args=ARGS, gate=None):
     """pass 1 through mtd_ql_local_accumulate_cluster, then mtd_ql_local_forces_bonds without and with a virial array on the same table.
     opt: dict(switch=, gate=, bonds=, average=); cluster: (v_min, r_link) or None; entry = "null": cluster == NULL, "zero": an all-zero
     struct; args: (r_cut, r_on, lmax, type_id, Ql_ref).  Both scratches start as garbage.  Returns dict(s, c, n, v, b, F, F_vir, raw,
-    partials, w, label, summary)."""
+    partials, w, label, summary).  gate: the stream the calls run on and how their inputs arrive (tests/stream_gate.py; None: the NULL
+    stream)."""
     lib = abi.load()
+    gate = gate or stream_gate.Plain()
     opt = dict(opt or {})
     bonds = opt.pop("bonds", None)
     r_cut, r_on, lmax, type_id, Ql_ref = args
@@ -39,8 +42,8 @@ def run_gpu(abi, pos, types, L, nl, dtype, opt=None, cluster=None, entry="cluste
     box = abi.Box.make(L)
     dt = abi.MTD_F32 if dtype == np.float32 else abi.MTD_F64
     tdt = torch.float32 if dtype == np.float32 else torch.float64
-    d_pos = torch.from_numpy(util.pack_postype(pos.astype(dtype), types, dtype)).cuda()
-    d_head, d_nn, d_nl = (torch.from_numpy(np.asarray(x).astype(np.int32)).cuda() for x in nl)
+    d_pos = gate.inp(util.pack_postype(pos.astype(dtype), types, dtype))
+    d_head, d_nn, d_nl = (gate.inp(np.asarray(x).astype(np.int32)) for x in nl)
     o = abi.QlLocalOptions.make(**opt)
     bd = abi.QlLocalBonds.make(bonds)
     cl = abi.ClusterParams.make(cluster if entry == "cluster" else None)
@@ -51,36 +54,39 @@ def run_gpu(abi, pos, types, L, nl, dtype, opt=None, cluster=None, entry="cluste
     p_part, p_c, p_n, p_v, p_b, p_w, p_label, p_sum = (C.c_void_p() for _ in range(8))
     n_part = C.c_uint()
     common = (abi.ptr(d_head), abi.ptr(d_nn), abi.ptr(d_nl), r_cut, r_on, lmax, type_id, util.dbl_array(Ql_ref), N, abi.ptr(scratch))
+    force = torch.full((N, 4), 3.0, dtype=tdt, device="cuda")
+    f_vir = torch.full((N, 4), 5.0, dtype=tdt, device="cuda")
+    virial = torch.full((6, N + 3), SENTINEL, dtype=tdt, device="cuda")
+    stream = gate.arm()
     rc = lib.mtd_ql_local_accumulate_cluster(N, abi.ptr(d_pos), dt, C.byref(box), *common, C.byref(p_part), C.byref(n_part), C.byref(p_c),
-                                             C.byref(p_n), None, C.byref(o), C.byref(p_v), C.byref(bd), C.byref(p_b), p_cl, abi.ptr(c_scratch),
+                                             C.byref(p_n), stream, C.byref(o), C.byref(p_v), C.byref(bd), C.byref(p_b), p_cl, abi.ptr(c_scratch),
                                              C.byref(p_w), C.byref(p_label), C.byref(p_sum))
     if expect:
         assert rc == expect
         return None
     abi.check(rc)
-    force = torch.full((N, 4), 3.0, dtype=tdt, device="cuda")
-    f_vir = torch.full((N, 4), 5.0, dtype=tdt, device="cuda")
-    virial = torch.full((6, N + 3), SENTINEL, dtype=tdt, device="cuda")
-    b_args = (None, bias, None)
+    b_args = (None, bias, stream)
     abi.check(lib.mtd_ql_local_forces_bonds(N, abi.ptr(d_pos), abi.ptr(force), dt, C.byref(box), *common, *b_args, C.byref(o), None, 0, C.byref(bd)))
     abi.check(lib.mtd_ql_local_forces_bonds(N, abi.ptr(d_pos), abi.ptr(f_vir), dt, C.byref(box), *common, *b_args, C.byref(o), abi.ptr(virial), N + 3,
                                             C.byref(bd)))
-    torch.cuda.synchronize()
-    s = scratch.cpu().numpy()
-    off = lambda p: (p.value - scratch.data_ptr()) // 8
-    partials = s[off(p_part):off(p_part) + n_part.value].copy()
-    take = lambda p: s[off(p):off(p) + N].copy()
-    out = dict(s=partials.sum() / N, c=take(p_c), n=take(p_n), v=take(p_v), b=take(p_b) if p_b.value else None, partials=partials,
-               F=force.cpu().numpy().astype(np.float64), F_vir=f_vir.cpu().numpy().astype(np.float64), raw=virial.cpu().numpy(),
-               w=None, label=None, summary=None)
-    if entry == "cluster" and cluster is not None:
-        raw = c_scratch.cpu().numpy()
-        at = lambda p: p.value - c_scratch.data_ptr()
-        out.update(w=raw[at(p_w):at(p_w) + 8 * N].view(np.float64).copy(), label=raw[at(p_label):at(p_label) + 4 * N].view(np.uint32).copy(),
-                   summary=raw[at(p_sum):at(p_sum) + 16].view(np.uint32).copy())
-    else:
-        assert p_w.value is None and p_label.value is None and p_sum.value is None
-    return out
+
+    def read():
+        s = scratch.cpu().numpy()
+        off = lambda p: (p.value - scratch.data_ptr()) // 8
+        partials = s[off(p_part):off(p_part) + n_part.value].copy()
+        take = lambda p: s[off(p):off(p) + N].copy()
+        out = dict(s=partials.sum() / N, c=take(p_c), n=take(p_n), v=take(p_v), b=take(p_b) if p_b.value else None, partials=partials,
+                   F=force.cpu().numpy().astype(np.float64), F_vir=f_vir.cpu().numpy().astype(np.float64), raw=virial.cpu().numpy(),
+                   w=None, label=None, summary=None)
+        if entry == "cluster" and cluster is not None:
+            raw = c_scratch.cpu().numpy()
+            at = lambda p: p.value - c_scratch.data_ptr()
+            out.update(w=raw[at(p_w):at(p_w) + 8 * N].view(np.float64).copy(), label=raw[at(p_label):at(p_label) + 4 * N].view(np.uint32).copy(),
+                       summary=raw[at(p_sum):at(p_sum) + 16].view(np.uint32).copy())
+        else:
+            assert p_w.value is None and p_label.value is None and p_sum.value is None
+        return out
+    return gate.done(read)
 
 
 _systems = {}

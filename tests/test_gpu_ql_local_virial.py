@@ -13,6 +13,7 @@ import pytest
 
 import ql_local_avg_ref as avg_ref
 import ql_local_virial_ref as vir_ref
+import stream_gate
 import util
 from test_gpu_ql_local_avg import brute_nlist, noisy_fcc, snapshot
 
@@ -30,36 +31,38 @@ BIAS = 0.9
 
 
 def run_gpu(abi, pos, types, L, nl, rcut, ron, lmax, type_id, Ql_ref, dtype, opt=None, n_global=None, bias=BIAS, tilt=None, bias_on_device=True,
-            pitch=None, pass_virial=True):
+            pitch=None, pass_virial=True, gate=None):
     """pass 1, then mtd_ql_local_forces_opt and mtd_ql_local_forces_virial on the same table.  Returns dict(F_opt, F, raw): the two force
-    arrays (N, 4) as stored and the whole virial buffer (6, pitch), which starts as SENTINEL.  The scratch starts as NaN."""
+    arrays (N, 4) as stored and the whole virial buffer (6, pitch), which starts as SENTINEL.  The scratch starts as NaN.  gate: the
+    stream the calls run on and how their inputs arrive (tests/stream_gate.py; None: the NULL stream)."""
     lib = abi.load()
+    gate = gate or stream_gate.Plain()
     N = len(pos)
     n_global = N if n_global is None else n_global
     pitch = N if pitch is None else pitch
     box = abi.Box.make(L, **(tilt or {}))
     dt = abi.MTD_F32 if dtype == np.float32 else abi.MTD_F64
     tdt = torch.float32 if dtype == np.float32 else torch.float64
-    d_pos = torch.from_numpy(util.pack_postype(pos.astype(dtype), types, dtype)).cuda()
-    d_head, d_nn, d_nl = (torch.from_numpy(np.asarray(x).astype(np.int32)).cuda() for x in nl)
+    d_pos = gate.inp(util.pack_postype(pos.astype(dtype), types, dtype))
+    d_head, d_nn, d_nl = (gate.inp(np.asarray(x).astype(np.int32)) for x in nl)
     assert int(np.asarray(nl[0]).astype(np.int64)[-1] + np.asarray(nl[1]).astype(np.int64)[-1]) <= len(nl[2])
     o = abi.QlLocalOptions.make(**(opt or {}))
     scratch = torch.full((lib.mtd_ql_local_scratch_doubles_opt(N, lmax, len(nl[2]), C.byref(o)),), float("nan"), dtype=torch.float64, device="cuda")
     p_part, p_c, p_n, p_v = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
     n_part = C.c_uint()
-    d_bias = torch.tensor([bias], dtype=torch.float64, device="cuda")
+    d_bias = gate.inp(np.array([bias], dtype=np.float64))
     common = (abi.ptr(d_head), abi.ptr(d_nn), abi.ptr(d_nl), rcut, ron, lmax, type_id, util.dbl_array(Ql_ref), n_global, abi.ptr(scratch))
-    b_args = (abi.ptr(d_bias) if bias_on_device else None, 0.0 if bias_on_device else bias, None)
-    abi.check(lib.mtd_ql_local_accumulate_opt(N, abi.ptr(d_pos), dt, C.byref(box), *common, C.byref(p_part), C.byref(n_part), C.byref(p_c),
-                                              C.byref(p_n), None, C.byref(o), C.byref(p_v)))
     f_opt = torch.full((N, 4), 3.0, dtype=tdt, device="cuda")
     f_vir = torch.full((N, 4), 5.0, dtype=tdt, device="cuda")
     virial = torch.full((6, pitch), SENTINEL, dtype=tdt, device="cuda")
+    stream = gate.arm()
+    b_args = (abi.ptr(d_bias) if bias_on_device else None, 0.0 if bias_on_device else bias, stream)
+    abi.check(lib.mtd_ql_local_accumulate_opt(N, abi.ptr(d_pos), dt, C.byref(box), *common, C.byref(p_part), C.byref(n_part), C.byref(p_c),
+                                              C.byref(p_n), stream, C.byref(o), C.byref(p_v)))
     abi.check(lib.mtd_ql_local_forces_opt(N, abi.ptr(d_pos), abi.ptr(f_opt), dt, C.byref(box), *common, *b_args, C.byref(o)))
     abi.check(lib.mtd_ql_local_forces_virial(N, abi.ptr(d_pos), abi.ptr(f_vir), dt, C.byref(box), *common, *b_args, C.byref(o),
                                              abi.ptr(virial) if pass_virial else None, pitch))
-    torch.cuda.synchronize()
-    return dict(F_opt=f_opt.cpu().numpy(), F=f_vir.cpu().numpy(), raw=virial.cpu().numpy())
+    return gate.done(lambda: dict(F_opt=f_opt.cpu().numpy(), F=f_vir.cpu().numpy(), raw=virial.cpu().numpy()))
 
 
 _refs = {}

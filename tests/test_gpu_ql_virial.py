@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import ql_virial_ref as vir_ref
+import stream_gate
 import util
 from test_gpu_ql_local_avg import brute_nlist, noisy_fcc
 
@@ -63,32 +64,34 @@ def snapshot(abi, cells, dtype):
 
 
 def run_gpu(abi, pos, types, L, nl, lmax, Ql_ref, dtype, mode=0, rcut=R_CUT, ron=R_ON, type_id=0, n_global=None, bias=BIAS, tilt=None,
-            bias_on_device=True, pitch=None, pass_virial=True):
+            bias_on_device=True, pitch=None, pass_virial=True, gate=None):
     """mtd_ql_accumulate, then mtd_ql_forces and mtd_ql_forces_virial on the same table.  Returns dict(F_plain, F, raw): the two force
-    arrays (N, 4) as stored and the whole virial buffer (6, pitch), which starts as SENTINEL."""
+    arrays (N, 4) as stored and the whole virial buffer (6, pitch), which starts as SENTINEL.  gate: the stream the calls run on and how
+    their inputs arrive (tests/stream_gate.py; None: the NULL stream)."""
     lib = abi.load()
+    gate = gate or stream_gate.Plain()
     N = len(pos)
     n_global = N if n_global is None else n_global
     pitch = N if pitch is None else pitch
     box = abi.Box.make(L, **(tilt or {}))
     dt = abi.MTD_F32 if dtype == np.float32 else abi.MTD_F64
     tdt = torch.float32 if dtype == np.float32 else torch.float64
-    d_pos = torch.from_numpy(util.pack_postype(pos.astype(dtype), types, dtype)).cuda()
-    d_head, d_nn, d_nl = (torch.from_numpy(np.asarray(x).astype(np.int32)).cuda() for x in nl)
+    d_pos = gate.inp(util.pack_postype(pos.astype(dtype), types, dtype))
+    d_head, d_nn, d_nl = (gate.inp(np.asarray(x).astype(np.int32)) for x in nl)
     assert int(np.asarray(nl[0]).astype(np.int64)[-1] + np.asarray(nl[1]).astype(np.int64)[-1]) <= len(nl[2])
     scratch = torch.zeros(lib.mtd_ql_scratch_doubles(lmax), dtype=torch.float64, device="cuda")
     ql = util.dbl_array(Ql_ref)
     geo = (C.byref(box), abi.ptr(d_head), abi.ptr(d_nn), abi.ptr(d_nl), mode, rcut, ron, lmax, type_id, ql, n_global, abi.ptr(scratch))
-    abi.check(lib.mtd_ql_accumulate(N, abi.ptr(d_pos), dt, *geo, None, None, None, None))
-    d_bias = torch.tensor([bias], dtype=torch.float64, device="cuda")
-    b_args = (abi.ptr(d_bias) if bias_on_device else None, 0.0 if bias_on_device else bias, None)
+    d_bias = gate.inp(np.array([bias], dtype=np.float64))
     f_plain = torch.full((N, 4), 3.0, dtype=tdt, device="cuda")
     f_vir = torch.full((N, 4), 5.0, dtype=tdt, device="cuda")
     virial = torch.full((6, pitch), SENTINEL, dtype=tdt, device="cuda")
+    stream = gate.arm()
+    abi.check(lib.mtd_ql_accumulate(N, abi.ptr(d_pos), dt, *geo, None, None, None, stream))
+    b_args = (abi.ptr(d_bias) if bias_on_device else None, 0.0 if bias_on_device else bias, stream)
     abi.check(lib.mtd_ql_forces(N, abi.ptr(d_pos), abi.ptr(f_plain), dt, *geo, *b_args))
     abi.check(lib.mtd_ql_forces_virial(N, abi.ptr(d_pos), abi.ptr(f_vir), dt, *geo, *b_args, abi.ptr(virial) if pass_virial else None, pitch))
-    torch.cuda.synchronize()
-    return dict(F_plain=f_plain.cpu().numpy(), F=f_vir.cpu().numpy(), raw=virial.cpu().numpy())
+    return gate.done(lambda: dict(F_plain=f_plain.cpu().numpy(), F=f_vir.cpu().numpy(), raw=virial.cpu().numpy()))
 
 
 _refs = {}

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import stream_gate
 import util
 
 torch = pytest.importorskip("torch")
@@ -13,34 +14,40 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 
-def run_gpu(abi, pos, types, L, nl, rcut, ron, lmax, type_id, Ql_ref, dtype, half=False, n_global=None, bias=0.9, tilt=None):
+def run_gpu(abi, pos, types, L, nl, rcut, ron, lmax, type_id, Ql_ref, dtype, half=False, n_global=None, bias=0.9, tilt=None, gate=None):
+    """mtd_ql_accumulate + mtd_ql_forces: (value, Q_l, Q_lm, F); gate: the stream the calls run on and how their inputs arrive
+    (tests/stream_gate.py; None: the NULL stream)"""
     lib = abi.load()
+    gate = gate or stream_gate.Plain()
     N = len(pos)
     n_global = N if n_global is None else n_global
     box = abi.Box.make(L, **(tilt or {}))
     dt = abi.MTD_F32 if dtype == np.float32 else abi.MTD_F64
-    d_pos = torch.from_numpy(util.pack_postype(pos.astype(dtype), types, dtype)).cuda()
-    d_head, d_nn, d_nl = (torch.from_numpy(x.astype(np.int32)).cuda() for x in nl)
+    d_pos = gate.inp(util.pack_postype(pos.astype(dtype), types, dtype))
+    d_head, d_nn, d_nl = (gate.inp(np.asarray(x).astype(np.int32)) for x in nl)
+    d_bias = gate.inp(np.array([bias], dtype=np.float64))
     scratch = torch.zeros(lib.mtd_ql_scratch_doubles(lmax), dtype=torch.float64, device="cuda")
+    force = torch.full((N, 4), 3.0, dtype=torch.float32 if dtype == np.float32 else torch.float64, device="cuda")
     p_val, p_ql, p_qlm = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    stream = gate.arm()
     abi.check(lib.mtd_ql_accumulate(N, abi.ptr(d_pos), dt, C.byref(box), abi.ptr(d_head), abi.ptr(d_nn), abi.ptr(d_nl), int(half),
                                     rcut, ron, lmax, type_id, util.dbl_array(Ql_ref), n_global, abi.ptr(scratch),
-                                    C.byref(p_val), C.byref(p_ql), C.byref(p_qlm), None))
-    torch.cuda.synchronize()
-    base = scratch.data_ptr()
-    s = scratch.cpu().numpy()
-    off = lambda p: (p.value - base) // 8
-    val = s[off(p_val)]
-    Ql = s[off(p_ql):off(p_ql) + lmax + 1].copy()
-    q = s[off(p_qlm):off(p_qlm) + 2 * (lmax + 1) ** 2]
-    Qlm = q[0::2] + 1j * q[1::2]
-    force = torch.full((N, 4), 3.0, dtype=torch.float32 if dtype == np.float32 else torch.float64, device="cuda")
-    d_bias = torch.tensor([bias], dtype=torch.float64, device="cuda")
+                                    C.byref(p_val), C.byref(p_ql), C.byref(p_qlm), stream))
+    # (the force pass only reads the scratch: value, Q_l and Q_lm are downloaded behind it)
     abi.check(lib.mtd_ql_forces(N, abi.ptr(d_pos), abi.ptr(force), dt, C.byref(box), abi.ptr(d_head), abi.ptr(d_nn), abi.ptr(d_nl),
                                 int(half), rcut, ron, lmax, type_id, util.dbl_array(Ql_ref), n_global, abi.ptr(scratch),
-                                abi.ptr(d_bias), 0.0, None))
-    torch.cuda.synchronize()
-    return val, Ql, Qlm, force.cpu().numpy().astype(np.float64)
+                                abi.ptr(d_bias), 0.0, stream))
+
+    def read():
+        base = scratch.data_ptr()
+        s = scratch.cpu().numpy()
+        off = lambda p: (p.value - base) // 8
+        val = s[off(p_val)]
+        Ql = s[off(p_ql):off(p_ql) + lmax + 1].copy()
+        q = s[off(p_qlm):off(p_qlm) + 2 * (lmax + 1) ** 2]
+        Qlm = q[0::2] + 1j * q[1::2]
+        return val, Ql, Qlm, force.cpu().numpy().astype(np.float64)
+    return gate.done(read)
 
 
 def run_ref(ref, pos, types, L, nl, rcut, ron, lmax, type_id, Ql_ref, half=False, n_global=None, bias=0.9, tilt=None):
