@@ -962,6 +962,85 @@ int mtd_es_forces(unsigned int n_particles, unsigned int n_ghost, const void *d_
                   mtd_stream_t stream, void *d_virial, unsigned int virial_pitch);
 
 /* ================================================================================================
+ * Local pair entropy (cv.pair_entropy_local) — no reference counterpart.  The local-entropy fingerprint of Piaggi and Parrinello
+ * (J. Chem. Phys. 147, 114112; PLUMED's PAIRENTROPIES): a pair entropy s_i from particle i's OWN smoothed g_i(r), optionally averaged
+ * over the first shell and counted through a switch — the smooth number of solid-like particles without a reference value, a template
+ * or an orientation.  The conventions of "Pair entropy" above hold wherever nothing else is said.
+ * Parameters: r_max > 0, sigma_r > 0, n_bins = B (1 .. MTD_PEL_MAX_BINS), a particle type t; an optional average window
+ * 0 <= a_on < a_cut <= r_max + 4 sigma_r; an optional switch with c0 > 0 and integer p >= 1.  Delta, r_b, r_on = r_max + 3 sigma_r,
+ * r_cut = r_max + 4 sigma_r, w, K, b_c and g_min = 1e-10 are those of the global variable.
+ * Entries (i, j) of a FULL list take part when both particles are of type t, j != i and r = |d| <= r_cut, d = minImage(r_i - r_j); f is
+ * the cosine window between r_on and r_cut.  EVERY LIST ENTRY MUST ADDRESS A CENTRAL PARTICLE (j < n_particles): the force on k reads
+ * W_j, alpha_j, s_j of its neighbours, which ghosts do not have; an entry j >= n_particles is skipped.  Single-domain runs only.
+ *     H_ib  = sum_{j in row i} f(r_ij) K(r_b - r_ij)        over the window |b - b_c| <= w, 0 <= b < B
+ *     N_t   = central particles of type t,  rho = N_t / V,  V = Lx Ly Lz
+ *     g_ib  = H_ib / (4 pi rho r_b^2)
+ *     phi_ib = g ln g - g + 1 where g_ib >= g_min, else 1   (empty bins are the common case here)
+ *     s_i   = -2 pi rho Delta sum_b r_b^2 phi_ib  (<= 0)    particles of another type: s = sbar = v = 0, no force
+ *     n_i   = sum_j f_a(r_ij),  sbar_i = (s_i + sum_j f_a(r_ij) s_j) / (1 + n_i)
+ *             f_a: the cosine window a_on .. a_cut over the same entries; without an average sbar_i = s_i and n_i = 0
+ *     v_i   = h(-sbar_i),  h(c) = x^p / (1 + x^p), x = max(c, 0) / c0;  without a switch v_i = sbar_i
+ *     CV    = (1 / N_global) sum_i v_i
+ * Gradient:
+ *     W_ib  = ds_i/dH_ib = -Delta ln g_ib / 2 where g_ib >= g_min, else 0
+ *     gamma_i = dv_i/dsbar_i  (= -h'(-sbar_i), or 1 without a switch; 0 for the other type)
+ *     alpha_j = gamma_j / (1 + n_j) + sum_{i in row j} f_a(r_ij) gamma_i / (1 + n_i)        (alpha = gamma without an average)
+ *     u_ij(W) = sum_{b in window} W_b K_b [ f'(r) + f(r) (r_b - r) / sigma_r^2 ]
+ *     t_ij  = alpha_i u_ij(W_i) + gamma_i f_a'(r_ij) (s_j - sbar_i) / (1 + n_i)
+ * Entry (i, j) gives +t_ij d / r to d(N CV)/dr_i and -t_ij d / r to d(N CV)/dr_j.  As a gather over row k of the symmetric list:
+ *     N dCV/dr_k = sum_{j in row k} (t_kj + t_jk) d_kj / r              F = -bias dCV/dr
+ * Virial (only with a virial pointer), layout, scalar type and pitch rule of mtd_ql_local_forces_virial:
+ *     virial_k[ab] = -(bias / N_global) [ 1/2 sum_{j in row k} d_a (t_kj + t_jk) d_b / r + delta_ab alpha_k X_k ]
+ *     X_k = -( s_k + 2 pi rho Delta sum_{g_kb >= g_min} r_b^2 g_kb ln g_kb )        the explicit volume derivative of s_k through rho
+ * A step is _accumulate then _forces with the same parameters, call block and scratch.  H_ib is summed in fixed-point integers, every
+ * other sum in a fixed order: two identical calls give identical bits (csrc/pair_entropy_local.hip has the rounding bound).  Arguments
+ * are checked before a device is touched: MTD_ERR_INVALID_ARGUMENT for null pointers, a non-finite or non-positive r_max or sigma_r,
+ * n_bins == 0, an unknown dtype, a d_scratch that is not 16-byte aligned, a virial pitch below n_particles, a bad average window or
+ * switch, n_global == 0; MTD_ERR_UNSUPPORTED for n_bins > MTD_PEL_MAX_BINS.
+ * ============================================================================================== */
+
+#define MTD_PEL_MAX_BINS 128
+
+typedef struct
+    {
+    double r_max, sigma_r;
+    unsigned int n_bins, type;
+    int average_on;                        /* a_on, a_cut are read when average_on != 0 */
+    double a_on, a_cut;
+    int switch_on;                         /* c0, p are read when switch_on != 0 */
+    double c0;
+    unsigned int p;
+    } mtd_pel_params;                      /* options all-zero = off */
+
+/* what the two calls of a step share beside the parameters: particles, box, list, scratch and the stream the launches go to */
+typedef struct
+    {
+    unsigned int n_particles, n_global;
+    const void *d_postype;
+    int dtype;
+    const mtd_box *box;
+    const unsigned int *d_head_list, *d_n_neigh, *d_nlist;
+    double *d_scratch;
+    mtd_stream_t stream;
+    } mtd_pel_call;
+
+/* device doubles the two calls share: block sums, six per-particle arrays and the table W_ib [n_particles][n_bins] */
+size_t mtd_pel_scratch_doubles(unsigned int n_particles, unsigned int n_bins);
+
+/* First pass.  On return *d_partials points at *n_partials block sums of v_i (consume with
+ * mtd_metad_set_cv_source(engine, slot, *d_partials, *n_partials, 1, 0, 1.0 / N_global, 0.0) or mtd_reduce_partials), *d_s at
+ * s_i[n_particles], *d_sbar at sbar_i and *d_v at v_i (each may be NULL), all inside c->d_scratch. */
+int mtd_pel_accumulate(const mtd_pel_params *p, const mtd_pel_call *c, const double **d_partials, unsigned int *n_partials,
+                       const double **d_s, const double **d_sbar, const double **d_v);
+
+/* Second pass, with what the last mtd_pel_accumulate (same p and c) left in c->d_scratch: writes d_force[0..n_particles) (w component
+ * 0; 0 for particles of another type); bias = *d_bias when d_bias != NULL, else bias_host.  d_virial == NULL: no virial, the kernel
+ * without the sums; the force array is the same, bit for bit, either way.  n_particles == 0 is success.  No atomics: bitwise
+ * reproducible. */
+int mtd_pel_forces(const mtd_pel_params *p, const mtd_pel_call *c, void *d_force, const double *d_bias, double bias_host,
+                   void *d_virial, unsigned int virial_pitch);
+
+/* ================================================================================================
  * Neighbour list of the stand-alone path (cell list, built on the device)
  * no reference counterpart: HOOMD's md::NeighborList is HOOMD core.  Produces the three arrays SteinhardtQl.cc:80-85 reads, in
  * HOOMD's layout: the neighbours of particle i are d_nlist[d_head_list[i] .. d_head_list[i] + d_n_neigh[i]).

@@ -37,6 +37,7 @@
 // give identical bits: integer adds inside a block, fixed orders everywhere else.
 #include "mtd_device.hpp"
 #include "row_walk.hpp"
+#include "pair_entropy_device.hpp"
 #include "dispatch.hpp"
 
 #include <cmath>
@@ -57,48 +58,6 @@ constexpr double PE_G_MIN = 1e-10;
 // the scratch, in doubles: sums [258] | value, explicit volume derivative, N_t, (pad) [4] | g [256] | (W_b, W_b r_b) [256][2] | block sums [257][PE_MAX_BLOCKS]
 constexpr size_t PE_OFF_SUMS = 0, PE_OFF_VALUE = 258, PE_OFF_EXPL = 259, PE_OFF_NT = 260, PE_OFF_G = 262, PE_OFF_W = PE_OFF_G + PE_MAX_BINS,
                  PE_OFF_PART = PE_OFF_W + 2 * PE_MAX_BINS, PE_TOTAL = PE_OFF_PART + (size_t)(PE_MAX_BINS + 1) * PE_MAX_BLOCKS;
-
-struct PeArgs
-    {
-    double delta, inv_delta;                               // r_max / B, B / r_max
-    double inv_s2;                                         // 1 / sigma^2
-    double neg_half_inv_s2;                                // -1 / (2 sigma^2)
-    double k0;                                             // K(0) = 1 / (sqrt(2 pi) sigma)
-    double s, s2;                                          // exp(-Delta^2 / 2 sigma^2) and its square
-    unsigned int B, w;
-    unsigned int trips, _pad;                              // min(w, the largest centre bin + 1): beyond it both chains are off the table
-    };
-
-// the bin constants beside the box (row_walk.hpp, in_vgpr): what the per-bin loop multiplies with lives in vector registers
-__device__ __forceinline__ PeArgs pe_in_vgpr(PeArgs p)
-    {
-    p.delta = in_vgpr(p.delta), p.inv_delta = in_vgpr(p.inv_delta), p.inv_s2 = in_vgpr(p.inv_s2), p.neg_half_inv_s2 = in_vgpr(p.neg_half_inv_s2);
-    p.k0 = in_vgpr(p.k0), p.s = in_vgpr(p.s), p.s2 = in_vgpr(p.s2);
-    return p;
-    }
-
-// The window of one entry at distance r: calls bin(b, K_b) for the centre bin c, then for c + t and c - t, t = 1 .. trips, both chains of
-// the recurrence side by side (header).  The trip count is the same for every lane (no divergent loop); b may lie OUTSIDE the table
-// (below 0, above B - 1, beyond the window's clipped end): the body tests or clamps it.
-template<typename F> __device__ __forceinline__ void pe_window(const PeArgs &p, const double r, F &&bin)
-    {
-    const int bc = (int)fmin(fmax(floor(r * p.inv_delta), 0.0), 1e9);      // (a NaN distance, two particles in one place, lands in bin 0)
-    const double xc = ((double)bc + 0.5) * p.delta - r;
-    const double kc = p.k0 * exp(xc * xc * p.neg_half_inv_s2);
-    const double e = exp(-xc * p.delta * p.inv_s2);
-    bin(bc, kc);
-    double ku = kc, fu = e * p.s, kd = kc, fd = p.s / e;
-    const int trips = (int)p.trips;
-    for (int t = 1; t <= trips; ++t)
-        {
-        ku *= fu;
-        fu *= p.s2;
-        kd *= fd;
-        fd *= p.s2;
-        bin(bc + t, ku);
-        bin(bc - t, kd);
-        }
-    }
 
 // ---- pass 1: the block's share of H_b and N_t ----------------------------------------------------------------------------------
 template<typename S4>

@@ -1247,6 +1247,138 @@ std::vector<double> EnvironmentSimilarity::getEnvironmentValues(unsigned int tim
     }
 
 // ------------------------------------------------------------------------------------------------
+// PairEntropyLocal
+// ------------------------------------------------------------------------------------------------
+
+PairEntropyLocal::PairEntropyLocal(std::shared_ptr<SystemDefinition> sysdef, double r_max, double sigma_r, unsigned int n_bins,
+                                   std::shared_ptr<NeighborList> nlist, unsigned int type, const std::string &log_suffix)
+    : NeighbourVariable(sysdef, "pair_entropy_local", log_suffix, nlist, type), m_par(), m_d_partials(nullptr), m_d_s(nullptr), m_d_sbar(nullptr),
+      m_d_v(nullptr), m_n_partials(0)
+    {
+    if (!nlist) throw std::runtime_error("cv.pair_entropy_local: a neighbour list is required");
+    if (!(r_max > 0.0) || !std::isfinite(r_max) || !(sigma_r > 0.0) || !std::isfinite(sigma_r))
+        throw std::runtime_error("cv.pair_entropy_local: r_max > 0 and sigma_r > 0 are required");
+    if (n_bins == 0 || n_bins > MTD_PEL_MAX_BINS) throw std::runtime_error("cv.pair_entropy_local: 1 <= n_bins <= 128 in this build");
+    m_par.r_max = r_max;
+    m_par.sigma_r = sigma_r;
+    m_par.n_bins = n_bins;
+    m_par.type = type;
+    m_scratch.resize(sizeof(double) * mtd_pel_scratch_doubles(m_pdata->getN(), n_bins));
+    m_sum.resize(sizeof(double));
+    }
+
+void PairEntropyLocal::setAverage(double a_on, double a_cut)
+    {
+    if (!(a_on >= 0.0) || !(a_on < a_cut) || !(a_cut <= getRCut()))
+        throw std::runtime_error("cv.pair_entropy_local: an average needs 0 <= r_on < r_cut <= r_max + 4 sigma_r");
+    m_par.average_on = 1;
+    m_par.a_on = a_on;
+    m_par.a_cut = a_cut;
+    invalidate();                                                    // sbar, v and alpha in the scratch belong to the old window
+    }
+
+void PairEntropyLocal::clearAverage()
+    {
+    m_par.average_on = 0;
+    m_par.a_on = m_par.a_cut = 0.0;
+    invalidate();
+    }
+
+void PairEntropyLocal::setSwitch(double c0, unsigned int p)
+    {
+    if (!(c0 > 0.0) || !std::isfinite(c0) || p == 0) throw std::runtime_error("cv.pair_entropy_local: a switch needs c0 > 0 and an integer p >= 1");
+    m_par.switch_on = 1;
+    m_par.c0 = c0;
+    m_par.p = p;
+    invalidate();                                                    // v and gamma in the scratch belong to the old switch
+    }
+
+void PairEntropyLocal::clearSwitch()
+    {
+    m_par.switch_on = 0;
+    m_par.c0 = 0.0;
+    m_par.p = 0;
+    invalidate();
+    }
+
+mtd_pel_call PairEntropyLocal::call(const mtd_box *box)
+    {
+    const Lists l = lists();
+    mtd_pel_call c;
+    c.n_particles = m_pdata->getN();
+    c.n_global = m_pdata->getNGlobal();
+    c.d_postype = m_pdata->positionsPtr();
+    c.dtype = m_pdata->getDtype();
+    c.box = box;
+    c.d_head_list = l.head;
+    c.d_n_neigh = l.n_neigh;
+    c.d_nlist = l.nlist;
+    c.d_scratch = (double *)m_scratch.data();
+    c.stream = m_exec_conf->getStream();
+    return c;
+    }
+
+void PairEntropyLocal::computeCV(unsigned int timestep)
+    {
+    ProfRange prof_range("CV");
+    if (fresh(timestep)) return;
+    requireFullList();
+    if (distributed())
+        throw std::runtime_error("cv.pair_entropy_local: domain-decomposed runs are not supported (W, alpha and s of a ghost "
+                                 "neighbour would have to be exchanged)");
+    requireReach(getRCut(), "r_max + 4 sigma_r");
+    m_nlist->compute(timestep);
+    const mtd_box box = m_pdata->getBox().toMtd();
+    const size_t need = sizeof(double) * mtd_pel_scratch_doubles(m_pdata->getN(), m_par.n_bins);
+    if (need > m_scratch.bytes()) m_scratch.resize(need);
+    const mtd_pel_call c = call(&box);
+    mtd_check(mtd_pel_accumulate(&m_par, &c, &m_d_partials, &m_n_partials, &m_d_s, &m_d_sbar, &m_d_v), "mtd_pel_accumulate");
+    computed(timestep);
+    }
+
+void PairEntropyLocal::enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot)
+    {
+    computeCV(timestep);
+    mtd_check(mtd_metad_set_cv_source(engine, slot, m_d_partials, m_n_partials, 1, 0, 1.0 / (double)m_pdata->getNGlobal(), 0.0),
+              "mtd_metad_set_cv_source");
+    }
+
+double PairEntropyLocal::getCurrentValue(unsigned int timestep)
+    {
+    computeCV(timestep);                                             // (sets the pointers: before they are handed on, here and below)
+    return readPartials(m_d_partials, m_n_partials, timestep);
+    }
+
+void PairEntropyLocal::computeBiasForces(unsigned int timestep)
+    {
+    ProfRange prof_range("Force");
+    if (!fresh(timestep)) computeCV(timestep);                       // W, alpha and s of THIS step's positions
+    m_nlist->compute(timestep);
+    const mtd_box box = m_pdata->getBox().toMtd();
+    const mtd_pel_call c = call(&box);
+    void *virial = virialTarget();                                   // constant pressure: the per-particle virial of the bias force beside it
+    mtd_check(mtd_pel_forces(&m_par, &c, m_force.data(), m_bias_device, m_bias, virial, getVirialPitch()), "mtd_pel_forces");
+    }
+
+std::vector<double> PairEntropyLocal::getLocalValues(unsigned int timestep)
+    {
+    computeCV(timestep);
+    return readBack(m_d_s, m_pdata->getN(), "s_i read-back", timestep);
+    }
+
+std::vector<double> PairEntropyLocal::getAveragedValues(unsigned int timestep)
+    {
+    computeCV(timestep);
+    return readBack(m_d_sbar, m_pdata->getN(), "sbar_i read-back", timestep);
+    }
+
+std::vector<double> PairEntropyLocal::getSwitchedValues(unsigned int timestep)
+    {
+    computeCV(timestep);
+    return readBack(m_d_v, m_pdata->getN(), "v_i read-back", timestep);
+    }
+
+// ------------------------------------------------------------------------------------------------
 // AspectRatio, Density
 // ------------------------------------------------------------------------------------------------
 

@@ -466,6 +466,36 @@ class EnvironmentSimilarity : public NeighbourVariable
         unsigned int m_n_partials;
     };
 
+//! Local pair entropy (no reference counterpart; include/mtd_abi.h "Local pair entropy"): the pair entropy s_i of every particle's own g_i(r),
+//! optionally averaged over the first shell and counted through a switch, s = (1/N_global) sum_i v_i.  Single-domain runs only: the force
+//! on a particle reads W_j, alpha_j and s_j of its neighbours, which a ghost does not have.
+class PairEntropyLocal : public NeighbourVariable
+    {
+    public:
+        PairEntropyLocal(std::shared_ptr<SystemDefinition> sysdef, double r_max, double sigma_r, unsigned int n_bins,
+                         std::shared_ptr<NeighborList> nlist, unsigned int type, const std::string &log_suffix = "");
+        double getCurrentValue(unsigned int timestep) override;
+        //! device-resident: the block sums of v_i become the engine's source of this variable, no host synchronisation
+        void enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot) override;
+        void computeBiasForces(unsigned int timestep) override;
+        //! the options of mtd_pel_params; every change invalidates the cached step
+        void setAverage(double a_on, double a_cut);                    //!< sbar_i over the cosine window a_on .. a_cut <= getRCut()
+        void clearAverage();
+        void setSwitch(double c0, unsigned int p);                     //!< v_i = h(-sbar_i), h(c) = x^p / (1 + x^p), x = max(c, 0) / c0
+        void clearSwitch();
+        std::vector<double> getLocalValues(unsigned int timestep);     //!< s_i of every local particle (0 for other types)
+        std::vector<double> getAveragedValues(unsigned int timestep);  //!< sbar_i (s_i without the average)
+        std::vector<double> getSwitchedValues(unsigned int timestep);  //!< v_i (sbar_i without the switch)
+        double getRCut() const { return m_par.r_max + 4.0 * m_par.sigma_r; }   //!< what the neighbour list must reach
+
+    private:
+        void computeCV(unsigned int timestep) override;
+        mtd_pel_call call(const mtd_box *box);
+        mtd_pel_params m_par;
+        const double *m_d_partials, *m_d_s, *m_d_sbar, *m_d_v;
+        unsigned int m_n_partials;
+    };
+
 //! AspectRatio.h / AspectRatio.cc:5-130 — box-shape CV, external virial only
 class AspectRatio : public CollectiveVariable
     {

@@ -397,6 +397,28 @@ PYBIND11_MODULE(_metadynamics, m)
             return py::array_t<double>({(ssize_t)v.size() / E, E}, v.data());
         });
 
+    // no reference counterpart: the per-particle pair entropy, averaged over the first shell and counted through a switch
+    py::class_<PairEntropyLocal, CollectiveVariable, std::shared_ptr<PairEntropyLocal>>(m, "PairEntropyLocal")
+        .def(py::init<std::shared_ptr<SystemDefinition>, double, double, unsigned int, std::shared_ptr<NeighborList>, unsigned int,
+                      const std::string &>())
+        .def("getRCut", &PairEntropyLocal::getRCut)
+        .def("setAverage", &PairEntropyLocal::setAverage)
+        .def("clearAverage", &PairEntropyLocal::clearAverage)
+        .def("setSwitch", &PairEntropyLocal::setSwitch)
+        .def("clearSwitch", &PairEntropyLocal::clearSwitch)
+        .def("getLocalValues", [](PairEntropyLocal &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getLocalValues(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        })
+        .def("getAveragedValues", [](PairEntropyLocal &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getAveragedValues(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        })
+        .def("getSwitchedValues", [](PairEntropyLocal &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getSwitchedValues(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        });
+
     py::class_<WellTemperedEnsemble, CollectiveVariable, std::shared_ptr<WellTemperedEnsemble>>(m, "WellTemperedEnsemble")
         .def(py::init<std::shared_ptr<SystemDefinition>, const std::string &>());
 

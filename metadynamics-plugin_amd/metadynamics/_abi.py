@@ -157,6 +157,33 @@ class EsParams(C.Structure):
         return o
 
 
+MTD_PEL_MAX_BINS = 128
+
+
+class PelParams(C.Structure):
+    """mtd_pel_params: the histogram, the particle type, the optional average window and the optional switch"""
+    _fields_ = [("r_max", C.c_double), ("sigma_r", C.c_double), ("n_bins", C.c_uint), ("type", C.c_uint), ("average_on", C.c_int),
+                ("a_on", C.c_double), ("a_cut", C.c_double), ("switch_on", C.c_int), ("c0", C.c_double), ("p", C.c_uint)]
+
+    @classmethod
+    def make(cls, r_max, sigma_r, n_bins, type_id, average=None, switch=None):
+        """average: (a_on, a_cut) or None; switch: (c0, p) or None.  Nothing is checked here: the entry points refuse what they do not take"""
+        o = cls()
+        o.r_max, o.sigma_r, o.n_bins, o.type = float(r_max), float(sigma_r), int(n_bins), int(type_id)
+        if average is not None:
+            o.average_on, o.a_on, o.a_cut = 1, float(average[0]), float(average[1])
+        if switch is not None:
+            o.switch_on, o.c0, o.p = 1, float(switch[0]), int(switch[1])
+        return o
+
+
+class PelCall(C.Structure):
+    """mtd_pel_call: particles, box, list, scratch and stream of one step"""
+    _fields_ = [("n_particles", C.c_uint), ("n_global", C.c_uint), ("d_postype", C.c_void_p), ("dtype", C.c_int), ("box", C.POINTER(Box)),
+                ("d_head_list", C.c_void_p), ("d_n_neigh", C.c_void_p), ("d_nlist", C.c_void_p), ("d_scratch", C.c_void_p),
+                ("stream", C.c_void_p)]
+
+
 _vp = C.c_void_p
 _dp = C.POINTER(C.c_double)
 _up = C.POINTER(C.c_uint)
@@ -314,6 +341,9 @@ _SIGNATURES = {
                                      C.POINTER(_vp), _up, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp]),
     "mtd_es_forces": (C.c_int, [C.c_uint, C.c_uint, _vp, _vp, C.c_int, C.POINTER(Box), _vp, _vp, _vp, C.c_uint, C.POINTER(EsParams), C.c_uint, _vp,
                                  _vp, C.c_double, _vp, _vp, C.c_uint]),
+    "mtd_pel_scratch_doubles": (C.c_size_t, [C.c_uint, C.c_uint]),
+    "mtd_pel_accumulate": (C.c_int, [C.POINTER(PelParams), C.POINTER(PelCall), C.POINTER(_vp), _up, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "mtd_pel_forces": (C.c_int, [C.POINTER(PelParams), C.POINTER(PelCall), _vp, _vp, C.c_double, _vp, C.c_uint]),
     "mtd_nlist_create": (C.c_int, [C.POINTER(_vp)]),
     "mtd_nlist_destroy": (C.c_int, [_vp]),
     "mtd_nlist_build": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp, C.c_int, C.POINTER(Box), C.c_double, C.c_int, C.c_int,

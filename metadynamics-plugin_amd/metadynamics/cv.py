@@ -428,6 +428,93 @@ class pair_entropy(_neighbour_variable):
         r_b = (np.arange(self.n_bins) + 0.5) * (self.r_max / self.n_bins)
         return r_b, np.asarray(self.cpp_force.getGr(context.current.system.getCurrentTimeStep()))
 
+
+class pair_entropy_local(_neighbour_variable):
+    """this build (no reference counterpart; include/mtd_abi.h "Local pair entropy"): the local-entropy fingerprint of Piaggi and Parrinello
+    (J. Chem. Phys. 147, 114112; PLUMED's PAIRENTROPIES).  Every particle of ``type`` gets the pair entropy s_i of its OWN smoothed
+    g_i(r), s_i = -2 pi rho int_0^r_max [g_i ln g_i - g_i + 1] r^2 dr (<= 0, strongly negative in a crystal) on ``n_bins`` midpoints with
+    Gaussians of width ``sigma_r``.  ``average=dict(r_on=..., r_cut=...)`` replaces it by its average over the particle and its first
+    shell, sbar_i = (s_i + sum_j f_a(r_ij) s_j) / (1 + sum_j f_a(r_ij)) with the cosine window f_a; ``switch=dict(c0=..., p=...)``
+    counts it, v_i = x^p / (1 + x^p), x = max(-sbar_i, 0) / c0.  CV = (1 / N) sum_i v_i: with both options CV * N is the smooth number of
+    solid-like particles, with no reference value, template or orientation to name.
+    Needs a full list that reaches ``r_max + 4 * sigma_r`` (``get_rcut``); single-domain runs only; n_bins <= 128; the average window
+    must end inside ``r_max + 4 * sigma_r``.
+
+    Virial (``get_virial``; mtd_pel_forces): half of every pair at each of its ends, and the explicit volume term of s_k on the diagonal
+    of particle k.  The sums are -bias * dCV/d(strain)."""
+
+    _cv = "cv.pair_entropy_local"
+
+    def __init__(self, r_max, sigma_r, n_bins, nlist, type, average=None, switch=None, name=None, sigma=1.0):
+        suffix = self._begin(sigma, name)
+        try:
+            type_list = context.current.type_names
+            r_max, sigma_r = float(r_max), float(sigma_r)
+            if type not in type_list or int(n_bins) != n_bins or not 1 <= int(n_bins) <= 128 or not 0.0 < r_max < float("inf") \
+                    or not 0.0 < sigma_r < float("inf") or float(nlist.r_cut) < r_max + 4.0 * sigma_r:
+                raise ValueError
+            self.type = type
+            self.nlist = nlist
+            self.r_max, self.sigma_r, self.n_bins = r_max, sigma_r, int(n_bins)
+            self.r_cut = r_max + 4.0 * sigma_r
+            options = (self._average(average), self._switch(switch))
+            self._full_list()
+            self.cpp_force = _metadynamics.PairEntropyLocal(context.current.system_definition, r_max, sigma_r, int(n_bins), nlist.cpp_nlist,
+                                                            type_list.index(type), suffix)
+            self._apply(*options)
+        except (TypeError, ValueError, KeyError, AttributeError, RuntimeError):
+            context.current.forces.remove(self)                      # refused: the run must not find a half-made variable
+            raise RuntimeError("Error creating collective variable.")
+        self._attach(type_list.index(type))
+
+    def _average(self, average):
+        if average is None:
+            return None
+        av = (float(average["r_on"]), float(average["r_cut"]))
+        if set(average.keys()) != {"r_on", "r_cut"} or not 0.0 <= av[0] < av[1] <= self.r_cut:
+            raise ValueError
+        return av
+
+    @staticmethod
+    def _switch(switch):
+        if switch is None:
+            return None
+        sw = (float(switch["c0"]), int(switch["p"]))
+        if set(switch.keys()) != {"c0", "p"} or int(switch["p"]) != switch["p"] or not 0.0 < sw[0] < float("inf") or sw[1] < 1:
+            raise ValueError
+        return sw
+
+    def _apply(self, av, sw):
+        if av is None:
+            self.cpp_force.clearAverage()
+        else:
+            self.cpp_force.setAverage(*av)
+        if sw is None:
+            self.cpp_force.clearSwitch()
+        else:
+            self.cpp_force.setSwitch(*sw)
+
+    def set_options(self, average=None, switch=None):
+        """replaces BOTH options (``None`` switches one off); takes effect with the next step.  A refused argument leaves the options as
+        they were"""
+        try:
+            options = (self._average(average), self._switch(switch))
+            self._apply(*options)
+        except (TypeError, KeyError, ValueError, AttributeError, RuntimeError):
+            raise RuntimeError("Error creating collective variable.")
+
+    def get_local(self):
+        """s_i of every particle at the current time step (0 for particles of another type)"""
+        return self.cpp_force.getLocalValues(context.current.system.getCurrentTimeStep())
+
+    def get_averaged(self):
+        """sbar_i of every particle at the current time step (s_i itself without an average)"""
+        return self.cpp_force.getAveragedValues(context.current.system.getCurrentTimeStep())
+
+    def get_switched(self):
+        """v_i of every particle at the current time step: what the CV averages (sbar_i itself without a switch)"""
+        return self.cpp_force.getSwitchedValues(context.current.system.getCurrentTimeStep())
+
 def environment_templates(structure, a):
     """the template environments of a cubic lattice with the conventional lattice constant ``a``, for ``cv.environment_similarity``:
     ``"fcc"`` 12 vectors of length a / sqrt(2), ``"bcc"`` 14 vectors (the 8 nearest of length a sqrt(3) / 2 and the 6 second neighbours of
