@@ -1481,7 +1481,7 @@ IntegratorMetaDynamics::IntegratorMetaDynamics(std::shared_ptr<SystemDefinition>
       m_T_shift(T_shift), m_stride(stride), m_is_initialized(false), m_filename(filename), m_overwrite(overwrite),
       m_is_appending(false), m_delimiter("\t"), m_use_grid(false), m_add_bias(add_bias), m_grid_period(0), m_cur_file(0),
       m_sigma_g(1.0), m_adaptive(false), m_temp(T), m_mode(mode), m_multiple_walkers(false), m_warned_single_walker(false), m_engine(nullptr),
-      m_allow_fused(true), m_used_fused(false), m_fused_n_partials(0)
+      m_allow_fused(true)
     {
     if (!(T_shift > 0.0) || !(W > 0.0)) throw std::runtime_error("IntegratorMetaDynamics: W and deltaT must be positive");   // asserts :58-59
     if (stride == 0) throw std::runtime_error("IntegratorMetaDynamics: stride must be positive");
@@ -1505,6 +1505,10 @@ void IntegratorMetaDynamics::registerCollectiveVariable(std::shared_ptr<Collecti
     item.m_cv_min = cv_min;
     item.m_cv_max = cv_max;
     item.m_num_points = (unsigned int)num_points;
+    // the only place that asks a variable for its class: planStep and graphPeriod read the answers
+    item.m_lamellar = std::dynamic_pointer_cast<LamellarOrderParameterGPU>(cv);
+    item.m_mesh = std::dynamic_pointer_cast<OrderParameterMeshGPU>(cv);
+    item.m_steinhardt = std::dynamic_pointer_cast<SteinhardtQl>(cv);
     m_variables.push_back(item);
     }
 
@@ -1688,33 +1692,66 @@ void IntegratorMetaDynamics::update(unsigned int timestep)
         m_variables[0].m_cv->compute(timestep);                        // :300 — bias forces *after* everything else
     }
 
-bool IntegratorMetaDynamics::fusedLamellarPossible() const
+// What this step does, decided in one place.  Variables of three kinds have launches beyond their own: lamellar variables share
+// the two launches of the fused step (fused.hip), ONE mesh may carry the lamellar sums in its assignment and the grid engine's launch
+// in its force pass (mesh.hip), and a variable that is alone on the grid may update the engine itself (cv.steinhardt).  What is
+// decided here is what MAY happen: the calls themselves can still decline at run time, and the step's functions fall back.
+IntegratorMetaDynamics::StepPlan IntegratorMetaDynamics::planStep() const
     {
-    if (m_adaptive) return false;                                      // the deposit width changes between the two launches
-    if (m_multiple_walkers) return false;                              // the walkers' increments are summed between the grid passes
-    if (!m_allow_fused || m_variables.empty() || m_variables.size() > MTD_METAD_MAX_CV) return false;
-    unsigned int n_modes = 0;
-    for (const auto &it : m_variables)
+    StepPlan p;
+    p.adaptive = m_adaptive;
+    p.walkers = m_multiple_walkers;
+    const size_t n = m_variables.size();
+    const bool mailbox = m_exec_conf->getMailbox() != nullptr;
+    std::vector<unsigned int> lam;
+    unsigned int n_modes = 0, n_mesh = 0;
+    for (unsigned int i = 0; i < n; ++i)
         {
-        auto lam = std::dynamic_pointer_cast<LamellarOrderParameterGPU>(it.m_cv);
-        if (!lam || lam->hasUmbrella()) return false;
-        n_modes += (unsigned int)lam->getLatticeVectors().size();
+        const CollectiveVariableItem &it = m_variables[i];
+        if (it.sharesLamellarLaunches())
+            {
+            lam.push_back(i);
+            n_modes += (unsigned int)it.m_lamellar->getLatticeVectors().size();
+            }
+        if (it.m_mesh)
+            {
+            p.mesh = it.m_mesh;
+            p.mesh_slot = i;
+            ++n_mesh;
+            }
         }
-    return n_modes <= MTD_MAX_MODES;
+    if (n_mesh != 1) p.mesh.reset();
+    // no shared launches: adaptive widths (the deposit width changes between the two launches), walkers (their increments are summed
+    // between the grid passes), setFusedPath(false), more modes than one launch holds
+    if (m_adaptive || m_multiple_walkers || !m_allow_fused || n_modes > MTD_MAX_MODES) lam.clear();
+    // a pure lamellar set takes the fused step (the mailbox form of the step: at most three sums)
+    p.fused_lamellar = n > 0 && lam.size() == n && n <= MTD_METAD_MAX_CV && (!mailbox || n <= 3);
+    // a mixed set: the one-wave chain handles <= 3 variables, and the shared launches sum this rank's particles only (off in a
+    // domain-decomposed run)
+    if (p.fused_lamellar || (!mailbox && n <= 3)) p.lam_slots = std::move(lam);
+    const bool mixed = !p.fused_lamellar && !p.lam_slots.empty();
+    // MTD_MESH_RIDER=0 keeps launch A (stepGeneric)
+    static const bool use_rider = [] { const char *e = std::getenv("MTD_MESH_RIDER"); return !(e && (e[0] == '0' || std::strcmp(e, "off") == 0)); }();
+    p.mesh_rider = mixed && use_rider && p.mesh != nullptr;           // (a mixed set has at most three lamellar variables: n <= 3)
+    // THE condition under which the one mesh carries the engine's launch: setFusedPath allows it, and beside shared lamellar launches
+    // only a mesh that may carry their sums too.  An UMBRELLA on that mesh is NOT excluded, here or in forcesWithBiasUpdate, unlike
+    // every other shared launch — kept as it is, named so that the fix has one line to change.
+    p.mesh_engine = p.mesh != nullptr && m_allow_fused && (!mixed || p.mesh_rider);
+    p.single = n == 1 && !m_multiple_walkers;
+    return p;
     }
 
-// the two-launch step (fused.hip): launch A = CV partial sums (+ deferred grid pass), launch B = grid update + forces
-void IntegratorMetaDynamics::fusedLamellarStep(unsigned int timestep)
+// the lamellar variables `slots` as one set for the launches they share (slot c of the set = variable slots[c])
+void IntegratorMetaDynamics::buildLamellarSet(const std::vector<unsigned int> &slots)
     {
-    const unsigned int n_cv = (unsigned int)m_variables.size();
     std::memset(&m_fused_set, 0, sizeof(m_fused_set));
-    m_fused_set.n_cv = n_cv;
+    m_fused_set.n_cv = (unsigned int)slots.size();
     m_fused_set.n_types = m_pdata->getNTypes();
+    m_fused_force_ptrs.assign(slots.size(), nullptr);
     unsigned int k = 0;
-    m_fused_force_ptrs.assign(n_cv, nullptr);
-    for (unsigned int c = 0; c < n_cv; ++c)
+    for (unsigned int c = 0; c < slots.size(); ++c)
         {
-        auto lam = std::static_pointer_cast<LamellarOrderParameterGPU>(m_variables[c].m_cv);
+        const auto &lam = m_variables[slots[c]].m_lamellar;
         m_fused_set.first[c] = k;
         for (const auto &v : lam->getLatticeVectors())
             {
@@ -1727,10 +1764,15 @@ void IntegratorMetaDynamics::fusedLamellarStep(unsigned int timestep)
         m_fused_force_ptrs[c] = lam->getForceArray().data();
         m_fused_set.trig_mode = std::max(m_fused_set.trig_mode, lam->getTrigMode());     // accurate (2) wins over hardware (1) over default
         }
-    m_fused_set.first[n_cv] = k;
+    m_fused_set.first[slots.size()] = k;
     m_fused_set.n_modes = k;
     if (m_fused_partials.bytes() == 0) m_fused_partials.resize(sizeof(double) * mtd_lamellar_scratch_doubles(m_pdata->getN()));
+    }
 
+// the two-launch step (fused.hip): launch A = CV partial sums (+ deferred grid pass), launch B = grid update + forces
+void IntegratorMetaDynamics::stepFusedLamellar(const StepPlan &plan, unsigned int timestep)
+    {
+    buildLamellarSet(plan.lam_slots);                                  // (every variable of the set)
     const mtd_box box = m_pdata->getGlobalBox().toMtd();
     hipStream_t s = m_exec_conf->getStream();
     // the whole step through one entry point: the two-launch form (CV pass + deferred grid pass, then chain + grid pass +
@@ -1740,57 +1782,7 @@ void IntegratorMetaDynamics::fusedLamellarStep(unsigned int timestep)
               "mtd_fused_step");
     // the step wrote every CV's force array for `timestep`: computeNetForce's cv->compute(timestep) is a no-op
     for (auto &it : m_variables) it.m_cv->markComputed(timestep);
-    m_used_fused = true;
-    }
-
-// A mixed set (e.g. lamellar + mesh): its lamellar CVs (those without an umbrella) are served by the two fused launches of
-// the pure lamellar step — launch A sums all of them in one pass over the positions and carries the deferred grid pass,
-// and the grid-engine launch of the step (the fused force kernel, which mtd_metad_update_bias runs without particles)
-// also carries their force blocks: no k_apply launch, no CV and force kernel per lamellar CV.  `slots`: their indices
-// among the grid's variables.
-std::vector<unsigned int> IntegratorMetaDynamics::mixedLamellarSlots() const
-    {
-    std::vector<unsigned int> slots;
-    if (!m_allow_fused || m_adaptive || m_multiple_walkers || m_variables.size() > 3) return slots;     // the one-wave chain handles <= 3 variables
-    unsigned int n_modes = 0;
-    for (unsigned int i = 0; i < m_variables.size(); ++i)
-        {
-        auto lam = std::dynamic_pointer_cast<LamellarOrderParameterGPU>(m_variables[i].m_cv);
-        if (lam && !lam->hasUmbrella())
-            {
-            slots.push_back(i);
-            n_modes += (unsigned int)lam->getLatticeVectors().size();
-            }
-        }
-    if (n_modes > MTD_MAX_MODES) slots.clear();
-    return slots;
-    }
-
-void IntegratorMetaDynamics::buildMixedLamellarSet(const std::vector<unsigned int> &slots)
-    {
-    std::memset(&m_fused_set, 0, sizeof(m_fused_set));
-    m_fused_set.n_cv = (unsigned int)slots.size();
-    m_fused_set.n_types = m_pdata->getNTypes();
-    m_fused_force_ptrs.assign(slots.size(), nullptr);
-    unsigned int k = 0;
-    for (unsigned int c = 0; c < slots.size(); ++c)
-        {
-        auto lam = std::static_pointer_cast<LamellarOrderParameterGPU>(m_variables[slots[c]].m_cv);
-        m_fused_set.first[c] = k;
-        for (const auto &v : lam->getLatticeVectors())
-            {
-            m_fused_set.hkl[k][0] = v.x;
-            m_fused_set.hkl[k][1] = v.y;
-            m_fused_set.hkl[k][2] = v.z;
-            ++k;
-            }
-        for (unsigned int t = 0; t < m_fused_set.n_types; ++t) m_fused_set.coeff[c][t] = lam->getMode()[t];
-        m_fused_force_ptrs[c] = lam->getForceArray().data();
-        m_fused_set.trig_mode = std::max(m_fused_set.trig_mode, lam->getTrigMode());
-        }
-    m_fused_set.first[slots.size()] = k;
-    m_fused_set.n_modes = k;
-    if (m_fused_partials.bytes() == 0) m_fused_partials.resize(sizeof(double) * mtd_lamellar_scratch_doubles(m_pdata->getN()));
+    m_route = {"fused", "-", "fused_step"};
     }
 
 void IntegratorMetaDynamics::setMixedLamellarSources(const std::vector<unsigned int> &slots, unsigned int n_partials)
@@ -1801,33 +1793,108 @@ void IntegratorMetaDynamics::setMixedLamellarSources(const std::vector<unsigned 
                   "mtd_metad_set_cv_source");
     }
 
-void IntegratorMetaDynamics::mixedLamellarCvPass(const std::vector<unsigned int> &slots, hipStream_t stream)
+// launch A of the fused step for the lamellar variables of a mixed set: their sums in one pass over the positions + the deferred grid pass
+void IntegratorMetaDynamics::mixedLamellarCvPass(const std::vector<unsigned int> &slots)
     {
-    buildMixedLamellarSet(slots);
+    buildLamellarSet(slots);
     const mtd_box box = m_pdata->getGlobalBox().toMtd();
     unsigned int n_partials = 0;
     mtd_check(mtd_fused_cv_pass(m_engine, &m_fused_set, m_pdata->getN(), m_pdata->positionsPtr(), m_pdata->getDtype(), &box,
-                                (double *)m_fused_partials.data(), &n_partials, stream),
+                                (double *)m_fused_partials.data(), &n_partials, m_exec_conf->getStream()),
               "mtd_fused_cv_pass");
     setMixedLamellarSources(slots, n_partials);
     }
 
-void IntegratorMetaDynamics::mixedLamellarForcePass(const std::vector<unsigned int> &slots, unsigned int timestep, hipStream_t stream,
-                                                    const std::shared_ptr<OrderParameterMeshGPU> &mesh, unsigned int mesh_slot)
+// Every set that is not purely lamellar, CV by CV.  The lamellar CVs of a mixed set (e.g. lamellar + mesh; those without an umbrella,
+// plan.lam_slots: their indices among the grid's variables) are served by the two fused launches of the pure lamellar step — launch A
+// sums all of them in one pass over the positions and carries the deferred grid pass, and the grid-engine launch of the step (the fused
+// force kernel, which mtd_metad_update_bias runs without particles) also carries their force blocks: no k_apply launch, no CV and force
+// kernel per lamellar CV.  In a domain-decomposed run each variable reduces its own sums over the ranks inside enqueueCurrentValue
+// (mailbox; the mesh: allreduceLarge or its slab decomposition) and the grid engine then runs on identical values everywhere.
+void IntegratorMetaDynamics::stepGeneric(const StepPlan &plan, unsigned int timestep)
     {
-    // one mesh variable beside the lamellar ones: the engine's launch inside the mesh's force pass (one launch instead of two)
-    if (mesh && stream == m_exec_conf->getStream()
-        && mesh->forcesWithBiasUpdate(timestep, m_engine, mesh_slot, &m_fused_set, slots.data(), m_fused_force_ptrs.data()))
+    const std::vector<unsigned int> &lam = plan.lam_slots;
+    m_route = {"generic", "-", "-"};
+    // 1. The lamellar sums.  One mesh CV beside the lamellar ones (BASELINE.json's config 3): the sums and the deferred grid pass RIDE in the
+    // mesh's assignment launches (mtd_mesh_set_lamellar_rider) instead of taking a launch and a second read of the position array
+    // of their own (launch A of the fused step, 7.9 us at config 3).  In the bin pipeline — every assignment of a mesh but its
+    // first — the sums are formed while the binning blocks wait for their atomics and the grid pass travels as extra blocks of
+    // the scatter launch: 140 -> 133 us per step.  (The first form, the sums inside the counting kernel's per-particle chain,
+    // measured SLOWER than launch A, 161.5 against 159.3 us, profiles/r3/mesh_rider_ab.log; it still carries the first step and
+    // MTD_MESH_RIDER=count.)
+    bool ridden = false;
+    if (plan.mesh_rider)
         {
-        for (unsigned int i : slots) m_variables[i].m_cv->markComputed(timestep);
-        return;
+        buildLamellarSet(lam);
+        unsigned int n_partials = 0;
+        ridden = plan.mesh->armLamellarRider(timestep, m_engine, &m_fused_set, (double *)m_fused_partials.data(), &n_partials);
+        if (ridden) setMixedLamellarSources(lam, n_partials);
         }
-    const mtd_box box = m_pdata->getGlobalBox().toMtd();
-    mtd_check(mtd_fused_force_pass_slots(m_engine, &m_fused_set, slots.data(), m_pdata->getN(), m_pdata->positionsPtr(),
-                                         m_fused_force_ptrs.data(), m_pdata->getDtype(), m_pdata->getNGlobal(), &box, timestep,
-                                         stream),
-              "mtd_fused_force_pass_slots");
-    for (unsigned int i : slots) m_variables[i].m_cv->markComputed(timestep);
+    if (ridden)
+        m_route.sums = "rider";
+    else if (!lam.empty())
+        {
+        mixedLamellarCvPass(lam);
+        m_route.sums = "launch_a";
+        }
+    // 2. The values of the other variables (:321-327) — they stay on the device.  A variable that is alone on the grid may run the
+    // engine's update fused with the tail of its own value (cv.steinhardt)
+    const bool self_updated = plan.single && m_variables[0].m_cv->enqueueValueAndBias(timestep, m_engine);
+    for (unsigned int i = 0; i < m_variables.size() && !self_updated; ++i)
+        if (std::find(lam.begin(), lam.end(), i) == lam.end())
+            m_variables[i].m_cv->enqueueCurrentValue(timestep, m_engine, i);
+    // 3. Nothing consumed the riders (the mesh launched no assignment): the sums are formed by launch A after all
+    if (ridden && plan.mesh->clearRider())
+        {
+        mixedLamellarCvPass(lam);
+        m_route.sums = "rider_then_launch_a";
+        }
+    // 4. The grid engine's launch
+    m_route.engine = enqueueEngine(plan, timestep, self_updated);
+    // update current bias potential derivative for every collective variable (:578-584)
+    const double *d_bias = mtd_metad_bias_device(m_engine);
+    for (unsigned int i = 0; i < m_variables.size(); ++i) m_variables[i].m_cv->setBiasFactorDevice(d_bias + i);
+    }
+
+// updateBiasPotential(timestep) on the device for the values enqueued above, by whoever can carry it; returns who did
+const char *IntegratorMetaDynamics::enqueueEngine(const StepPlan &plan, unsigned int timestep, bool self_updated)
+    {
+    const std::vector<unsigned int> &lam = plan.lam_slots;
+    hipStream_t s = m_exec_conf->getStream();
+    if (lam.empty() && plan.walkers)
+        {
+        // sum up the walkers' increments between the two grid passes (:393-409)
+        // without a communicator this process is the only walker (a run with one partition: test/test_2d.py:29 sets the
+        // flag in a serial run) — said once, so that nobody runs independent walkers believing the bias is shared
+        if (!m_exec_conf->getWalkerCommunicator() && !m_warned_single_walker)
+            {
+            std::cerr << "integrate.mode_metadynamics: multiple_walkers is set but no walker communicator "
+                         "(ExecutionConfiguration::setWalkerCommunicator): running as a single walker." << std::endl;
+            m_warned_single_walker = true;
+            }
+        mtd_check(mtd_metad_update_bias_walkers(m_engine, m_exec_conf->getWalkerCommunicator(), timestep, s), "mtd_metad_update_bias_walkers");
+        return "walkers";
+        }
+    if (lam.empty() && self_updated) return "self";
+    // one mesh variable on the grid (alone, beside lamellar variables that share launches, or beside variables of other kinds): the
+    // engine's launch — with the lamellar variables' force blocks — inside its force pass, one launch instead of two
+    const bool with_lam = !lam.empty();
+    const bool merged = plan.mesh_engine
+                        && plan.mesh->forcesWithBiasUpdate(timestep, m_engine, plan.mesh_slot, with_lam ? &m_fused_set : nullptr,
+                                                           with_lam ? lam.data() : nullptr, with_lam ? m_fused_force_ptrs.data() : nullptr);
+    if (merged)
+        ;
+    else if (with_lam)
+        {
+        const mtd_box box = m_pdata->getGlobalBox().toMtd();
+        mtd_check(mtd_fused_force_pass_slots(m_engine, &m_fused_set, lam.data(), m_pdata->getN(), m_pdata->positionsPtr(),
+                                             m_fused_force_ptrs.data(), m_pdata->getDtype(), m_pdata->getNGlobal(), &box, timestep, s),
+                  "mtd_fused_force_pass_slots");
+        }
+    else   // (also setFusedPath(false): every CV its own kernels and the engine's own launch, as the reference's classes do it)
+        mtd_check(mtd_metad_update_bias(m_engine, timestep, s), "mtd_metad_update_bias");
+    for (unsigned int i : lam) m_variables[i].m_cv->markComputed(timestep);
+    return merged ? "mesh_merged" : (with_lam ? "lamellar_slots" : "own");
     }
 
 // :314-588, grid branch
@@ -1836,8 +1903,9 @@ void IntegratorMetaDynamics::updateBiasPotential(unsigned int timestep)
     ProfRange prof_range("Metadynamics");
     if (m_variables.empty()) return;                                   // :317-318
     hipStream_t s = m_exec_conf->getStream();
+    const StepPlan plan = planStep();
 
-    if (m_adaptive && (timestep % m_stride == 0))                      // :333-341
+    if (plan.adaptive && (timestep % m_stride == 0))                   // :333-341
         {
         // compute derivatives of collective variables, then the instantaneous estimate of the standard deviation matrix
         for (auto &it : m_variables) it.m_cv->computeDerivatives(timestep);
@@ -1845,156 +1913,14 @@ void IntegratorMetaDynamics::updateBiasPotential(unsigned int timestep)
         }
 
     // Domain decomposition (the reference: MPI_Allreduce inside every CV's computeCV, the root rank computes the bias and broadcasts
-    // it, :346-351, :571-575): every rank keeps the replicated grid.  A pure lamellar set takes the fused step, whose two launches
-    // carry the sums through the mailbox themselves; any other set goes CV by CV — each variable reduces its own sums over the
-    // ranks inside enqueueCurrentValue (mailbox; the mesh: allreduceLarge or its slab decomposition) and the grid engine then
-    // runs on identical values everywhere, no broadcast.
-    mtd_comm *const mailbox = m_exec_conf->getMailbox();
-    if (fusedLamellarPossible() && (!mailbox || m_variables.size() <= 3))          // (the mailbox form of the step: at most three sums)
-        {
-        if (mailbox) mtd_check(mtd_metad_set_comm(m_engine, mailbox), "mtd_metad_set_comm");
-        fusedLamellarStep(timestep);
-        }
+    // it, :346-351, :571-575): every rank keeps the replicated grid.  The fused step's two launches carry the sums through the
+    // mailbox themselves; any other set reduces CV by CV (stepGeneric) and the engine needs no mailbox, no broadcast.
+    if (mtd_comm *const mailbox = m_exec_conf->getMailbox())
+        mtd_check(mtd_metad_set_comm(m_engine, plan.fused_lamellar ? mailbox : nullptr), "mtd_metad_set_comm");
+    if (plan.fused_lamellar)
+        stepFusedLamellar(plan, timestep);
     else
-        {
-        if (mailbox) mtd_check(mtd_metad_set_comm(m_engine, nullptr), "mtd_metad_set_comm");
-        m_used_fused = false;
-        // collect values of collective variables (:321-327) — they stay on the device
-        // (the shared launches of a mixed set sum this rank's particles only: off in a domain-decomposed run)
-        const std::vector<unsigned int> lam_slots = mailbox ? std::vector<unsigned int>() : mixedLamellarSlots();
-        // The lamellar CVs' two launches depend on little of what the other CVs do: they go to a SIDE STREAM — launch A (one
-        // pass over the positions + the deferred grid pass) runs beside the other CVs' kernels (the mesh assignment), the
-        // grid-engine launch with the lamellar force blocks waits for the event that says "all CV values are there" and runs
-        // beside what the main stream still has to do for the forces (the mesh's two inverse transforms); the main stream
-        // takes up again after it.  Three events order the streams.  Opt-in (MTD_SIDE_STREAM=1): measured slower, mini_hoomd.h.
-        hipStream_t side = lam_slots.empty() ? nullptr : m_exec_conf->getSideStream();
-        hipStream_t ls = side ? side : s;
-        std::shared_ptr<OrderParameterMeshGPU> hooked;
-        if (side)
-            {
-            hip_check(hipEventRecord(m_exec_conf->getEvent(0), s), "hipEventRecord");              // positions / last step's work
-            hip_check(hipStreamWaitEvent(side, m_exec_conf->getEvent(0), 0), "hipStreamWaitEvent");
-            // exactly one other variable and it is a mesh: its CV sums are complete after the fused z pass, two passes early
-            if (m_variables.size() == lam_slots.size() + 1)
-                for (unsigned int i = 0; i < m_variables.size(); ++i)
-                    if (std::find(lam_slots.begin(), lam_slots.end(), i) == lam_slots.end())
-                        hooked = std::dynamic_pointer_cast<OrderParameterMeshGPU>(m_variables[i].m_cv);
-            if (hooked) hooked->setCvEvent(m_exec_conf->getEvent(1));
-            }
-        // One mesh CV beside the lamellar ones (BASELINE.json's config 3): the lamellar sums and the deferred grid pass RIDE in the
-        // mesh's assignment launches (mtd_mesh_set_lamellar_rider) instead of taking a launch and a second read of the position array
-        // of their own (launch A of the fused step, 7.9 us at config 3).  In the bin pipeline — every assignment of a mesh but its
-        // first — the sums are formed while the binning blocks wait for their atomics and the grid pass travels as extra blocks of
-        // the scatter launch: 140 -> 133 us per step.  (The first form, the sums inside the counting kernel's per-particle chain,
-        // measured SLOWER than launch A, 161.5 against 159.3 us, profiles/r3/mesh_rider_ab.log; it still carries the first step and
-        // MTD_MESH_RIDER=count.)  MTD_MESH_RIDER=0 keeps launch A.
-        std::shared_ptr<OrderParameterMeshGPU> carrier;
-        static const bool use_rider = [] { const char *e = std::getenv("MTD_MESH_RIDER"); return !(e && (e[0] == '0' || std::strcmp(e, "off") == 0)); }();
-        if (!lam_slots.empty() && !side && use_rider && lam_slots.size() <= 3)
-            {
-            unsigned int n_mesh = 0;
-            for (unsigned int i = 0; i < m_variables.size(); ++i)
-                if (std::find(lam_slots.begin(), lam_slots.end(), i) == lam_slots.end())
-                    if (auto mesh = std::dynamic_pointer_cast<OrderParameterMeshGPU>(m_variables[i].m_cv))
-                        {
-                        carrier = mesh;
-                        ++n_mesh;
-                        }
-            if (n_mesh != 1) carrier.reset();
-            }
-        bool ridden = false;
-        if (carrier)
-            {
-            buildMixedLamellarSet(lam_slots);
-            unsigned int n_partials = 0;
-            ridden = carrier->armLamellarRider(timestep, m_engine, &m_fused_set, (double *)m_fused_partials.data(), &n_partials);
-            if (ridden) setMixedLamellarSources(lam_slots, n_partials);
-            }
-        if (!lam_slots.empty() && !ridden) mixedLamellarCvPass(lam_slots, ls);
-        // The grid-engine launch of such a step (chain + grid pass + lamellar forces, 11 us, HBM-bound) needs the CV sums, which
-        // are complete after the mesh's z pass; the inverse x/y transform that follows (17 us, one LDS-filling block per CU,
-        // latency-bound) needs nothing of the engine: the engine's launch can go to a second stream BESIDE the inverse transform.
-        // Two events: "z pass done" (mtd_mesh_set_cv_event) lets the second stream start; "engine done" holds the main stream
-        // before the first kernel that reads the bias factors.
-        // MEASURED SLOWER, opt-in (MTD_MESH_OVERLAP=1): config 3 takes 141.1 / 142.9 / 142.8 us per step with it against 126.7 /
-        // 126.3 / 126.5 on one stream (alternating processes on one box, profiles/r4/mesh_ab.log) — the two cross-queue
-        // dependencies cost more than twice what the overlap of an 11 us launch can return, as round 3's wider form did (mini_hoomd.h).
-        static const bool overlap_on = [] { const char *e = std::getenv("MTD_MESH_OVERLAP"); return e && e[0] == '1'; }();
-        hipStream_t beside = nullptr;
-        if (ridden && !side && overlap_on)
-            {
-            beside = m_exec_conf->getSideStream(true);
-            carrier->setCvEvent(m_exec_conf->getEvent(1));
-            }
-        // a variable that is alone on the grid may run the engine's update fused with the tail of its own value (cv.steinhardt)
-        const bool self_updated = m_variables.size() == 1 && !m_multiple_walkers && m_variables[0].m_cv->enqueueValueAndBias(timestep, m_engine);
-        for (unsigned int i = 0; i < m_variables.size() && !self_updated; ++i)
-            if (std::find(lam_slots.begin(), lam_slots.end(), i) == lam_slots.end())
-                m_variables[i].m_cv->enqueueCurrentValue(timestep, m_engine, i);
-        if (ridden && carrier->clearRider())
-            {
-            mixedLamellarCvPass(lam_slots, ls);                        // (nothing consumed the riders: the sums are formed by launch A after all)
-            if (beside) hip_check(hipEventRecord(m_exec_conf->getEvent(1), s), "hipEventRecord");      // (no z pass ran either)
-            }
-        if (beside)
-            {
-            carrier->setCvEvent(nullptr);
-            hip_check(hipStreamWaitEvent(beside, m_exec_conf->getEvent(1), 0), "hipStreamWaitEvent");
-            ls = beside;
-            }
-        if (side)
-            {
-            if (hooked)
-                hooked->setCvEvent(nullptr);
-            else
-                hip_check(hipEventRecord(m_exec_conf->getEvent(1), s), "hipEventRecord");          // every other CV's value is enqueued
-            hip_check(hipStreamWaitEvent(side, m_exec_conf->getEvent(1), 0), "hipStreamWaitEvent");
-            }
-        if (!lam_slots.empty())
-            {
-            unsigned int carrier_slot = 0;
-            for (unsigned int i = 0; i < m_variables.size(); ++i)
-                if (m_variables[i].m_cv == carrier) carrier_slot = i;
-            mixedLamellarForcePass(lam_slots, timestep, ls, carrier, carrier_slot);
-            if (side || beside)
-                {
-                hip_check(hipEventRecord(m_exec_conf->getEvent(2), ls), "hipEventRecord");         // bias factors, grid arrays, lamellar forces
-                hip_check(hipStreamWaitEvent(s, m_exec_conf->getEvent(2), 0), "hipStreamWaitEvent");
-                }
-            }
-        else if (m_multiple_walkers)
-            {
-            // sum up the walkers' increments between the two grid passes (:393-409)
-            // without a communicator this process is the only walker (a run with one partition: test/test_2d.py:29 sets the
-            // flag in a serial run) — said once, so that nobody runs independent walkers believing the bias is shared
-            if (!m_exec_conf->getWalkerCommunicator() && !m_warned_single_walker)
-                {
-                std::cerr << "integrate.mode_metadynamics: multiple_walkers is set but no walker communicator "
-                             "(ExecutionConfiguration::setWalkerCommunicator): running as a single walker." << std::endl;
-                m_warned_single_walker = true;
-                }
-            mtd_check(mtd_metad_update_bias_walkers(m_engine, m_exec_conf->getWalkerCommunicator(), timestep, s), "mtd_metad_update_bias_walkers");
-            }
-        else if (!self_updated)
-            {
-            // one mesh variable on the grid (alone or beside variables of other kinds): the engine's launch inside its force pass
-            std::shared_ptr<OrderParameterMeshGPU> only_mesh;
-            unsigned int mesh_slot = 0, n_mesh = 0;
-            for (unsigned int i = 0; i < m_variables.size(); ++i)
-                if (auto mesh = std::dynamic_pointer_cast<OrderParameterMeshGPU>(m_variables[i].m_cv))
-                    {
-                    only_mesh = mesh;
-                    mesh_slot = i;
-                    ++n_mesh;
-                    }
-            // (setFusedPath(false): every CV its own kernels and the engine's own launch, as the reference's classes do it)
-            if (!(m_allow_fused && n_mesh == 1 && only_mesh->forcesWithBiasUpdate(timestep, m_engine, mesh_slot, nullptr, nullptr, nullptr)))
-                mtd_check(mtd_metad_update_bias(m_engine, timestep, s), "mtd_metad_update_bias");
-            }
-        // update current bias potential derivative for every collective variable (:578-584)
-        const double *d_bias = mtd_metad_bias_device(m_engine);
-        for (unsigned int i = 0; i < m_variables.size(); ++i) m_variables[i].m_cv->setBiasFactorDevice(d_bias + i);
-        }
+        stepGeneric(plan, timestep);
 
     // write hills information (:523-550) — needs host values, only when a hills file was requested
     if (m_is_initialized && (timestep % m_stride == 0) && m_add_bias && m_file.is_open())
@@ -2023,6 +1949,12 @@ void IntegratorMetaDynamics::updateBiasPotential(unsigned int timestep)
         else
             writeGrid(m_grid_fname1, timestep);
         }
+    }
+
+std::string IntegratorMetaDynamics::lastStepRoute() const
+    {
+    if (!m_route.step[0]) return "";
+    return std::string(m_route.step) + " sums=" + m_route.sums + " engine=" + m_route.engine;
     }
 
 double IntegratorMetaDynamics::getLogValue(const std::string &quantity, unsigned int)
@@ -2142,17 +2074,14 @@ unsigned int IntegratorMetaDynamics::graphPeriod() const
     {
     if (!m_is_initialized || !m_use_grid || !m_engine || m_variables.empty()) return 0;
     if (m_adaptive || m_multiple_walkers || m_file.is_open() || m_grid_period) return 0;
-    if (m_exec_conf->getMailbox() || m_exec_conf->getSideStream()) return 0;
-    if (fusedLamellarPossible()) return 0;                             // two launches per step: measured slower from a graph
+    if (m_exec_conf->getMailbox()) return 0;
+    if (planStep().fused_lamellar) return 0;                            // two launches per step: measured slower from a graph
     if (m_pdata->getPressureFlag()) return 0;                          // (the mesh CV's virial is read back on the host)
     for (const auto &it : m_variables)
         {
         if (it.m_cv->hasUmbrella()) return 0;                           // the umbrella adds to a HOST bias factor every step
-        const bool known = std::dynamic_pointer_cast<LamellarOrderParameterGPU>(it.m_cv) || std::dynamic_pointer_cast<OrderParameterMeshGPU>(it.m_cv)
-                           || std::dynamic_pointer_cast<SteinhardtQl>(it.m_cv);
-        if (!known) return 0;
-        if (auto st = std::dynamic_pointer_cast<SteinhardtQl>(it.m_cv))
-            if (!st->graphSafe()) return 0;
+        if (!it.m_lamellar && !it.m_mesh && !it.m_steinhardt) return 0;
+        if (it.m_steinhardt && !it.m_steinhardt->graphSafe()) return 0;
         }
     for (const auto &f : m_forces)                                     // every compute of the step is one of the variables
         {

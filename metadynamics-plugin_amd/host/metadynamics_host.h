@@ -202,8 +202,6 @@ class OrderParameterMeshGPU : public CollectiveVariable
         //! rank keeps the whole mesh and the ranks sum their assignments (M + 1 doubles per step, :630).  Before the first step.
         void setSlabDecomposition(bool on);
         bool getSlabDecomposition() const { return m_slab; }
-        //! event recorded when the CV partial sums of the next compute are complete (mtd_mesh_set_cv_event); nullptr clears
-        void setCvEvent(hipEvent_t e) { mtd_mesh_set_cv_event(m_mesh, (void *)e); }
         //! the lamellar CVs of a mixed set (and the engine's deferred grid pass) ride in this mesh's next particle pass
         //! (mtd_mesh_set_lamellar_rider); false when the mesh cannot carry them or is already up to date for `timestep`
         bool armLamellarRider(unsigned int timestep, mtd_metad *engine, const mtd_lamellar_set *set, double *d_partials,
@@ -573,7 +571,11 @@ class IntegratorMetaDynamics
         //! and pure lamellar sets, whose two-launch step measures SLOWER from a graph (profiles/r4/graph_ab.log).
         unsigned int graphPeriod() const;
         void setFusedPath(bool enable) { m_allow_fused = enable; }     // default on: two launches per step for lamellar CVs
-        bool usedFusedPath() const { return m_used_fused; }
+        bool usedFusedPath() const { return std::strcmp(m_route.step, "fused") == 0; }
+        //! What the most recent step did, written by the step's functions as they ran: "<step> sums=<sums> engine=<engine>" with
+        //! step fused | generic; sums (the lamellar sums of a mixed set) - | launch_a | rider | rider_then_launch_a; engine (who
+        //! enqueued the grid engine's launch) fused_step | lamellar_slots | mesh_merged | walkers | self | own.  Empty before the first step.
+        std::string lastStepRoute() const;
         mtd_metad *getEngine() { return m_engine; }
         //! CV values and dV/ds_c of the most recent bias update (synchronises)
         std::vector<double> getCurrentValues();
@@ -585,6 +587,24 @@ class IntegratorMetaDynamics
             std::shared_ptr<CollectiveVariable> m_cv;
             double m_sigma, m_cv_min, m_cv_max;
             unsigned int m_num_points;
+            // the variable's kind, cast once at registration: at most one is set, none for every other kind
+            std::shared_ptr<LamellarOrderParameterGPU> m_lamellar;
+            std::shared_ptr<OrderParameterMeshGPU> m_mesh;
+            std::shared_ptr<SteinhardtQl> m_steinhardt;
+            //! a lamellar variable that may take the launches lamellar variables share (an umbrella adds to a HOST bias factor)
+            bool sharesLamellarLaunches() const { return m_lamellar && !m_lamellar->hasUmbrella(); }
+            };
+        //! What one step of the variable set does, decided once per step (planStep); the functions of the step only read it
+        struct StepPlan
+            {
+            bool fused_lamellar = false;             //!< the pure lamellar step (stepFusedLamellar), else stepGeneric
+            std::vector<unsigned int> lam_slots;     //!< the lamellar variables that share launches: all of a pure set, those of a mixed set
+            std::shared_ptr<OrderParameterMeshGPU> mesh;   //!< the mesh variable if the set has exactly one, and its slot
+            unsigned int mesh_slot = 0;
+            bool mesh_rider = false;                 //!< that mesh may carry the lamellar sums in its assignment (armLamellarRider)
+            bool mesh_engine = false;                //!< that mesh may carry the engine's launch in its force pass (forcesWithBiasUpdate)
+            bool single = false;                     //!< one variable, which may update the engine itself (enqueueValueAndBias)
+            bool walkers = false, adaptive = false;
             };
 
         void updateBiasPotential(unsigned int timestep);               // :314-588
@@ -594,14 +614,13 @@ class IntegratorMetaDynamics
         void setupGrid();                                              // :590-661 (device side: mtd_metad_create)
         void readGrid(const std::string &filename);                    // :928-1000
         void writeGrid(const std::string &filename, unsigned int timestep);   // :831-926
-        bool fusedLamellarPossible() const;
-        void fusedLamellarStep(unsigned int timestep);
-        std::vector<unsigned int> mixedLamellarSlots() const;
-        void buildMixedLamellarSet(const std::vector<unsigned int> &slots);
+        StepPlan planStep() const;
+        void stepFusedLamellar(const StepPlan &plan, unsigned int timestep);
+        void stepGeneric(const StepPlan &plan, unsigned int timestep);
+        const char *enqueueEngine(const StepPlan &plan, unsigned int timestep, bool self_updated);
+        void buildLamellarSet(const std::vector<unsigned int> &slots);
         void setMixedLamellarSources(const std::vector<unsigned int> &slots, unsigned int n_partials);
-        void mixedLamellarCvPass(const std::vector<unsigned int> &slots, hipStream_t stream);
-        void mixedLamellarForcePass(const std::vector<unsigned int> &slots, unsigned int timestep, hipStream_t stream,
-                                    const std::shared_ptr<OrderParameterMeshGPU> &mesh = nullptr, unsigned int mesh_slot = 0);
+        void mixedLamellarCvPass(const std::vector<unsigned int> &slots);
 
         std::shared_ptr<SystemDefinition> m_sysdef;
         std::shared_ptr<ParticleData> m_pdata;
@@ -629,10 +648,10 @@ class IntegratorMetaDynamics
         bool m_multiple_walkers, m_warned_single_walker;
 
         mtd_metad *m_engine;
-        bool m_allow_fused, m_used_fused;
+        bool m_allow_fused;
+        struct { const char *step, *sums, *engine; } m_route = {"", "-", "-"};
         mtd_lamellar_set m_fused_set;
         DeviceBuffer m_fused_partials;
-        unsigned int m_fused_n_partials;
         std::vector<void *> m_fused_force_ptrs;
     };
 

@@ -126,11 +126,6 @@ class ExecutionConfiguration
             int n = mtd_device_count();
             if (n <= 0) throw std::runtime_error("metadynamics: no HIP device (this build has no CPU path)");
             }
-        ~ExecutionConfiguration()
-            {
-            for (hipEvent_t e : m_events) if (e) (void)hipEventDestroy(e);
-            if (m_side) (void)hipStreamDestroy(m_side);
-            }
         ExecutionConfiguration(const ExecutionConfiguration &) = delete;
         ExecutionConfiguration &operator=(const ExecutionConfiguration &) = delete;
         bool isCUDAEnabled() const { return true; }   // name kept from the reference (cv.py:260)
@@ -138,25 +133,10 @@ class ExecutionConfiguration
         //! every launch of the host classes goes to this stream from now on (default: the null stream, like the reference's
         //! drivers).  A caller that captures steps into a hipGraph needs a stream of its own: the null stream cannot be captured.
         void setStream(uintptr_t stream) { m_stream = reinterpret_cast<hipStream_t>(stream); }
-        //! A second stream for launches that depend on little of what the main stream is doing (mixed CV sets: the lamellar
-        //! CV pass beside the mesh assignment, the grid-engine launch beside the mesh's inverse transforms), ordered against
-        //! the main stream by the three events below.  OFF unless MTD_SIDE_STREAM=1: measured at config 3 (10^6 particles,
-        //! 128^3 mesh + one lamellar CV) the step takes 187.9 us with it against 180.6 us on one stream — the kernels it lets
-        //! run side by side are all memory-bound, and three cross-stream events cost more than the overlap returns.
-        //! (unconditional = true: the stream itself, whatever the switch says — the integrator's narrower use of it, one launch
-        //! beside the mesh's inverse transform, is decided there)
-        hipStream_t getSideStream(bool unconditional = false)
-            {
-            static const bool on = [] { const char *e = std::getenv("MTD_SIDE_STREAM"); return e && e[0] == '1'; }();
-            if (!on && !unconditional) return nullptr;
-            if (!m_side)
-                {
-                hip_check(hipStreamCreateWithFlags(&m_side, hipStreamNonBlocking), "hipStreamCreateWithFlags");
-                for (hipEvent_t &e : m_events) hip_check(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreateWithFlags");
-                }
-            return m_side;
-            }
-        hipEvent_t getEvent(unsigned int i) const { return m_events[i]; }
+        //! (The host classes leave this stream nowhere.  A second stream for the lamellar launches of a mixed set, ordered by three
+        //! events, was tried and removed: at config 3 — 10^6 particles, 128^3 mesh + one lamellar CV — the step took 187.9 us with
+        //! it against 180.6 us on one stream: the kernels it let run side by side are all memory-bound, and the cross-stream events
+        //! cost more than the overlap returned.  DESIGN_HISTORY.md §4.4.)
         void sync() const { hip_check(hipStreamSynchronize(m_stream), "hipStreamSynchronize"); }
 
         //! Domain decomposition: the role of HOOMD's MPI communicator (ExecutionConfiguration::getMPICommunicator) for this
@@ -240,8 +220,6 @@ class ExecutionConfiguration
 
     private:
         hipStream_t m_stream;
-        hipStream_t m_side = nullptr;
-        hipEvent_t m_events[3] = {nullptr, nullptr, nullptr};
         mtd_comm *m_comm = nullptr;
         mtd_rccl *m_walkers = nullptr;
         mtd_rccl *m_large = nullptr;

@@ -458,6 +458,7 @@ PYBIND11_MODULE(_metadynamics, m)
         // this build
         .def("setFusedPath", &IntegratorMetaDynamics::setFusedPath)
         .def("usedFusedPath", &IntegratorMetaDynamics::usedFusedPath)
+        .def("lastStepRoute", &IntegratorMetaDynamics::lastStepRoute)
         .def("graphPeriod", &IntegratorMetaDynamics::graphPeriod)
         .def("getCurrentValues", &IntegratorMetaDynamics::getCurrentValues)
         .def("getBiasFactors", &IntegratorMetaDynamics::getBiasFactors)

@@ -485,7 +485,7 @@ def _check_host_run(ref, out, o, kinds, tmp_path, tag):
 
 
 def test_four_lamellar_cvs_through_the_host_classes(api, ref, tmp_path):
-    """four cv.lamellar on one grid: fusedLamellarPossible() admits them (up to 6), the step is k_fused_cv<..., 4, ...> +
+    """four cv.lamellar on one grid: planStep() takes the fused step for them (up to 6), the step is k_fused_cv<..., 4, ...> +
     k_fused_force_general; the same run with setFusedPath(False) (every CV its own kernels, the four-launch grid sequence) leaves the same
     grid; CV values, bias factors, the dumped grid and the forces of the last step against the oracle's 4-variable engine"""
     kinds = ["lam"] * 4
@@ -499,7 +499,7 @@ def test_four_lamellar_cvs_through_the_host_classes(api, ref, tmp_path):
 
 
 def test_three_lamellar_cvs_and_a_density_through_the_host_classes(api, ref, tmp_path):
-    """a mixed 4-variable set: mixedLamellarSlots() serves at most three variables, so every CV runs its own kernels and the grid the
+    """a mixed 4-variable set: planStep() shares lamellar launches in sets of at most three variables, so every CV runs its own kernels and the grid the
     four-launch sequence — against the oracle driven with the device's CV values"""
     kinds = ["lam", "density", "lam", "lam"]
     out, o = _host_run(api, ref, tmp_path, kinds, None, "mixed")
