@@ -1041,6 +1041,99 @@ int mtd_pel_forces(const mtd_pel_params *p, const mtd_pel_call *c, void *d_force
                    void *d_virial, unsigned int virial_pitch);
 
 /* ================================================================================================
+ * Debye structure factor (cv.debye_structure_factor) — no reference counterpart.  The intensity of diffraction peaks from the Debye
+ * scattering function (Niu, Piaggi, Invernizzi and Parrinello, PNAS 115, 5348 (2018)): a bias variable for crystallisation that needs
+ * only wave numbers Q read off a diffraction pattern, invariant under rotation and translation; peaks with weights of opposite sign
+ * select one polymorph against another.  The conventions of "Pair entropy" above hold wherever nothing else is said.
+ * Parameters: a particle type t, a cut-off r_cut > 0, P = n_q wave numbers Q_p > 0 (1 <= P <= MTD_DSF_MAX_Q), weights c_p (finite,
+ * any sign).  Entries (i, j) of a FULL list take part when both particles are of type t, j != i and r = |d| <= r_cut,
+ * d = minImage(r_i - r_j).  The central particles are the n_particles local ones; entries may address the n_ghost particles stored
+ * behind them.
+ *     x = pi r / r_cut,  w(r) = sin x / x              (the window of the literature; w(r_cut) = 0)
+ *     y_p = Q_p r,       phi_p = w(r) sin y_p / y_p
+ *     w'(r)  = (pi / r_cut) (x cos x - sin x) / x^2
+ *     phi_p' = w' sin y_p / y_p + w Q_p (y_p cos y_p - sin y_p) / y_p^2
+ *     A_p = sum_entries phi_p(r_ij)                     N_t = central particles of type t (slot P of the sums: the all-reduce makes
+ *                                                       both global)
+ *     I_p = 1 + A_p / N_t,  s = sum_p c_p I_p           (N_t == 0: s = 0, I_p = 0, no forces)
+ *     s_i = sum_p c_p (1 + sum_{j in row i} phi_p(r_ij)) for type t, else 0;  s = (1 / N_t) sum_i s_i
+ * An entry with r = 0 exactly counts with phi_p = 1 and u = 0.
+ * Gradient: u_kj = sum_p c_p phi_p'(r_kj), ds/dr_k = (2 / N_t) sum_{j in row k} u_kj d_kj / r_kj (the mirror entry gives the same amount
+ * whether j is local or a ghost: no reaction force on ghosts), F = -bias ds/dr.
+ * Virial (only with a virial pointer): virial_k[ab] = -(bias / N_t) sum_{j in row k} u_kj d_a d_b / r_kj, symmetric, half of every pair at
+ * each end; no explicit volume term, because the normalisation is N_t and not a density.  sum_k virial_k = -bias ds/d eps.  Layout,
+ * scalar type and pitch rule of mtd_pe_forces.
+ * THE FORCE IS DISCONTINUOUS AT r_cut: w is the published window, w(r_cut) = 0 but w'(r_cut) = -1 / r_cut, so an entry that crosses the
+ * cut-off changes ds/dr by sinc(Q_p r_cut) / r_cut per peak, divided by N_t (with the factor 2 of the mirror entry).  The window is
+ * kept as published.
+ * Spectrum (a diagnostic, not biased): I(Q_m) = 1 + (1 / N_t) sum_entries w(r) sin(Q_m r) / (Q_m r) on
+ * Q_m = q_min + m (q_max - q_min) / (n_q - 1), m = 0 .. n_q - 1 (n_q == 1: Q_0 = q_min); 1 <= n_q <= MTD_DSF_MAX_SPECTRUM,
+ * 0 < q_min <= q_max.
+ * A step is _accumulate, (mtd_comm_allreduce_small of *d_sums in a domain-decomposed run), _finalize, _forces with the same parameters,
+ * call block and scratch.  By default the first pass also stores every particle's unscaled gradient and virial sums, and _forces only
+ * scales them by bias / N_t (mtd_dsf_set_store_gradient).  Every sum has a fixed order and there are no atomics: two identical calls
+ * give identical bits.  Arguments are checked before a device is touched: MTD_ERR_INVALID_ARGUMENT for null pointers, a non-finite or
+ * non-positive r_cut or Q, a non-finite weight, n_q == 0, an unknown dtype, a d_scratch that is not 16-byte aligned, a virial pitch
+ * below n_particles, q_min > q_max; MTD_ERR_UNSUPPORTED for n_q above the two capacities.
+ * ============================================================================================== */
+
+#define MTD_DSF_MAX_Q 8
+#define MTD_DSF_MAX_SPECTRUM 256
+
+typedef struct
+    {
+    unsigned int type;
+    double r_cut;
+    unsigned int n_q;                      /* P */
+    double q[MTD_DSF_MAX_Q], c[MTD_DSF_MAX_Q];
+    } mtd_dsf_params;
+
+/* what the calls of a step share beside the parameters: particles, box, list, scratch and the stream the launches go to */
+typedef struct
+    {
+    unsigned int n_particles, n_ghost;     /* d_postype holds n_particles + n_ghost entries */
+    const void *d_postype;
+    int dtype;
+    const mtd_box *box;
+    const unsigned int *d_head_list, *d_n_neigh, *d_nlist;
+    double *d_scratch;
+    mtd_stream_t stream;
+    } mtd_dsf_call;
+
+/* device doubles the calls share: sums, value, intensities, spectrum, block sums and ten per-particle arrays */
+size_t mtd_dsf_scratch_doubles(unsigned int n_particles);
+
+/* 1 (default): mtd_dsf_accumulate stores the unscaled gradient and the six virial sums of every particle, mtd_dsf_forces scales them;
+ * 0: mtd_dsf_forces walks the rows a second time.  Process-wide, read by both calls: change it between steps, not inside one.
+ * profiles/r24/README.md has the timings of both. */
+int mtd_dsf_set_store_gradient(int enable);
+
+/* This rank's sums: on return *d_sums points at *n_sums = P + 1 doubles inside c->d_scratch, A_0 .. A_{P-1} and N_t, ready for
+ * mtd_comm_allreduce_small. */
+int mtd_dsf_accumulate(const mtd_dsf_params *p, const mtd_dsf_call *c, double **d_sums, unsigned int *n_sums);
+
+/* The (reduced) sums -> s and I_p.  *d_value points at s, one device double (consume with
+ * mtd_metad_set_cv_source(engine, slot, *d_value, 1, 1, 0, 1.0, 0.0)), *d_intensity at I_p[P], *d_local (may be NULL) at
+ * s_i[n_particles] of the last mtd_dsf_accumulate, all inside c->d_scratch. */
+int mtd_dsf_finalize(const mtd_dsf_params *p, const mtd_dsf_call *c, const double **d_value, const double **d_intensity,
+                     const double **d_local);
+
+/* Writes d_force[0..n_particles) (w component 0; 0 for particles of another type) with what the last mtd_dsf_accumulate and
+ * mtd_dsf_finalize (same p and c) left in c->d_scratch; bias = *d_bias when d_bias != NULL, else bias_host.  d_virial == NULL: no
+ * virial; the force array is the same, bit for bit, either way.  Every row [0, n_particles) of the virial is written,
+ * [n_particles, virial_pitch) is left alone.  n_particles == 0 is success. */
+int mtd_dsf_forces(const mtd_dsf_params *p, const mtd_dsf_call *c, void *d_force, const double *d_bias, double bias_host, void *d_virial,
+                   unsigned int virial_pitch);
+
+/* The spectrum of the configuration in c (p gives type and r_cut; its peaks are not read).  _spectrum leaves this rank's sums, n_q + 1
+ * doubles (T_m = sum_entries w(r) sin(Q_m r) / r and N_t), at *d_sums inside c->d_scratch, ready for mtd_comm_allreduce_small;
+ * _spectrum_finalize turns the (reduced) sums into I(Q_m)[n_q] at *d_spectrum.  They use their own part of the scratch: a step's
+ * results stay valid. */
+int mtd_dsf_spectrum(const mtd_dsf_params *p, const mtd_dsf_call *c, double q_min, double q_max, unsigned int n_q, double **d_sums,
+                     unsigned int *n_sums);
+int mtd_dsf_spectrum_finalize(const mtd_dsf_call *c, double q_min, double q_max, unsigned int n_q, const double **d_spectrum);
+
+/* ================================================================================================
  * Neighbour list of the stand-alone path (cell list, built on the device)
  * no reference counterpart: HOOMD's md::NeighborList is HOOMD core.  Produces the three arrays SteinhardtQl.cc:80-85 reads, in
  * HOOMD's layout: the neighbours of particle i are d_nlist[d_head_list[i] .. d_head_list[i] + d_n_neigh[i]).

@@ -1379,6 +1379,124 @@ std::vector<double> PairEntropyLocal::getSwitchedValues(unsigned int timestep)
     }
 
 // ------------------------------------------------------------------------------------------------
+// DebyeStructureFactor
+// ------------------------------------------------------------------------------------------------
+
+DebyeStructureFactor::DebyeStructureFactor(std::shared_ptr<SystemDefinition> sysdef, const std::vector<double> &q, const std::vector<double> &weights,
+                                           double r_cut, std::shared_ptr<NeighborList> nlist, unsigned int type, const std::string &log_suffix)
+    : NeighbourVariable(sysdef, "debye_structure_factor", log_suffix, nlist, type), m_par(), m_d_value(nullptr), m_d_intensity(nullptr),
+      m_d_local(nullptr)
+    {
+    if (!nlist) throw std::runtime_error("cv.debye_structure_factor: a neighbour list is required");
+    if (!(r_cut > 0.0) || !std::isfinite(r_cut)) throw std::runtime_error("cv.debye_structure_factor: r_cut > 0 is required");
+    if (q.empty() || q.size() > MTD_DSF_MAX_Q) throw std::runtime_error("cv.debye_structure_factor: 1 to 8 wave numbers in this build");
+    if (weights.size() != q.size()) throw std::runtime_error("cv.debye_structure_factor: one weight per wave number is required");
+    for (size_t k = 0; k < q.size(); ++k)
+        {
+        if (!(q[k] > 0.0) || !std::isfinite(q[k]) || !std::isfinite(weights[k]))
+            throw std::runtime_error("cv.debye_structure_factor: wave numbers > 0 and finite weights are required");
+        m_par.q[k] = q[k];
+        m_par.c[k] = weights[k];
+        }
+    m_par.type = type;
+    m_par.r_cut = r_cut;
+    m_par.n_q = (unsigned int)q.size();
+    m_scratch.resize(sizeof(double) * mtd_dsf_scratch_doubles(m_pdata->getN()));
+    }
+
+mtd_dsf_call DebyeStructureFactor::call(const mtd_box *box)
+    {
+    const size_t need = sizeof(double) * mtd_dsf_scratch_doubles(m_pdata->getN());
+    if (need > m_scratch.bytes())                                    // (more particles than at the last call: nothing in the scratch is this step's)
+        {
+        m_scratch.resize(need);
+        invalidate();
+        }
+    const Lists l = lists();
+    mtd_dsf_call c;
+    c.n_particles = m_pdata->getN();
+    c.n_ghost = m_pdata->getNGhosts();
+    c.d_postype = m_pdata->positionsPtr();
+    c.dtype = m_pdata->getDtype();
+    c.box = box;
+    c.d_head_list = l.head;
+    c.d_n_neigh = l.n_neigh;
+    c.d_nlist = l.nlist;
+    c.d_scratch = (double *)m_scratch.data();
+    c.stream = m_exec_conf->getStream();
+    return c;
+    }
+
+void DebyeStructureFactor::computeCV(unsigned int timestep)
+    {
+    ProfRange prof_range("CV");
+    if (fresh(timestep)) return;
+    requireFullList();
+    requireReach(getRCut(), "r_cut");
+    m_nlist->compute(timestep);
+    const mtd_box box = m_pdata->getBox().toMtd();
+    const mtd_dsf_call c = call(&box);
+    double *d_sums = nullptr;
+    unsigned int n_sums = 0;
+    mtd_check(mtd_dsf_accumulate(&m_par, &c, &d_sums, &n_sums), "mtd_dsf_accumulate");
+    // A_p and N_t over the ranks: the central particles of a rank are its local ones, their neighbours may be ghosts
+    if (distributed()) m_exec_conf->allreduceSmall(d_sums, n_sums, m_exec_conf->getStream());
+    mtd_check(mtd_dsf_finalize(&m_par, &c, &m_d_value, &m_d_intensity, &m_d_local), "mtd_dsf_finalize");
+    computed(timestep);
+    }
+
+void DebyeStructureFactor::enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot)
+    {
+    computeCV(timestep);
+    mtd_check(mtd_metad_set_cv_source(engine, slot, m_d_value, 1, 1, 0, 1.0, 0.0), "mtd_metad_set_cv_source");
+    }
+
+double DebyeStructureFactor::getCurrentValue(unsigned int timestep)
+    {
+    computeCV(timestep);
+    return readValue(m_d_value, timestep);
+    }
+
+std::vector<double> DebyeStructureFactor::getIntensities(unsigned int timestep)
+    {
+    computeCV(timestep);
+    return readBack(m_d_intensity, m_par.n_q, "I_p read-back", timestep);
+    }
+
+std::vector<double> DebyeStructureFactor::getLocalValues(unsigned int timestep)
+    {
+    computeCV(timestep);
+    return readBack(m_d_local, m_pdata->getN(), "s_i read-back", timestep);
+    }
+
+std::vector<double> DebyeStructureFactor::getSpectrum(unsigned int timestep, double q_min, double q_max, unsigned int n_q)
+    {
+    if (!(q_min > 0.0) || !std::isfinite(q_min) || !std::isfinite(q_max) || q_min > q_max || n_q == 0 || n_q > MTD_DSF_MAX_SPECTRUM)
+        throw std::runtime_error("cv.debye_structure_factor: a spectrum needs 0 < q_min <= q_max and 1 <= n_q <= 256");
+    computeCV(timestep);                                             // the checks of the list, and the list itself
+    const mtd_box box = m_pdata->getBox().toMtd();
+    const mtd_dsf_call c = call(&box);
+    double *d_sums = nullptr;
+    unsigned int n_sums = 0;
+    mtd_check(mtd_dsf_spectrum(&m_par, &c, q_min, q_max, n_q, &d_sums, &n_sums), "mtd_dsf_spectrum");
+    if (distributed()) m_exec_conf->allreduceSmall(d_sums, n_sums, m_exec_conf->getStream());
+    const double *d_spectrum = nullptr;
+    mtd_check(mtd_dsf_spectrum_finalize(&c, q_min, q_max, n_q, &d_spectrum), "mtd_dsf_spectrum_finalize");
+    return readBack(d_spectrum, n_q, "spectrum read-back", timestep);
+    }
+
+void DebyeStructureFactor::computeBiasForces(unsigned int timestep)
+    {
+    ProfRange prof_range("Force");
+    if (!fresh(timestep)) computeCV(timestep);                       // the sums of THIS step's positions
+    m_nlist->compute(timestep);
+    const mtd_box box = m_pdata->getBox().toMtd();
+    const mtd_dsf_call c = call(&box);
+    void *virial = virialTarget();                                   // constant pressure: the per-particle virial of the bias force beside it
+    mtd_check(mtd_dsf_forces(&m_par, &c, m_force.data(), m_bias_device, m_bias, virial, getVirialPitch()), "mtd_dsf_forces");
+    }
+
+// ------------------------------------------------------------------------------------------------
 // AspectRatio, Density
 // ------------------------------------------------------------------------------------------------
 

@@ -494,6 +494,31 @@ class PairEntropyLocal : public NeighbourVariable
         unsigned int m_n_partials;
     };
 
+//! Debye structure factor (no reference counterpart; include/mtd_abi.h "Debye structure factor"): the weighted intensities of diffraction
+//! peaks at given wave numbers from the Debye scattering function of one particle type.  Works domain-decomposed: the only exchange is
+//! one allreduceSmall of the P + 1 sums (and of the n_q + 1 sums of a spectrum).
+class DebyeStructureFactor : public NeighbourVariable
+    {
+    public:
+        DebyeStructureFactor(std::shared_ptr<SystemDefinition> sysdef, const std::vector<double> &q, const std::vector<double> &weights,
+                             double r_cut, std::shared_ptr<NeighborList> nlist, unsigned int type, const std::string &log_suffix = "");
+        double getCurrentValue(unsigned int timestep) override;
+        //! device-resident: the value in the scratch becomes the engine's source of this variable, no host synchronisation
+        void enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot) override;
+        void computeBiasForces(unsigned int timestep) override;
+        std::vector<double> getIntensities(unsigned int timestep);     //!< I_p of the P peaks
+        std::vector<double> getLocalValues(unsigned int timestep);     //!< s_i of every local particle (0 for other types)
+        //! I(Q_m) on n_q equally spaced wave numbers q_min .. q_max: a diagnostic, all-reduced in a distributed run, not biased
+        std::vector<double> getSpectrum(unsigned int timestep, double q_min, double q_max, unsigned int n_q);
+        double getRCut() const { return m_par.r_cut; }                 //!< what the neighbour list must reach
+
+    private:
+        void computeCV(unsigned int timestep) override;
+        mtd_dsf_call call(const mtd_box *box);
+        mtd_dsf_params m_par;
+        const double *m_d_value, *m_d_intensity, *m_d_local;
+    };
+
 //! AspectRatio.h / AspectRatio.cc:5-130 — box-shape CV, external virial only
 class AspectRatio : public CollectiveVariable
     {

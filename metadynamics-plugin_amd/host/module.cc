@@ -419,6 +419,24 @@ PYBIND11_MODULE(_metadynamics, m)
             return py::array_t<double>((ssize_t)v.size(), v.data());
         });
 
+    // no reference counterpart: the intensities of diffraction peaks from the Debye scattering function
+    py::class_<DebyeStructureFactor, CollectiveVariable, std::shared_ptr<DebyeStructureFactor>>(m, "DebyeStructureFactor")
+        .def(py::init<std::shared_ptr<SystemDefinition>, const std::vector<double> &, const std::vector<double> &, double,
+                      std::shared_ptr<NeighborList>, unsigned int, const std::string &>())
+        .def("getRCut", &DebyeStructureFactor::getRCut)
+        .def("getIntensities", [](DebyeStructureFactor &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getIntensities(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        })
+        .def("getLocalValues", [](DebyeStructureFactor &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getLocalValues(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        })
+        .def("getSpectrum", [](DebyeStructureFactor &cv, unsigned int timestep, double q_min, double q_max, unsigned int n_q) {
+            const std::vector<double> v = cv.getSpectrum(timestep, q_min, q_max, n_q);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        });
+
     py::class_<WellTemperedEnsemble, CollectiveVariable, std::shared_ptr<WellTemperedEnsemble>>(m, "WellTemperedEnsemble")
         .def(py::init<std::shared_ptr<SystemDefinition>, const std::string &>());
 

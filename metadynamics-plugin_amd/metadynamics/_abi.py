@@ -184,6 +184,35 @@ class PelCall(C.Structure):
                 ("stream", C.c_void_p)]
 
 
+MTD_DSF_MAX_Q = 8
+MTD_DSF_MAX_SPECTRUM = 256
+
+
+class DsfParams(C.Structure):
+    """mtd_dsf_params: the particle type, the cut-off, the wave numbers of the peaks and their weights"""
+    _fields_ = [("type", C.c_uint), ("r_cut", C.c_double), ("n_q", C.c_uint), ("q", C.c_double * MTD_DSF_MAX_Q),
+                ("c", C.c_double * MTD_DSF_MAX_Q)]
+
+    @classmethod
+    def make(cls, type_id, r_cut, q, c=None, n_q=None):
+        """q, c: up to MTD_DSF_MAX_Q numbers each (weights default to 1); n_q overrides the count (to hand over a refused one).
+        Nothing is checked here: the entry points refuse what they do not take"""
+        o = cls()
+        q = [float(v) for v in q]
+        c = [1.0] * len(q) if c is None else [float(v) for v in c]
+        o.type, o.r_cut, o.n_q = int(type_id), float(r_cut), len(q) if n_q is None else int(n_q)
+        for k in range(min(len(q), MTD_DSF_MAX_Q)):
+            o.q[k], o.c[k] = q[k], c[k]
+        return o
+
+
+class DsfCall(C.Structure):
+    """mtd_dsf_call: particles, ghosts, box, list, scratch and stream of one step"""
+    _fields_ = [("n_particles", C.c_uint), ("n_ghost", C.c_uint), ("d_postype", C.c_void_p), ("dtype", C.c_int), ("box", C.POINTER(Box)),
+                ("d_head_list", C.c_void_p), ("d_n_neigh", C.c_void_p), ("d_nlist", C.c_void_p), ("d_scratch", C.c_void_p),
+                ("stream", C.c_void_p)]
+
+
 _vp = C.c_void_p
 _dp = C.POINTER(C.c_double)
 _up = C.POINTER(C.c_uint)
@@ -344,6 +373,13 @@ _SIGNATURES = {
     "mtd_pel_scratch_doubles": (C.c_size_t, [C.c_uint, C.c_uint]),
     "mtd_pel_accumulate": (C.c_int, [C.POINTER(PelParams), C.POINTER(PelCall), C.POINTER(_vp), _up, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "mtd_pel_forces": (C.c_int, [C.POINTER(PelParams), C.POINTER(PelCall), _vp, _vp, C.c_double, _vp, C.c_uint]),
+    "mtd_dsf_scratch_doubles": (C.c_size_t, [C.c_uint]),
+    "mtd_dsf_set_store_gradient": (C.c_int, [C.c_int]),
+    "mtd_dsf_accumulate": (C.c_int, [C.POINTER(DsfParams), C.POINTER(DsfCall), C.POINTER(_vp), _up]),
+    "mtd_dsf_finalize": (C.c_int, [C.POINTER(DsfParams), C.POINTER(DsfCall), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "mtd_dsf_forces": (C.c_int, [C.POINTER(DsfParams), C.POINTER(DsfCall), _vp, _vp, C.c_double, _vp, C.c_uint]),
+    "mtd_dsf_spectrum": (C.c_int, [C.POINTER(DsfParams), C.POINTER(DsfCall), C.c_double, C.c_double, C.c_uint, C.POINTER(_vp), _up]),
+    "mtd_dsf_spectrum_finalize": (C.c_int, [C.POINTER(DsfCall), C.c_double, C.c_double, C.c_uint, C.POINTER(_vp)]),
     "mtd_nlist_create": (C.c_int, [C.POINTER(_vp)]),
     "mtd_nlist_destroy": (C.c_int, [_vp]),
     "mtd_nlist_build": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp, C.c_int, C.POINTER(Box), C.c_double, C.c_int, C.c_int,

@@ -515,6 +515,71 @@ class pair_entropy_local(_neighbour_variable):
         """v_i of every particle at the current time step: what the CV averages (sbar_i itself without a switch)"""
         return self.cpp_force.getSwitchedValues(context.current.system.getCurrentTimeStep())
 
+
+class debye_structure_factor(_neighbour_variable):
+    """this build (no reference counterpart; include/mtd_abi.h "Debye structure factor"): the intensity of diffraction peaks from the
+    Debye scattering function of the particles of one type (Niu, Piaggi, Invernizzi and Parrinello, PNAS 115, 5348 (2018)),
+    I(Q) = 1 + (1 / N) sum_{i != j} w(r_ij) sin(Q r_ij) / (Q r_ij) over the pairs within ``r_cut`` with the window
+    w(r) = sin(pi r / r_cut) / (pi r / r_cut).  ``q`` is one wave number or a sequence of up to 8, read off an experimental or computed
+    diffraction pattern (``get_spectrum`` gives the pattern of the current configuration); CV = sum_p weights[p] * I(q[p]), weights 1.0
+    each by default, and two peaks with weights of opposite sign select one polymorph against another.  It needs no template, no
+    reference value and no orientation, and is invariant under rotation and translation.  The reach of the list is the resolution of
+    the variable: the contrast between crystal and liquid grows with ``r_cut``.
+    Needs a full list that reaches ``r_cut`` (``get_rcut``); works in domain-decomposed runs.
+
+    The window is the published one: it vanishes at ``r_cut`` but its slope does not, so the bias force is discontinuous there, by
+    sinc(Q r_cut) / r_cut per pair and peak, divided by N.
+
+    Virial (``get_virial``; mtd_dsf_forces): half of every pair at each of its ends, no explicit volume term (the normalisation is the
+    particle number, not a density).  The sums are -bias * dCV/d(strain)."""
+
+    _cv = "cv.debye_structure_factor"
+
+    def __init__(self, q, r_cut, nlist, type, weights=None, name=None, sigma=1.0):
+        suffix = self._begin(sigma, name)
+        try:
+            type_list = context.current.type_names
+            q = [float(q)] if not hasattr(q, "__len__") else [float(v) for v in q]
+            weights = [1.0] * len(q) if weights is None else \
+                ([float(weights)] if not hasattr(weights, "__len__") else [float(v) for v in weights])
+            r_cut = float(r_cut)
+            inf = float("inf")
+            if type not in type_list or not 1 <= len(q) <= 8 or len(weights) != len(q) or not all(0.0 < v < inf for v in q) \
+                    or not all(-inf < v < inf for v in weights) or not 0.0 < r_cut < inf or float(nlist.r_cut) < r_cut:
+                raise ValueError
+            self.type = type
+            self.nlist = nlist
+            self.q, self.weights = q, weights
+            self.r_cut = r_cut
+            self._full_list()
+            self.cpp_force = _metadynamics.DebyeStructureFactor(context.current.system_definition, q, weights, r_cut, nlist.cpp_nlist,
+                                                                type_list.index(type), suffix)
+        except (TypeError, ValueError, AttributeError, RuntimeError):
+            context.current.forces.remove(self)                      # refused: the run must not find a half-made variable
+            raise RuntimeError("Error creating collective variable.")
+        self._attach(type_list.index(type))
+
+    def get_intensities(self):
+        """I(q[p]) of every peak at the current time step"""
+        return self.cpp_force.getIntensities(context.current.system.getCurrentTimeStep())
+
+    def get_local(self):
+        """s_i of every particle at the current time step, sum_p weights[p] * (1 + sum_j w sin(q r) / (q r)) over its own row (0 for
+        particles of another type); the CV is their mean over the particles of the type"""
+        return self.cpp_force.getLocalValues(context.current.system.getCurrentTimeStep())
+
+    def get_spectrum(self, q_min, q_max, n_q):
+        """(Q_m, I(Q_m)) on ``n_q`` (1 .. 256) equally spaced wave numbers from ``q_min`` > 0 to ``q_max`` at the current time step: a
+        diagnostic to find the peak positions of a configuration; it is not biased"""
+        import numpy as np
+        q_min, q_max = float(q_min), float(q_max)
+        if int(n_q) != n_q or not 1 <= int(n_q) <= 256 or not 0.0 < q_min <= q_max < float("inf"):
+            raise RuntimeError("cv.debye_structure_factor: a spectrum needs 0 < q_min <= q_max and 1 <= n_q <= 256")
+        n_q = int(n_q)
+        dq = (q_max - q_min) / (n_q - 1) if n_q > 1 else 0.0
+        return q_min + np.arange(n_q) * dq, np.asarray(self.cpp_force.getSpectrum(context.current.system.getCurrentTimeStep(), q_min, q_max, n_q))
+
+
 def environment_templates(structure, a):
     """the template environments of a cubic lattice with the conventional lattice constant ``a``, for ``cv.environment_similarity``:
     ``"fcc"`` 12 vectors of length a / sqrt(2), ``"bcc"`` 14 vectors (the 8 nearest of length a sqrt(3) / 2 and the 6 second neighbours of
