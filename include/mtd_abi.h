@@ -1134,6 +1134,96 @@ int mtd_dsf_spectrum(const mtd_dsf_params *p, const mtd_dsf_call *c, double q_mi
 int mtd_dsf_spectrum_finalize(const mtd_dsf_call *c, double q_min, double q_max, unsigned int n_q, const double **d_spectrum);
 
 /* ================================================================================================
+ * Coordination number (cv.coordination) — no reference counterpart.  The coordination number of the particles of one type A by those of
+ * a type B through a rational switching function (PLUMED's COORDINATION / COORDINATIONNUMBER), plain or counted through a switch: the
+ * variable of ion pairing, nucleation from solution, demixing and solvation shells, and the first one here that looks at pairs of two
+ * different types.  The conventions of "Debye structure factor" above hold wherever nothing else is said.
+ * Parameters: types A (centres) and B (partners), A = B allowed; r_0 > 0, d_0 >= 0, r_cut > d_0; integers 1 <= n < m <= MTD_COORD_MAX_M.
+ * Entries (i, j) of a FULL list take part when type_i = A and type_j = B, j != i and r = |minImage(r_i - r_j)| <= r_cut.  The centres
+ * are the n_particles local particles; entries may address the n_ghost particles stored behind them.
+ *     x    = max(r - d_0, 0) / r_0
+ *     s(x) = (1 - x^n) / (1 - x^m) = P_n(x) / P_m(x),   P_k(x) = 1 + x + ... + x^(k-1)
+ * The geometric-sum form IS the definition: it has no singularity at x = 1 and no cancellation near it (s(1) = n / m,
+ * ds/dx(1) = n (n - m) / (2 m)); the quotient form is 0 / 0 there and loses digits beside it.  The kernels evaluate P_k and P_k' by
+ * Horner's rule, as tests/coordination_ref.py does; the default pair (6, 12) is compiled as 1 / (1 + x^6), which is the same function.
+ * Stretched, as PLUMED's default:  s~(r) = (s - s_c) / (1 - s_c),  s_c = s((r_cut - d_0) / r_0), formed once on the host in fp64.
+ * s~(r <= d_0) = 1 with gradient 0, s~(r_cut) = 0.  THE FORCE IS DISCONTINUOUS AT r_cut: the slope there is not zero, so an entry that
+ * crosses the cut-off changes ds/dr by |s'(r_cut)| / (1 - s_c) / N_A.  The function is kept as published.
+ *     n_i = sum_{j in row i, taking part} s~(r_ij)  for i of type A, else 0
+ *     v_i = g(n_i),   s = (1 / N_A) sum_i v_i       N_A = centres of type A; N_A == 0: s = 0, no forces
+ * g(c) = c (plain), or with switch_on  h(c) = y^p / (1 + y^p), y = c / c0 (p >= 1, c0 > 0), or 1 - h with `less`: s N_A is then the
+ * smooth number of A particles with at least (at most) c0 B neighbours.
+ * Gradient, in the gather form on a full list, for every local k:
+ *     ds/dr_k = (1 / N_A) sum_{j in row k, j != k, r <= r_cut} s~'(r_kj) d_kj / r_kj ( [k in A, j in B] g'(n_k) + [k in B, j in A] g'(n_j) )
+ * with d_kj = minImage(r_k - r_j); F = -bias ds/dr.  Both brackets count when A = B.  Particles of neither type get F = 0, and so do
+ * entries with r = 0 or r <= d_0.
+ * Virial (only with a virial pointer): virial_k[ab] = -(bias / (2 N_A)) sum_{same entries} s~' d_a d_b / r (same bracket): half of
+ * every pair at each end, symmetric, sum_k virial_k = -bias ds/d eps, no explicit volume term.  Layout, scalar type and pitch rule of
+ * mtd_pe_forces.
+ * Domain decomposition: the plain variable needs no per-particle value of a neighbour and runs with ghosts; its only exchange is one
+ * mtd_comm_allreduce_small of the two sums.  With a switch g'(n_j) of a ghost is not known: n_ghost > 0 together with switch_on is
+ * MTD_ERR_UNSUPPORTED.
+ * A step is _accumulate, (mtd_comm_allreduce_small of *d_sums in a domain-decomposed run), _finalize, _forces with the same parameters,
+ * call block and scratch.  Plain: _accumulate walks the rows once and stores n_i and every particle's unscaled gradient and virial sums,
+ * _forces scales them by bias / N_A.  With a switch: _accumulate forms n_i, v_i and g'(n_i), _forces walks the rows a second time and
+ * reads g'(n_j) of the neighbours.  Every sum has a fixed order and there are no atomics: two identical calls give identical bits.
+ * Arguments are checked before a device is touched: MTD_ERR_INVALID_ARGUMENT for null pointers, non-finite or out-of-range parameters
+ * (r_0, d_0, r_cut, n = 0, n >= m, and with switch_on c0 and p), an unknown dtype, a d_scratch that is not 16-byte aligned, a virial
+ * pitch below n_particles; MTD_ERR_UNSUPPORTED for m > MTD_COORD_MAX_M and for a switch with ghosts.
+ * ============================================================================================== */
+
+#define MTD_COORD_MAX_M 32
+
+typedef struct
+    {
+    unsigned int type_a, type_b;           /* centres and partners */
+    double r_0, d_0;
+    unsigned int n, m;
+    double r_cut;
+    int switch_on;
+    double c0;
+    unsigned int p;
+    int less;                              /* 1 - h in place of h */
+    } mtd_coord_params;
+
+/* the fields of mtd_dsf_call */
+typedef struct
+    {
+    unsigned int n_particles, n_ghost;     /* d_postype holds n_particles + n_ghost entries */
+    const void *d_postype;
+    int dtype;
+    const mtd_box *box;
+    const unsigned int *d_head_list, *d_n_neigh, *d_nlist;
+    double *d_scratch;
+    mtd_stream_t stream;
+    } mtd_coord_call;
+
+/* device doubles the calls share: sums, value, block sums and twelve per-particle arrays */
+size_t mtd_coord_scratch_doubles(unsigned int n_particles);
+
+/* 1 (default): (n, m) = (6, 12) runs the pair term compiled for it, 1 / (1 + x^6) (an identity for m = 2 n); 0: it takes the general
+ * Horner loop like every other pair.  Both meet the tolerances at and around x = 1.  Process-wide, read by _accumulate and _forces:
+ * change it between steps, not inside one.  profiles/r25/README.md has the timings of both. */
+int mtd_coord_set_compiled_pair(int enable);
+
+/* This rank's sums: on return *d_sums points at *n_sums = 2 doubles inside c->d_scratch, sum_i v_i and N_A, ready for
+ * mtd_comm_allreduce_small. */
+int mtd_coord_accumulate(const mtd_coord_params *p, const mtd_coord_call *c, double **d_sums, unsigned int *n_sums);
+
+/* The (reduced) sums -> s.  *d_value points at s, one device double (consume with
+ * mtd_metad_set_cv_source(engine, slot, *d_value, 1, 1, 0, 1.0, 0.0)), *d_local (may be NULL) at n_i[n_particles] and *d_switched (may
+ * be NULL) at v_i[n_particles] of the last mtd_coord_accumulate (v_i = n_i without a switch), all inside c->d_scratch. */
+int mtd_coord_finalize(const mtd_coord_params *p, const mtd_coord_call *c, const double **d_value, const double **d_local,
+                       const double **d_switched);
+
+/* Writes d_force[0..n_particles) (w component 0; 0 for particles of neither type) with what the last mtd_coord_accumulate and
+ * mtd_coord_finalize (same p and c) left in c->d_scratch; bias = *d_bias when d_bias != NULL, else bias_host.  d_virial == NULL: no
+ * virial; the force array is the same, bit for bit, either way.  Every row [0, n_particles) of the virial is written,
+ * [n_particles, virial_pitch) is left alone.  n_particles == 0 is success. */
+int mtd_coord_forces(const mtd_coord_params *p, const mtd_coord_call *c, void *d_force, const double *d_bias, double bias_host,
+                     void *d_virial, unsigned int virial_pitch);
+
+/* ================================================================================================
  * Neighbour list of the stand-alone path (cell list, built on the device)
  * no reference counterpart: HOOMD's md::NeighborList is HOOMD core.  Produces the three arrays SteinhardtQl.cc:80-85 reads, in
  * HOOMD's layout: the neighbours of particle i are d_nlist[d_head_list[i] .. d_head_list[i] + d_n_neigh[i]).

@@ -1,5 +1,5 @@
 // row_walk.hpp — the lane-group walk over one row of a full neighbour list, written once (device; steinhardt_local.hip, pair_entropy.hip,
-// env_similarity.hip).
+// env_similarity.hip, debye.hip, coordination.hip).
 //
 // G lanes (a DPP quad, or half a DPP row) share one central particle; lane q takes entries q, q + G, ... of its row.  Here: the centre of
 // a group (RowCentre / row_centre), the walk itself with its look-ahead (row_walk), the group's sum (group_sum), the zero that keeps the
@@ -8,12 +8,16 @@
 // __forceinline__ and holds no state of its own: a kernel that uses a piece has the instruction stream of the kernel that wrote it out
 // (profiles/r20/README.md compares them kernel by kernel).
 //
-// The walk lives in THREE forms, and a change to the look-ahead, the list format or the skip rule is made in all of them:
+// The walk lives in FOUR forms, and a change to the look-ahead, the list format or the skip rule is made in all of them:
 //   row_walk                   here: both passes of pair_entropy.hip and of env_similarity.hip; as row_walk_entries<.., GHOSTS = false>
 //                              the link pass of cluster.hip (local entries only: the rule of QllWalker, switched at compile time)
 //   QllWalker                  steinhardt_local.hip: its four gather passes, through qll_entries
 //   three loops written out    k_qll_accumulate, k_qll_forces and k_qll_forces_tile of steinhardt_local.hip (through a walker their bits
 //                              or their speed did not stay the parent's: profiles/r10/README.md)
+//   row_walk_pairs             here, at the end: coordination.hip.  The walk of row_walk with TWO types: the centre (row_centre_pairs) is
+//                              of type A or B, and an entry takes part as (A centre, B partner), as (B centre, A partner) or as both when
+//                              A = B; the body is told which.  Ghosts are walked, as in row_walk.  A function of its own, so that the
+//                              kernels on row_walk keep their instruction streams
 // They differ in ONE rule on purpose.  QllWalker::position and the three loops load a neighbour's position for j < N only: the Steinhardt
 // passes read per-particle table rows of their neighbours, which ghosts do not have, so an entry j >= N is skipped.  row_walk loads it for
 // every j != ROW_NONE: the rows of these two variables may address ghost particles stored behind the N local ones
@@ -172,6 +176,61 @@ __device__ __forceinline__ void row_store_virial(scalar *v, const unsigned int v
     nt_store((scalar)(DIAG ? vyy * h + diag : vyy * h), v + 3 * (size_t)virial_pitch);
     nt_store((scalar)(vyz * h), v + 4 * (size_t)virial_pitch);
     nt_store((scalar)(DIAG ? vzz * h + diag : vzz * h), v + 5 * (size_t)virial_pitch);
+    }
+
+// The two-type forms of row_centre and row_walk (coordination.hip).  The centre owns a row when it is of type A or of type B.  The walk
+// calls body(j, as_centre, as_partner, dx, dy, dz, rsq), d = minImage(r_i - r_j), for every entry of lane q with j != i and
+// rsq <= a.rcutsq that plays a role: as_centre = (type_i == A and type_j == B), the entry counts in n_i; as_partner = (type_i == B and
+// type_j == A), the mirror entry counts in n_j and its gradient falls on i.  With A = B both hold.  Look-ahead and ghost rule of row_walk.
+template<typename S4, int LMAX>
+__device__ __forceinline__ RowCentre row_centre_pairs(const QlArgs<LMAX> &a, const unsigned int type_a, const unsigned int type_b,
+                                                      const S4 *postype, const unsigned int *head_list, const unsigned int *n_neigh,
+                                                      const unsigned int i)
+    {
+    Particle p = {0.0, 0.0, 0.0, -1};
+    unsigned int start = 0, cnt = 0;
+    if (i < a.N)
+        {
+        p = scalar4_traits<S4>::load(postype, i);
+        if ((unsigned int)p.type == type_a || (unsigned int)p.type == type_b)
+            {
+            start = head_list[i];
+            cnt = n_neigh[i];
+            }
+        }
+    return {i, p, start, cnt};
+    }
+
+template<int G, typename S4, typename F>
+__device__ __forceinline__ void row_walk_pairs(const QlArgs<4> &a, const unsigned int type_a, const unsigned int type_b,
+                                               const S4 *__restrict__ postype, const unsigned int *__restrict__ nlist, const RowCentre &c,
+                                               const unsigned int q, F &&body)
+    {
+    const bool centre_a = (unsigned int)c.p.type == type_a, centre_b = (unsigned int)c.p.type == type_b;
+    unsigned int e = q;
+    unsigned int j0 = e < c.cnt ? nlist[c.start + e] : ROW_NONE;
+    unsigned int j1 = e + G < c.cnt ? nlist[c.start + e + G] : ROW_NONE;
+    S4 pos0 = row_zero<S4>();
+    if (j0 != ROW_NONE) pos0 = postype[j0];
+#pragma unroll 1
+    for (; e < c.cnt; e += G)
+        {
+        const unsigned int j2 = e + 2 * G < c.cnt ? nlist[c.start + e + 2 * G] : ROW_NONE;
+        S4 pos1 = row_zero<S4>();
+        if (j1 != ROW_NONE) pos1 = postype[j1];
+        if (j0 != c.i)
+            {
+            const Particle pj = scalar4_traits<S4>::unpack(pos0);
+            double dx = c.p.x - pj.x, dy = c.p.y - pj.y, dz = c.p.z - pj.z;
+            min_image(a, dx, dy, dz);
+            const double rsq = dx * dx + dy * dy + dz * dz;
+            const bool as_centre = centre_a && (unsigned int)pj.type == type_b, as_partner = centre_b && (unsigned int)pj.type == type_a;
+            if ((as_centre || as_partner) && rsq <= a.rcutsq) body(j0, as_centre, as_partner, dx, dy, dz, rsq);
+            }
+        j0 = j1;
+        j1 = j2;
+        pos0 = pos1;
+        }
     }
 
 // blocks of a launch that walks `ppb` central particles per block and round: one per chunk, at least one, at most `max_blocks` (the

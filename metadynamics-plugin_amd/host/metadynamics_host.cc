@@ -1497,6 +1497,129 @@ void DebyeStructureFactor::computeBiasForces(unsigned int timestep)
     }
 
 // ------------------------------------------------------------------------------------------------
+// CoordinationNumber
+// ------------------------------------------------------------------------------------------------
+
+CoordinationNumber::CoordinationNumber(std::shared_ptr<SystemDefinition> sysdef, double r_0, double d_0, unsigned int n, unsigned int m,
+                                       double r_cut, std::shared_ptr<NeighborList> nlist, unsigned int type_a, unsigned int type_b,
+                                       const std::string &log_suffix)
+    : NeighbourVariable(sysdef, "coordination", log_suffix, nlist, type_a), m_par(), m_d_value(nullptr), m_d_local(nullptr), m_d_switched(nullptr)
+    {
+    if (!nlist) throw std::runtime_error("cv.coordination: a neighbour list is required");
+    if (!(r_0 > 0.0) || !std::isfinite(r_0)) throw std::runtime_error("cv.coordination: r_0 > 0 is required");
+    if (!(d_0 >= 0.0) || !std::isfinite(d_0)) throw std::runtime_error("cv.coordination: d_0 >= 0 is required");
+    if (!(r_cut > d_0) || !std::isfinite(r_cut)) throw std::runtime_error("cv.coordination: r_cut > d_0 is required");
+    if (n == 0 || n >= m) throw std::runtime_error("cv.coordination: 1 <= n < m is required");
+    if (m > MTD_COORD_MAX_M) throw std::runtime_error("cv.coordination: m <= 32 in this build");
+    m_par.type_a = type_a;
+    m_par.type_b = type_b;
+    m_par.r_0 = r_0;
+    m_par.d_0 = d_0;
+    m_par.n = n;
+    m_par.m = m;
+    m_par.r_cut = r_cut;
+    m_scratch.resize(sizeof(double) * mtd_coord_scratch_doubles(m_pdata->getN()));
+    }
+
+void CoordinationNumber::setSwitch(double c0, unsigned int p, bool less)
+    {
+    if (!(c0 > 0.0) || !std::isfinite(c0) || p == 0) throw std::runtime_error("cv.coordination: a switch needs c0 > 0 and an integer p >= 1");
+    m_par.switch_on = 1;
+    m_par.c0 = c0;
+    m_par.p = p;
+    m_par.less = less ? 1 : 0;
+    invalidate();                                                    // v_i and g'(n_i) in the scratch belong to the old switch
+    }
+
+void CoordinationNumber::clearSwitch()
+    {
+    m_par.switch_on = 0;
+    m_par.c0 = 0.0;
+    m_par.p = 0;
+    m_par.less = 0;
+    invalidate();
+    }
+
+mtd_coord_call CoordinationNumber::call(const mtd_box *box)
+    {
+    const size_t need = sizeof(double) * mtd_coord_scratch_doubles(m_pdata->getN());
+    if (need > m_scratch.bytes())                                    // (more particles than at the last call: nothing in the scratch is this step's)
+        {
+        m_scratch.resize(need);
+        invalidate();
+        }
+    const Lists l = lists();
+    mtd_coord_call c;
+    c.n_particles = m_pdata->getN();
+    c.n_ghost = m_pdata->getNGhosts();
+    c.d_postype = m_pdata->positionsPtr();
+    c.dtype = m_pdata->getDtype();
+    c.box = box;
+    c.d_head_list = l.head;
+    c.d_n_neigh = l.n_neigh;
+    c.d_nlist = l.nlist;
+    c.d_scratch = (double *)m_scratch.data();
+    c.stream = m_exec_conf->getStream();
+    return c;
+    }
+
+void CoordinationNumber::computeCV(unsigned int timestep)
+    {
+    ProfRange prof_range("CV");
+    if (fresh(timestep)) return;
+    requireFullList();
+    if (distributed() && m_par.switch_on)
+        throw std::runtime_error("cv.coordination: domain-decomposed runs are not supported with a switch (g'(n_j) of a ghost neighbour would "
+                                 "have to be exchanged)");
+    requireReach(getRCut(), "r_cut");
+    m_nlist->compute(timestep);
+    const mtd_box box = m_pdata->getBox().toMtd();
+    const mtd_coord_call c = call(&box);
+    double *d_sums = nullptr;
+    unsigned int n_sums = 0;
+    mtd_check(mtd_coord_accumulate(&m_par, &c, &d_sums, &n_sums), "mtd_coord_accumulate");
+    // sum v_i and N_A over the ranks: the central particles of a rank are its local ones, their neighbours may be ghosts
+    if (distributed()) m_exec_conf->allreduceSmall(d_sums, n_sums, m_exec_conf->getStream());
+    mtd_check(mtd_coord_finalize(&m_par, &c, &m_d_value, &m_d_local, &m_d_switched), "mtd_coord_finalize");
+    computed(timestep);
+    }
+
+void CoordinationNumber::enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot)
+    {
+    computeCV(timestep);
+    mtd_check(mtd_metad_set_cv_source(engine, slot, m_d_value, 1, 1, 0, 1.0, 0.0), "mtd_metad_set_cv_source");
+    }
+
+double CoordinationNumber::getCurrentValue(unsigned int timestep)
+    {
+    computeCV(timestep);
+    return readValue(m_d_value, timestep);
+    }
+
+std::vector<double> CoordinationNumber::getLocalValues(unsigned int timestep)
+    {
+    computeCV(timestep);
+    return readBack(m_d_local, m_pdata->getN(), "n_i read-back", timestep);
+    }
+
+std::vector<double> CoordinationNumber::getSwitchedValues(unsigned int timestep)
+    {
+    computeCV(timestep);
+    return readBack(m_d_switched, m_pdata->getN(), "v_i read-back", timestep);
+    }
+
+void CoordinationNumber::computeBiasForces(unsigned int timestep)
+    {
+    ProfRange prof_range("Force");
+    if (!fresh(timestep)) computeCV(timestep);                       // the sums of THIS step's positions
+    m_nlist->compute(timestep);
+    const mtd_box box = m_pdata->getBox().toMtd();
+    const mtd_coord_call c = call(&box);
+    void *virial = virialTarget();                                   // constant pressure: the per-particle virial of the bias force beside it
+    mtd_check(mtd_coord_forces(&m_par, &c, m_force.data(), m_bias_device, m_bias, virial, getVirialPitch()), "mtd_coord_forces");
+    }
+
+// ------------------------------------------------------------------------------------------------
 // AspectRatio, Density
 // ------------------------------------------------------------------------------------------------
 

@@ -519,6 +519,33 @@ class DebyeStructureFactor : public NeighbourVariable
         const double *m_d_value, *m_d_intensity, *m_d_local;
     };
 
+//! Coordination number (no reference counterpart; include/mtd_abi.h "Coordination number"): the mean number of partners of type B around
+//! the particles of type A through a rational switching function, plain or counted through a switch on every particle's number.  The
+//! plain variable works domain-decomposed: the only exchange is one allreduceSmall of two sums.  With a switch: single-domain runs only,
+//! the force on a particle reads g'(n_j) of its neighbours, which a ghost does not have.
+class CoordinationNumber : public NeighbourVariable
+    {
+    public:
+        CoordinationNumber(std::shared_ptr<SystemDefinition> sysdef, double r_0, double d_0, unsigned int n, unsigned int m, double r_cut,
+                           std::shared_ptr<NeighborList> nlist, unsigned int type_a, unsigned int type_b, const std::string &log_suffix = "");
+        double getCurrentValue(unsigned int timestep) override;
+        //! device-resident: the value in the scratch becomes the engine's source of this variable, no host synchronisation
+        void enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot) override;
+        void computeBiasForces(unsigned int timestep) override;
+        std::vector<double> getLocalValues(unsigned int timestep);     //!< n_i of every local particle (0 for particles not of type A)
+        std::vector<double> getSwitchedValues(unsigned int timestep);  //!< v_i = g(n_i) (n_i without a switch)
+        //! h(c) = y^p / (1 + y^p), y = c / c0, or 1 - h with `less`; every change invalidates the cached step
+        void setSwitch(double c0, unsigned int p, bool less);
+        void clearSwitch();
+        double getRCut() const { return m_par.r_cut; }                 //!< what the neighbour list must reach
+
+    private:
+        void computeCV(unsigned int timestep) override;
+        mtd_coord_call call(const mtd_box *box);
+        mtd_coord_params m_par;
+        const double *m_d_value, *m_d_local, *m_d_switched;
+    };
+
 //! AspectRatio.h / AspectRatio.cc:5-130 — box-shape CV, external virial only
 class AspectRatio : public CollectiveVariable
     {

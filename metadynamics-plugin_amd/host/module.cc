@@ -437,6 +437,22 @@ PYBIND11_MODULE(_metadynamics, m)
             return py::array_t<double>((ssize_t)v.size(), v.data());
         });
 
+    // no reference counterpart: the coordination number between two particle types through a rational switching function
+    py::class_<CoordinationNumber, CollectiveVariable, std::shared_ptr<CoordinationNumber>>(m, "CoordinationNumber")
+        .def(py::init<std::shared_ptr<SystemDefinition>, double, double, unsigned int, unsigned int, double, std::shared_ptr<NeighborList>,
+                      unsigned int, unsigned int, const std::string &>())
+        .def("getRCut", &CoordinationNumber::getRCut)
+        .def("setSwitch", &CoordinationNumber::setSwitch)
+        .def("clearSwitch", &CoordinationNumber::clearSwitch)
+        .def("getLocalValues", [](CoordinationNumber &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getLocalValues(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        })
+        .def("getSwitchedValues", [](CoordinationNumber &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getSwitchedValues(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        });
+
     py::class_<WellTemperedEnsemble, CollectiveVariable, std::shared_ptr<WellTemperedEnsemble>>(m, "WellTemperedEnsemble")
         .def(py::init<std::shared_ptr<SystemDefinition>, const std::string &>());
 

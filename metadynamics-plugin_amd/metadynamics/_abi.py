@@ -213,6 +213,30 @@ class DsfCall(C.Structure):
                 ("stream", C.c_void_p)]
 
 
+MTD_COORD_MAX_M = 32
+
+
+class CoordParams(C.Structure):
+    """mtd_coord_params: the two particle types, the rational switching function, the cut-off and the optional switch on n_i"""
+    _fields_ = [("type_a", C.c_uint), ("type_b", C.c_uint), ("r_0", C.c_double), ("d_0", C.c_double), ("n", C.c_uint), ("m", C.c_uint),
+                ("r_cut", C.c_double), ("switch_on", C.c_int), ("c0", C.c_double), ("p", C.c_uint), ("less", C.c_int)]
+
+    @classmethod
+    def make(cls, type_a, type_b, r_0, r_cut, d_0=0.0, n=6, m=12, switch=None):
+        """switch: None or (c0, p[, less]).  Nothing is checked here: the entry points refuse what they do not take"""
+        o = cls()
+        o.type_a, o.type_b, o.r_0, o.d_0, o.n, o.m, o.r_cut = int(type_a), int(type_b), float(r_0), float(d_0), int(n), int(m), float(r_cut)
+        if switch is not None:
+            o.switch_on, o.c0, o.p = 1, float(switch[0]), int(switch[1])
+            o.less = int(bool(switch[2])) if len(switch) > 2 else 0
+        return o
+
+
+class CoordCall(C.Structure):
+    """mtd_coord_call: particles, ghosts, box, list, scratch and stream of one step (the fields of mtd_dsf_call)"""
+    _fields_ = DsfCall._fields_
+
+
 _vp = C.c_void_p
 _dp = C.POINTER(C.c_double)
 _up = C.POINTER(C.c_uint)
@@ -380,6 +404,11 @@ _SIGNATURES = {
     "mtd_dsf_forces": (C.c_int, [C.POINTER(DsfParams), C.POINTER(DsfCall), _vp, _vp, C.c_double, _vp, C.c_uint]),
     "mtd_dsf_spectrum": (C.c_int, [C.POINTER(DsfParams), C.POINTER(DsfCall), C.c_double, C.c_double, C.c_uint, C.POINTER(_vp), _up]),
     "mtd_dsf_spectrum_finalize": (C.c_int, [C.POINTER(DsfCall), C.c_double, C.c_double, C.c_uint, C.POINTER(_vp)]),
+    "mtd_coord_scratch_doubles": (C.c_size_t, [C.c_uint]),
+    "mtd_coord_set_compiled_pair": (C.c_int, [C.c_int]),
+    "mtd_coord_accumulate": (C.c_int, [C.POINTER(CoordParams), C.POINTER(CoordCall), C.POINTER(_vp), _up]),
+    "mtd_coord_finalize": (C.c_int, [C.POINTER(CoordParams), C.POINTER(CoordCall), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "mtd_coord_forces": (C.c_int, [C.POINTER(CoordParams), C.POINTER(CoordCall), _vp, _vp, C.c_double, _vp, C.c_uint]),
     "mtd_nlist_create": (C.c_int, [C.POINTER(_vp)]),
     "mtd_nlist_destroy": (C.c_int, [_vp]),
     "mtd_nlist_build": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp, C.c_int, C.POINTER(Box), C.c_double, C.c_int, C.c_int,

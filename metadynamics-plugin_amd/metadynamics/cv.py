@@ -580,6 +580,88 @@ class debye_structure_factor(_neighbour_variable):
         return q_min + np.arange(n_q) * dq, np.asarray(self.cpp_force.getSpectrum(context.current.system.getCurrentTimeStep(), q_min, q_max, n_q))
 
 
+class coordination(_neighbour_variable):
+    """this build (no reference counterpart; include/mtd_abi.h "Coordination number"): the coordination number of the particles of
+    ``type`` (A) by those of ``partner`` (B; ``None``: A itself) through the rational switching function of PLUMED's COORDINATION,
+    s(r) = (1 - x^n) / (1 - x^m) with x = max(r - d_0, 0) / r_0, stretched so that it is 1 up to ``d_0`` and 0 at ``r_cut``
+    (``None``: the reach of the list): n_i = sum_{j of type B} s(r_ij), CV = (1 / N_A) sum_i g(n_i) with g(c) = c or, with
+    ``switch=dict(c0=..., p=...[, less=True])``, h(c) = y^p / (1 + y^p), y = c / c0 (1 - h with ``less``) — CV * N_A is then the smooth
+    number of A particles with at least (at most) c0 B neighbours.  1 <= n < m <= 32.  The function has no singularity at x = 1: it is
+    evaluated as a quotient of geometric sums.
+    Needs a full list that reaches ``r_cut`` (``get_rcut``); with two types a device-built list builds all pairs.  The plain variable
+    works in domain-decomposed runs, a switch does not (g' of a ghost neighbour would have to be exchanged).
+
+    The stretched function vanishes at ``r_cut`` but its slope does not, so the bias force is discontinuous there, by
+    |s'(r_cut)| / (1 - s(r_cut)) per pair, divided by N_A.
+
+    Virial (``get_virial``; mtd_coord_forces): half of every pair at each of its ends, no explicit volume term (the normalisation is
+    the particle number, not a density).  The sums are -bias * dCV/d(strain)."""
+
+    _cv = "cv.coordination"
+
+    def __init__(self, r_0, nlist, type, partner=None, d_0=0.0, n=6, m=12, r_cut=None, switch=None, name=None, sigma=1.0):
+        suffix = self._begin(sigma, name)
+        try:
+            type_list = context.current.type_names
+            partner = type if partner is None else partner
+            r_0, d_0 = float(r_0), float(d_0)
+            r_cut = float(nlist.r_cut) if r_cut is None else float(r_cut)
+            inf = float("inf")
+            if type not in type_list or partner not in type_list or int(n) != n or int(m) != m or not 1 <= int(n) < int(m) <= 32 \
+                    or not 0.0 < r_0 < inf or not 0.0 <= d_0 < r_cut < inf or float(nlist.r_cut) < r_cut:
+                raise ValueError
+            sw = self._switch(switch)
+            self.type, self.partner = type, partner
+            self.nlist = nlist
+            self.r_0, self.d_0, self.n, self.m, self.r_cut = r_0, d_0, int(n), int(m), r_cut
+            self._full_list()
+            self.cpp_force = _metadynamics.CoordinationNumber(context.current.system_definition, r_0, d_0, int(n), int(m), r_cut,
+                                                              nlist.cpp_nlist, type_list.index(type), type_list.index(partner), suffix)
+            if sw is not None:
+                self.cpp_force.setSwitch(*sw)
+        except (TypeError, ValueError, KeyError, AttributeError, RuntimeError):
+            context.current.forces.remove(self)                      # refused: the run must not find a half-made variable
+            raise RuntimeError("Error creating collective variable.")
+        self._attach(type_list.index(type))
+        self._attach(type_list.index(partner))                       # (two types: a device-built list then builds all pairs)
+
+    @staticmethod
+    def _switch(switch):
+        """the checks of cv.environment_similarity._switch, with the optional ``less``"""
+        if switch is None:
+            return None
+        sw = (float(switch["c0"]), int(switch["p"]), bool(switch.get("less", False)))
+        if not {"c0", "p"} <= set(switch.keys()) <= {"c0", "p", "less"} or int(switch["p"]) != switch["p"] \
+                or not 0.0 < sw[0] < float("inf") or sw[1] < 1:
+            raise ValueError
+        return sw
+
+    def get_rcut(self):
+        """the cut-off this CV asks of the neighbour list, by type pair: ``r_cut`` for the pair {type, partner}, -1 for every other"""
+        names = context.current.type_names
+        pair = {self.type, self.partner}
+        return {(a, b): (self.r_cut if {a, b} == pair else -1.0) for i, a in enumerate(names) for b in names[i:]}
+
+    def get_local(self):
+        """n_i of every particle at the current time step (0 for particles that are not of ``type``)"""
+        return self.cpp_force.getLocalValues(context.current.system.getCurrentTimeStep())
+
+    def get_switched(self):
+        """v_i = g(n_i) of every particle at the current time step: what the CV averages (n_i itself without a switch)"""
+        return self.cpp_force.getSwitchedValues(context.current.system.getCurrentTimeStep())
+
+    def set_switch(self, switch):
+        """``dict(c0=..., p=...[, less=True])`` or ``None`` (no switch); takes effect with the next step"""
+        try:
+            sw = self._switch(switch)
+            if sw is None:
+                self.cpp_force.clearSwitch()
+            else:
+                self.cpp_force.setSwitch(*sw)
+        except (TypeError, KeyError, ValueError, AttributeError, RuntimeError):
+            raise RuntimeError("Error creating collective variable.")
+
+
 def environment_templates(structure, a):
     """the template environments of a cubic lattice with the conventional lattice constant ``a``, for ``cv.environment_similarity``:
     ``"fcc"`` 12 vectors of length a / sqrt(2), ``"bcc"`` 14 vectors (the 8 nearest of length a sqrt(3) / 2 and the 6 second neighbours of
