@@ -1012,7 +1012,8 @@ typedef struct
     unsigned int p;
     } mtd_pel_params;                      /* options all-zero = off */
 
-/* what the two calls of a step share beside the parameters: particles, box, list, scratch and the stream the launches go to */
+/* what the two calls of a step share beside the parameters: the fields of mtd_row_call (below, "Debye structure factor"), with N_global
+ * in the place of n_ghost */
 typedef struct
     {
     unsigned int n_particles, n_global;
@@ -1088,7 +1089,8 @@ typedef struct
     double q[MTD_DSF_MAX_Q], c[MTD_DSF_MAX_Q];
     } mtd_dsf_params;
 
-/* what the calls of a step share beside the parameters: particles, box, list, scratch and the stream the launches go to */
+/* The call block of the variables that walk the rows of a full neighbour list: what the calls of a step share beside the parameters —
+ * particles, box, list, scratch and the stream the launches go to.  One structure under the name of each unit that takes it. */
 typedef struct
     {
     unsigned int n_particles, n_ghost;     /* d_postype holds n_particles + n_ghost entries */
@@ -1098,7 +1100,8 @@ typedef struct
     const unsigned int *d_head_list, *d_n_neigh, *d_nlist;
     double *d_scratch;
     mtd_stream_t stream;
-    } mtd_dsf_call;
+    } mtd_row_call;
+typedef mtd_row_call mtd_dsf_call;
 
 /* device doubles the calls share: sums, value, intensities, spectrum, block sums and ten per-particle arrays */
 size_t mtd_dsf_scratch_doubles(unsigned int n_particles);
@@ -1186,17 +1189,7 @@ typedef struct
     int less;                              /* 1 - h in place of h */
     } mtd_coord_params;
 
-/* the fields of mtd_dsf_call */
-typedef struct
-    {
-    unsigned int n_particles, n_ghost;     /* d_postype holds n_particles + n_ghost entries */
-    const void *d_postype;
-    int dtype;
-    const mtd_box *box;
-    const unsigned int *d_head_list, *d_n_neigh, *d_nlist;
-    double *d_scratch;
-    mtd_stream_t stream;
-    } mtd_coord_call;
+typedef mtd_row_call mtd_coord_call;     /* "Debye structure factor" */
 
 /* device doubles the calls share: sums, value, block sums and twelve per-particle arrays */
 size_t mtd_coord_scratch_doubles(unsigned int n_particles);

@@ -30,14 +30,14 @@
 //                      CN_FORCE   mtd_coord_forces with a switch: the second walk, g'(n_j) read from the per-particle table; force and
 //                                 (with VIR) virial scaled and stored
 //                    PLAIN and COUNT leave this block's share of sum v_i and N_A
-//   k_cn_scale       mtd_coord_forces without a switch: one thread per particle scales the stored sums by -bias / N_A and -bias / (2 N_A)
-//   k_cn_sums        one wave per slot adds the blocks' doubles in the fixed order of wave_sum (as k_dsf_sums)
+//   k_row_scale      (row_scale.hpp) mtd_coord_forces without a switch: one thread per particle scales the stored sums by -bias / N_A
+//                    and -bias / (2 N_A)
+//   k_row_sums       (row_walk.hpp) one wave per slot adds the blocks' doubles in the fixed order of wave_sum
 //   k_cn_finalize    s from the (reduced) sums
 // Fixed summation order everywhere (a lane's entries in row order, the DPP tree of group_sum, a thread's chunks in order, block_sum,
 // wave_sum), no atomics: two identical calls give identical bits, and a row gives the same bits wherever it lies in the list.
 #include "mtd_device.hpp"
-#include "row_walk.hpp"
-#include "dispatch.hpp"
+#include "row_scale.hpp"
 
 #include <atomic>
 #include <cmath>
@@ -51,7 +51,7 @@ using namespace mtd;
 constexpr int CN_THREADS = 256;
 constexpr int CN_G = 8;                                    // lanes per central particle
 constexpr int CN_PPB = CN_THREADS / CN_G;                  // central particles per block and round
-constexpr unsigned int CN_MAX_BLOCKS = 1024;               // columns of block sums in the scratch
+constexpr unsigned int CN_MAX_BLOCKS = ROW_MAX_BLOCKS;     // columns of block sums in the scratch
 
 // the scratch, in doubles: sums [2] | value, N_A [2] | (pad) | block sums [2][CN_MAX_BLOCKS]
 // | n_i [n] | v_i [n] | g'(n_i) [n] | gradient sums [3][n] | virial sums [6][n], n = n_particles rounded up to 2
@@ -59,8 +59,6 @@ constexpr size_t CN_OFF_SUMS = 0, CN_OFF_VALUE = 2, CN_OFF_NA = 3, CN_OFF_PART =
 constexpr int CN_ROW_N = 0, CN_ROW_V = 1, CN_ROW_DG = 2, CN_ROW_GRAD = 3, CN_ROWS = 12;   // (the six virial rows follow the gradient's)
 
 enum { CN_PLAIN = 0, CN_COUNT = 1, CN_FORCE = 2 };
-
-inline size_t cn_pitch(unsigned int n_particles) { return ((size_t)n_particles + 1) & ~(size_t)1; }
 
 struct CnArgs
     {
@@ -259,41 +257,12 @@ __global__ __launch_bounds__(CN_THREADS) void k_cn_walk(const QlArgs<4> a_in, co
         }
     }
 
-// one wave per slot: the blocks' values in the fixed order of wave_sum
-__global__ __launch_bounds__(MTD_WAVE) void k_cn_sums(const unsigned int n_blocks, const double *__restrict__ part, double *__restrict__ sums)
-    {
-    const double *row = part + (size_t)blockIdx.x * CN_MAX_BLOCKS;
-    double v = 0.0;
-    for (unsigned int k = threadIdx.x; k < n_blocks; k += MTD_WAVE) v += row[k];
-    v = wave_sum(v);
-    if (threadIdx.x == 0) sums[blockIdx.x] = v;
-    }
-
 __global__ __launch_bounds__(MTD_WAVE) void k_cn_finalize(double *__restrict__ scratch)
     {
     if (threadIdx.x != 0) return;
     const double n_a = scratch[CN_OFF_SUMS + 1];
     scratch[CN_OFF_VALUE] = n_a > 0.0 ? scratch[CN_OFF_SUMS] / n_a : 0.0;
     scratch[CN_OFF_NA] = n_a;
-    }
-
-// the stored sums of every particle -> force and virial
-template<typename S4, bool VIR>
-__global__ __launch_bounds__(CN_THREADS) void k_cn_scale(const unsigned int N, const double *__restrict__ scratch, const size_t pitch,
-                                                         S4 *__restrict__ force, const double *__restrict__ d_bias, const double bias_host,
-                                                         typename scalar4_traits<S4>::scalar *__restrict__ virial, const unsigned int virial_pitch)
-    {
-    typedef typename scalar4_traits<S4>::scalar scalar;
-    const unsigned int i = blockIdx.x * CN_THREADS + threadIdx.x;
-    if (i >= N) return;
-    const double n_a = scratch[CN_OFF_NA];
-    const double bias = d_bias ? *d_bias : bias_host;
-    const double scale_f = n_a > 0.0 ? -bias / n_a : 0.0, scale_v = n_a > 0.0 ? -0.5 * bias / n_a : 0.0;
-    const double *o = scratch + CN_OFF_PER_PARTICLE + CN_ROW_GRAD * pitch + i;
-    nt_store(scalar4_traits<S4>::make((scalar)(o[0] * scale_f), (scalar)(o[pitch] * scale_f), (scalar)(o[2 * pitch] * scale_f), (scalar)0), force + i);
-    if constexpr (VIR)
-        row_store_virial<false>(virial + i, virial_pitch, o[3 * pitch], o[4 * pitch], o[5 * pitch], o[6 * pitch], o[7 * pitch], o[8 * pitch], scale_v,
-                                0.0);
     }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
@@ -348,7 +317,7 @@ extern "C" {
 
 size_t mtd_coord_scratch_doubles(unsigned int n_particles)
     {
-    return CN_OFF_PER_PARTICLE + CN_ROWS * cn_pitch(n_particles);
+    return CN_OFF_PER_PARTICLE + CN_ROWS * row_pitch(n_particles);
     }
 
 int mtd_coord_set_compiled_pair(int enable)
@@ -368,7 +337,7 @@ int mtd_coord_accumulate(const mtd_coord_params *p, const mtd_coord_call *c, dou
     hipStream_t s = (hipStream_t)c->stream;
     const unsigned int blocks = row_blocks(c->n_particles, CN_PPB, CN_MAX_BLOCKS);
     double *part = c->d_scratch + CN_OFF_PART, *per_particle = c->d_scratch + CN_OFF_PER_PARTICLE;
-    const size_t pitch = cn_pitch(c->n_particles);
+    const size_t pitch = row_pitch(c->n_particles);
     const CnArgs d = cn_args(p);
     dispatch_s4(c->dtype, [&](auto t)
         {
@@ -386,7 +355,7 @@ int mtd_coord_accumulate(const mtd_coord_params *p, const mtd_coord_call *c, dou
             });
         });
     MTD_LAUNCH_CHECK();
-    k_cn_sums<<<2, MTD_WAVE, 0, s>>>(blocks, part, c->d_scratch + CN_OFF_SUMS);
+    k_row_sums<CN_MAX_BLOCKS><<<2, MTD_WAVE, 0, s>>>(blocks, 2, 0, part, c->d_scratch + CN_OFF_SUMS);
     MTD_LAUNCH_CHECK();
     *d_sums = c->d_scratch + CN_OFF_SUMS;
     *n_sums = 2;
@@ -401,7 +370,7 @@ int mtd_coord_finalize(const mtd_coord_params *p, const mtd_coord_call *c, const
     if (rc) return rc;
     k_cn_finalize<<<1, MTD_WAVE, 0, (hipStream_t)c->stream>>>(c->d_scratch);
     MTD_LAUNCH_CHECK();
-    const size_t pitch = cn_pitch(c->n_particles);
+    const size_t pitch = row_pitch(c->n_particles);
     *d_value = c->d_scratch + CN_OFF_VALUE;
     if (d_local) *d_local = c->d_scratch + CN_OFF_PER_PARTICLE + CN_ROW_N * pitch;
     if (d_switched) *d_switched = c->d_scratch + CN_OFF_PER_PARTICLE + CN_ROW_V * pitch;
@@ -420,21 +389,11 @@ int mtd_coord_forces(const mtd_coord_params *p, const mtd_coord_call *c, void *d
     if (rc) return rc;
     if (c->n_particles == 0) return MTD_SUCCESS;
     hipStream_t s = (hipStream_t)c->stream;
-    const size_t pitch = cn_pitch(c->n_particles);
+    const size_t pitch = row_pitch(c->n_particles);
     if (!p->switch_on)
         {
-        const unsigned int blocks = (c->n_particles + CN_THREADS - 1) / CN_THREADS;
-        dispatch_s4(c->dtype, [&](auto t)
-            {
-            return dispatch_bool(d_virial != nullptr, [&](auto vir)
-                {
-                typedef typename decltype(t)::type S4;
-                typedef typename scalar4_traits<S4>::scalar scalar;
-                k_cn_scale<S4, decltype(vir)::value><<<blocks, CN_THREADS, 0, s>>>(c->n_particles, c->d_scratch, pitch, (S4 *)d_force, d_bias,
-                                                                                    bias_host, (scalar *)d_virial, virial_pitch);
-                return 0;
-                });
-            });
+        row_scale(c->dtype, c->n_particles, c->d_scratch + CN_OFF_PER_PARTICLE + CN_ROW_GRAD * pitch, pitch, c->d_scratch + CN_OFF_NA, 0.0, -1.0, -0.5,
+                  d_force, d_bias, bias_host, d_virial, virial_pitch, s);
         MTD_LAUNCH_CHECK();
         return MTD_SUCCESS;
         }

@@ -26,9 +26,10 @@
 //                                                               unscaled (N_t and the bias are not known yet)
 //                      <1, 0, 0, 0>                             mtd_dsf_accumulate after mtd_dsf_set_store_gradient(0)
 //                      <0, 1, VIR, 0>                           mtd_dsf_forces after the same: a second walk, force and virial scaled
-//   k_dsf_scale      mtd_dsf_forces by default: one thread per particle scales the stored sums by -2 bias / N_t and -bias / N_t
+//   k_row_scale      (row_scale.hpp) mtd_dsf_forces by default: one thread per particle scales the stored sums by -2 bias / N_t and
+//                    -bias / N_t
 //   Storing wins because the second walk repeats every sine and cosine: profiles/r24/README.md has both timings.
-//   k_dsf_sums       one wave per slot adds the blocks' doubles in the fixed order of wave_sum (as k_pe_sums)
+//   k_row_sums       (row_walk.hpp) one wave per slot adds the blocks' doubles in the fixed order of wave_sum
 //   k_dsf_finalize   I_p and s from the (reduced) sums
 //   k_dsf_spectrum   the diagnostic.  blockIdx.y takes EIGHT consecutive Q_m; per entry the window, sin and cos of Q_m0 r and of
 //                    dQ r, then seven angle additions (at most seven steps from a directly evaluated pair: the recurrence adds
@@ -36,9 +37,8 @@
 // Fixed summation order everywhere (a lane's entries in row order, the DPP tree of group_sum, a thread's chunks in order, block_sum,
 // wave_sum), no atomics: two identical calls give identical bits, and a row gives the same bits wherever it lies in the list.
 #include "mtd_device.hpp"
-#include "row_walk.hpp"
+#include "row_scale.hpp"
 #include "debye_device.hpp"
-#include "dispatch.hpp"
 
 #include <atomic>
 #include <cmath>
@@ -52,7 +52,7 @@ using namespace mtd;
 constexpr int DSF_THREADS = 256;
 constexpr int DSF_G = 8;                                   // lanes per central particle
 constexpr int DSF_PPB = DSF_THREADS / DSF_G;               // central particles per block and round
-constexpr unsigned int DSF_MAX_BLOCKS = 1024;              // columns of block sums in the scratch
+constexpr unsigned int DSF_MAX_BLOCKS = ROW_MAX_BLOCKS;    // columns of block sums in the scratch
 constexpr int DSF_TILE = 8;                                // wave numbers of the spectrum per block row
 
 // the scratch, in doubles: sums [16] | value, N_t [2] | I_p [8] | (pad) | spectrum sums [258] | spectrum [256] | block sums [257][DSF_MAX_BLOCKS]
@@ -60,8 +60,6 @@ constexpr int DSF_TILE = 8;                                // wave numbers of th
 constexpr size_t DSF_OFF_SUMS = 0, DSF_OFF_VALUE = 16, DSF_OFF_NT = 17, DSF_OFF_I = 18, DSF_OFF_SPEC_SUMS = 32,
                  DSF_OFF_SPEC = DSF_OFF_SPEC_SUMS + MTD_DSF_MAX_SPECTRUM + 2, DSF_OFF_PART = DSF_OFF_SPEC + MTD_DSF_MAX_SPECTRUM,
                  DSF_OFF_PER_PARTICLE = DSF_OFF_PART + (size_t)(MTD_DSF_MAX_SPECTRUM + 1) * DSF_MAX_BLOCKS;
-
-inline size_t dsf_pitch(unsigned int n_particles) { return ((size_t)n_particles + 1) & ~(size_t)1; }
 
 template<int P> struct DsfArgs
     {
@@ -209,19 +207,6 @@ __global__ __launch_bounds__(DSF_THREADS) void k_dsf_walk(const QlArgs<4> a_in, 
         }
     }
 
-// one wave per slot: the blocks' values in the fixed order of wave_sum; slot `from[k]` of the block sums goes to sums[k]
-__global__ __launch_bounds__(MTD_WAVE) void k_dsf_sums(const unsigned int n_blocks, const unsigned int n_live, const unsigned int count_row,
-                                                       const double *__restrict__ part, double *__restrict__ sums)
-    {
-    // the slots [0, n_live) are rows [0, n_live) of the block sums; slot n_live is the count, kept in row `count_row`
-    const unsigned int src = blockIdx.x < n_live ? blockIdx.x : count_row;
-    const double *row = part + (size_t)src * DSF_MAX_BLOCKS;
-    double v = 0.0;
-    for (unsigned int k = threadIdx.x; k < n_blocks; k += MTD_WAVE) v += row[k];
-    v = wave_sum(v);
-    if (threadIdx.x == 0) sums[blockIdx.x] = v;
-    }
-
 struct DsfPeaks
     {
     double c[MTD_DSF_MAX_Q];
@@ -241,25 +226,6 @@ __global__ __launch_bounds__(MTD_WAVE) void k_dsf_finalize(const DsfPeaks pk, do
         }
     scratch[DSF_OFF_VALUE] = value;
     scratch[DSF_OFF_NT] = n_t;
-    }
-
-// the stored sums of every particle -> force and virial
-template<typename S4, bool VIR>
-__global__ __launch_bounds__(DSF_THREADS) void k_dsf_scale(const unsigned int N, const double *__restrict__ scratch, const size_t pitch,
-                                                           S4 *__restrict__ force, const double *__restrict__ d_bias, const double bias_host,
-                                                           typename scalar4_traits<S4>::scalar *__restrict__ virial, const unsigned int virial_pitch)
-    {
-    typedef typename scalar4_traits<S4>::scalar scalar;
-    const unsigned int i = blockIdx.x * DSF_THREADS + threadIdx.x;
-    if (i >= N) return;
-    const double n_t = scratch[DSF_OFF_NT];
-    const double bias = d_bias ? *d_bias : bias_host;
-    const double scale_f = n_t > 0.0 ? -2.0 * bias / n_t : 0.0, scale_v = n_t > 0.0 ? -bias / n_t : 0.0;
-    const double *o = scratch + DSF_OFF_PER_PARTICLE + pitch + i;
-    nt_store(scalar4_traits<S4>::make((scalar)(o[0] * scale_f), (scalar)(o[pitch] * scale_f), (scalar)(o[2 * pitch] * scale_f), (scalar)0), force + i);
-    if constexpr (VIR)
-        row_store_virial<false>(virial + i, virial_pitch, o[3 * pitch], o[4 * pitch], o[5 * pitch], o[6 * pitch], o[7 * pitch], o[8 * pitch], scale_v,
-                                0.0);
     }
 
 // ---- the spectrum ----------------------------------------------------------------------------------------------------------------
@@ -422,7 +388,7 @@ extern "C" {
 
 size_t mtd_dsf_scratch_doubles(unsigned int n_particles)
     {
-    return DSF_OFF_PER_PARTICLE + 10 * dsf_pitch(n_particles);
+    return DSF_OFF_PER_PARTICLE + 10 * row_pitch(n_particles);
     }
 
 int mtd_dsf_set_store_gradient(int enable)
@@ -442,7 +408,7 @@ int mtd_dsf_accumulate(const mtd_dsf_params *p, const mtd_dsf_call *c, double **
     hipStream_t s = (hipStream_t)c->stream;
     const unsigned int blocks = row_blocks(c->n_particles, DSF_PPB, DSF_MAX_BLOCKS);
     double *part = c->d_scratch + DSF_OFF_PART, *per_particle = c->d_scratch + DSF_OFF_PER_PARTICLE;
-    const size_t pitch = dsf_pitch(c->n_particles);
+    const size_t pitch = row_pitch(c->n_particles);
     const bool store = g_store_gradient.load() != 0;
     unsigned int P_compiled = 0;
     dispatch_s4(c->dtype, [&](auto t)
@@ -463,7 +429,7 @@ int mtd_dsf_accumulate(const mtd_dsf_params *p, const mtd_dsf_call *c, double **
             });
         });
     MTD_LAUNCH_CHECK();
-    k_dsf_sums<<<p->n_q + 1, MTD_WAVE, 0, s>>>(blocks, p->n_q, P_compiled, part, c->d_scratch + DSF_OFF_SUMS);
+    k_row_sums<DSF_MAX_BLOCKS><<<p->n_q + 1, MTD_WAVE, 0, s>>>(blocks, p->n_q, P_compiled, part, c->d_scratch + DSF_OFF_SUMS);
     MTD_LAUNCH_CHECK();
     *d_sums = c->d_scratch + DSF_OFF_SUMS;
     *n_sums = p->n_q + 1;
@@ -499,21 +465,11 @@ int mtd_dsf_forces(const mtd_dsf_params *p, const mtd_dsf_call *c, void *d_force
     if (rc) return rc;
     if (c->n_particles == 0) return MTD_SUCCESS;
     hipStream_t s = (hipStream_t)c->stream;
-    const size_t pitch = dsf_pitch(c->n_particles);
+    const size_t pitch = row_pitch(c->n_particles);
     if (g_store_gradient.load() != 0)
         {
-        const unsigned int blocks = (c->n_particles + DSF_THREADS - 1) / DSF_THREADS;
-        dispatch_s4(c->dtype, [&](auto t)
-            {
-            return dispatch_bool(d_virial != nullptr, [&](auto vir)
-                {
-                typedef typename decltype(t)::type S4;
-                typedef typename scalar4_traits<S4>::scalar scalar;
-                k_dsf_scale<S4, decltype(vir)::value><<<blocks, DSF_THREADS, 0, s>>>(c->n_particles, c->d_scratch, pitch, (S4 *)d_force, d_bias,
-                                                                                      bias_host, (scalar *)d_virial, virial_pitch);
-                return 0;
-                });
-            });
+        row_scale(c->dtype, c->n_particles, c->d_scratch + DSF_OFF_PER_PARTICLE + pitch, pitch, c->d_scratch + DSF_OFF_NT, 0.0, -2.0, -1.0, d_force,
+                  d_bias, bias_host, d_virial, virial_pitch, s);
         MTD_LAUNCH_CHECK();
         return MTD_SUCCESS;
         }
@@ -561,7 +517,7 @@ int mtd_dsf_spectrum(const mtd_dsf_params *p, const mtd_dsf_call *c, double q_mi
         return 0;
         });
     MTD_LAUNCH_CHECK();
-    k_dsf_sums<<<n_q + 1, MTD_WAVE, 0, s>>>(blocks, n_q, MTD_DSF_MAX_SPECTRUM, part, c->d_scratch + DSF_OFF_SPEC_SUMS);
+    k_row_sums<DSF_MAX_BLOCKS><<<n_q + 1, MTD_WAVE, 0, s>>>(blocks, n_q, MTD_DSF_MAX_SPECTRUM, part, c->d_scratch + DSF_OFF_SPEC_SUMS);
     MTD_LAUNCH_CHECK();
     *d_sums = c->d_scratch + DSF_OFF_SPEC_SUMS;
     *n_sums = n_q + 1;

@@ -27,13 +27,12 @@
 //                    if that environment is closed (FUSED) the same Gaussians give sum_j G_kj and the six sums of G_a d_b, nine doubles per
 //                    particle in the scratch, and the step walks the rows ONCE (the general path with its second Gaussian ran out of scalar
 //                    registers in this form and keeps two walks)
-//   k_es_scale       FUSED: force and virial are those sums times -bias / N_global, one lane per particle
+//   k_row_scale      (row_scale.hpp) FUSED: force and virial are those sums times -bias / N_global, one lane per particle
 //   k_es_forces      otherwise: a gather over row k that reads beta_j (<= 4 doubles) per entry — not at all when beta is 1 everywhere
 //                    (CONSTB; ghost neighbours then need no table).  Fixed summation order, no atomics; the four lanes' sums are added by
 //                    two DPP moves.  VIR adds the six sums -1/2 G_a d_b; VIR = false is the kernel without them
 #include "mtd_device.hpp"
-#include "row_walk.hpp"
-#include "dispatch.hpp"
+#include "row_scale.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -46,13 +45,12 @@ using namespace mtd;
 constexpr int ES_THREADS = 256;
 constexpr int ES_G = 4;                                    // lanes per central particle
 constexpr int ES_PPB = ES_THREADS / ES_G;                  // central particles per block and round
-constexpr unsigned int ES_MAX_BLOCKS = 1024;               // block sums in the scratch
+constexpr unsigned int ES_MAX_BLOCKS = ROW_MAX_BLOCKS;     // block sums in the scratch
 constexpr unsigned int ES_MAX_PER_ENV = 32;
 
 // the scratch, in doubles, with n = n_particles rounded up to even:
 //     k^e_i [n][4] | beta^e_i [n][4] | k_i [n] | v_i [n] | block sums [ES_MAX_BLOCKS] | FUSED: sum_j G_kj and sum_j G_a d_b [9][n]
 constexpr int ES_N_GSUMS = 9;
-__host__ __device__ inline size_t es_even(const unsigned int n) { return ((size_t)n + 1) & ~(size_t)1; }
 
 struct EsArgs
     {
@@ -156,7 +154,7 @@ __global__ __launch_bounds__(ES_THREADS) void k_es_accumulate(const QlArgs<4> a_
     const double neg_inv4s2 = in_vgpr(p.neg_inv4s2), cs = in_vgpr(p.c);
     const unsigned int tid = threadIdx.x, g = tid / ES_G, q = tid % ES_G;
     const unsigned int n_chunks = (a.N + ES_PPB - 1) / ES_PPB;
-    const size_t n_even = es_even(a.N);
+    const size_t n_even = row_pitch(a.N);
     asm volatile("" : "+v"(scratch));                            // (the output pointers in vector registers: they are used once per particle)
     double *__restrict__ out_ke = scratch, *__restrict__ out_beta = scratch + 4 * n_even, *__restrict__ out_k = scratch + 8 * n_even,
                         *__restrict__ out_v = scratch + 9 * n_even, *__restrict__ part = scratch + 10 * n_even,
@@ -267,29 +265,8 @@ __global__ __launch_bounds__(ES_THREADS) void k_es_accumulate(const QlArgs<4> a_
     if (tid == 0) part[blockIdx.x] = v_sum;
     }
 
-// ---- pass 2, FUSED: the sums of pass 1 times -bias / N_global ------------------------------------------------------------------------
-template<typename S4, bool VIR>
-__global__ __launch_bounds__(ES_THREADS) void k_es_scale(const unsigned int N, const unsigned int n_global, const double *__restrict__ scratch,
-                                                         S4 *__restrict__ force, const double *__restrict__ d_bias, const double bias_host,
-                                                         typename scalar4_traits<S4>::scalar *__restrict__ virial, const unsigned int virial_pitch)
-    {
-    typedef typename scalar4_traits<S4>::scalar scalar;
-    const size_t n_even = es_even(N);
-    const double *__restrict__ gsum = scratch + 10 * n_even + ES_MAX_BLOCKS;
-    const double scale = -(d_bias ? *d_bias : bias_host) / (double)n_global;
-    const unsigned int i = blockIdx.x * ES_THREADS + threadIdx.x;
-    if (i >= N) return;
-    nt_store(scalar4_traits<S4>::make((scalar)(gsum[i] * scale), (scalar)(gsum[n_even + i] * scale), (scalar)(gsum[2 * n_even + i] * scale), (scalar)0),
-             force + i);
-    if constexpr (VIR)
-        {
-        const double h = -0.5 * scale;
-#pragma unroll
-        for (int c = 0; c < 6; ++c) nt_store((scalar)(gsum[(3 + c) * n_even + i] * h), virial + c * (size_t)virial_pitch + i);
-        }
-    }
-
-// ---- pass 2, otherwise: the gather over row k (CONSTB: beta = 1 with an environment that is not closed; never with CLOSED) -------------
+// ---- pass 2 (FUSED: k_row_scale of row_scale.hpp, the sums of pass 1 times -bias / N_global); otherwise: the gather over row k
+// (CONSTB: beta = 1 with an environment that is not closed; never with CLOSED) ------------------------------------------------------------
 template<typename S4, bool VIR, bool CLOSED, bool CONSTB>
 __global__ __launch_bounds__(ES_THREADS) void k_es_forces(const QlArgs<4> a_in, const EsArgs p, const EsTable T, const S4 *__restrict__ postype,
                                                           const unsigned int *__restrict__ head_list, const unsigned int *__restrict__ n_neigh,
@@ -304,7 +281,7 @@ __global__ __launch_bounds__(ES_THREADS) void k_es_forces(const QlArgs<4> a_in, 
     const double neg_inv4s2 = in_vgpr(p.neg_inv4s2), cs = in_vgpr(p.c);
     const unsigned int tid = threadIdx.x, g = tid / ES_G, q = tid % ES_G;
     const unsigned int n_chunks = (a.N + ES_PPB - 1) / ES_PPB;
-    const double *__restrict__ beta = scratch + 4 * es_even(a.N);
+    const double *__restrict__ beta = scratch + 4 * row_pitch(a.N);
     es_load_table(T, s_t);
     const int n_env = (int)p.n_env;
     const double scale = in_vgpr(-(d_bias ? *d_bias : bias_host) / (double)a.n_global);
@@ -448,7 +425,7 @@ extern "C" {
 
 size_t mtd_es_scratch_doubles(unsigned int n_particles)
     {
-    return (10 + ES_N_GSUMS) * es_even(n_particles) + ES_MAX_BLOCKS;
+    return (10 + ES_N_GSUMS) * row_pitch(n_particles) + ES_MAX_BLOCKS;
     }
 
 int mtd_es_accumulate(unsigned int n_particles, unsigned int n_ghost, const void *d_postype, int dtype, const mtd_box *box,
@@ -478,7 +455,7 @@ int mtd_es_accumulate(unsigned int n_particles, unsigned int n_ghost, const void
             });
         });
     MTD_LAUNCH_CHECK();
-    const size_t n = es_even(n_particles);
+    const size_t n = row_pitch(n_particles);
     *d_partials = d_scratch + 10 * n;
     *n_partials = blocks;
     if (d_ke) *d_ke = d_scratch;
@@ -501,6 +478,15 @@ int mtd_es_forces(unsigned int n_particles, unsigned int n_ghost, const void *d_
     hipStream_t s = (hipStream_t)stream;
     const double *tab = ql_device_table<4>(s, rc);
     if (rc) return rc;
+    // mtd_es_accumulate has left the gradient sums (FUSED): one lane per particle scales them by -bias / N_global and bias / (2 N_global)
+    if (su.const_beta && su.closed)
+        {
+        const size_t pitch = row_pitch(n_particles);
+        row_scale(dtype, n_particles, d_scratch + 10 * pitch + ROW_MAX_BLOCKS, pitch, nullptr, (double)n_global, -1.0, 0.5, d_force, d_bias,
+                  bias_host, d_virial, virial_pitch, s);
+        MTD_LAUNCH_CHECK();
+        return MTD_SUCCESS;
+        }
     const unsigned int blocks = row_blocks(n_particles, ES_PPB, ES_MAX_BLOCKS);
     dispatch_s4(dtype, [&](auto t)
         {
@@ -508,13 +494,6 @@ int mtd_es_forces(unsigned int n_particles, unsigned int n_ghost, const void *d_
             {
             typedef typename decltype(t)::type S4;
             typedef typename scalar4_traits<S4>::scalar scalar;
-            // mtd_es_accumulate has left the gradient sums: one lane per particle scales them
-            if (su.const_beta && su.closed)
-                {
-                k_es_scale<S4, decltype(vir)::value><<<(n_particles + ES_THREADS - 1) / ES_THREADS, ES_THREADS, 0, s>>>(
-                    n_particles, n_global, d_scratch, (S4 *)d_force, d_bias, bias_host, (scalar *)d_virial, virial_pitch);
-                return 0;
-                }
             const auto gather = [&](auto closed, auto constb)
                 {
                 k_es_forces<S4, decltype(vir)::value, decltype(closed)::value, decltype(constb)::value><<<blocks, ES_THREADS, 0, s>>>(

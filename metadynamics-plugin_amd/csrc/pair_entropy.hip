@@ -25,7 +25,7 @@
 //                    the block first counts the entries E of the rows it will walk (an upper bound of its adds per bin), takes
 //                    2^x > E K(0) and scales by 2^(62 - x), so a bin stays below 2^62 + E / 2 < 2^63.  The image is converted back
 //                    (exact: a power of two) and stored as one double per bin and block, bin-major
-//   k_pe_sums        one wave per bin adds the blocks' doubles in the fixed order of wave_sum: H_0 .. H_{B-1} and N_t (slot B, a count:
+//   k_row_sums       (row_walk.hpp) one wave per bin adds the blocks' doubles in the fixed order of wave_sum: H_0 .. H_{B-1} and N_t (slot B, a count:
 //                    exact) as doubles, ready for the all-reduce of a domain-decomposed run
 //   k_pe_finalize    one block: g_b, S, W_b, the explicit volume derivative, N_t; block sums in the fixed order of block_sum
 //   k_pe_forces      a gather over row k with the pairs (W_b, W_b r_b) in LDS (4 KB, a zero pair at either end), so that a bin costs one
@@ -52,7 +52,7 @@ constexpr int PE_THREADS = 256;
 constexpr int PE_G = 8;                                    // lanes per central particle
 constexpr int PE_PPB = PE_THREADS / PE_G;                  // central particles per block and round
 constexpr unsigned int PE_MAX_BINS = 256;
-constexpr unsigned int PE_MAX_BLOCKS = 1024;               // columns of block sums in the scratch
+constexpr unsigned int PE_MAX_BLOCKS = ROW_MAX_BLOCKS;     // columns of block sums in the scratch
 constexpr double PE_G_MIN = 1e-10;
 
 // the scratch, in doubles: sums [258] | value, explicit volume derivative, N_t, (pad) [4] | g [256] | (W_b, W_b r_b) [256][2] | block sums [257][PE_MAX_BLOCKS]
@@ -103,16 +103,6 @@ __global__ __launch_bounds__(PE_THREADS) void k_pe_accumulate(const QlArgs<4> a_
     __syncthreads();
     for (unsigned int b = tid; b <= p.B; b += PE_THREADS)
         part[(size_t)b * PE_MAX_BLOCKS + blockIdx.x] = b < p.B ? (double)s_h[b] * inv_scale : (double)s_h[b];
-    }
-
-// one wave per slot: the blocks' values in the fixed order of wave_sum
-__global__ __launch_bounds__(MTD_WAVE) void k_pe_sums(const unsigned int n_blocks, const double *__restrict__ part, double *__restrict__ sums)
-    {
-    const double *row = part + (size_t)blockIdx.x * PE_MAX_BLOCKS;
-    double v = 0.0;
-    for (unsigned int k = threadIdx.x; k < n_blocks; k += MTD_WAVE) v += row[k];
-    v = wave_sum(v);
-    if (threadIdx.x == 0) sums[blockIdx.x] = v;
     }
 
 // ---- g_b, S, W_b, the explicit volume derivative ------------------------------------------------------------------------------
@@ -298,7 +288,7 @@ int mtd_pe_accumulate(unsigned int n_particles, const void *d_postype, int dtype
         return 0;
         });
     MTD_LAUNCH_CHECK();
-    k_pe_sums<<<n_bins + 1, MTD_WAVE, 0, s>>>(blocks, part, d_scratch + PE_OFF_SUMS);
+    k_row_sums<PE_MAX_BLOCKS><<<n_bins + 1, MTD_WAVE, 0, s>>>(blocks, n_bins + 1, 0, part, d_scratch + PE_OFF_SUMS);
     MTD_LAUNCH_CHECK();
     *d_sums = d_scratch + PE_OFF_SUMS;
     *n_sums = n_bins + 1;

@@ -51,14 +51,13 @@ using namespace mtd;
 constexpr int PEL_THREADS = 256;
 constexpr int PEL_G = 8;                                   // lanes per central particle
 constexpr int PEL_PPB = PEL_THREADS / PEL_G;               // central particles per block and round
-constexpr unsigned int PEL_MAX_BLOCKS = 1024;              // columns of block sums in the scratch
+constexpr unsigned int PEL_MAX_BLOCKS = ROW_MAX_BLOCKS;    // columns of block sums in the scratch
 constexpr double PEL_G_MIN = 1e-10;
 
 // the scratch, in doubles, with n = n_particles rounded up to even:
 //     block counts of N_t [1024] | block sums of v_i [1024] | s [n] | sbar [n] | v [n] | gn [n] | alpha [n] | X [n] | W [n_particles][B]
 constexpr size_t PEL_OFF_CNT = 0, PEL_OFF_PART = PEL_MAX_BLOCKS, PEL_OFF_ARR = 2 * (size_t)PEL_MAX_BLOCKS;
 constexpr int PEL_N_ARR = 6;
-__host__ __device__ inline size_t pel_even(const unsigned int n) { return ((size_t)n + 1) & ~(size_t)1; }
 
 struct PelOpt
     {
@@ -75,7 +74,7 @@ struct PelArrays
 
 __host__ __device__ inline PelArrays pel_arrays(double *scratch, const unsigned int N)
     {
-    const size_t n = pel_even(N);
+    const size_t n = row_pitch(N);
     double *a = scratch + PEL_OFF_ARR;
     return {a, a + n, a + 2 * n, a + 3 * n, a + 4 * n, a + 5 * n, a + PEL_N_ARR * n};
     }
@@ -442,7 +441,7 @@ extern "C" {
 
 size_t mtd_pel_scratch_doubles(unsigned int n_particles, unsigned int n_bins)
     {
-    return PEL_OFF_ARR + PEL_N_ARR * pel_even(n_particles) + (size_t)n_particles * n_bins;
+    return PEL_OFF_ARR + PEL_N_ARR * row_pitch(n_particles) + (size_t)n_particles * n_bins;
     }
 
 int mtd_pel_accumulate(const mtd_pel_params *par, const mtd_pel_call *c, const double **d_partials, unsigned int *n_partials,

@@ -1,16 +1,19 @@
-// row_walk.hpp — the lane-group walk over one row of a full neighbour list, written once (device; steinhardt_local.hip, pair_entropy.hip,
-// env_similarity.hip, debye.hip, coordination.hip).
+// row_walk.hpp — the lane-group walk over one row of a full neighbour list, written once (device; steinhardt_local.hip, cluster.hip,
+// pair_entropy.hip, pair_entropy_local.hip, env_similarity.hip, debye.hip, coordination.hip; the scaling of stored gradient sums, which
+// three of them share, is in row_scale.hpp).
 //
 // G lanes (a DPP quad, or half a DPP row) share one central particle; lane q takes entries q, q + G, ... of its row.  Here: the centre of
 // a group (RowCentre / row_centre), the walk itself with its look-ahead (row_walk), the group's sum (group_sum), the zero that keeps the
 // smoothing table's loads inside a loop (loop_table), the moves of wave-uniform constants into vector registers (in_vgpr), the store of a
-// particle's virial by lane 0 of its group (row_store_virial) and the block count of a launch (row_blocks).  Everything is
-// __forceinline__ and holds no state of its own: a kernel that uses a piece has the instruction stream of the kernel that wrote it out
-// (profiles/r20/README.md compares them kernel by kernel).
+// particle's virial by lane 0 of its group (row_store_virial), the block count of a launch (row_blocks) with the width of a table of
+// block sums (ROW_MAX_BLOCKS), the kernel that adds such a table up (k_row_sums) and the pitch of per-particle rows in a scratch
+// (row_pitch).  Everything a walk kernel calls is __forceinline__ and holds no state of its own: a kernel that uses a piece has the
+// instruction stream of the kernel that wrote it out (profiles/r20/README.md and profiles/r26/README.md compare them kernel by kernel).
 //
 // The walk lives in FOUR forms, and a change to the look-ahead, the list format or the skip rule is made in all of them:
-//   row_walk                   here: both passes of pair_entropy.hip and of env_similarity.hip; as row_walk_entries<.., GHOSTS = false>
-//                              the link pass of cluster.hip (local entries only: the rule of QllWalker, switched at compile time)
+//   row_walk                   here: both passes of pair_entropy.hip and of env_similarity.hip, the walk and the spectrum of debye.hip; as
+//                              row_walk_entries<.., GHOSTS = false> the passes of pair_entropy_local.hip and the link pass of cluster.hip
+//                              (local entries only: the rule of QllWalker, switched at compile time)
 //   QllWalker                  steinhardt_local.hip: its four gather passes, through qll_entries
 //   three loops written out    k_qll_accumulate, k_qll_forces and k_qll_forces_tile of steinhardt_local.hip (through a walker their bits
 //                              or their speed did not stay the parent's: profiles/r10/README.md)
@@ -232,6 +235,29 @@ __device__ __forceinline__ void row_walk_pairs(const QlArgs<4> &a, const unsigne
         pos0 = pos1;
         }
     }
+
+// columns of a unit's table of block sums [row][ROW_MAX_BLOCKS] in its scratch; each unit's own name for it stays, as an alias, in the
+// bodies of its walk kernels
+constexpr unsigned int ROW_MAX_BLOCKS = 1024;
+
+// One wave per slot adds the blocks' doubles of such a table in the fixed order of wave_sum: lane k takes the columns k, k + 64, ...
+// The slots [0, n_live) are rows [0, n_live) of the table; a slot from n_live on is the count, kept in row `count_row` (debye.hip: behind
+// the rows of the COMPILED peak count).  With n_live = gridDim.x slot b is row b (pair_entropy.hip, coordination.hip).  MAX_BLOCKS is the
+// unit's alias of ROW_MAX_BLOCKS; a template, so that only a unit that launches it holds a copy.
+template<unsigned int MAX_BLOCKS>
+static __global__ __launch_bounds__(MTD_WAVE) void k_row_sums(const unsigned int n_blocks, const unsigned int n_live, const unsigned int count_row,
+                                                              const double *__restrict__ part, double *__restrict__ sums)
+    {
+    const unsigned int src = blockIdx.x < n_live ? blockIdx.x : count_row;
+    const double *row = part + (size_t)src * MAX_BLOCKS;
+    double v = 0.0;
+    for (unsigned int k = threadIdx.x; k < n_blocks; k += MTD_WAVE) v += row[k];
+    v = wave_sum(v);
+    if (threadIdx.x == 0) sums[blockIdx.x] = v;
+    }
+
+// pitch, in doubles, of the per-particle rows in a scratch: n_particles rounded up to even, so that every row is 16-byte aligned
+__host__ __device__ inline size_t row_pitch(const unsigned int n) { return ((size_t)n + 1) & ~(size_t)1; }
 
 // blocks of a launch that walks `ppb` central particles per block and round: one per chunk, at least one, at most `max_blocks` (the
 // columns of block sums a unit's scratch holds)

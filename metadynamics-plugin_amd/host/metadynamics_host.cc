@@ -758,13 +758,13 @@ double SteinhardtQl::getLogValue(const std::string &quantity, unsigned int times
     }
 
 // ------------------------------------------------------------------------------------------------
-// NeighbourVariable: what SteinhardtLocal, PairEntropy and EnvironmentSimilarity share
+// NeighbourVariable: what the six variables that walk the rows of a full neighbour list share
 // ------------------------------------------------------------------------------------------------
 
 NeighbourVariable::NeighbourVariable(std::shared_ptr<SystemDefinition> sysdef, const char *kind, const std::string &log_suffix,
                                      std::shared_ptr<NeighborList> nlist, unsigned int type)
     : CollectiveVariable(sysdef, kind + log_suffix), m_prefix(std::string("cv.") + kind + ": "), m_nlist(nlist), m_type(type),
-      m_cv_last_updated(0), m_have_computed(false)
+      m_d_value(nullptr), m_cv_last_updated(0), m_have_computed(false)
     {
     }
 
@@ -784,6 +784,55 @@ NeighbourVariable::Lists NeighbourVariable::lists() const
     {
     return {(const unsigned int *)m_nlist->getHeadList().data(), (const unsigned int *)m_nlist->getNNeighArray().data(),
             (const unsigned int *)m_nlist->getNListArray().data()};
+    }
+
+mtd_row_call NeighbourVariable::rowCall(const mtd_box *box) const
+    {
+    const Lists l = lists();
+    mtd_row_call c;
+    c.n_particles = m_pdata->getN();
+    c.n_ghost = m_pdata->getNGhosts();
+    c.d_postype = m_pdata->positionsPtr();
+    c.dtype = m_pdata->getDtype();
+    c.box = box;
+    c.d_head_list = l.head;
+    c.d_n_neigh = l.n_neigh;
+    c.d_nlist = l.nlist;
+    c.d_scratch = (double *)m_scratch.data();
+    c.stream = m_exec_conf->getStream();
+    return c;
+    }
+
+void NeighbourVariable::growScratch(size_t bytes)
+    {
+    if (bytes <= m_scratch.bytes()) return;
+    m_scratch.resize(bytes);
+    invalidate();
+    }
+
+void NeighbourVariable::reduceOverRanks(double *d_sums, unsigned int n_sums)
+    {
+    if (distributed()) m_exec_conf->allreduceSmall(d_sums, n_sums, m_exec_conf->getStream());
+    }
+
+NeighbourVariable::ForcePass::ForcePass(NeighbourVariable &cv, unsigned int timestep) : range("Force")
+    {
+    if (!cv.fresh(timestep)) cv.computeCV(timestep);                 // what the force pass reads of THIS step's positions
+    cv.m_nlist->compute(timestep);
+    box = cv.m_pdata->getBox().toMtd();
+    virial = cv.virialTarget();                                      // constant pressure: the per-particle virial of the bias force beside it
+    }
+
+double NeighbourVariable::getCurrentValue(unsigned int timestep)
+    {
+    computeCV(timestep);                                             // (sets the pointer: before it is handed on, here and below)
+    return readValue(m_d_value, timestep);
+    }
+
+void NeighbourVariable::enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot)
+    {
+    computeCV(timestep);
+    mtd_check(mtd_metad_set_cv_source(engine, slot, m_d_value, 1, 1, 0, 1.0, 0.0), "mtd_metad_set_cv_source");
     }
 
 std::vector<double> NeighbourVariable::readBack(const double *d_src, size_t n, const char *what, unsigned int timestep)
@@ -857,7 +906,7 @@ void SteinhardtLocal::computeCV(unsigned int timestep)
     // (never shrinks)
     const size_t need = sizeof(double) * mtd_ql_local_scratch_doubles_bonds(m_pdata->getN(), m_lmax,
                                                                             m_nlist->getNListArray().bytes() / sizeof(unsigned int), &m_opt, &m_bonds);
-    if (need > m_scratch.bytes()) m_scratch.resize(need);
+    growScratch(need);
     if (m_cluster.on)
         {
         requireReach(m_cluster.r_link, "r_link");
@@ -970,15 +1019,11 @@ double SteinhardtLocal::getCurrentValue(unsigned int timestep)
 
 void SteinhardtLocal::computeBiasForces(unsigned int timestep)
     {
-    ProfRange prof_range("Force");
-    if (!fresh(timestep)) computeCV(timestep);                       // the table of THIS step's positions
-    m_nlist->compute(timestep);
-    const mtd_box box = m_pdata->getBox().toMtd();
+    const ForcePass f(*this, timestep);                              // (the table of THIS step's positions)
     const Lists l = lists();
-    void *virial = virialTarget();                                   // constant pressure: the per-particle virial of the bias force beside it
-    mtd_check(mtd_ql_local_forces_bonds(m_pdata->getN(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &box, l.head, l.n_neigh,
+    mtd_check(mtd_ql_local_forces_bonds(m_pdata->getN(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &f.box, l.head, l.n_neigh,
                                         l.nlist, m_rcut, m_ron, m_lmax, m_type, m_Ql_ref.data(), m_pdata->getNGlobal(),
-                                        (const double *)m_scratch.data(), m_bias_device, m_bias, m_exec_conf->getStream(), &m_opt, virial,
+                                        (const double *)m_scratch.data(), m_bias_device, m_bias, m_exec_conf->getStream(), &m_opt, f.virial,
                                         getVirialPitch(), &m_bonds),
               "mtd_ql_local_forces_bonds");
     }
@@ -1045,8 +1090,7 @@ std::vector<double> SteinhardtLocal::getCoordination(unsigned int timestep)
 
 PairEntropy::PairEntropy(std::shared_ptr<SystemDefinition> sysdef, double r_max, double sigma_r, unsigned int n_bins,
                          std::shared_ptr<NeighborList> nlist, unsigned int type, const std::string &log_suffix)
-    : NeighbourVariable(sysdef, "pair_entropy", log_suffix, nlist, type), m_r_max(r_max), m_sigma_r(sigma_r), m_n_bins(n_bins), m_d_value(nullptr),
-      m_d_g(nullptr)
+    : NeighbourVariable(sysdef, "pair_entropy", log_suffix, nlist, type), m_r_max(r_max), m_sigma_r(sigma_r), m_n_bins(n_bins), m_d_g(nullptr)
     {
     if (!nlist) throw std::runtime_error("cv.pair_entropy: a neighbour list is required");
     if (!(r_max > 0.0) || !std::isfinite(r_max) || !(sigma_r > 0.0) || !std::isfinite(sigma_r))
@@ -1071,21 +1115,9 @@ void PairEntropy::computeCV(unsigned int timestep)
                                 m_n_bins, m_type, (double *)m_scratch.data(), &d_sums, &n_sums, s),
               "mtd_pe_accumulate");
     // H_b and N_t over the ranks: the central particles of a rank are its local ones, their neighbours may be ghosts
-    if (distributed()) m_exec_conf->allreduceSmall(d_sums, n_sums, s);
+    reduceOverRanks(d_sums, n_sums);
     mtd_check(mtd_pe_finalize(&box, m_r_max, m_sigma_r, m_n_bins, (double *)m_scratch.data(), &m_d_value, &m_d_g, s), "mtd_pe_finalize");
     computed(timestep);
-    }
-
-void PairEntropy::enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot)
-    {
-    computeCV(timestep);
-    mtd_check(mtd_metad_set_cv_source(engine, slot, m_d_value, 1, 1, 0, 1.0, 0.0), "mtd_metad_set_cv_source");
-    }
-
-double PairEntropy::getCurrentValue(unsigned int timestep)
-    {
-    computeCV(timestep);
-    return readValue(m_d_value, timestep);
     }
 
 std::vector<double> PairEntropy::getGr(unsigned int timestep)
@@ -1096,14 +1128,10 @@ std::vector<double> PairEntropy::getGr(unsigned int timestep)
 
 void PairEntropy::computeBiasForces(unsigned int timestep)
     {
-    ProfRange prof_range("Force");
-    if (!fresh(timestep)) computeCV(timestep);                       // the W_b of THIS step's positions
-    m_nlist->compute(timestep);
-    const mtd_box box = m_pdata->getBox().toMtd();
+    const ForcePass f(*this, timestep);                              // (the W_b of THIS step's positions)
     const Lists l = lists();
-    void *virial = virialTarget();                                   // constant pressure: the per-particle virial of the bias force beside it
-    mtd_check(mtd_pe_forces(m_pdata->getN(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &box, l.head, l.n_neigh, l.nlist, m_r_max,
-                            m_sigma_r, m_n_bins, m_type, (const double *)m_scratch.data(), m_bias_device, m_bias, m_exec_conf->getStream(), virial,
+    mtd_check(mtd_pe_forces(m_pdata->getN(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &f.box, l.head, l.n_neigh, l.nlist, m_r_max,
+                            m_sigma_r, m_n_bins, m_type, (const double *)m_scratch.data(), m_bias_device, m_bias, m_exec_conf->getStream(), f.virial,
                             getVirialPitch()),
               "mtd_pe_forces");
     }
@@ -1177,8 +1205,7 @@ void EnvironmentSimilarity::computeCV(unsigned int timestep)
     requireReach(getRCut(), "r_cut");
     m_nlist->compute(timestep);
     const mtd_box box = m_pdata->getBox().toMtd();
-    const size_t need = sizeof(double) * mtd_es_scratch_doubles(m_pdata->getN());
-    if (need > m_scratch.bytes()) m_scratch.resize(need);
+    growScratch(sizeof(double) * mtd_es_scratch_doubles(m_pdata->getN()));
     const Lists l = lists();
     mtd_check(mtd_es_accumulate(m_pdata->getN(), m_pdata->getNGhosts(), m_pdata->positionsPtr(), m_pdata->getDtype(), &box, l.head, l.n_neigh,
                                 l.nlist, m_type, &m_par, m_pdata->getNGlobal(), (double *)m_scratch.data(), &m_d_partials, &m_n_partials, &m_d_k, &m_d_ke, &m_d_v, m_exec_conf->getStream()),
@@ -1213,14 +1240,10 @@ double EnvironmentSimilarity::getCurrentValue(unsigned int timestep)
 
 void EnvironmentSimilarity::computeBiasForces(unsigned int timestep)
     {
-    ProfRange prof_range("Force");
-    if (!fresh(timestep)) computeCV(timestep);                       // beta of THIS step's positions
-    m_nlist->compute(timestep);
-    const mtd_box box = m_pdata->getBox().toMtd();
+    const ForcePass f(*this, timestep);                              // (beta of THIS step's positions)
     const Lists l = lists();
-    void *virial = virialTarget();                                   // constant pressure: the per-particle virial of the bias force beside it
-    mtd_check(mtd_es_forces(m_pdata->getN(), m_pdata->getNGhosts(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &box, l.head,
-                            l.n_neigh, l.nlist, m_type, &m_par, m_pdata->getNGlobal(), (const double *)m_scratch.data(), m_bias_device, m_bias, m_exec_conf->getStream(), virial, getVirialPitch()),
+    mtd_check(mtd_es_forces(m_pdata->getN(), m_pdata->getNGhosts(), m_pdata->positionsPtr(), m_force.data(), m_pdata->getDtype(), &f.box, l.head,
+                            l.n_neigh, l.nlist, m_type, &m_par, m_pdata->getNGlobal(), (const double *)m_scratch.data(), m_bias_device, m_bias, m_exec_conf->getStream(), f.virial, getVirialPitch()),
               "mtd_es_forces");
     }
 
@@ -1303,19 +1326,8 @@ void PairEntropyLocal::clearSwitch()
 
 mtd_pel_call PairEntropyLocal::call(const mtd_box *box)
     {
-    const Lists l = lists();
-    mtd_pel_call c;
-    c.n_particles = m_pdata->getN();
-    c.n_global = m_pdata->getNGlobal();
-    c.d_postype = m_pdata->positionsPtr();
-    c.dtype = m_pdata->getDtype();
-    c.box = box;
-    c.d_head_list = l.head;
-    c.d_n_neigh = l.n_neigh;
-    c.d_nlist = l.nlist;
-    c.d_scratch = (double *)m_scratch.data();
-    c.stream = m_exec_conf->getStream();
-    return c;
+    const mtd_row_call r = rowCall(box);                             // N_global stands where the others have the ghost count
+    return {r.n_particles, m_pdata->getNGlobal(), r.d_postype, r.dtype, r.box, r.d_head_list, r.d_n_neigh, r.d_nlist, r.d_scratch, r.stream};
     }
 
 void PairEntropyLocal::computeCV(unsigned int timestep)
@@ -1329,8 +1341,7 @@ void PairEntropyLocal::computeCV(unsigned int timestep)
     requireReach(getRCut(), "r_max + 4 sigma_r");
     m_nlist->compute(timestep);
     const mtd_box box = m_pdata->getBox().toMtd();
-    const size_t need = sizeof(double) * mtd_pel_scratch_doubles(m_pdata->getN(), m_par.n_bins);
-    if (need > m_scratch.bytes()) m_scratch.resize(need);
+    growScratch(sizeof(double) * mtd_pel_scratch_doubles(m_pdata->getN(), m_par.n_bins));
     const mtd_pel_call c = call(&box);
     mtd_check(mtd_pel_accumulate(&m_par, &c, &m_d_partials, &m_n_partials, &m_d_s, &m_d_sbar, &m_d_v), "mtd_pel_accumulate");
     computed(timestep);
@@ -1351,13 +1362,9 @@ double PairEntropyLocal::getCurrentValue(unsigned int timestep)
 
 void PairEntropyLocal::computeBiasForces(unsigned int timestep)
     {
-    ProfRange prof_range("Force");
-    if (!fresh(timestep)) computeCV(timestep);                       // W, alpha and s of THIS step's positions
-    m_nlist->compute(timestep);
-    const mtd_box box = m_pdata->getBox().toMtd();
-    const mtd_pel_call c = call(&box);
-    void *virial = virialTarget();                                   // constant pressure: the per-particle virial of the bias force beside it
-    mtd_check(mtd_pel_forces(&m_par, &c, m_force.data(), m_bias_device, m_bias, virial, getVirialPitch()), "mtd_pel_forces");
+    const ForcePass f(*this, timestep);                              // (W, alpha and s of THIS step's positions)
+    const mtd_pel_call c = call(&f.box);
+    mtd_check(mtd_pel_forces(&m_par, &c, m_force.data(), m_bias_device, m_bias, f.virial, getVirialPitch()), "mtd_pel_forces");
     }
 
 std::vector<double> PairEntropyLocal::getLocalValues(unsigned int timestep)
@@ -1384,8 +1391,7 @@ std::vector<double> PairEntropyLocal::getSwitchedValues(unsigned int timestep)
 
 DebyeStructureFactor::DebyeStructureFactor(std::shared_ptr<SystemDefinition> sysdef, const std::vector<double> &q, const std::vector<double> &weights,
                                            double r_cut, std::shared_ptr<NeighborList> nlist, unsigned int type, const std::string &log_suffix)
-    : NeighbourVariable(sysdef, "debye_structure_factor", log_suffix, nlist, type), m_par(), m_d_value(nullptr), m_d_intensity(nullptr),
-      m_d_local(nullptr)
+    : NeighbourVariable(sysdef, "debye_structure_factor", log_suffix, nlist, type), m_par(), m_d_intensity(nullptr), m_d_local(nullptr)
     {
     if (!nlist) throw std::runtime_error("cv.debye_structure_factor: a neighbour list is required");
     if (!(r_cut > 0.0) || !std::isfinite(r_cut)) throw std::runtime_error("cv.debye_structure_factor: r_cut > 0 is required");
@@ -1406,25 +1412,8 @@ DebyeStructureFactor::DebyeStructureFactor(std::shared_ptr<SystemDefinition> sys
 
 mtd_dsf_call DebyeStructureFactor::call(const mtd_box *box)
     {
-    const size_t need = sizeof(double) * mtd_dsf_scratch_doubles(m_pdata->getN());
-    if (need > m_scratch.bytes())                                    // (more particles than at the last call: nothing in the scratch is this step's)
-        {
-        m_scratch.resize(need);
-        invalidate();
-        }
-    const Lists l = lists();
-    mtd_dsf_call c;
-    c.n_particles = m_pdata->getN();
-    c.n_ghost = m_pdata->getNGhosts();
-    c.d_postype = m_pdata->positionsPtr();
-    c.dtype = m_pdata->getDtype();
-    c.box = box;
-    c.d_head_list = l.head;
-    c.d_n_neigh = l.n_neigh;
-    c.d_nlist = l.nlist;
-    c.d_scratch = (double *)m_scratch.data();
-    c.stream = m_exec_conf->getStream();
-    return c;
+    growScratch(sizeof(double) * mtd_dsf_scratch_doubles(m_pdata->getN()));   // (more particles than at the last call)
+    return rowCall(box);
     }
 
 void DebyeStructureFactor::computeCV(unsigned int timestep)
@@ -1439,22 +1428,9 @@ void DebyeStructureFactor::computeCV(unsigned int timestep)
     double *d_sums = nullptr;
     unsigned int n_sums = 0;
     mtd_check(mtd_dsf_accumulate(&m_par, &c, &d_sums, &n_sums), "mtd_dsf_accumulate");
-    // A_p and N_t over the ranks: the central particles of a rank are its local ones, their neighbours may be ghosts
-    if (distributed()) m_exec_conf->allreduceSmall(d_sums, n_sums, m_exec_conf->getStream());
+    reduceOverRanks(d_sums, n_sums);                                 // A_p and N_t: a rank's central particles are its local ones, their neighbours may be ghosts
     mtd_check(mtd_dsf_finalize(&m_par, &c, &m_d_value, &m_d_intensity, &m_d_local), "mtd_dsf_finalize");
     computed(timestep);
-    }
-
-void DebyeStructureFactor::enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot)
-    {
-    computeCV(timestep);
-    mtd_check(mtd_metad_set_cv_source(engine, slot, m_d_value, 1, 1, 0, 1.0, 0.0), "mtd_metad_set_cv_source");
-    }
-
-double DebyeStructureFactor::getCurrentValue(unsigned int timestep)
-    {
-    computeCV(timestep);
-    return readValue(m_d_value, timestep);
     }
 
 std::vector<double> DebyeStructureFactor::getIntensities(unsigned int timestep)
@@ -1479,7 +1455,7 @@ std::vector<double> DebyeStructureFactor::getSpectrum(unsigned int timestep, dou
     double *d_sums = nullptr;
     unsigned int n_sums = 0;
     mtd_check(mtd_dsf_spectrum(&m_par, &c, q_min, q_max, n_q, &d_sums, &n_sums), "mtd_dsf_spectrum");
-    if (distributed()) m_exec_conf->allreduceSmall(d_sums, n_sums, m_exec_conf->getStream());
+    reduceOverRanks(d_sums, n_sums);
     const double *d_spectrum = nullptr;
     mtd_check(mtd_dsf_spectrum_finalize(&c, q_min, q_max, n_q, &d_spectrum), "mtd_dsf_spectrum_finalize");
     return readBack(d_spectrum, n_q, "spectrum read-back", timestep);
@@ -1487,13 +1463,9 @@ std::vector<double> DebyeStructureFactor::getSpectrum(unsigned int timestep, dou
 
 void DebyeStructureFactor::computeBiasForces(unsigned int timestep)
     {
-    ProfRange prof_range("Force");
-    if (!fresh(timestep)) computeCV(timestep);                       // the sums of THIS step's positions
-    m_nlist->compute(timestep);
-    const mtd_box box = m_pdata->getBox().toMtd();
-    const mtd_dsf_call c = call(&box);
-    void *virial = virialTarget();                                   // constant pressure: the per-particle virial of the bias force beside it
-    mtd_check(mtd_dsf_forces(&m_par, &c, m_force.data(), m_bias_device, m_bias, virial, getVirialPitch()), "mtd_dsf_forces");
+    const ForcePass f(*this, timestep);                              // (the sums of THIS step's positions)
+    const mtd_dsf_call c = call(&f.box);
+    mtd_check(mtd_dsf_forces(&m_par, &c, m_force.data(), m_bias_device, m_bias, f.virial, getVirialPitch()), "mtd_dsf_forces");
     }
 
 // ------------------------------------------------------------------------------------------------
@@ -1503,7 +1475,7 @@ void DebyeStructureFactor::computeBiasForces(unsigned int timestep)
 CoordinationNumber::CoordinationNumber(std::shared_ptr<SystemDefinition> sysdef, double r_0, double d_0, unsigned int n, unsigned int m,
                                        double r_cut, std::shared_ptr<NeighborList> nlist, unsigned int type_a, unsigned int type_b,
                                        const std::string &log_suffix)
-    : NeighbourVariable(sysdef, "coordination", log_suffix, nlist, type_a), m_par(), m_d_value(nullptr), m_d_local(nullptr), m_d_switched(nullptr)
+    : NeighbourVariable(sysdef, "coordination", log_suffix, nlist, type_a), m_par(), m_d_local(nullptr), m_d_switched(nullptr)
     {
     if (!nlist) throw std::runtime_error("cv.coordination: a neighbour list is required");
     if (!(r_0 > 0.0) || !std::isfinite(r_0)) throw std::runtime_error("cv.coordination: r_0 > 0 is required");
@@ -1542,25 +1514,8 @@ void CoordinationNumber::clearSwitch()
 
 mtd_coord_call CoordinationNumber::call(const mtd_box *box)
     {
-    const size_t need = sizeof(double) * mtd_coord_scratch_doubles(m_pdata->getN());
-    if (need > m_scratch.bytes())                                    // (more particles than at the last call: nothing in the scratch is this step's)
-        {
-        m_scratch.resize(need);
-        invalidate();
-        }
-    const Lists l = lists();
-    mtd_coord_call c;
-    c.n_particles = m_pdata->getN();
-    c.n_ghost = m_pdata->getNGhosts();
-    c.d_postype = m_pdata->positionsPtr();
-    c.dtype = m_pdata->getDtype();
-    c.box = box;
-    c.d_head_list = l.head;
-    c.d_n_neigh = l.n_neigh;
-    c.d_nlist = l.nlist;
-    c.d_scratch = (double *)m_scratch.data();
-    c.stream = m_exec_conf->getStream();
-    return c;
+    growScratch(sizeof(double) * mtd_coord_scratch_doubles(m_pdata->getN()));   // (more particles than at the last call)
+    return rowCall(box);
     }
 
 void CoordinationNumber::computeCV(unsigned int timestep)
@@ -1578,22 +1533,9 @@ void CoordinationNumber::computeCV(unsigned int timestep)
     double *d_sums = nullptr;
     unsigned int n_sums = 0;
     mtd_check(mtd_coord_accumulate(&m_par, &c, &d_sums, &n_sums), "mtd_coord_accumulate");
-    // sum v_i and N_A over the ranks: the central particles of a rank are its local ones, their neighbours may be ghosts
-    if (distributed()) m_exec_conf->allreduceSmall(d_sums, n_sums, m_exec_conf->getStream());
+    reduceOverRanks(d_sums, n_sums);                                 // sum v_i and N_A: a rank's central particles are its local ones, their neighbours may be ghosts
     mtd_check(mtd_coord_finalize(&m_par, &c, &m_d_value, &m_d_local, &m_d_switched), "mtd_coord_finalize");
     computed(timestep);
-    }
-
-void CoordinationNumber::enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot)
-    {
-    computeCV(timestep);
-    mtd_check(mtd_metad_set_cv_source(engine, slot, m_d_value, 1, 1, 0, 1.0, 0.0), "mtd_metad_set_cv_source");
-    }
-
-double CoordinationNumber::getCurrentValue(unsigned int timestep)
-    {
-    computeCV(timestep);
-    return readValue(m_d_value, timestep);
     }
 
 std::vector<double> CoordinationNumber::getLocalValues(unsigned int timestep)
@@ -1610,13 +1552,9 @@ std::vector<double> CoordinationNumber::getSwitchedValues(unsigned int timestep)
 
 void CoordinationNumber::computeBiasForces(unsigned int timestep)
     {
-    ProfRange prof_range("Force");
-    if (!fresh(timestep)) computeCV(timestep);                       // the sums of THIS step's positions
-    m_nlist->compute(timestep);
-    const mtd_box box = m_pdata->getBox().toMtd();
-    const mtd_coord_call c = call(&box);
-    void *virial = virialTarget();                                   // constant pressure: the per-particle virial of the bias force beside it
-    mtd_check(mtd_coord_forces(&m_par, &c, m_force.data(), m_bias_device, m_bias, virial, getVirialPitch()), "mtd_coord_forces");
+    const ForcePass f(*this, timestep);                              // (the sums of THIS step's positions)
+    const mtd_coord_call c = call(&f.box);
+    mtd_check(mtd_coord_forces(&m_par, &c, m_force.data(), m_bias_device, m_bias, f.virial, getVirialPitch()), "mtd_coord_forces");
     }
 
 // ------------------------------------------------------------------------------------------------

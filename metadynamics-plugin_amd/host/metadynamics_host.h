@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "mini_hoomd.h"
+#include "prof.h"
 
 namespace mtdhost
 {
@@ -316,16 +317,22 @@ class SteinhardtQl : public CollectiveVariable
         bool m_sym_ok;
     };
 
-//! What the variables that walk the rows of a FULL neighbour list share (SteinhardtLocal, PairEntropy, EnvironmentSimilarity): the list,
-//! the particle type, the scratch the passes leave their results in, "this step is computed already", the refusals of a list that does
-//! not fit, the synchronising read-backs and the cv_<name> log quantity.  A subclass supplies computeCV (its checks in its own order:
-//! full list, distributed, reach, then the list's compute) and the force pass.  SteinhardtQl stays outside: its lists have a mode and
-//! a symmetrised copy.
+//! What the variables that walk the rows of a FULL neighbour list share (SteinhardtLocal, PairEntropy, EnvironmentSimilarity,
+//! PairEntropyLocal, DebyeStructureFactor, CoordinationNumber): the list, the particle type, the scratch the passes leave their results
+//! in and its growth, "this step is computed already", the refusals of a list that does not fit, the call block of a step, the
+//! all-reduce of a step's sums, the opening of a force pass, the value as one device double, the synchronising read-backs and the
+//! cv_<name> log quantity.  A subclass supplies computeCV (its checks in its own order: full list, distributed, reach, then the list's
+//! compute) and the force pass.  SteinhardtQl stays outside: its lists have a mode and a symmetrised copy.
 class NeighbourVariable : public CollectiveVariable
     {
     public:
         std::vector<std::string> getProvidedLogQuantities() override;  //!< the umbrella's and cv_<name>
         double getLogValue(const std::string &quantity, unsigned int timestep) override;
+        //! For a variable whose value is ONE device double that computeCV leaves at m_d_value (PairEntropy, DebyeStructureFactor,
+        //! CoordinationNumber): the synchronising read-back, and that double as the engine's source, no host synchronisation.  The
+        //! variables that average block sums override both
+        double getCurrentValue(unsigned int timestep) override;
+        void enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot) override;
 
     protected:
         //! `kind` ("pair_entropy"): the variable is called kind + log_suffix and its messages begin with "cv.<kind>: "
@@ -347,6 +354,21 @@ class NeighbourVariable : public CollectiveVariable
             const unsigned int *head, *n_neigh, *nlist;
             };
         Lists lists() const;
+        //! the call block of this step's passes (include/mtd_abi.h, mtd_row_call): particles, ghosts, `box`, the list, m_scratch, the stream
+        mtd_row_call rowCall(const mtd_box *box) const;
+        //! m_scratch holds at least `bytes`; when it had to grow nothing in it is any step's (computeCV forms it anew: invalidate)
+        void growScratch(size_t bytes);
+        //! a domain-decomposed run adds the ranks' n_sums doubles at d_sums: the same bits everywhere afterwards
+        void reduceOverRanks(double *d_sums, unsigned int n_sums);
+        //! The opening of every computeBiasForces: the "Force" range, computeCV unless this step is computed, the list, the box and where
+        //! the virial goes (CollectiveVariable::virialTarget)
+        struct ForcePass
+            {
+            ForcePass(NeighbourVariable &cv, unsigned int timestep);
+            ProfRange range;
+            mtd_box box;
+            void *virial;
+            };
         //! computeCV, then synchronising copies: n doubles at d_src; one double; the sum of the block sums times 1 / N_global (through m_sum).
         //! A caller that hands on a pointer computeCV sets calls computeCV itself first
         std::vector<double> readBack(const double *d_src, size_t n, const char *what, unsigned int timestep);
@@ -357,6 +379,7 @@ class NeighbourVariable : public CollectiveVariable
         std::shared_ptr<NeighborList> m_nlist;
         unsigned int m_type;
         DeviceBuffer m_scratch, m_sum;                                 // (m_sum: one double, sized by the variables that reduce block sums)
+        const double *m_d_value;                                       // the value inside m_scratch, where it is one double (see getCurrentValue)
 
     private:
         unsigned int m_cv_last_updated;
@@ -420,9 +443,6 @@ class PairEntropy : public NeighbourVariable
     public:
         PairEntropy(std::shared_ptr<SystemDefinition> sysdef, double r_max, double sigma_r, unsigned int n_bins,
                     std::shared_ptr<NeighborList> nlist, unsigned int type, const std::string &log_suffix = "");
-        double getCurrentValue(unsigned int timestep) override;
-        //! device-resident: the value in the scratch becomes the engine's source of this variable, no host synchronisation
-        void enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot) override;
         void computeBiasForces(unsigned int timestep) override;
         std::vector<double> getGr(unsigned int timestep);              //!< g_b of the n_bins bins (r_b = (b + 1/2) r_max / n_bins)
         double getRCut() const { return m_r_max + 4.0 * m_sigma_r; }   //!< what the neighbour list must reach
@@ -431,7 +451,7 @@ class PairEntropy : public NeighbourVariable
         void computeCV(unsigned int timestep) override;
         double m_r_max, m_sigma_r;
         unsigned int m_n_bins;
-        const double *m_d_value, *m_d_g;
+        const double *m_d_g;
     };
 
 //! Environment similarity (no reference counterpart; include/mtd_abi.h "Environment similarity"): every particle's neighbourhood compared
@@ -502,9 +522,6 @@ class DebyeStructureFactor : public NeighbourVariable
     public:
         DebyeStructureFactor(std::shared_ptr<SystemDefinition> sysdef, const std::vector<double> &q, const std::vector<double> &weights,
                              double r_cut, std::shared_ptr<NeighborList> nlist, unsigned int type, const std::string &log_suffix = "");
-        double getCurrentValue(unsigned int timestep) override;
-        //! device-resident: the value in the scratch becomes the engine's source of this variable, no host synchronisation
-        void enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot) override;
         void computeBiasForces(unsigned int timestep) override;
         std::vector<double> getIntensities(unsigned int timestep);     //!< I_p of the P peaks
         std::vector<double> getLocalValues(unsigned int timestep);     //!< s_i of every local particle (0 for other types)
@@ -514,9 +531,9 @@ class DebyeStructureFactor : public NeighbourVariable
 
     private:
         void computeCV(unsigned int timestep) override;
-        mtd_dsf_call call(const mtd_box *box);
+        mtd_dsf_call call(const mtd_box *box);                         //!< rowCall behind a scratch grown to this step's particle count
         mtd_dsf_params m_par;
-        const double *m_d_value, *m_d_intensity, *m_d_local;
+        const double *m_d_intensity, *m_d_local;
     };
 
 //! Coordination number (no reference counterpart; include/mtd_abi.h "Coordination number"): the mean number of partners of type B around
@@ -528,9 +545,6 @@ class CoordinationNumber : public NeighbourVariable
     public:
         CoordinationNumber(std::shared_ptr<SystemDefinition> sysdef, double r_0, double d_0, unsigned int n, unsigned int m, double r_cut,
                            std::shared_ptr<NeighborList> nlist, unsigned int type_a, unsigned int type_b, const std::string &log_suffix = "");
-        double getCurrentValue(unsigned int timestep) override;
-        //! device-resident: the value in the scratch becomes the engine's source of this variable, no host synchronisation
-        void enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot) override;
         void computeBiasForces(unsigned int timestep) override;
         std::vector<double> getLocalValues(unsigned int timestep);     //!< n_i of every local particle (0 for particles not of type A)
         std::vector<double> getSwitchedValues(unsigned int timestep);  //!< v_i = g(n_i) (n_i without a switch)
@@ -541,9 +555,9 @@ class CoordinationNumber : public NeighbourVariable
 
     private:
         void computeCV(unsigned int timestep) override;
-        mtd_coord_call call(const mtd_box *box);
+        mtd_coord_call call(const mtd_box *box);                       //!< rowCall behind a scratch grown to this step's particle count
         mtd_coord_params m_par;
-        const double *m_d_value, *m_d_local, *m_d_switched;
+        const double *m_d_local, *m_d_switched;
     };
 
 //! AspectRatio.h / AspectRatio.cc:5-130 — box-shape CV, external virial only

@@ -178,7 +178,7 @@ class PelParams(C.Structure):
 
 
 class PelCall(C.Structure):
-    """mtd_pel_call: particles, box, list, scratch and stream of one step"""
+    """mtd_pel_call: particles, box, list, scratch and stream of one step (RowCall with n_global in the place of n_ghost)"""
     _fields_ = [("n_particles", C.c_uint), ("n_global", C.c_uint), ("d_postype", C.c_void_p), ("dtype", C.c_int), ("box", C.POINTER(Box)),
                 ("d_head_list", C.c_void_p), ("d_n_neigh", C.c_void_p), ("d_nlist", C.c_void_p), ("d_scratch", C.c_void_p),
                 ("stream", C.c_void_p)]
@@ -206,12 +206,14 @@ class DsfParams(C.Structure):
         return o
 
 
-class DsfCall(C.Structure):
-    """mtd_dsf_call: particles, ghosts, box, list, scratch and stream of one step"""
+class RowCall(C.Structure):
+    """mtd_row_call (mtd_dsf_call, mtd_coord_call): particles, ghosts, box, list, scratch and stream of one step"""
     _fields_ = [("n_particles", C.c_uint), ("n_ghost", C.c_uint), ("d_postype", C.c_void_p), ("dtype", C.c_int), ("box", C.POINTER(Box)),
                 ("d_head_list", C.c_void_p), ("d_n_neigh", C.c_void_p), ("d_nlist", C.c_void_p), ("d_scratch", C.c_void_p),
                 ("stream", C.c_void_p)]
 
+
+DsfCall = CoordCall = RowCall
 
 MTD_COORD_MAX_M = 32
 
@@ -230,11 +232,6 @@ class CoordParams(C.Structure):
             o.switch_on, o.c0, o.p = 1, float(switch[0]), int(switch[1])
             o.less = int(bool(switch[2])) if len(switch) > 2 else 0
         return o
-
-
-class CoordCall(C.Structure):
-    """mtd_coord_call: particles, ghosts, box, list, scratch and stream of one step (the fields of mtd_dsf_call)"""
-    _fields_ = DsfCall._fields_
 
 
 _vp = C.c_void_p

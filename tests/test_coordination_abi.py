@@ -32,7 +32,11 @@ def test_symbols_exported_declared_and_registered(abi):
 
 
 def _header_fields(name):
-    """[(C type, field)] of `typedef struct { ... } name;` in include/mtd_abi.h, `a, b` declarations split"""
+    """[(C type, field)] of `typedef struct { ... } name;` in include/mtd_abi.h, `a, b` declarations split; a name that is
+    `typedef other name;` has the fields of `other`"""
+    alias = re.search(r"typedef\s+(\w+)\s+%s\s*;" % name, _header())
+    if alias:
+        return _header_fields(alias.group(1))
     body = re.search(r"typedef struct\s*\{([^}]*)\}\s*%s\s*;" % name, _header()).group(1)
     out = []
     for decl in body.split(";"):

@@ -3,7 +3,8 @@
 Compiles csrc/<unit> (steinhardt_local.hip unless given) of <git revision> and of this tree to gfx950 assembly with the Makefile's
 flags and compares, kernel by kernel (those whose name holds <prefix>, k_qll unless given): instruction count, identical text, identical
 opcode sequence; for a kernel whose sequence differs, whether the histogram of its fp64 opcodes is the other revision's.  With
-pair_entropy.hip k_pe and env_similarity.hip k_es it serves the units that share row_walk.hpp (profiles/r20).
+pair_entropy.hip k_pe and env_similarity.hip k_es it serves the units that share row_walk.hpp (profiles/r20, profiles/r26).  "Text" is
+the instruction lines without the kernel's number in its branch targets (.LBB<number>_<block>).
 For steinhardt_local.hip: a revision with this tree's kernel names is compared name by
 name (all 60 instantiations: profiles/r10/qll_isa_cmp.txt); the 24 kernels of a revision from before the options with the plain
 instantiations of this tree (k_qll_accumulate<.., QLL_PLAIN>, k_qll_forces<.., false>, k_qll_forces_tile<.., false>:
@@ -41,7 +42,8 @@ def kernels(path, prefix):
             out[name] = cur
             cur = None
         elif t and not t.startswith(".") and not t.startswith(";"):
-            cur.append(re.sub(r"\s*;.*", "", t))
+            # (a branch target .LBB<n>_<block> carries the kernel's number in its unit, which moves when a kernel before it comes or goes)
+            cur.append(re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\s*;.*", "", t)))
     names = list(out)
     dem = subprocess.run(["c++filt"] + names, capture_output=True, text=True, check=True).stdout.strip().split("\n")
     short = [re.sub(r"\(anonymous namespace\)::|void |HIP_vector_type<|, 4u>", "", re.sub(r"\(mtd::.*", "", d)) for d in dem]

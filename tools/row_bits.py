@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Developer tool: did cv.pair_entropy or cv.environment_similarity move a bit between two builds of libmtd_hip.so?  Both units walk the
-rows of a neighbour list through csrc/row_walk.hpp; this goes through the C ABI (mtd_pe_*, mtd_es_*) with the snapshot builders of
-tests/util.py and the parameter values of tests/test_gpu_pair_entropy.py and tests/test_gpu_env_similarity.py.  All cases are small:
+"""Developer tool: did cv.pair_entropy, cv.environment_similarity, cv.debye_structure_factor or cv.coordination move a bit between two
+builds of libmtd_hip.so?  All four walk the rows of a neighbour list through csrc/row_walk.hpp and share the kernels of
+csrc/row_scale.hpp; this goes through the C ABI (mtd_pe_*, mtd_es_*, mtd_dsf_*, mtd_coord_*) with the snapshot builders of tests/util.py
+and the parameter values of tests/test_gpu_pair_entropy.py, test_gpu_env_similarity.py, test_gpu_debye.py and test_gpu_coordination.py.
+All cases are small:
 noisy fcc crystals of N = 500 (a multiple of neither 32 nor 64) and N = 108 (environment similarity: one full chunk of 64 and a partial
 one), fp32 and fp64 arrays, with and without the virial.
   pair entropy             n_bins 40 and 256 (the limit) on N = 500, 32 bins on N = 108; two types, so that some rows are empty; a
@@ -9,8 +11,13 @@ one), fp32 and fp64 arrays, with and without the virial.
   environment similarity   every entry of VARIANTS of the test (fcc: the fused single walk; two, two_switch: the closed general path;
                            half_fcc: beta = 1 with an open environment), the diamond templates (open, general path), two types, the
                            ghost-row case, the triclinic case
-Per case every output array of both entry points: pair entropy sums, value, g, force, virial; environment similarity k^e_i, k_i, v_i, block
-sums, force, virial.
+  Debye structure factor   1, 2, 3 and 8 peaks on N = 500, each with the stored gradient and with the second walk
+                           (mtd_dsf_set_store_gradient); a spectrum of 256 points and one of 5; N = 108, two types, the ghost rows (both
+                           routes), the triclinic case
+  coordination number      plain and switched with (n, m) = (6, 12) and (8, 14) on N = 500; N = 108; two types with A != B and with
+                           A = B; the plain variable on the ghost rows (a switch refuses ghosts); the triclinic case
+Per case every output array of the entry points: pair entropy sums, value, g, force, virial; environment similarity k^e_i, k_i, v_i, block
+sums, force, virial; Debye sums, value, I_p, s_i, spectrum sums, spectrum, force, virial; coordination sums, value, n_i, v_i, force, virial.
 usage: MTD_LIB_OVERRIDE=<lib> tools/row_bits.py dump <out.npz>
        tools/row_bits.py compare <a.npz> <b.npz>                         np.array_equal on every array; exit status 1 when one differs"""
 import ctypes as C
@@ -121,6 +128,60 @@ def run_es(abi, lib, s, templates, window, lam, sw, type_id, dtype, virial):
     return outputs(abi, force, vir, scratch, N, dict(partials=(p_part, n_part.value), ke=(p_ke, 4 * N), k=(p_k, N), v=(p_v, N)))
 
 
+def run_dsf(abi, lib, s, peaks, r_cut, store, spectrum, type_id, dtype, virial):
+    import torch
+    q, c = peaks
+    d_pos, lists = device_arrays(s, r_cut, dtype)
+    N = s["n_rows"]
+    box = abi.Box.make(s["L"], **(s["tilt"] or {}))
+    par = abi.DsfParams.make(type_id, r_cut, q, c=c)
+    dt = abi.MTD_F32 if dtype == np.float32 else abi.MTD_F64
+    scratch = torch.zeros(lib.mtd_dsf_scratch_doubles(N), dtype=torch.float64, device="cuda")
+    p_sums, p_value, p_I, p_local, p_ssums, p_spec = (C.c_void_p() for _ in range(6))
+    n_sums, n_ssums = C.c_uint(), C.c_uint()
+    call = abi.DsfCall(N, len(s["pos"]) - N, abi.ptr(d_pos), dt, C.pointer(box), *(abi.ptr(x) for x in lists), abi.ptr(scratch), None)
+    force = torch.full((N, 4), 3.0, dtype=d_pos.dtype, device="cuda")
+    pitch = N + 3
+    vir = torch.full((6, pitch), 7.0, dtype=d_pos.dtype, device="cuda") if virial else None
+    d_bias = torch.tensor([0.9], dtype=torch.float64, device="cuda")
+    abi.check(lib.mtd_dsf_set_store_gradient(1 if store else 0))
+    try:
+        abi.check(lib.mtd_dsf_accumulate(C.byref(par), C.byref(call), C.byref(p_sums), C.byref(n_sums)))
+        abi.check(lib.mtd_dsf_finalize(C.byref(par), C.byref(call), C.byref(p_value), C.byref(p_I), C.byref(p_local)))
+        abi.check(lib.mtd_dsf_forces(C.byref(par), C.byref(call), abi.ptr(force), abi.ptr(d_bias), 0.0, abi.ptr(vir) if virial else None,
+                                     pitch if virial else 0))
+        named = dict(sums=(p_sums, n_sums.value), value=(p_value, 1), I=(p_I, len(q)), local=(p_local, N))
+        if spectrum is not None:
+            abi.check(lib.mtd_dsf_spectrum(C.byref(par), C.byref(call), *spectrum, C.byref(p_ssums), C.byref(n_ssums)))
+            abi.check(lib.mtd_dsf_spectrum_finalize(C.byref(call), *spectrum, C.byref(p_spec)))
+            named.update(spectrum_sums=(p_ssums, n_ssums.value), spectrum=(p_spec, spectrum[2]))
+    finally:
+        abi.check(lib.mtd_dsf_set_store_gradient(1))
+    return outputs(abi, force, vir, scratch, N, named)
+
+
+def run_cn(abi, lib, s, pair, nm, r_cut, switch, dtype, virial):
+    import torch
+    from test_gpu_coordination import R0
+    d_pos, lists = device_arrays(s, r_cut, dtype)
+    N = s["n_rows"]
+    box = abi.Box.make(s["L"], **(s["tilt"] or {}))
+    par = abi.CoordParams.make(pair[0], pair[1], R0, r_cut, n=nm[0], m=nm[1], switch=switch)
+    dt = abi.MTD_F32 if dtype == np.float32 else abi.MTD_F64
+    scratch = torch.zeros(lib.mtd_coord_scratch_doubles(N), dtype=torch.float64, device="cuda")
+    p_sums, p_value, p_local, p_switched, n_sums = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint()
+    call = abi.CoordCall(N, len(s["pos"]) - N, abi.ptr(d_pos), dt, C.pointer(box), *(abi.ptr(x) for x in lists), abi.ptr(scratch), None)
+    force = torch.full((N, 4), 3.0, dtype=d_pos.dtype, device="cuda")
+    pitch = N + 3
+    vir = torch.full((6, pitch), 7.0, dtype=d_pos.dtype, device="cuda") if virial else None
+    d_bias = torch.tensor([0.9], dtype=torch.float64, device="cuda")
+    abi.check(lib.mtd_coord_accumulate(C.byref(par), C.byref(call), C.byref(p_sums), C.byref(n_sums)))
+    abi.check(lib.mtd_coord_finalize(C.byref(par), C.byref(call), C.byref(p_value), C.byref(p_local), C.byref(p_switched)))
+    abi.check(lib.mtd_coord_forces(C.byref(par), C.byref(call), abi.ptr(force), abi.ptr(d_bias), 0.0, abi.ptr(vir) if virial else None,
+                                   pitch if virial else 0))
+    return outputs(abi, force, vir, scratch, N, dict(sums=(p_sums, n_sums.value), value=(p_value, 1), local=(p_local, N), switched=(p_switched, N)))
+
+
 def cases():
     """(name, runner, system, arguments after the system) — the virial flag and the dtype are added by dump"""
     import env_similarity_ref as es
@@ -138,6 +199,29 @@ def cases():
     out.append(("es_two_types_t1", run_es, "two_types", (VARIANTS["two_switch"][0], window, 20.0, SWITCH, 1)))
     out.append(("es_ghosts", run_es, "ghosts", (VARIANTS["fcc"][0], window, 100.0, None, 0)))
     out.append(("es_triclinic", run_es, "triclinic", (VARIANTS["fcc"][0], (R_ON, R_CUT, 1.55), 100.0, None, 0)))
+    from test_gpu_coordination import R_CUT as CN_R_CUT, SWITCHES
+    from test_gpu_debye import PEAKS
+    peaks = dict(PEAKS)
+    peaks[2] = tuple(x[:2] for x in PEAKS[3])
+    for P in (1, 2, 3, 8):                                 # (the compiled peak counts are 1, 2, 4, 8: three peaks run the kernel of four)
+        for store in (True, False):
+            out.append(("dsf_n500_q%d_%s" % (P, "store" if store else "walk"), run_dsf, "n500",
+                        (peaks[P], 2.4, store, (2.0, 12.0, 256) if P == 1 and store else None, 0)))
+    out.append(("dsf_n108_q3", run_dsf, "n108", (peaks[3], 1.5, True, (2.0, 12.0, 5), 0)))
+    out.append(("dsf_two_types_t1", run_dsf, "two_types", (peaks[3], 2.4, True, None, 1)))
+    out.append(("dsf_ghosts_q3", run_dsf, "ghosts", (peaks[3], 2.4, True, None, 0)))
+    out.append(("dsf_ghosts_q3_walk", run_dsf, "ghosts", (peaks[3], 2.4, False, None, 0)))
+    out.append(("dsf_triclinic", run_dsf, "triclinic", (peaks[2], 1.5, True, None, 0)))
+    for mode in ("plain", "switch"):
+        for nm in ((6, 12), (8, 14)):
+            out.append(("cn_n500_%s_%d_%d" % ((mode,) + nm), run_cn, "n500", ((0, 0), nm, CN_R_CUT, SWITCHES[mode])))
+            out.append(("cn_two_types_ab_%s_%d_%d" % ((mode,) + nm), run_cn, "two_types", ((0, 1), nm, CN_R_CUT, SWITCHES[mode])))
+        out.append(("cn_n108_" + mode, run_cn, "n108", ((0, 0), (6, 12), 1.5, SWITCHES[mode])))
+        out.append(("cn_two_types_bb_" + mode, run_cn, "two_types", ((1, 1), (6, 12), CN_R_CUT, SWITCHES[mode])))
+        out.append(("cn_triclinic_" + mode, run_cn, "triclinic", ((0, 0), (6, 12), 1.5, SWITCHES[mode])))
+    out.append(("cn_two_types_ba_less", run_cn, "two_types", ((1, 0), (6, 12), CN_R_CUT, SWITCHES["less"])))
+    for nm in ((6, 12), (8, 14)):                          # (a switch refuses ghosts)
+        out.append(("cn_ghosts_plain_%d_%d" % nm, run_cn, "ghosts", ((0, 0), nm, CN_R_CUT, None)))
     return out
 
 
