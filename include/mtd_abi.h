@@ -1217,6 +1217,95 @@ int mtd_coord_forces(const mtd_coord_params *p, const mtd_coord_call *c, void *d
                      void *d_virial, unsigned int virial_pitch);
 
 /* ================================================================================================
+ * Tetrahedral order (cv.tetrahedral) — no reference counterpart.  The angle between two bonds of one particle, what tells a tetrahedral
+ * network from a dense liquid: the tetrahedral order parameter q of Chau and Hardin (Mol. Phys. 93, 511) and of Errington and
+ * Debenedetti (Nature 409, 318) in a smooth, weighted form over all neighbours inside the window, or the three-body penalty of
+ * Stillinger and Weber, sum_{j<k} h_ij h_ik (cos theta_jik + 1/3)^2: ice, silicon, germanium, mW water, clathrates.  Rotation invariant,
+ * unlike "Environment similarity".  The conventions of "Debye structure factor" above hold wherever nothing else is said.
+ * Parameters: a particle type t; 0 <= r_on < r_cut; cos0 in [-1, 1] (-1/3: the tetrahedral angle); `normalise`; with `normalise` an
+ * optional switch (c0 > 0, integer p >= 1) and an optional gate (1 <= n_lo < n_hi), the functions of mtd_ql_local_options.
+ * Entries (i, j) of a FULL list take part when i and j are both of type t, j != i and 0 < r = |d| <= r_cut, with
+ * d = minImage(r_j - r_i) and u = d / r (an entry with r = 0 has no direction and takes no part).  f(r) is the cosine window of the
+ * Steinhardt passes between r_on and r_cut.  SINGLE-DOMAIN ONLY: every per-particle array ends at n_particles, an entry j >= n_particles
+ * is skipped, and n_ghost > 0 is MTD_ERR_UNSUPPORTED.
+ * Per central particle i, over its entries j:
+ *     n_i = sum f_ij                 m_i = sum f_ij^2
+ *     b_i = sum f_ij u_ij   (3)      T_i = sum f_ij u_ij (x) u_ij   (symmetric, 6 stored)
+ *     A_i = sum_{j<k} f_ij f_ik (u_ij.u_ik - cos0)^2
+ *         = 1/2 [ (T:T - m) - 2 cos0 (b.b - m) + cos0^2 (n^2 - m) ]          T:T = sum_ab T_ab^2 over all nine
+ *     W_i = sum_{j<k} f_ij f_ik = 1/2 (n^2 - m)
+ *     kappa = 1 / (1/3 + cos0^2)     (9/4 at cos0 = -1/3: the Errington-Debenedetti normalisation, 0 for uniformly random directions)
+ *     normalise:      t_i = 1 - kappa A_i / W_i  where W_i >= MTD_TET_W_MIN, else t_i = 0 with zero gradient
+ *                     v_i = g(n_i) h(t_i),  h(t) = x^p / (1 + x^p), x = max(t, 0) / c0   (h(t) = t without a switch, g = 1 without a gate)
+ *     not normalised: v_i = A_i          (the three-body penalty; switch and gate are MTD_ERR_INVALID_ARGUMENT)
+ *     s = (1 / N_t) sum_i v_i,   N_t the particles of the type; N_t = 0: s = 0, no forces
+ * The kernels evaluate the moment form, O(n) per row; tests/tetrahedral_ref.py restates the pair sum.  Lattice values: t_i = 1 and
+ * A_i = 0 on the four diamond vectors, t_i = 3/11 on the twelve fcc vectors (cos0 = -1/3).
+ * Gradient.  The adjoint of particle i is alpha = dv_i / d(n, m, b, T), eleven numbers (alpha_T a symmetric matrix), from
+ *     dA/dn = cos0^2 n      dA/dm = -(1 - cos0)^2 / 2      dA/db = -2 cos0 b      dA/dT = T
+ *     dW/dn = n             dW/dm = -1/2
+ *     dt/dmu = -kappa (dA/dmu W - A dW/dmu) / W^2
+ *     alpha_mu = g h'(t) dt/dmu + [mu = n] g'(n) h(t)                         (not normalised: alpha = dA/dmu)
+ * An entry has
+ *     g_ij = dv_i/dd_ij = u [ f' (alpha_n + 2 f alpha_m + alpha_b.u + u.alpha_T.u) - (f/r) (alpha_b.u + 2 u.alpha_T.u) ] + (f/r) [ alpha_b + 2 alpha_T u ]
+ * and gives +g_ij to d(N_t s)/dr_j and -g_ij to d(N_t s)/dr_i.  As a gather over row k of a symmetric list:
+ *     N_t ds/dr_k = sum_{j in row k} [ -g_kj(d_kj) + g_jk(-d_kj) ],     F = -bias ds/dr
+ * The second term reads alpha_j of the neighbour.  The pair term is NOT parallel to d, although the variable is rotation invariant:
+ * sum_k F_k = 0 and the torque sum_k r_k x F_k = 0 both hold.
+ * Virial (only with a virial pointer): half of every entry at each of its ends,
+ *     virial_k[ab] = -(bias / N_t) 1/2 sum_{j in row k} [ g_kj,a d_kj,b + g_jk,a d_jk,b ]
+ * with no explicit volume term; a particle's six stored components (xx xy xz yy yz zz, the first index the force's) need not be those of
+ * a symmetric matrix, the sum over k is symmetric.  Layout, scalar type and pitch rule of mtd_pe_forces.
+ * KNOWN PROPERTY.  Without a gate a particle whose pair weight W_i is tiny but not zero (one neighbour well inside the window, a second
+ * one just entering it) has a bounded t_i and a gradient of order 1 / f: inherent to a weighted mean.  The gate with n_lo >= 1 removes
+ * it: for 1 < n <= 2, W >= n - 1, and g vanishes quadratically at n_lo.  Dilute systems should use the gate.
+ * A step is _accumulate, _finalize, _forces with the same parameters, call block and scratch.  _accumulate walks the rows once and
+ * stores n_i, t_i (A_i when not normalised), v_i and the adjoint row of every particle — ROW-major, twelve doubles (eleven and a pad);
+ * _forces walks the rows a second time and reads alpha_j of the neighbours.  Every sum has a fixed order and there are no atomics: two
+ * identical calls give identical bits.  Arguments are checked before a device is touched: MTD_ERR_INVALID_ARGUMENT for null pointers,
+ * non-finite or out-of-range parameters (r_on, r_cut, cos0, with switch_on c0 and p, with gate_on n_lo and n_hi), a switch or a gate
+ * without `normalise`, an unknown dtype, a d_scratch that is not 16-byte aligned, a virial pitch below n_particles;
+ * MTD_ERR_UNSUPPORTED for n_ghost > 0.
+ * ============================================================================================== */
+
+#define MTD_TET_W_MIN 1e-12
+
+typedef struct
+    {
+    unsigned int type;
+    double r_cut, r_on;
+    double cos0;
+    int normalise;
+    int switch_on;
+    double c0;
+    unsigned int p;
+    int gate_on;
+    double n_lo, n_hi;
+    } mtd_tet_params;
+
+typedef mtd_row_call mtd_tet_call;       /* "Debye structure factor" */
+
+/* device doubles the calls share: sums, value, block sums, three per-particle arrays and the adjoint table */
+size_t mtd_tet_scratch_doubles(unsigned int n_particles);
+
+/* This rank's sums: on return *d_sums points at *n_sums = 2 doubles inside c->d_scratch, sum_i v_i and N_t. */
+int mtd_tet_accumulate(const mtd_tet_params *p, const mtd_tet_call *c, double **d_sums, unsigned int *n_sums);
+
+/* The sums -> s.  *d_value points at s, one device double (consume with
+ * mtd_metad_set_cv_source(engine, slot, *d_value, 1, 1, 0, 1.0, 0.0)), *d_local (may be NULL) at t_i[n_particles] (A_i when not
+ * normalised), *d_switched (may be NULL) at v_i[n_particles] and *d_coordination (may be NULL) at n_i[n_particles] of the last
+ * mtd_tet_accumulate, all inside c->d_scratch. */
+int mtd_tet_finalize(const mtd_tet_params *p, const mtd_tet_call *c, const double **d_value, const double **d_local,
+                     const double **d_switched, const double **d_coordination);
+
+/* Writes d_force[0..n_particles) (w component 0; 0 for particles of another type) with what the last mtd_tet_accumulate and
+ * mtd_tet_finalize (same p and c) left in c->d_scratch; bias = *d_bias when d_bias != NULL, else bias_host.  d_virial == NULL: no
+ * virial; the force array is the same, bit for bit, either way.  Every row [0, n_particles) of the virial is written,
+ * [n_particles, virial_pitch) is left alone.  n_particles == 0 is success. */
+int mtd_tet_forces(const mtd_tet_params *p, const mtd_tet_call *c, void *d_force, const double *d_bias, double bias_host,
+                   void *d_virial, unsigned int virial_pitch);
+
+/* ================================================================================================
  * Neighbour list of the stand-alone path (cell list, built on the device)
  * no reference counterpart: HOOMD's md::NeighborList is HOOMD core.  Produces the three arrays SteinhardtQl.cc:80-85 reads, in
  * HOOMD's layout: the neighbours of particle i are d_nlist[d_head_list[i] .. d_head_list[i] + d_n_neigh[i]).

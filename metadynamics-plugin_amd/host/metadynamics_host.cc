@@ -1558,6 +1558,111 @@ void CoordinationNumber::computeBiasForces(unsigned int timestep)
     }
 
 // ------------------------------------------------------------------------------------------------
+// TetrahedralOrder
+// ------------------------------------------------------------------------------------------------
+
+TetrahedralOrder::TetrahedralOrder(std::shared_ptr<SystemDefinition> sysdef, double r_cut, double r_on, double cos0, bool normalise,
+                                   std::shared_ptr<NeighborList> nlist, unsigned int type, const std::string &log_suffix)
+    : NeighbourVariable(sysdef, "tetrahedral", log_suffix, nlist, type), m_par(), m_d_local(nullptr), m_d_switched(nullptr),
+      m_d_coordination(nullptr)
+    {
+    if (!nlist) throw std::runtime_error("cv.tetrahedral: a neighbour list is required");
+    if (!(r_on >= 0.0) || !(r_on < r_cut) || !std::isfinite(r_cut)) throw std::runtime_error("cv.tetrahedral: 0 <= r_on < r_cut is required");
+    if (!(cos0 >= -1.0) || !(cos0 <= 1.0)) throw std::runtime_error("cv.tetrahedral: -1 <= cos0 <= 1 is required");
+    m_par.type = type;
+    m_par.r_cut = r_cut;
+    m_par.r_on = r_on;
+    m_par.cos0 = cos0;
+    m_par.normalise = normalise ? 1 : 0;
+    m_scratch.resize(sizeof(double) * mtd_tet_scratch_doubles(m_pdata->getN()));
+    }
+
+void TetrahedralOrder::setSwitch(double c0, unsigned int p)
+    {
+    if (!m_par.normalise) throw std::runtime_error("cv.tetrahedral: a switch needs the normalised variable");
+    if (!(c0 > 0.0) || !std::isfinite(c0) || p == 0) throw std::runtime_error("cv.tetrahedral: a switch needs c0 > 0 and an integer p >= 1");
+    m_par.switch_on = 1;
+    m_par.c0 = c0;
+    m_par.p = p;
+    invalidate();                                                    // v_i and the adjoint rows in the scratch belong to the old switch
+    }
+
+void TetrahedralOrder::clearSwitch()
+    {
+    m_par.switch_on = 0;
+    m_par.c0 = 0.0;
+    m_par.p = 0;
+    invalidate();
+    }
+
+void TetrahedralOrder::setGate(double n_lo, double n_hi)
+    {
+    if (!m_par.normalise) throw std::runtime_error("cv.tetrahedral: a gate needs the normalised variable");
+    if (!(n_lo >= 1.0) || !(n_lo < n_hi) || !std::isfinite(n_hi)) throw std::runtime_error("cv.tetrahedral: a gate needs 1 <= n_lo < n_hi");
+    m_par.gate_on = 1;
+    m_par.n_lo = n_lo;
+    m_par.n_hi = n_hi;
+    invalidate();
+    }
+
+void TetrahedralOrder::clearGate()
+    {
+    m_par.gate_on = 0;
+    m_par.n_lo = m_par.n_hi = 0.0;
+    invalidate();
+    }
+
+mtd_tet_call TetrahedralOrder::call(const mtd_box *box)
+    {
+    growScratch(sizeof(double) * mtd_tet_scratch_doubles(m_pdata->getN()));   // (more particles than at the last call)
+    return rowCall(box);
+    }
+
+void TetrahedralOrder::computeCV(unsigned int timestep)
+    {
+    ProfRange prof_range("CV");
+    if (fresh(timestep)) return;
+    requireFullList();
+    if (distributed())
+        throw std::runtime_error("cv.tetrahedral: domain-decomposed runs are not supported (the adjoint row of a ghost neighbour would have "
+                                 "to be exchanged)");
+    requireReach(getRCut(), "r_cut");
+    m_nlist->compute(timestep);
+    const mtd_box box = m_pdata->getBox().toMtd();
+    const mtd_tet_call c = call(&box);
+    double *d_sums = nullptr;
+    unsigned int n_sums = 0;
+    mtd_check(mtd_tet_accumulate(&m_par, &c, &d_sums, &n_sums), "mtd_tet_accumulate");
+    mtd_check(mtd_tet_finalize(&m_par, &c, &m_d_value, &m_d_local, &m_d_switched, &m_d_coordination), "mtd_tet_finalize");
+    computed(timestep);
+    }
+
+std::vector<double> TetrahedralOrder::getLocalValues(unsigned int timestep)
+    {
+    computeCV(timestep);
+    return readBack(m_d_local, m_pdata->getN(), "t_i read-back", timestep);
+    }
+
+std::vector<double> TetrahedralOrder::getSwitchedValues(unsigned int timestep)
+    {
+    computeCV(timestep);
+    return readBack(m_d_switched, m_pdata->getN(), "v_i read-back", timestep);
+    }
+
+std::vector<double> TetrahedralOrder::getCoordination(unsigned int timestep)
+    {
+    computeCV(timestep);
+    return readBack(m_d_coordination, m_pdata->getN(), "n_i read-back", timestep);
+    }
+
+void TetrahedralOrder::computeBiasForces(unsigned int timestep)
+    {
+    const ForcePass f(*this, timestep);                              // (the adjoint rows of THIS step's positions)
+    const mtd_tet_call c = call(&f.box);
+    mtd_check(mtd_tet_forces(&m_par, &c, m_force.data(), m_bias_device, m_bias, f.virial, getVirialPitch()), "mtd_tet_forces");
+    }
+
+// ------------------------------------------------------------------------------------------------
 // AspectRatio, Density
 // ------------------------------------------------------------------------------------------------
 

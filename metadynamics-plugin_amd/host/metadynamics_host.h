@@ -318,7 +318,7 @@ class SteinhardtQl : public CollectiveVariable
     };
 
 //! What the variables that walk the rows of a FULL neighbour list share (SteinhardtLocal, PairEntropy, EnvironmentSimilarity,
-//! PairEntropyLocal, DebyeStructureFactor, CoordinationNumber): the list, the particle type, the scratch the passes leave their results
+//! PairEntropyLocal, DebyeStructureFactor, CoordinationNumber, TetrahedralOrder): the list, the particle type, the scratch the passes leave their results
 //! in and its growth, "this step is computed already", the refusals of a list that does not fit, the call block of a step, the
 //! all-reduce of a step's sums, the opening of a force pass, the value as one device double, the synchronising read-backs and the
 //! cv_<name> log quantity.  A subclass supplies computeCV (its checks in its own order: full list, distributed, reach, then the list's
@@ -558,6 +558,33 @@ class CoordinationNumber : public NeighbourVariable
         mtd_coord_call call(const mtd_box *box);                       //!< rowCall behind a scratch grown to this step's particle count
         mtd_coord_params m_par;
         const double *m_d_local, *m_d_switched;
+    };
+
+//! Tetrahedral order (no reference counterpart; include/mtd_abi.h "Tetrahedral order"): the bond-angle order t_i of every particle from the
+//! moments of its neighbour row, optionally counted through a switch and gated by the coordination, or the three-body penalty A_i;
+//! s = (1/N_t) sum_i v_i.  Single-domain runs only: the force on a particle reads the adjoint row of its neighbours, which a ghost does
+//! not have.
+class TetrahedralOrder : public NeighbourVariable
+    {
+    public:
+        TetrahedralOrder(std::shared_ptr<SystemDefinition> sysdef, double r_cut, double r_on, double cos0, bool normalise,
+                         std::shared_ptr<NeighborList> nlist, unsigned int type, const std::string &log_suffix = "");
+        void computeBiasForces(unsigned int timestep) override;
+        std::vector<double> getLocalValues(unsigned int timestep);     //!< t_i of every local particle (A_i when not normalised; 0 for other types)
+        std::vector<double> getSwitchedValues(unsigned int timestep);  //!< v_i = g(n_i) h(t_i) (t_i without options; A_i when not normalised)
+        std::vector<double> getCoordination(unsigned int timestep);    //!< n_i = sum_j f(r_ij)
+        //! the switch and the gate of mtd_ql_local_options, with n_lo >= 1; both need `normalise`; every change invalidates the cached step
+        void setSwitch(double c0, unsigned int p);                     //!< h(t) = x^p / (1 + x^p), x = max(t, 0) / c0
+        void clearSwitch();
+        void setGate(double n_lo, double n_hi);                        //!< g(n) = smoothstep from n_lo to n_hi
+        void clearGate();
+        double getRCut() const { return m_par.r_cut; }                 //!< what the neighbour list must reach
+
+    private:
+        void computeCV(unsigned int timestep) override;
+        mtd_tet_call call(const mtd_box *box);                         //!< rowCall behind a scratch grown to this step's particle count
+        mtd_tet_params m_par;
+        const double *m_d_local, *m_d_switched, *m_d_coordination;
     };
 
 //! AspectRatio.h / AspectRatio.cc:5-130 — box-shape CV, external virial only

@@ -453,6 +453,28 @@ PYBIND11_MODULE(_metadynamics, m)
             return py::array_t<double>((ssize_t)v.size(), v.data());
         });
 
+    // no reference counterpart: the three-body bond-angle order of one particle type from the moments of every neighbour row
+    py::class_<TetrahedralOrder, CollectiveVariable, std::shared_ptr<TetrahedralOrder>>(m, "TetrahedralOrder")
+        .def(py::init<std::shared_ptr<SystemDefinition>, double, double, double, bool, std::shared_ptr<NeighborList>, unsigned int,
+                      const std::string &>())
+        .def("getRCut", &TetrahedralOrder::getRCut)
+        .def("setSwitch", &TetrahedralOrder::setSwitch)
+        .def("clearSwitch", &TetrahedralOrder::clearSwitch)
+        .def("setGate", &TetrahedralOrder::setGate)
+        .def("clearGate", &TetrahedralOrder::clearGate)
+        .def("getLocalValues", [](TetrahedralOrder &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getLocalValues(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        })
+        .def("getSwitchedValues", [](TetrahedralOrder &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getSwitchedValues(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        })
+        .def("getCoordination", [](TetrahedralOrder &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getCoordination(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        });
+
     py::class_<WellTemperedEnsemble, CollectiveVariable, std::shared_ptr<WellTemperedEnsemble>>(m, "WellTemperedEnsemble")
         .def(py::init<std::shared_ptr<SystemDefinition>, const std::string &>());
 

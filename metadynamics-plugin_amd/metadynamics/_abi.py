@@ -207,7 +207,7 @@ class DsfParams(C.Structure):
 
 
 class RowCall(C.Structure):
-    """mtd_row_call (mtd_dsf_call, mtd_coord_call): particles, ghosts, box, list, scratch and stream of one step"""
+    """mtd_row_call (mtd_dsf_call, mtd_coord_call, mtd_tet_call): particles, ghosts, box, list, scratch and stream of one step"""
     _fields_ = [("n_particles", C.c_uint), ("n_ghost", C.c_uint), ("d_postype", C.c_void_p), ("dtype", C.c_int), ("box", C.POINTER(Box)),
                 ("d_head_list", C.c_void_p), ("d_n_neigh", C.c_void_p), ("d_nlist", C.c_void_p), ("d_scratch", C.c_void_p),
                 ("stream", C.c_void_p)]
@@ -231,6 +231,28 @@ class CoordParams(C.Structure):
         if switch is not None:
             o.switch_on, o.c0, o.p = 1, float(switch[0]), int(switch[1])
             o.less = int(bool(switch[2])) if len(switch) > 2 else 0
+        return o
+
+
+TetCall = RowCall
+
+MTD_TET_W_MIN = 1e-12
+
+
+class TetParams(C.Structure):
+    """mtd_tet_params: the particle type, the window, cos0, the normalisation and the optional switch and gate on t_i and n_i"""
+    _fields_ = [("type", C.c_uint), ("r_cut", C.c_double), ("r_on", C.c_double), ("cos0", C.c_double), ("normalise", C.c_int),
+                ("switch_on", C.c_int), ("c0", C.c_double), ("p", C.c_uint), ("gate_on", C.c_int), ("n_lo", C.c_double), ("n_hi", C.c_double)]
+
+    @classmethod
+    def make(cls, type_id, r_cut, r_on, cos0=-1.0 / 3.0, normalise=True, switch=None, gate=None):
+        """switch: None or (c0, p); gate: None or (n_lo, n_hi).  Nothing is checked here: the entry points refuse what they do not take"""
+        o = cls()
+        o.type, o.r_cut, o.r_on, o.cos0, o.normalise = int(type_id), float(r_cut), float(r_on), float(cos0), int(bool(normalise))
+        if switch is not None:
+            o.switch_on, o.c0, o.p = 1, float(switch[0]), int(switch[1])
+        if gate is not None:
+            o.gate_on, o.n_lo, o.n_hi = 1, float(gate[0]), float(gate[1])
         return o
 
 
@@ -406,6 +428,10 @@ _SIGNATURES = {
     "mtd_coord_accumulate": (C.c_int, [C.POINTER(CoordParams), C.POINTER(CoordCall), C.POINTER(_vp), _up]),
     "mtd_coord_finalize": (C.c_int, [C.POINTER(CoordParams), C.POINTER(CoordCall), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "mtd_coord_forces": (C.c_int, [C.POINTER(CoordParams), C.POINTER(CoordCall), _vp, _vp, C.c_double, _vp, C.c_uint]),
+    "mtd_tet_scratch_doubles": (C.c_size_t, [C.c_uint]),
+    "mtd_tet_accumulate": (C.c_int, [C.POINTER(TetParams), C.POINTER(TetCall), C.POINTER(_vp), _up]),
+    "mtd_tet_finalize": (C.c_int, [C.POINTER(TetParams), C.POINTER(TetCall), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "mtd_tet_forces": (C.c_int, [C.POINTER(TetParams), C.POINTER(TetCall), _vp, _vp, C.c_double, _vp, C.c_uint]),
     "mtd_nlist_create": (C.c_int, [C.POINTER(_vp)]),
     "mtd_nlist_destroy": (C.c_int, [_vp]),
     "mtd_nlist_build": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp, C.c_int, C.POINTER(Box), C.c_double, C.c_int, C.c_int,

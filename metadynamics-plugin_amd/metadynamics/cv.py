@@ -662,6 +662,99 @@ class coordination(_neighbour_variable):
             raise RuntimeError("Error creating collective variable.")
 
 
+class tetrahedral(_neighbour_variable):
+    """this build (no reference counterpart; include/mtd_abi.h "Tetrahedral order"): the three-body bond-angle order of the particles of
+    ``type``, the variable of ice, silicon, germanium, mW water and clathrates.  With f the cosine window between ``r_on`` and ``r_cut``
+    and u_ij the unit vector from i to its neighbour j,
+    A_i = sum_{j<k} f_ij f_ik (u_ij.u_ik - cos0)^2,  W_i = sum_{j<k} f_ij f_ik,  t_i = 1 - A_i / (W_i (1/3 + cos0^2)).
+    With ``cos0 = -1/3`` t_i is the tetrahedral order parameter of Chau and Hardin and of Errington and Debenedetti as a weighted mean over
+    ALL pairs of neighbours inside the window (the nearest-four form of the literature is not differentiable): 1 on a diamond lattice,
+    3/11 on fcc, 0 for uniformly random directions.  CV = (1 / N_type) sum_i g(n_i) h(t_i); ``switch=dict(c0=..., p=...)``:
+    h(t) = x^p / (1 + x^p), x = max(t, 0) / c0 — CV * N_type is then the smooth number of tetrahedral particles;
+    ``gate=dict(n_lo=..., n_hi=...)`` (1 <= n_lo < n_hi): a smoothstep in the coordination n_i = sum_j f_ij.  ``normalise=False``: CV is
+    the mean of A_i itself, the three-body penalty of Stillinger and Weber; switch and gate are refused then.  Rotation invariant, unlike
+    ``cv.environment_similarity("diamond")``.
+
+    Needs a full list that reaches ``r_cut``; single-domain runs only (the force on a particle reads a table row of its neighbours,
+    which a ghost does not have).  A particle with no or one neighbour has t_i = 0.
+
+    Known property: without a gate a particle whose pair weight W_i is tiny but not zero (a second neighbour just entering the window)
+    has a bounded t_i and a gradient of order 1 / f, inherent to a weighted mean.  The gate with n_lo >= 1 removes it; dilute systems
+    should use the gate.
+
+    Virial (``get_virial``; mtd_tet_forces): half of every entry at each of its ends, no explicit volume term.  The pair term is not
+    parallel to the pair vector, so one particle's six components are not those of a symmetric matrix; their sum over the particles is,
+    and it is -bias * dCV/d(strain)."""
+
+    _cv = "cv.tetrahedral"
+
+    def __init__(self, r_cut, r_on, nlist, type, cos0=-1.0 / 3.0, normalise=True, switch=None, gate=None, name=None, sigma=1.0):
+        suffix = self._begin(sigma, name)
+        try:
+            type_list = context.current.type_names
+            r_cut, r_on, cos0 = float(r_cut), float(r_on), float(cos0)
+            if type not in type_list or not 0.0 <= r_on < r_cut < float("inf") or not -1.0 <= cos0 <= 1.0 or float(nlist.r_cut) < r_cut:
+                raise ValueError
+            normalise = bool(normalise)
+            sw, gt = self._options(switch, gate, normalise)
+            self.type = type
+            self.nlist = nlist
+            self.r_cut, self.r_on, self.cos0, self.normalise = r_cut, r_on, cos0, normalise
+            self._full_list()
+            self.cpp_force = _metadynamics.TetrahedralOrder(context.current.system_definition, r_cut, r_on, cos0, normalise, nlist.cpp_nlist,
+                                                            type_list.index(type), suffix)
+            self._apply(sw, gt)
+        except (TypeError, ValueError, KeyError, AttributeError, RuntimeError):
+            context.current.forces.remove(self)                      # refused: the run must not find a half-made variable
+            raise RuntimeError("Error creating collective variable.")
+        self._attach(type_list.index(type))
+
+    @staticmethod
+    def _options(switch, gate, normalise):
+        """the checks of cv.steinhardt_local.set_options, with n_lo >= 1; both options need the normalised variable"""
+        sw = None if switch is None else (float(switch["c0"]), int(switch["p"]))
+        gt = None if gate is None else (float(gate["n_lo"]), float(gate["n_hi"]))
+        if sw is not None and (set(switch.keys()) != {"c0", "p"} or int(switch["p"]) != switch["p"] or not 0.0 < sw[0] < float("inf")
+                               or sw[1] < 1):
+            raise ValueError
+        if gt is not None and (set(gate.keys()) != {"n_lo", "n_hi"} or not 1.0 <= gt[0] < gt[1] < float("inf")):
+            raise ValueError
+        if not normalise and (sw is not None or gt is not None):
+            raise ValueError
+        return sw, gt
+
+    def _apply(self, sw, gt):
+        if sw is None:
+            self.cpp_force.clearSwitch()
+        else:
+            self.cpp_force.setSwitch(*sw)
+        if gt is None:
+            self.cpp_force.clearGate()
+        else:
+            self.cpp_force.setGate(*gt)
+
+    def get_local(self):
+        """t_i of every particle at the current time step (A_i with ``normalise=False``; 0 for particles of another type)"""
+        return self.cpp_force.getLocalValues(context.current.system.getCurrentTimeStep())
+
+    def get_switched(self):
+        """v_i = g(n_i) h(t_i) of every particle at the current time step: what the CV averages"""
+        return self.cpp_force.getSwitchedValues(context.current.system.getCurrentTimeStep())
+
+    def get_coordination(self):
+        """n_i = sum_j f(r_ij): the smoothed number of neighbours of every particle at the current time step"""
+        return self.cpp_force.getCoordination(context.current.system.getCurrentTimeStep())
+
+    def set_options(self, switch=None, gate=None):
+        """replaces switch and gate (the defaults switch them off); takes effect with the next step.  A refused call leaves both as they
+        were"""
+        try:
+            sw, gt = self._options(switch, gate, self.normalise)     # everything is checked before anything is changed
+            self._apply(sw, gt)
+        except (TypeError, KeyError, ValueError, AttributeError, RuntimeError):
+            raise RuntimeError("Error creating collective variable.")
+
+
 def environment_templates(structure, a):
     """the template environments of a cubic lattice with the conventional lattice constant ``a``, for ``cv.environment_similarity``:
     ``"fcc"`` 12 vectors of length a / sqrt(2), ``"bcc"`` 14 vectors (the 8 nearest of length a sqrt(3) / 2 and the 6 second neighbours of
