@@ -1203,6 +1203,29 @@ int mtd_coord_set_compiled_pair(int enable);
  * mtd_comm_allreduce_small. */
 int mtd_coord_accumulate(const mtd_coord_params *p, const mtd_coord_call *c, double **d_sums, unsigned int *n_sums);
 
+/* The switched coordination number restricted to the largest cluster ("Clusters" above):
+ *     s = (1 / N_A) sum_i w_i v_i,   N_A the UNMASKED count of the centres
+ * with the clusters of mtd_cluster_largest built from the v_i of this call, type = A: the nodes are the A particles with v_i >= v_min
+ * ("liquid-like": at least c0 neighbours; with `less` at most c0: cavitation), linked within r_link — the variable of ten Wolde and
+ * Frenkel for vapour-liquid nucleation and of nucleation from solution.  With two types the nodes are still the A particles only, and
+ * the list must hold the A-A pairs up to r_link although the variable itself reads A-B pairs only; a device-built list with two
+ * attached types builds all pairs.  Membership is piecewise constant (PLUMED's treatment): the gradient is the one above with
+ * g'(n_i) -> w_i g'(n_i), and the variable jumps when clusters merge or split.  The launches: the walk of mtd_coord_accumulate,
+ * mtd_cluster_largest on the v row just written, one launch that stores 0 over g'(n_i) of every particle with w_i = 0 (stored, not
+ * multiplied: a non-finite entry comes out 0 too) and leaves the block sums of w_i v_i, the sums kernel.  mtd_coord_finalize and
+ * mtd_coord_forces (with its virial) then run unchanged on the masked table: there is no force entry point of its own.  *d_switched of
+ * mtd_coord_finalize stays the UNMASKED v_i, the values the clusters were built from.  d_cluster_scratch:
+ * mtd_cluster_scratch_bytes(n_particles) bytes, 16-byte aligned, separate from c->d_scratch, whose layout and size do not change;
+ * *d_w, *d_label, *d_summary (each may be NULL) point into it as mtd_cluster_largest leaves them.  The stream is c->stream.
+ * cluster == NULL or on == 0: mtd_coord_accumulate, bit for bit (that entry point forwards here); the three pointers are set to NULL.
+ * With the option on, before a device is touched: everything mtd_coord_accumulate refuses, as there; MTD_ERR_INVALID_ARGUMENT for
+ * r_link <= 0 or not finite, v_min not finite, a NULL or misaligned d_cluster_scratch, c->d_nlist == NULL with particles;
+ * MTD_ERR_UNSUPPORTED without a switch (the plain route stores summed gradients, which cannot be masked afterwards) and for
+ * n_ghost > 0 (single-domain runs only: a cluster would be cut at the domain boundary). */
+int mtd_coord_accumulate_cluster(const mtd_coord_params *p, const mtd_coord_call *c, const mtd_cluster_params *cluster,
+                                 void *d_cluster_scratch, double **d_sums, unsigned int *n_sums, const double **d_w,
+                                 const unsigned int **d_label, const unsigned int **d_summary);
+
 /* The (reduced) sums -> s.  *d_value points at s, one device double (consume with
  * mtd_metad_set_cv_source(engine, slot, *d_value, 1, 1, 0, 1.0, 0.0)), *d_local (may be NULL) at n_i[n_particles] and *d_switched (may
  * be NULL) at v_i[n_particles] of the last mtd_coord_accumulate (v_i = n_i without a switch), all inside c->d_scratch. */
@@ -1290,6 +1313,27 @@ size_t mtd_tet_scratch_doubles(unsigned int n_particles);
 
 /* This rank's sums: on return *d_sums points at *n_sums = 2 doubles inside c->d_scratch, sum_i v_i and N_t. */
 int mtd_tet_accumulate(const mtd_tet_params *p, const mtd_tet_call *c, double **d_sums, unsigned int *n_sums);
+
+/* The tetrahedral order restricted to the largest cluster ("Clusters" above):
+ *     s = (1 / N_t) sum_i w_i v_i,   N_t the UNMASKED count of the type
+ * with the clusters of mtd_cluster_largest built from the v_i of this call: the nodes are the particles of the type with v_i >= v_min,
+ * linked within r_link — the ice, silicon or mW-water nucleus.  Membership is piecewise constant (PLUMED's treatment): the gradient is
+ * the one above with alpha_i -> w_i alpha_i, and the variable jumps when clusters merge or split.  The launches: the walk of
+ * mtd_tet_accumulate, mtd_cluster_largest on the v row just written, one launch that stores 0 over the adjoint row of every particle
+ * with w_i = 0 (stored, not multiplied: a non-finite entry comes out 0 too) and leaves the block sums of w_i v_i, the sums kernel.
+ * mtd_tet_finalize and mtd_tet_forces (with its virial) then run unchanged on the masked table: there is no force entry point of its
+ * own.  *d_switched of mtd_tet_finalize stays the UNMASKED v_i, the values the clusters were built from.  d_cluster_scratch:
+ * mtd_cluster_scratch_bytes(n_particles) bytes, 16-byte aligned, separate from c->d_scratch, whose layout and size do not change;
+ * *d_w, *d_label, *d_summary (each may be NULL) point into it as mtd_cluster_largest leaves them.  The stream is c->stream.
+ * cluster == NULL or on == 0: mtd_tet_accumulate, bit for bit (that entry point forwards here); the three pointers are set to NULL.
+ * With the option on, before a device is touched: everything mtd_tet_accumulate refuses, as there (n_ghost > 0 among it:
+ * MTD_ERR_UNSUPPORTED); MTD_ERR_INVALID_ARGUMENT for r_link <= 0 or not finite, v_min not finite, a NULL or misaligned
+ * d_cluster_scratch, c->d_nlist == NULL with particles, and for normalise == 0 (A_i is a penalty, not an order: the status a switch or a
+ * gate has there).
+ * The name spells the unit out: the four mtd_tet_* entry points above are the plain variable's, a set its own tests count. */
+int mtd_tetrahedral_accumulate_cluster(const mtd_tet_params *p, const mtd_tet_call *c, const mtd_cluster_params *cluster,
+                                       void *d_cluster_scratch, double **d_sums, unsigned int *n_sums, const double **d_w,
+                                       const unsigned int **d_label, const unsigned int **d_summary);
 
 /* The sums -> s.  *d_value points at s, one device double (consume with
  * mtd_metad_set_cv_source(engine, slot, *d_value, 1, 1, 0, 1.0, 0.0)), *d_local (may be NULL) at t_i[n_particles] (A_i when not

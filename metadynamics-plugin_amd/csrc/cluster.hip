@@ -3,7 +3,8 @@
 // No reference counterpart.  What nucleation studies bias is not the number of solid particles but the size of the LARGEST CONNECTED
 // CLUSTER of them (ten Wolde, Ruiz-Montero and Frenkel; PLUMED's DFSCLUSTERING + CLUSTER_NATOMS / CLUSTER_PROPERTIES).  This unit labels the
 // clusters and hands back the 0 / 1 mask of the largest; it knows nothing of what made the per-particle value v, so any variable that has
-// one per particle can use it (steinhardt_local.hip does).  Definition of nodes, edges and outputs: include/mtd_abi.h, "Clusters".
+// one per particle can use it (steinhardt_local.hip, coordination.hip and tetrahedral.hip do).  Definition of nodes, edges and outputs:
+// include/mtd_abi.h, "Clusters".
 //
 // Lock-free union-find with hooking by the smaller index: a root is only ever hooked under a SMALLER index, so the root of a component
 // is its smallest member when the link pass is done, whatever order the edges arrived in.

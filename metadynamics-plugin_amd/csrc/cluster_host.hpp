@@ -1,5 +1,5 @@
 // cluster_host.hpp — what every entry point that takes mtd_cluster_params refuses before a device is touched (host only; cluster.hip and
-// the units that run the cluster pass between their own launches: steinhardt_local.hip)
+// the units that run the cluster pass between their own launches: steinhardt_local.hip, coordination.hip, tetrahedral.hip)
 #pragma once
 
 #include "mtd_abi.h"

@@ -32,12 +32,17 @@
 //                    PLAIN and COUNT leave this block's share of sum v_i and N_A
 //   k_row_scale      (row_scale.hpp) mtd_coord_forces without a switch: one thread per particle scales the stored sums by -bias / N_A
 //                    and -bias / (2 N_A)
+//   k_row_mask       (row_mask.hpp) mtd_coord_accumulate_cluster: between the CN_COUNT walk and k_row_sums, after the cluster pass of
+//                    cluster.hip on the v_i just written — g'(n_i) of every particle outside the largest cluster set to 0, the block
+//                    sums of slot 0 replaced by those of w_i v_i.  CN_FORCE then runs unchanged on the masked table
 //   k_row_sums       (row_walk.hpp) one wave per slot adds the blocks' doubles in the fixed order of wave_sum
 //   k_cn_finalize    s from the (reduced) sums
 // Fixed summation order everywhere (a lane's entries in row order, the DPP tree of group_sum, a thread's chunks in order, block_sum,
 // wave_sum), no atomics: two identical calls give identical bits, and a row gives the same bits wherever it lies in the list.
 #include "mtd_device.hpp"
 #include "row_scale.hpp"
+#include "row_mask.hpp"
+#include "cluster_host.hpp"
 
 #include <atomic>
 #include <cmath>
@@ -328,9 +333,28 @@ int mtd_coord_set_compiled_pair(int enable)
 
 int mtd_coord_accumulate(const mtd_coord_params *p, const mtd_coord_call *c, double **d_sums, unsigned int *n_sums)
     {
+    return mtd_coord_accumulate_cluster(p, c, nullptr, nullptr, d_sums, n_sums, nullptr, nullptr, nullptr);
+    }
+
+int mtd_coord_accumulate_cluster(const mtd_coord_params *p, const mtd_coord_call *c, const mtd_cluster_params *cluster, void *d_cluster_scratch,
+                                 double **d_sums, unsigned int *n_sums, const double **d_w, const unsigned int **d_label,
+                                 const unsigned int **d_summary)
+    {
     if (!d_sums || !n_sums) return MTD_ERR_INVALID_ARGUMENT;
     int rc = cn_check(p, c);
+    const bool masked = cluster_on(cluster);
+    if (masked && (rc == MTD_SUCCESS || rc == MTD_ERR_UNSUPPORTED))
+        {
+        // what mtd_cluster_largest would refuse, refused here: before the first launch of this call, and ahead of what is merely not built
+        if (cluster_refuse(cluster) != 0) return MTD_ERR_INVALID_ARGUMENT;
+        if (!d_cluster_scratch || ((uintptr_t)d_cluster_scratch & 15u) != 0 || (c->n_particles && !c->d_nlist)) return MTD_ERR_INVALID_ARGUMENT;
+        }
     if (rc) return rc;
+    if (masked)
+        {
+        // the plain route stores summed gradients, which cannot be masked afterwards; g'(n_j) of a ghost is not known (cn_check, with a switch)
+        if (!p->switch_on || c->n_ghost > 0) return MTD_ERR_UNSUPPORTED;
+        }
     QlArgs<4> a;
     rc = cn_ql_args(a, p, c);
     if (rc) return rc;
@@ -355,10 +379,25 @@ int mtd_coord_accumulate(const mtd_coord_params *p, const mtd_coord_call *c, dou
             });
         });
     MTD_LAUNCH_CHECK();
+    const double *w = nullptr;
+    const unsigned int *label = nullptr, *summary = nullptr;
+    if (masked)
+        {
+        // the nodes are the A particles with v_i >= v_min; the mask of the largest cluster, then g'(n_i) and the block sums masked with it
+        const double *v = per_particle + CN_ROW_V * pitch;
+        rc = mtd_cluster_largest(c->n_particles, c->d_postype, c->dtype, c->box, c->d_head_list, c->d_n_neigh, c->d_nlist, p->type_a, v, cluster,
+                                 d_cluster_scratch, &label, nullptr, &w, &summary, c->stream);
+        if (rc) return rc;
+        row_mask(c->n_particles, blocks, 1, w, v, per_particle + CN_ROW_DG * pitch, part, s);
+        MTD_LAUNCH_CHECK();
+        }
     k_row_sums<CN_MAX_BLOCKS><<<2, MTD_WAVE, 0, s>>>(blocks, 2, 0, part, c->d_scratch + CN_OFF_SUMS);
     MTD_LAUNCH_CHECK();
     *d_sums = c->d_scratch + CN_OFF_SUMS;
     *n_sums = 2;
+    if (d_w) *d_w = w;
+    if (d_label) *d_label = label;
+    if (d_summary) *d_summary = summary;
     return MTD_SUCCESS;
     }
 

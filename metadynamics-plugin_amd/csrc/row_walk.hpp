@@ -1,6 +1,6 @@
 // row_walk.hpp — the lane-group walk over one row of a full neighbour list, written once (device; steinhardt_local.hip, cluster.hip,
 // pair_entropy.hip, pair_entropy_local.hip, env_similarity.hip, debye.hip, coordination.hip; the scaling of stored gradient sums, which
-// three of them share, is in row_scale.hpp).
+// three of them share, is in row_scale.hpp; the mask of the largest cluster on a per-particle table, which two of them share, in row_mask.hpp).
 //
 // G lanes (a DPP quad, or half a DPP row) share one central particle; lane q takes entries q, q + G, ... of its row.  Here: the centre of
 // a group (RowCentre / row_centre), the walk itself with its look-ahead (row_walk), the group's sum (group_sum), the zero that keeps the

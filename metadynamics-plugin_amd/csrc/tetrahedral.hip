@@ -23,6 +23,9 @@
 //   k_tet_forces       the gather over row k.  An entry gives -g_kj(d) + g_jk(-d); with beta = alpha_k (+/-) alpha_j — the sum for n, m
 //                      and T, the difference for b, which is odd in d — both terms are ONE evaluation of f, f', u and of the bracket.  The
 //                      centre's alpha stays in registers, the neighbour's comes from the table
+//   k_row_mask         (row_mask.hpp) mtd_tetrahedral_accumulate_cluster: between k_tet_accumulate and k_row_sums, after the cluster pass of
+//                      cluster.hip on the v_i just written — the adjoint row of every particle outside the largest cluster set to 0,
+//                      the block sums of slot 0 replaced by those of w_i v_i.  k_tet_forces then runs unchanged on the masked table
 //   k_row_sums         (row_walk.hpp) one wave per slot adds the blocks' doubles in the fixed order of wave_sum
 //   k_tet_finalize     s from the (reduced) sums
 // An entry with r = 0 has no direction: it takes no part.  Fixed summation order everywhere (a lane's entries in row order, the DPP tree
@@ -30,7 +33,9 @@
 // the same bits wherever it lies in the list.
 #include "mtd_device.hpp"
 #include "row_walk.hpp"
+#include "row_mask.hpp"
 #include "dispatch.hpp"
+#include "cluster_host.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -332,8 +337,23 @@ size_t mtd_tet_scratch_doubles(unsigned int n_particles)
 
 int mtd_tet_accumulate(const mtd_tet_params *p, const mtd_tet_call *c, double **d_sums, unsigned int *n_sums)
     {
+    return mtd_tetrahedral_accumulate_cluster(p, c, nullptr, nullptr, d_sums, n_sums, nullptr, nullptr, nullptr);
+    }
+
+int mtd_tetrahedral_accumulate_cluster(const mtd_tet_params *p, const mtd_tet_call *c, const mtd_cluster_params *cluster,
+                                       void *d_cluster_scratch, double **d_sums, unsigned int *n_sums, const double **d_w,
+                                       const unsigned int **d_label, const unsigned int **d_summary)
+    {
     if (!d_sums || !n_sums) return MTD_ERR_INVALID_ARGUMENT;
     int rc = tet_check(p, c);
+    const bool masked = cluster_on(cluster);
+    if (masked && (rc == MTD_SUCCESS || rc == MTD_ERR_UNSUPPORTED))
+        {
+        // what mtd_cluster_largest would refuse, refused here: before the first launch of this call, and ahead of what is merely not built
+        if (cluster_refuse(cluster) != 0) return MTD_ERR_INVALID_ARGUMENT;
+        if (!d_cluster_scratch || ((uintptr_t)d_cluster_scratch & 15u) != 0 || (c->n_particles && !c->d_nlist)) return MTD_ERR_INVALID_ARGUMENT;
+        if (!p->normalise) return MTD_ERR_INVALID_ARGUMENT;          // A_i is a penalty, not an order: as a switch or a gate there
+        }
     if (rc) return rc;
     QlArgs<4> a;
     rc = tet_ql_args(a, p, c);
@@ -353,10 +373,26 @@ int mtd_tet_accumulate(const mtd_tet_params *p, const mtd_tet_call *c, double **
         return 0;
         });
     MTD_LAUNCH_CHECK();
+    const double *w = nullptr;
+    const unsigned int *label = nullptr, *summary = nullptr;
+    if (masked)
+        {
+        // the nodes are the particles of the type with v_i >= v_min; the mask of the largest cluster, then the adjoint rows and the
+        // block sums masked with it
+        const double *v = per_particle + TET_ROW_V * pitch;
+        rc = mtd_cluster_largest(c->n_particles, c->d_postype, c->dtype, c->box, c->d_head_list, c->d_n_neigh, c->d_nlist, p->type, v, cluster,
+                                 d_cluster_scratch, &label, nullptr, &w, &summary, c->stream);
+        if (rc) return rc;
+        row_mask(c->n_particles, blocks, TET_ALPHA, w, v, per_particle + TET_ROWS * pitch, part, s);
+        MTD_LAUNCH_CHECK();
+        }
     k_row_sums<TET_MAX_BLOCKS><<<2, MTD_WAVE, 0, s>>>(blocks, 2, 0, part, c->d_scratch + TET_OFF_SUMS);
     MTD_LAUNCH_CHECK();
     *d_sums = c->d_scratch + TET_OFF_SUMS;
     *n_sums = 2;
+    if (d_w) *d_w = w;
+    if (d_label) *d_label = label;
+    if (d_summary) *d_summary = summary;
     return MTD_SUCCESS;
     }
 

@@ -858,6 +858,51 @@ double NeighbourVariable::readPartials(const double *d_partials, unsigned int n_
     return readValue((const double *)m_sum.data(), timestep);
     }
 
+void NeighbourVariable::setLargestCluster(LargestCluster &cl, double v_min, double r_link)
+    {
+    if (!std::isfinite(v_min) || !(r_link > 0.0) || !std::isfinite(r_link))
+        throw std::runtime_error(m_prefix + "a cluster needs a finite v_min and r_link > 0");
+    requireReach(r_link, "r_link");
+    cl.par.on = 1;
+    cl.par.v_min = v_min;
+    cl.par.r_link = r_link;
+    invalidate();                                                    // the table in the scratch is the unmasked one
+    }
+
+void NeighbourVariable::clearLargestCluster(LargestCluster &cl)
+    {
+    cl.par.on = 0;
+    cl.par.v_min = cl.par.r_link = 0.0;
+    invalidate();
+    }
+
+void *NeighbourVariable::largestClusterScratch(LargestCluster &cl)
+    {
+    if (!cl.par.on) return nullptr;
+    requireReach(cl.par.r_link, "r_link");
+    const size_t need = mtd_cluster_scratch_bytes(m_pdata->getN());
+    if (need > cl.scratch.bytes()) cl.scratch.resize(need);
+    return cl.scratch.data();
+    }
+
+std::vector<unsigned int> NeighbourVariable::readClusterWords(const LargestCluster &cl, const unsigned int *const *d_src, size_t n, const char *what,
+                                                              unsigned int timestep)
+    {
+    if (!cl.par.on) throw std::runtime_error(m_prefix + "no clusters without the cluster option");
+    computeCV(timestep);                                             // (sets the pointers: before they are read)
+    m_exec_conf->sync();
+    std::vector<unsigned int> out(n);
+    if (!out.empty()) hip_check(hipMemcpy(out.data(), *d_src, sizeof(unsigned int) * n, hipMemcpyDeviceToHost), what);
+    return out;
+    }
+
+std::vector<double> NeighbourVariable::readClusterMask(const LargestCluster &cl, unsigned int timestep)
+    {
+    if (!cl.par.on) throw std::runtime_error(m_prefix + "no clusters without the cluster option");
+    computeCV(timestep);
+    return readBack(cl.d_w, m_pdata->getN(), "cluster mask read-back", timestep);
+    }
+
 std::vector<std::string> NeighbourVariable::getProvidedLogQuantities()
     {
     auto list = CollectiveVariable::getProvidedLogQuantities();
@@ -1505,6 +1550,7 @@ void CoordinationNumber::setSwitch(double c0, unsigned int p, bool less)
 
 void CoordinationNumber::clearSwitch()
     {
+    if (m_cluster.par.on) throw std::runtime_error("cv.coordination: the largest cluster needs the switch (clear the cluster first)");
     m_par.switch_on = 0;
     m_par.c0 = 0.0;
     m_par.p = 0;
@@ -1532,11 +1578,35 @@ void CoordinationNumber::computeCV(unsigned int timestep)
     const mtd_coord_call c = call(&box);
     double *d_sums = nullptr;
     unsigned int n_sums = 0;
-    mtd_check(mtd_coord_accumulate(&m_par, &c, &d_sums, &n_sums), "mtd_coord_accumulate");
+    void *cluster_scratch = largestClusterScratch(m_cluster);
+    mtd_check(mtd_coord_accumulate_cluster(&m_par, &c, &m_cluster.par, cluster_scratch, &d_sums, &n_sums, &m_cluster.d_w, &m_cluster.d_label,
+                                           &m_cluster.d_summary),
+              "mtd_coord_accumulate_cluster");
     reduceOverRanks(d_sums, n_sums);                                 // sum v_i and N_A: a rank's central particles are its local ones, their neighbours may be ghosts
     mtd_check(mtd_coord_finalize(&m_par, &c, &m_d_value, &m_d_local, &m_d_switched), "mtd_coord_finalize");
     computed(timestep);
     }
+
+void CoordinationNumber::setCluster(double v_min, double r_link)
+    {
+    // without a switch the first pass stores summed gradients, which cannot be masked afterwards
+    if (!m_par.switch_on) throw std::runtime_error("cv.coordination: the largest cluster needs a switch");
+    setLargestCluster(m_cluster, v_min, r_link);
+    }
+
+void CoordinationNumber::clearCluster() { clearLargestCluster(m_cluster); }
+
+std::vector<unsigned int> CoordinationNumber::getClusterLabels(unsigned int timestep)
+    {
+    return readClusterWords(m_cluster, &m_cluster.d_label, m_pdata->getN(), "cluster label read-back", timestep);
+    }
+
+std::vector<unsigned int> CoordinationNumber::getLargestCluster(unsigned int timestep)
+    {
+    return readClusterWords(m_cluster, &m_cluster.d_summary, 4, "cluster summary read-back", timestep);
+    }
+
+std::vector<double> CoordinationNumber::getClusterMask(unsigned int timestep) { return readClusterMask(m_cluster, timestep); }
 
 std::vector<double> CoordinationNumber::getLocalValues(unsigned int timestep)
     {
@@ -1632,10 +1702,33 @@ void TetrahedralOrder::computeCV(unsigned int timestep)
     const mtd_tet_call c = call(&box);
     double *d_sums = nullptr;
     unsigned int n_sums = 0;
-    mtd_check(mtd_tet_accumulate(&m_par, &c, &d_sums, &n_sums), "mtd_tet_accumulate");
+    void *cluster_scratch = largestClusterScratch(m_cluster);
+    mtd_check(mtd_tetrahedral_accumulate_cluster(&m_par, &c, &m_cluster.par, cluster_scratch, &d_sums, &n_sums, &m_cluster.d_w,
+                                                 &m_cluster.d_label, &m_cluster.d_summary),
+              "mtd_tetrahedral_accumulate_cluster");
     mtd_check(mtd_tet_finalize(&m_par, &c, &m_d_value, &m_d_local, &m_d_switched, &m_d_coordination), "mtd_tet_finalize");
     computed(timestep);
     }
+
+void TetrahedralOrder::setCluster(double v_min, double r_link)
+    {
+    if (!m_par.normalise) throw std::runtime_error("cv.tetrahedral: the largest cluster needs the normalised variable");
+    setLargestCluster(m_cluster, v_min, r_link);
+    }
+
+void TetrahedralOrder::clearCluster() { clearLargestCluster(m_cluster); }
+
+std::vector<unsigned int> TetrahedralOrder::getClusterLabels(unsigned int timestep)
+    {
+    return readClusterWords(m_cluster, &m_cluster.d_label, m_pdata->getN(), "cluster label read-back", timestep);
+    }
+
+std::vector<unsigned int> TetrahedralOrder::getLargestCluster(unsigned int timestep)
+    {
+    return readClusterWords(m_cluster, &m_cluster.d_summary, 4, "cluster summary read-back", timestep);
+    }
+
+std::vector<double> TetrahedralOrder::getClusterMask(unsigned int timestep) { return readClusterMask(m_cluster, timestep); }
 
 std::vector<double> TetrahedralOrder::getLocalValues(unsigned int timestep)
     {

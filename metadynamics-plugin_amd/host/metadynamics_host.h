@@ -374,8 +374,27 @@ class NeighbourVariable : public CollectiveVariable
         std::vector<double> readBack(const double *d_src, size_t n, const char *what, unsigned int timestep);
         double readValue(const double *d_src, unsigned int timestep);
         double readPartials(const double *d_partials, unsigned int n_partials, unsigned int timestep);
+        //! The largest-cluster option of a variable whose accumulate takes mtd_cluster_params (include/mtd_abi.h "Clusters";
+        //! CoordinationNumber, TetrahedralOrder — SteinhardtLocal keeps its own members): the parameters, a scratch that grows and never
+        //! shrinks, and where the cluster pass of the last computeCV left mask, labels and summary
+        struct LargestCluster
+            {
+            mtd_cluster_params par = {0, 0.0, 0.0};
+            DeviceBuffer scratch;
+            const double *d_w = nullptr;
+            const unsigned int *d_label = nullptr, *d_summary = nullptr;
+            };
+        //! v_min finite, r_link > 0 and within the reach of a device-built list, else throws and leaves the option as it was; both invalidate
+        void setLargestCluster(LargestCluster &cl, double v_min, double r_link);
+        void clearLargestCluster(LargestCluster &cl);
+        //! at compute time: NULL with the option off; else the reach checked again (the list may have changed) and the scratch grown
+        void *largestClusterScratch(LargestCluster &cl);
+        //! throws without the option; computeCV, then a synchronising copy of n words at *d_src (read after computeCV has set it)
+        std::vector<unsigned int> readClusterWords(const LargestCluster &cl, const unsigned int *const *d_src, size_t n, const char *what,
+                                                   unsigned int timestep);
+        std::vector<double> readClusterMask(const LargestCluster &cl, unsigned int timestep);
 
-        std::string m_prefix;                                          // "cv.<kind>: "
+        std::string m_prefix;                                         // "cv.<kind>: "
         std::shared_ptr<NeighborList> m_nlist;
         unsigned int m_type;
         DeviceBuffer m_scratch, m_sum;                                 // (m_sum: one double, sized by the variables that reduce block sums)
@@ -550,14 +569,24 @@ class CoordinationNumber : public NeighbourVariable
         std::vector<double> getSwitchedValues(unsigned int timestep);  //!< v_i = g(n_i) (n_i without a switch)
         //! h(c) = y^p / (1 + y^p), y = c / c0, or 1 - h with `less`; every change invalidates the cached step
         void setSwitch(double c0, unsigned int p, bool less);
-        void clearSwitch();
+        void clearSwitch();                                            //!< throws while a cluster is on
         double getRCut() const { return m_par.r_cut; }                 //!< what the neighbour list must reach
+        //! the largest cluster of mtd_cluster_params (include/mtd_abi.h "Clusters"): the variable becomes (1/N_A) sum of v_i over the
+        //! largest connected cluster of A particles with v_i >= v_min, linked within r_link; needs a switch; single-domain only.
+        //! getSwitchedValues stays unmasked
+        void setCluster(double v_min, double r_link);                  //!< v_min finite, r_link > 0 and within the reach of a device-built list
+        void clearCluster();
+        //! the only places that read the cluster pass back; all three throw without the option
+        std::vector<unsigned int> getClusterLabels(unsigned int timestep);   //!< smallest index of i's cluster, MTD_CLUSTER_NONE for a non-node
+        std::vector<double> getClusterMask(unsigned int timestep);           //!< w_i: 1 for the members of the largest cluster, else 0
+        std::vector<unsigned int> getLargestCluster(unsigned int timestep);  //!< {root, members, number of clusters, number of nodes}
 
     private:
         void computeCV(unsigned int timestep) override;
         mtd_coord_call call(const mtd_box *box);                       //!< rowCall behind a scratch grown to this step's particle count
         mtd_coord_params m_par;
         const double *m_d_local, *m_d_switched;
+        LargestCluster m_cluster;
     };
 
 //! Tetrahedral order (no reference counterpart; include/mtd_abi.h "Tetrahedral order"): the bond-angle order t_i of every particle from the
@@ -579,12 +608,22 @@ class TetrahedralOrder : public NeighbourVariable
         void setGate(double n_lo, double n_hi);                        //!< g(n) = smoothstep from n_lo to n_hi
         void clearGate();
         double getRCut() const { return m_par.r_cut; }                 //!< what the neighbour list must reach
+        //! the largest cluster of mtd_cluster_params (include/mtd_abi.h "Clusters"): the variable becomes (1/N_t) sum of v_i over the
+        //! largest connected cluster of particles with v_i >= v_min, linked within r_link; needs `normalise`.  getSwitchedValues stays
+        //! unmasked
+        void setCluster(double v_min, double r_link);                  //!< v_min finite, r_link > 0 and within the reach of a device-built list
+        void clearCluster();
+        //! the only places that read the cluster pass back; all three throw without the option
+        std::vector<unsigned int> getClusterLabels(unsigned int timestep);   //!< smallest index of i's cluster, MTD_CLUSTER_NONE for a non-node
+        std::vector<double> getClusterMask(unsigned int timestep);           //!< w_i: 1 for the members of the largest cluster, else 0
+        std::vector<unsigned int> getLargestCluster(unsigned int timestep);  //!< {root, members, number of clusters, number of nodes}
 
     private:
         void computeCV(unsigned int timestep) override;
         mtd_tet_call call(const mtd_box *box);                         //!< rowCall behind a scratch grown to this step's particle count
         mtd_tet_params m_par;
         const double *m_d_local, *m_d_switched, *m_d_coordination;
+        LargestCluster m_cluster;
     };
 
 //! AspectRatio.h / AspectRatio.cc:5-130 — box-shape CV, external virial only

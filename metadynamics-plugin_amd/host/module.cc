@@ -444,6 +444,20 @@ PYBIND11_MODULE(_metadynamics, m)
         .def("getRCut", &CoordinationNumber::getRCut)
         .def("setSwitch", &CoordinationNumber::setSwitch)
         .def("clearSwitch", &CoordinationNumber::clearSwitch)
+        .def("setCluster", &CoordinationNumber::setCluster)
+        .def("clearCluster", &CoordinationNumber::clearCluster)
+        .def("getClusterLabels", [](CoordinationNumber &cv, unsigned int timestep) {
+            const std::vector<unsigned int> v = cv.getClusterLabels(timestep);
+            return py::array_t<unsigned int>((ssize_t)v.size(), v.data());
+        })
+        .def("getClusterMask", [](CoordinationNumber &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getClusterMask(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        })
+        .def("getLargestCluster", [](CoordinationNumber &cv, unsigned int timestep) {
+            const std::vector<unsigned int> v = cv.getLargestCluster(timestep);
+            return py::make_tuple(v[0], v[1], v[2], v[3]);
+        })
         .def("getLocalValues", [](CoordinationNumber &cv, unsigned int timestep) {
             const std::vector<double> v = cv.getLocalValues(timestep);
             return py::array_t<double>((ssize_t)v.size(), v.data());
@@ -462,6 +476,20 @@ PYBIND11_MODULE(_metadynamics, m)
         .def("clearSwitch", &TetrahedralOrder::clearSwitch)
         .def("setGate", &TetrahedralOrder::setGate)
         .def("clearGate", &TetrahedralOrder::clearGate)
+        .def("setCluster", &TetrahedralOrder::setCluster)
+        .def("clearCluster", &TetrahedralOrder::clearCluster)
+        .def("getClusterLabels", [](TetrahedralOrder &cv, unsigned int timestep) {
+            const std::vector<unsigned int> v = cv.getClusterLabels(timestep);
+            return py::array_t<unsigned int>((ssize_t)v.size(), v.data());
+        })
+        .def("getClusterMask", [](TetrahedralOrder &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getClusterMask(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        })
+        .def("getLargestCluster", [](TetrahedralOrder &cv, unsigned int timestep) {
+            const std::vector<unsigned int> v = cv.getLargestCluster(timestep);
+            return py::make_tuple(v[0], v[1], v[2], v[3]);
+        })
         .def("getLocalValues", [](TetrahedralOrder &cv, unsigned int timestep) {
             const std::vector<double> v = cv.getLocalValues(timestep);
             return py::array_t<double>((ssize_t)v.size(), v.data());

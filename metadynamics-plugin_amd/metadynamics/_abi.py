@@ -426,10 +426,14 @@ _SIGNATURES = {
     "mtd_coord_scratch_doubles": (C.c_size_t, [C.c_uint]),
     "mtd_coord_set_compiled_pair": (C.c_int, [C.c_int]),
     "mtd_coord_accumulate": (C.c_int, [C.POINTER(CoordParams), C.POINTER(CoordCall), C.POINTER(_vp), _up]),
+    "mtd_coord_accumulate_cluster": (C.c_int, [C.POINTER(CoordParams), C.POINTER(CoordCall), C.POINTER(ClusterParams), _vp, C.POINTER(_vp), _up,
+                                               C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "mtd_coord_finalize": (C.c_int, [C.POINTER(CoordParams), C.POINTER(CoordCall), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "mtd_coord_forces": (C.c_int, [C.POINTER(CoordParams), C.POINTER(CoordCall), _vp, _vp, C.c_double, _vp, C.c_uint]),
     "mtd_tet_scratch_doubles": (C.c_size_t, [C.c_uint]),
     "mtd_tet_accumulate": (C.c_int, [C.POINTER(TetParams), C.POINTER(TetCall), C.POINTER(_vp), _up]),
+    "mtd_tetrahedral_accumulate_cluster": (C.c_int, [C.POINTER(TetParams), C.POINTER(TetCall), C.POINTER(ClusterParams), _vp, C.POINTER(_vp),
+                                                     _up, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "mtd_tet_finalize": (C.c_int, [C.POINTER(TetParams), C.POINTER(TetCall), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "mtd_tet_forces": (C.c_int, [C.POINTER(TetParams), C.POINTER(TetCall), _vp, _vp, C.c_double, _vp, C.c_uint]),
     "mtd_nlist_create": (C.c_int, [C.POINTER(_vp)]),

@@ -580,7 +580,40 @@ class debye_structure_factor(_neighbour_variable):
         return q_min + np.arange(n_q) * dq, np.asarray(self.cpp_force.getSpectrum(context.current.system.getCurrentTimeStep(), q_min, q_max, n_q))
 
 
-class coordination(_neighbour_variable):
+class _largest_cluster(object):
+    """``set_cluster`` and the three read-backs of the variables that restrict their sum to the largest cluster of particles with
+    v_i >= v_min (cv.coordination, cv.tetrahedral; include/mtd_abi.h "Clusters").  cv.steinhardt_local has the option as a keyword of
+    its own."""
+
+    def set_cluster(self, cluster):
+        """``dict(v_min=..., r_link=...)`` (exactly these keys; v_min finite, 0 < r_link < inf and within the reach of a device-built list)
+        or ``None`` (off); takes effect with the next step.  A refused call leaves the option as it was"""
+        try:
+            if cluster is None:
+                self.cpp_force.clearCluster()
+                return
+            cl = (float(cluster["v_min"]), float(cluster["r_link"]))
+            if set(cluster.keys()) != {"v_min", "r_link"} or not abs(cl[0]) < float("inf") or not 0.0 < cl[1] < float("inf"):
+                raise ValueError
+            self.cpp_force.setCluster(*cl)                # everything is checked before anything is changed
+        except (TypeError, KeyError, ValueError, AttributeError, RuntimeError):
+            raise RuntimeError("Error creating collective variable.")
+
+    def get_cluster_labels(self):
+        """uint32 per particle: the smallest particle index of its cluster, 0xffffffff for a particle that is not solid (needs ``cluster``)"""
+        return self.cpp_force.getClusterLabels(context.current.system.getCurrentTimeStep())
+
+    def get_cluster_mask(self):
+        """w_i: 1.0 for the members of the largest cluster, 0.0 for everybody else (needs ``cluster``)"""
+        return self.cpp_force.getClusterMask(context.current.system.getCurrentTimeStep())
+
+    def get_largest_cluster(self):
+        """(root, members, n_clusters, n_nodes): the smallest particle index of the largest cluster and its member count, the number of
+        clusters and of solid particles; root is 0xffffffff and members 0 when nothing is solid (needs ``cluster``)"""
+        return self.cpp_force.getLargestCluster(context.current.system.getCurrentTimeStep())
+
+
+class coordination(_neighbour_variable, _largest_cluster):
     """this build (no reference counterpart; include/mtd_abi.h "Coordination number"): the coordination number of the particles of
     ``type`` (A) by those of ``partner`` (B; ``None``: A itself) through the rational switching function of PLUMED's COORDINATION,
     s(r) = (1 - x^n) / (1 - x^m) with x = max(r - d_0, 0) / r_0, stretched so that it is 1 up to ``d_0`` and 0 at ``r_cut``
@@ -593,6 +626,16 @@ class coordination(_neighbour_variable):
 
     The stretched function vanishes at ``r_cut`` but its slope does not, so the bias force is discontinuous there, by
     |s'(r_cut)| / (1 - s(r_cut)) per pair, divided by N_A.
+
+    ``set_cluster(dict(v_min=..., r_link=...))``: the LARGEST CLUSTER of "liquid-like" particles, the variable of ten Wolde and Frenkel
+    for vapour-liquid nucleation and of nucleation from solution (with ``less`` in the switch: of cavitation).  Needs a switch.  Nodes are
+    the particles of ``type`` with v_i >= v_min, two nodes are linked when one lists the other within r_link, and
+    CV = (1 / N_A) sum_{i in the largest cluster} v_i, N_A still all particles of the type: CV * N_A is the smooth size of the largest
+    cluster and does not charge for the small embryos of a large box.  Membership is piecewise constant, so the force is the gradient of
+    the v_i of the members alone: the variable JUMPS when clusters merge or split.  Single-domain runs only.  ``get_switched()`` stays
+    unmasked — it is what the clusters are built from; ``get_cluster_mask()``, ``get_cluster_labels()`` and ``get_largest_cluster()``
+    give the rest.  With two types the nodes are the ``type`` particles only and the list must hold their pairs up to r_link (a
+    device-built list with two attached types builds all pairs).  ``set_switch(None)`` is refused while the option is on.
 
     Virial (``get_virial``; mtd_coord_forces): half of every pair at each of its ends, no explicit volume term (the normalisation is
     the particle number, not a density).  The sums are -bias * dCV/d(strain)."""
@@ -662,7 +705,7 @@ class coordination(_neighbour_variable):
             raise RuntimeError("Error creating collective variable.")
 
 
-class tetrahedral(_neighbour_variable):
+class tetrahedral(_neighbour_variable, _largest_cluster):
     """this build (no reference counterpart; include/mtd_abi.h "Tetrahedral order"): the three-body bond-angle order of the particles of
     ``type``, the variable of ice, silicon, germanium, mW water and clathrates.  With f the cosine window between ``r_on`` and ``r_cut``
     and u_ij the unit vector from i to its neighbour j,
@@ -681,6 +724,13 @@ class tetrahedral(_neighbour_variable):
     Known property: without a gate a particle whose pair weight W_i is tiny but not zero (a second neighbour just entering the window)
     has a bounded t_i and a gradient of order 1 / f, inherent to a weighted mean.  The gate with n_lo >= 1 removes it; dilute systems
     should use the gate.
+
+    ``set_cluster(dict(v_min=..., r_link=...))``: the LARGEST CLUSTER of tetrahedral particles, the ice, silicon or mW-water nucleus.
+    Needs ``normalise``.  Nodes are the particles of the type with v_i >= v_min, two nodes are linked when one lists the other within
+    r_link, and CV = (1 / N_type) sum_{i in the largest cluster} v_i, N_type still all particles of the type.  Membership is piecewise
+    constant, so the force is the gradient of the v_i of the members alone: the variable JUMPS when clusters merge or split.
+    Single-domain runs only.  ``get_switched()`` stays unmasked — it is what the clusters are built from; ``get_cluster_mask()``,
+    ``get_cluster_labels()`` and ``get_largest_cluster()`` give the rest.
 
     Virial (``get_virial``; mtd_tet_forces): half of every entry at each of its ends, no explicit volume term.  The pair term is not
     parallel to the pair vector, so one particle's six components are not those of a symmetric matrix; their sum over the particles is,

@@ -2,7 +2,8 @@
 """Developer tool: mtd_cluster_largest alone (csrc/cluster.hip) on the config 5 snapshot of tools/bench_ql_local.py (256 000-particle noisy
 fcc crystal, list at 1.4, r_link 1.2) for three masks of solid particles: every particle (one cluster of 256 000: the worst case for the
 link pass), a spherical nucleus of the given radii in an otherwise non-solid box (what the option is for), and nothing; prints us per
-call and the summary.  usage: tools/bench_cluster.py [calls] [radius ...]
+call and the summary.  usage: tools/bench_cluster.py [calls] [radius ...] [--r-list R]   (--r-list: the reach of the list, default 1.4; 1.5 and
+2.4 are the lists of tools/bench_cn.py and tools/bench_tet.py, whose --cluster variants run this pass inside their step)
 Run under rocprofv3 --kernel-trace --stats for the per-kernel table."""
 import ctypes as C
 import os
@@ -15,12 +16,18 @@ import torch
 import util
 from metadynamics import _abi as abi
 
-calls = int(sys.argv[1]) if len(sys.argv) > 1 else 200
-radii = [float(x) for x in sys.argv[2:]] or [6.0, 12.0]
+argv = sys.argv[1:]
+r_list = 1.4
+if "--r-list" in argv:
+    k = argv.index("--r-list")
+    r_list = float(argv[k + 1])
+    del argv[k:k + 2]
+calls = int(argv[0]) if len(argv) > 0 else 200
+radii = [float(x) for x in argv[1:]] or [6.0, 12.0]
 pos, L = util.fcc_lattice(40)
 pos = pos + np.random.default_rng(777).normal(0, 0.05, pos.shape)
 N = len(pos)
-nl = util.build_nlist(pos, L, 1.4)
+nl = util.build_nlist(pos, L, r_list)
 lib = abi.load()
 box = abi.Box.make(L)
 d_pos = torch.from_numpy(util.pack_postype(pos, np.zeros(N, dtype=np.int32), np.float64)).cuda()
