@@ -1350,6 +1350,85 @@ int mtd_tet_forces(const mtd_tet_params *p, const mtd_tet_call *c, void *d_force
                    void *d_virial, unsigned int virial_pitch);
 
 /* ================================================================================================
+ * Bragg intensity (cv.bragg) — no reference counterpart.  The intensity of chosen Bragg peaks, i.e. the structure factor at chosen
+ * reciprocal-lattice vectors: the phase-free companion of "Lamellar order parameter" above.  That variable takes Re rho_k and so depends
+ * on where the density wave sits in the box (a shift by a quarter period takes it from its maximum to zero); |rho_k| does not.  It is
+ * what order-disorder studies of block copolymers bias, the variable of the interface-pinning method (Pedersen, J. Chem. Phys. 139,
+ * 104102) and of crystallisation along a chosen lattice direction.  Oriented, unlike "Debye structure factor"; O(N K), no neighbour list.
+ * Parameters: K = n_modes integer triples (h, k, l), 1 <= K <= MTD_BRAGG_MAX_MODES; an amplitude a(t) per particle type (finite, any
+ * sign, n_types <= MTD_MAX_TYPES); weights w_k (finite, any sign; the Python layer defaults to 1 / K); `modulus`; the trigonometry of
+ * "Lamellar order parameter" (trig_mode; same precondition, same rule for when the hardware instructions are taken).
+ *     q_k   = 2 pi (h b1' + k b2' + l b3'),  b_i' the reciprocal rows of the GLOBAL box
+ *     rho_k = sum_j a(type_j) exp(i q_k . r_j)         over ALL particles of all ranks
+ *     A1 = sum_j |a_j|,  A2 = sum_j a_j^2
+ *     s = sum_k w_k |rho_k|^2 / A1^2                   (default)
+ *     s = sum_k w_k |rho_k| / A1                       (modulus != 0)
+ *     S_k = |rho_k|^2 / A2                             (the structure factor at q_k: a diagnostic, 0 when A2 = 0)
+ * Both forms lie in [0, sum_k w_k] for weights >= 0: 1 for a perfect density wave of one sign, O(1 / N) (default) or O(1 / sqrt N)
+ * (modulus) for N random positions.  A1 = 0 (no particle with an amplitude): s = 0, S_k = 0, every coefficient 0, no forces; nothing NaN.
+ * Gradient, with phi_kj = q_k . r_j, alpha_k = ds / d Re rho_k and beta_k = ds / d Im rho_k:
+ *     default:  (alpha_k, beta_k) = 2 w_k (Re rho_k, Im rho_k) / A1^2
+ *     modulus:  (alpha_k, beta_k) = w_k (Re rho_k, Im rho_k) / (|rho_k| A1), both 0 when |rho_k| = 0 (the modulus has a cusp there; the
+ *               force of a mode stays below w_k |q_k| |a_j| |bias| / A1 however small |rho_k| is)
+ *     ds/dr_j = a_j sum_k q_k (-alpha_k sin phi_kj + beta_k cos phi_kj),   F_j = -bias ds/dr_j,  force.w = 0
+ * This is the exact gradient: the factor 2 of the lamellar force (quirk Q1) has no place here.  s does not change when all particles are
+ * shifted together, so sum_j F_j = 0.  The phase depends on fractional coordinates only, so s does not change under an affine strain of
+ * box and positions either: THE BIAS FORCE HAS NO VIRIAL and these entry points write none.
+ * Arithmetic of the lamellar kernels: fractional projections in fp64, the phase in turns rounded once to fp32, fp32 trigonometry; every
+ * term is added in fp64, in a fixed order, no atomics: two identical calls give identical bits, and two splits of the particles over
+ * ranks give sums that differ by fp64 rounding only.
+ * A step is _accumulate, (mtd_comm_allreduce_small of *d_sums in a domain-decomposed run: any split of the particles over the ranks
+ * will do, there are no ghosts), _finalize, _forces with the same parameters, call block and scratch.  Arguments are checked before a
+ * device is touched: MTD_ERR_INVALID_ARGUMENT for null pointers, n_modes == 0, n_types == 0 or above MTD_MAX_TYPES, a non-finite
+ * weight or amplitude, an unknown dtype or trig mode, a d_scratch that is not 16-byte aligned, n_global == 0, a box without volume;
+ * MTD_ERR_UNSUPPORTED for n_modes > MTD_BRAGG_MAX_MODES.
+ * ============================================================================================== */
+
+#define MTD_BRAGG_MAX_MODES 16
+
+typedef struct
+    {
+    unsigned int n_modes;                      /* K */
+    int hkl[MTD_BRAGG_MAX_MODES][3];
+    unsigned int n_types;
+    double coeff[MTD_MAX_TYPES];               /* a(t) */
+    double weights[MTD_BRAGG_MAX_MODES];       /* w_k */
+    int modulus;
+    int trig_mode;                             /* enum mtd_trig_mode */
+    } mtd_bragg_params;
+
+/* What the calls of a step share beside the parameters.  n_global, the particles of all ranks, enters no formula (the normalisation is
+ * A1); it tells an empty system, which is refused, from a rank that happens to hold no particle (n_particles == 0), which is not. */
+typedef struct
+    {
+    unsigned int n_particles;
+    const void *d_postype;
+    int dtype;
+    const mtd_box *global_box;
+    unsigned int n_global;
+    double *d_scratch;
+    mtd_stream_t stream;
+    } mtd_bragg_call;
+
+/* device doubles the calls share: sums, value, S_k, coefficients and the rows of block sums; the same for every particle count */
+size_t mtd_bragg_scratch_doubles(unsigned int n_particles);
+
+/* This rank's sums: on return *d_sums points at *n_sums = 2 K + 2 doubles inside c->d_scratch — Re rho_0, Im rho_0, ..., A1, A2 —
+ * ready for mtd_comm_allreduce_small. */
+int mtd_bragg_accumulate(const mtd_bragg_params *p, const mtd_bragg_call *c, double **d_sums, unsigned int *n_sums);
+
+/* The (reduced) sums -> s, S_k and the coefficients.  *d_value points at s, one device double (consume with
+ * mtd_metad_set_cv_source(engine, slot, *d_value, 1, 1, 0, 1.0, 0.0)); *d_structure_factors at S_k[K]; *d_amplitudes at the K pairs
+ * (Re rho_k, Im rho_k), which are the sums themselves; *d_gradient at the K pairs (alpha_k, beta_k) — each of the three may be NULL —
+ * all inside c->d_scratch. */
+int mtd_bragg_finalize(const mtd_bragg_params *p, const mtd_bragg_call *c, const double **d_value, const double **d_structure_factors,
+                       const double **d_amplitudes, const double **d_gradient);
+
+/* Writes d_force[0..n_particles) (w component 0) with the coefficients the last mtd_bragg_finalize (same p and c) left in
+ * c->d_scratch; bias = *d_bias when d_bias != NULL, else bias_host.  n_particles == 0 is success. */
+int mtd_bragg_forces(const mtd_bragg_params *p, const mtd_bragg_call *c, void *d_force, const double *d_bias, double bias_host);
+
+/* ================================================================================================
  * Neighbour list of the stand-alone path (cell list, built on the device)
  * no reference counterpart: HOOMD's md::NeighborList is HOOMD core.  Produces the three arrays SteinhardtQl.cc:80-85 reads, in
  * HOOMD's layout: the neighbours of particle i are d_nlist[d_head_list[i] .. d_head_list[i] + d_n_neigh[i]).

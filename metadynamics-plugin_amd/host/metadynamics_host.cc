@@ -1756,6 +1756,119 @@ void TetrahedralOrder::computeBiasForces(unsigned int timestep)
     }
 
 // ------------------------------------------------------------------------------------------------
+// BraggIntensity
+// ------------------------------------------------------------------------------------------------
+
+BraggIntensity::BraggIntensity(std::shared_ptr<SystemDefinition> sysdef, const std::vector<double> &mode, const std::vector<int3> &lattice_vectors,
+                               const std::vector<double> &weights, bool modulus, const std::string &suffix)
+    : CollectiveVariable(sysdef, "cv_bragg" + suffix), m_par(), m_d_value(nullptr), m_d_structure(nullptr), m_d_amplitudes(nullptr),
+      m_cv_last_updated(0), m_have_computed(false)
+    {
+    if (mode.size() != m_pdata->getNTypes())
+        throw std::runtime_error("cv.bragg: Number of mode parameters has to equal the number of particle types!");
+    if (mode.size() > MTD_MAX_TYPES) throw std::runtime_error("cv.bragg: too many particle types");
+    if (lattice_vectors.empty() || lattice_vectors.size() > MTD_BRAGG_MAX_MODES)
+        throw std::runtime_error("cv.bragg: between 1 and " + std::to_string(MTD_BRAGG_MAX_MODES) + " lattice vectors are supported");
+    for (double a : mode)
+        if (!std::isfinite(a)) throw std::runtime_error("cv.bragg: finite mode parameters are required");
+    m_par.n_modes = (unsigned int)lattice_vectors.size();
+    m_par.n_types = (unsigned int)mode.size();
+    for (unsigned int k = 0; k < m_par.n_modes; ++k)
+        {
+        m_par.hkl[k][0] = lattice_vectors[k].x;
+        m_par.hkl[k][1] = lattice_vectors[k].y;
+        m_par.hkl[k][2] = lattice_vectors[k].z;
+        }
+    for (unsigned int t = 0; t < m_par.n_types; ++t) m_par.coeff[t] = mode[t];
+    m_par.modulus = modulus ? 1 : 0;
+    m_par.trig_mode = MTD_TRIG_DEFAULT;
+    setWeights(weights);
+    m_scratch.resize(sizeof(double) * mtd_bragg_scratch_doubles(m_pdata->getN()));
+    }
+
+void BraggIntensity::setWeights(const std::vector<double> &weights)
+    {
+    if (weights.size() != m_par.n_modes) throw std::runtime_error("cv.bragg: one weight per lattice vector is required");
+    for (double w : weights)
+        if (!std::isfinite(w)) throw std::runtime_error("cv.bragg: finite weights are required");
+    for (unsigned int k = 0; k < m_par.n_modes; ++k) m_par.weights[k] = weights[k];
+    m_have_computed = false;
+    }
+
+void BraggIntensity::setTrigMode(int mode)
+    {
+    if (mode != MTD_TRIG_DEFAULT && mode != MTD_TRIG_HARDWARE && mode != MTD_TRIG_ACCURATE)
+        throw std::runtime_error("cv.bragg: trig mode must be 0 (default), 1 (hardware) or 2 (accurate)");
+    m_par.trig_mode = mode;
+    m_have_computed = false;
+    }
+
+mtd_bragg_call BraggIntensity::call(const mtd_box *box)
+    {
+    mtd_bragg_call c;
+    c.n_particles = m_pdata->getN();
+    c.d_postype = m_pdata->positionsPtr();
+    c.dtype = m_pdata->getDtype();
+    c.global_box = box;
+    c.n_global = m_pdata->getNGlobal();
+    c.d_scratch = (double *)m_scratch.data();
+    c.stream = m_exec_conf->getStream();
+    return c;
+    }
+
+void BraggIntensity::computeCV(unsigned int timestep)
+    {
+    ProfRange prof_range("CV");
+    if (m_have_computed && m_cv_last_updated == timestep) return;
+    const mtd_box box = m_pdata->getGlobalBox().toMtd();
+    const mtd_bragg_call c = call(&box);
+    double *d_sums = nullptr;
+    unsigned int n_sums = 0;
+    mtd_check(mtd_bragg_accumulate(&m_par, &c, &d_sums, &n_sums), "mtd_bragg_accumulate");
+    // rho_k, A1 and A2 of all ranks: any split of the particles will do, the same bits everywhere afterwards
+    if (distributed()) m_exec_conf->allreduceSmall(d_sums, n_sums, m_exec_conf->getStream());
+    mtd_check(mtd_bragg_finalize(&m_par, &c, &m_d_value, &m_d_structure, &m_d_amplitudes, nullptr), "mtd_bragg_finalize");
+    m_have_computed = true;
+    m_cv_last_updated = timestep;
+    }
+
+std::vector<double> BraggIntensity::readBack(const double *const *d_src, size_t n, const char *what, unsigned int timestep)
+    {
+    computeCV(timestep);                                             // (sets the pointer: before it is read)
+    m_exec_conf->sync();
+    std::vector<double> out(n);
+    hip_check(hipMemcpy(out.data(), *d_src, sizeof(double) * n, hipMemcpyDeviceToHost), what);
+    return out;
+    }
+
+double BraggIntensity::getCurrentValue(unsigned int timestep) { return readBack(&m_d_value, 1, "cv read-back", timestep)[0]; }
+
+void BraggIntensity::enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot)
+    {
+    computeCV(timestep);
+    mtd_check(mtd_metad_set_cv_source(engine, slot, m_d_value, 1, 1, 0, 1.0, 0.0), "mtd_metad_set_cv_source");
+    }
+
+std::vector<double> BraggIntensity::getStructureFactors(unsigned int timestep)
+    {
+    return readBack(&m_d_structure, m_par.n_modes, "S_k read-back", timestep);
+    }
+
+std::vector<double> BraggIntensity::getAmplitudes(unsigned int timestep)
+    {
+    return readBack(&m_d_amplitudes, 2 * m_par.n_modes, "rho_k read-back", timestep);
+    }
+
+void BraggIntensity::computeBiasForces(unsigned int timestep)
+    {
+    ProfRange prof_range("Force");
+    computeCV(timestep);                                             // (the coefficients of THIS step's positions)
+    const mtd_box box = m_pdata->getGlobalBox().toMtd();
+    const mtd_bragg_call c = call(&box);
+    mtd_check(mtd_bragg_forces(&m_par, &c, m_force.data(), m_bias_device, m_bias), "mtd_bragg_forces");
+    }
+
+// ------------------------------------------------------------------------------------------------
 // AspectRatio, Density
 // ------------------------------------------------------------------------------------------------
 

@@ -626,6 +626,51 @@ class TetrahedralOrder : public NeighbourVariable
         LargestCluster m_cluster;
     };
 
+//! Bragg intensity (no reference counterpart; include/mtd_abi.h "Bragg intensity"): s = sum_k w_k |rho_k|^2 / A1^2 (or sum_k w_k |rho_k| / A1)
+//! over chosen reciprocal-lattice vectors of the global box — the lamellar variable without its dependence on where the density wave
+//! sits.  A plain CollectiveVariable on purpose: not a LamellarOrderParameterGPU (the integrator would fuse it into the lamellar
+//! launches, which sum Re rho_k) and not a NeighbourVariable (there is no list).  The integrator takes its value as one device double
+//! (enqueueCurrentValue) and hands the bias factor back on the device.  Computed once per time step; an option that changes invalidates.
+//! Works domain-decomposed with any split of the particles: the only exchange is one allreduceSmall of the 2K + 2 sums.  The bias force
+//! has no virial (the phases depend on fractional coordinates only), and none is written.
+class BraggIntensity : public CollectiveVariable
+    {
+    public:
+        BraggIntensity(std::shared_ptr<SystemDefinition> sysdef, const std::vector<double> &mode, const std::vector<int3> &lattice_vectors,
+                       const std::vector<double> &weights, bool modulus, const std::string &suffix = "");
+        double getCurrentValue(unsigned int timestep) override;
+        void enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot) override;
+        void computeBiasForces(unsigned int timestep) override;
+        std::vector<std::string> getProvidedLogQuantities() override
+            {
+            auto l = CollectiveVariable::getProvidedLogQuantities();
+            l.push_back(m_cv_name);
+            return l;
+            }
+        double getLogValue(const std::string &quantity, unsigned int timestep) override
+            {
+            if (quantity == m_cv_name) return getCurrentValue(timestep);
+            return CollectiveVariable::getLogValue(quantity, timestep);
+            }
+        std::vector<double> getStructureFactors(unsigned int timestep);    //!< S_k = |rho_k|^2 / A2
+        std::vector<double> getAmplitudes(unsigned int timestep);          //!< Re rho_0, Im rho_0, Re rho_1, ...: 2 K numbers
+        void setWeights(const std::vector<double> &weights);               //!< K finite numbers
+        std::vector<double> getWeights() const { return std::vector<double>(m_par.weights, m_par.weights + m_par.n_modes); }
+        void setTrigMode(int mode);                                        //!< MTD_TRIG_DEFAULT / _HARDWARE / _ACCURATE, as cv.lamellar
+        int getTrigMode() const { return m_par.trig_mode; }
+        bool getModulus() const { return m_par.modulus != 0; }
+
+    private:
+        void computeCV(unsigned int timestep);
+        mtd_bragg_call call(const mtd_box *box);
+        std::vector<double> readBack(const double *const *d_src, size_t n, const char *what, unsigned int timestep);
+        mtd_bragg_params m_par;
+        DeviceBuffer m_scratch;
+        const double *m_d_value, *m_d_structure, *m_d_amplitudes;
+        unsigned int m_cv_last_updated;
+        bool m_have_computed;
+    };
+
 //! AspectRatio.h / AspectRatio.cc:5-130 — box-shape CV, external virial only
 class AspectRatio : public CollectiveVariable
     {

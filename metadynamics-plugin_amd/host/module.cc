@@ -259,6 +259,26 @@ PYBIND11_MODULE(_metadynamics, m)
         .def("setTrigMode", &LamellarOrderParameterGPU::setTrigMode)
         .def("getTrigMode", &LamellarOrderParameterGPU::getTrigMode);
 
+    // no reference counterpart: the intensity of chosen Bragg peaks, the lamellar variable without its phase
+    py::class_<BraggIntensity, CollectiveVariable, std::shared_ptr<BraggIntensity>>(m, "BraggIntensity")
+        .def(py::init<std::shared_ptr<SystemDefinition>, const std::vector<double> &, const std::vector<int3> &, const std::vector<double> &, bool,
+                      const std::string &>())
+        .def("getStructureFactors", [](BraggIntensity &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getStructureFactors(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        })
+        .def("getAmplitudes", [](BraggIntensity &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getAmplitudes(timestep);
+            py::array_t<double> out({(ssize_t)(v.size() / 2), (ssize_t)2});
+            std::copy(v.begin(), v.end(), out.mutable_data());
+            return out;
+        })
+        .def("setWeights", &BraggIntensity::setWeights)
+        .def("getWeights", &BraggIntensity::getWeights)
+        .def("getModulus", &BraggIntensity::getModulus)
+        .def("setTrigMode", &BraggIntensity::setTrigMode)
+        .def("getTrigMode", &BraggIntensity::getTrigMode);
+
     // OrderParameterMesh.cc:1181-1193 / OrderParameterMeshGPU.cc:571-584
     py::class_<OrderParameterMeshGPU, CollectiveVariable, std::shared_ptr<OrderParameterMeshGPU>>(m, "OrderParameterMeshGPU")
         .def(py::init<std::shared_ptr<SystemDefinition>, unsigned int, unsigned int, unsigned int, std::vector<double>, std::vector<int3>>())

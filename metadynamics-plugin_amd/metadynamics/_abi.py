@@ -256,6 +256,38 @@ class TetParams(C.Structure):
         return o
 
 
+MTD_BRAGG_MAX_MODES = 16
+MTD_TRIG_DEFAULT, MTD_TRIG_HARDWARE, MTD_TRIG_ACCURATE = 0, 1, 2
+
+
+class BraggParams(C.Structure):
+    """mtd_bragg_params: the lattice vectors, the amplitude of every particle type, the weights, the form and the trigonometry"""
+    _fields_ = [("n_modes", C.c_uint), ("hkl", (C.c_int * 3) * MTD_BRAGG_MAX_MODES), ("n_types", C.c_uint), ("coeff", C.c_double * MTD_MAX_TYPES),
+                ("weights", C.c_double * MTD_BRAGG_MAX_MODES), ("modulus", C.c_int), ("trig_mode", C.c_int)]
+
+    @classmethod
+    def make(cls, hkl, coeff, weights=None, modulus=False, trig_mode=0, n_modes=None, n_types=None):
+        """hkl: up to MTD_BRAGG_MAX_MODES triples; coeff: a(t) per type; weights default to 1 / K; n_modes, n_types override the counts (to
+        hand over refused ones).  Nothing is checked here: the entry points refuse what they do not take"""
+        o = cls()
+        weights = [1.0 / len(hkl)] * len(hkl) if weights is None else [float(w) for w in weights]
+        o.n_modes = len(hkl) if n_modes is None else int(n_modes)
+        o.n_types = len(coeff) if n_types is None else int(n_types)
+        for k in range(min(len(hkl), MTD_BRAGG_MAX_MODES)):
+            o.hkl[k][:] = [int(x) for x in hkl[k]]
+            o.weights[k] = weights[k]
+        for t in range(min(len(coeff), MTD_MAX_TYPES)):
+            o.coeff[t] = float(coeff[t])
+        o.modulus, o.trig_mode = int(bool(modulus)), int(trig_mode)
+        return o
+
+
+class BraggCall(C.Structure):
+    """mtd_bragg_call: particles, the GLOBAL box, the particle count of all ranks, scratch and stream of one step"""
+    _fields_ = [("n_particles", C.c_uint), ("d_postype", C.c_void_p), ("dtype", C.c_int), ("global_box", C.POINTER(Box)), ("n_global", C.c_uint),
+                ("d_scratch", C.c_void_p), ("stream", C.c_void_p)]
+
+
 _vp = C.c_void_p
 _dp = C.POINTER(C.c_double)
 _up = C.POINTER(C.c_uint)
@@ -436,6 +468,10 @@ _SIGNATURES = {
                                                      _up, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "mtd_tet_finalize": (C.c_int, [C.POINTER(TetParams), C.POINTER(TetCall), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "mtd_tet_forces": (C.c_int, [C.POINTER(TetParams), C.POINTER(TetCall), _vp, _vp, C.c_double, _vp, C.c_uint]),
+    "mtd_bragg_scratch_doubles": (C.c_size_t, [C.c_uint]),
+    "mtd_bragg_accumulate": (C.c_int, [C.POINTER(BraggParams), C.POINTER(BraggCall), C.POINTER(_vp), _up]),
+    "mtd_bragg_finalize": (C.c_int, [C.POINTER(BraggParams), C.POINTER(BraggCall), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "mtd_bragg_forces": (C.c_int, [C.POINTER(BraggParams), C.POINTER(BraggCall), _vp, _vp, C.c_double]),
     "mtd_nlist_create": (C.c_int, [C.POINTER(_vp)]),
     "mtd_nlist_destroy": (C.c_int, [_vp]),
     "mtd_nlist_build": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp, C.c_int, C.POINTER(Box), C.c_double, C.c_int, C.c_int,

@@ -115,6 +115,86 @@ class lamellar(_collective_variable):
         self.cpp_force.setTrigMode(codes[mode])
 
 
+class bragg(_collective_variable):
+    """this build (no reference counterpart; include/mtd_abi.h "Bragg intensity"): the intensity of chosen Bragg peaks,
+    CV = sum_k weights[k] |rho_k|^2 / A1^2 with rho_k = sum_j a(type_j) exp(i q_k . r_j) over all particles and A1 = sum_j |a(type_j)|,
+    or with ``modulus=True`` CV = sum_k weights[k] |rho_k| / A1.  ``mode`` and ``lattice_vectors`` are those of ``cv.lamellar`` (at most
+    16 vectors), ``weights`` default to 1 / K each, and both forms then lie between 0 and 1: 1 for a perfect density wave, O(1 / N) for
+    random positions (O(1 / sqrt N) with ``modulus``).
+
+    ``cv.lamellar`` takes the real part of rho_k and so depends on where the density wave sits in the box: a bias on it must both order
+    the system and hold the pattern at the origin, and lamellae or a crystal that form at any other phase get no credit.  This variable
+    does not change when all particles are shifted together; it is oriented, unlike ``cv.debye_structure_factor``, and costs O(N K)
+    without a neighbour list.  It is what order-disorder studies of block copolymers and the interface-pinning method bias.
+
+    The bias force is the exact gradient (no factor 2 of ``cv.lamellar``'s quirk) and sums to zero over the particles.  The variable
+    depends on fractional coordinates only, so the bias force has NO VIRIAL and none is written: a constant-pressure run needs no
+    correction.  With ``modulus=True`` the gradient has a cusp where a peak vanishes; the force stays bounded there.
+    Works in domain-decomposed runs with any split of the particles."""
+
+    def __init__(self, mode, lattice_vectors, weights=None, modulus=False, name=None, sigma=1.0):
+        if name is not None:
+            name = "_" + name
+            suffix = name
+        else:
+            suffix = ""
+        _collective_variable.__init__(self, sigma, name)
+        try:
+            if len(lattice_vectors) == 0 or len(lattice_vectors) > 16:
+                raise ValueError
+            cpp_mode = _mode_vector(mode, "cv.bragg")
+            cpp_lattice_vectors = _metadynamics.std_vector_int3()
+            for l in lattice_vectors:
+                if len(l) != 3:
+                    raise ValueError
+                cpp_lattice_vectors.append(_metadynamics.make_int3(int(l[0]), int(l[1]), int(l[2])))
+            weights = self._weights(weights, len(lattice_vectors))
+            self.cpp_force = _metadynamics.BraggIntensity(context.current.system_definition, cpp_mode, cpp_lattice_vectors, weights,
+                                                          bool(modulus), suffix)
+        except (TypeError, ValueError, AttributeError, RuntimeError):
+            context.current.forces.remove(self)                      # refused: the run must not find a half-made variable
+            raise RuntimeError("Error creating collective variable.")
+        self.lattice_vectors = [tuple(int(x) for x in l) for l in lattice_vectors]
+        self.weights = weights
+        self.modulus = bool(modulus)
+
+    @staticmethod
+    def _weights(weights, n):
+        """None: 1 / n each; else n finite numbers"""
+        if weights is None:
+            return [1.0 / n] * n
+        weights = [float(weights)] if not hasattr(weights, "__len__") else [float(w) for w in weights]
+        inf = float("inf")
+        if len(weights) != n or not all(-inf < w < inf for w in weights):
+            raise ValueError
+        return weights
+
+    def set_weights(self, weights):
+        """one weight per lattice vector (None: 1 / K each); the value of the current time step is formed anew"""
+        try:
+            weights = self._weights(weights, len(self.lattice_vectors))
+        except (TypeError, ValueError):
+            raise RuntimeError("Error setting parameters of collective variable.")
+        self.cpp_force.setWeights(weights)
+        self.weights = weights
+
+    def set_trig_mode(self, mode):
+        """the trigonometry of this variable's kernels: "hardware", "accurate" or "default", as ``cv.lamellar.set_trig_mode``"""
+        codes = {"default": 0, "hardware": 1, "accurate": 2}
+        if mode not in codes:
+            raise RuntimeError("Error setting parameters of collective variable.")
+        self.cpp_force.setTrigMode(codes[mode])
+
+    def get_structure_factors(self):
+        """S_k = |rho_k|^2 / sum_j a_j^2 of every lattice vector at the current time step: N for a perfect density wave, about 1 for
+        random positions"""
+        return self.cpp_force.getStructureFactors(context.current.system.getCurrentTimeStep())
+
+    def get_amplitudes(self):
+        """(Re rho_k, Im rho_k) of every lattice vector at the current time step, an array of shape (K, 2)"""
+        return self.cpp_force.getAmplitudes(context.current.system.getCurrentTimeStep())
+
+
 class aspect_ratio(_collective_variable):
     """cv.py:275-305"""
 
