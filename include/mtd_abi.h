@@ -1429,6 +1429,102 @@ int mtd_bragg_finalize(const mtd_bragg_params *p, const mtd_bragg_call *c, const
 int mtd_bragg_forces(const mtd_bragg_params *p, const mtd_bragg_call *c, void *d_force, const double *d_bias, double bias_host);
 
 /* ================================================================================================
+ * Probe volume (cv.probe_volume) — no reference counterpart.  The coarse-grained number of particles in a region fixed in space, the
+ * variable of the INDUS method (Patel, Varilly, Chandler, Garde, J. Stat. Phys. 145, 265 (2011)): it is biased to empty a cavity next to
+ * a surface, to fill or drain a pore, to drive cavitation at a chosen place, to hold a slab at a given filling.  Every other variable
+ * here is a property of the whole box; this one says where.  O(N), positions and types only, no neighbour list.
+ *     s   = N~_v = sum_i a(type_i) h(d_i),   d_i = min_image(r_i - c)            over ALL particles of all ranks
+ *     N_v        = sum_i a(type_i) [d_i inside the sharp region]                 (a diagnostic, not biased)
+ * a(t): a weight per particle type (finite, any sign, n_types <= MTD_MAX_TYPES); c: the centre; min_image: HOOMD's BoxDim::minImage of
+ * the GLOBAL box.  Smoothing is one-dimensional, the truncated and shifted Gaussian of the paper with width sigma_s and cut-off r_c:
+ *     Phi(u) = [exp(-u^2 / 2 sigma_s^2) - exp(-r_c^2 / 2 sigma_s^2)] / k      for |u| < r_c, else 0
+ *     k      = sqrt(2 pi) sigma_s erf(r_c / (sqrt2 sigma_s)) - 2 r_c exp(-r_c^2 / 2 sigma_s^2)
+ *     G(u)   = 0 (u <= -r_c),  1 (u >= r_c),  else  1/2 + [sqrt(pi/2) sigma_s erf(u / (sqrt2 sigma_s)) - u exp(-r_c^2 / 2 sigma_s^2)] / k
+ * G' = Phi; both are continuous and Phi(+-r_c) = 0, so h and the bias force are continuous (the force has a kink at the shell's edge).
+ * Shapes:
+ *     MTD_PROBE_BOX       half-widths w along the lab axes, each > 0 or +inf (unbounded: a slab, a channel), at least one finite:
+ *                         h = prod over the bounded axes of [G(w - d) - G(-w - d)]  (the paper's form),
+ *                         dh/dd_al = [Phi(-w_al - d_al) - Phi(w_al - d_al)] (the other factors)
+ *     MTD_PROBE_SPHERE    radius R > r_c:  h = G(R - |d|),  grad h = -Phi(R - |d|) d / |d|  (0 at |d| = 0, where Phi(R) = 0)
+ *     MTD_PROBE_CYLINDER  axis along lab x, y or z (axis = 0, 1, 2), radius R > r_c, half-length half_width[axis] > 0 or +inf:
+ *                         h = G(R - d_perp) [G(w - d_ax) - G(-w - d_ax)]
+ * Sphere and cylinder smooth RADIALLY.  That is not the paper's three-dimensional convolution of the indicator; the two agree for
+ * sigma_s << R.  "Inside the sharp region": -w_al <= d_al < w_al on every bounded axis, |d| < R, d_perp < R.
+ * The centre is handed over in FRACTIONAL coordinates f of the global box, c = lo + f_0 a_1 + f_1 a_2 + f_2 a_3 with the lattice
+ * vectors a_1 = (Lx, 0, 0), a_2 = (xy Ly, Ly, 0), a_3 = (xz Lz, yz Lz, Lz): under a box change it follows the box affinely.  Widths, R,
+ * sigma_s and r_c stay absolute lengths.
+ * THE FIT RULE.  Region and shell must lie inside the cell that min_image maps into; it is checked against the box of every call (the
+ * box changes in constant-pressure runs) and a region that does not fit is refused with MTD_ERR_INVALID_ARGUMENT.  With the extent
+ * e_al = w_al + r_c (box; cylinder axis) or R + r_c (sphere; across a cylinder) on every bounded lab axis al:
+ *     a box with xy = xz = yz = 0:   e_al <= L_al / 2;
+ *     any other box: with b_i' row i of the inverse of the matrix of lattice vectors (b_i' . a_j = delta_ij), for every lattice vector
+ *                    a_i that has a non-zero component along a bounded axis: sum over the bounded al of |b_i'[al]| e_al <= (1 + 1e-12) / 2
+ *                    (1e-12 for the roundings of the inverse), and b_i'[al] = 0 for every unbounded al.
+ * Force: F_i = -bias a_i grad h(d_i), the exact gradient, written for EVERY particle (0 outside region and shell; force.w = 0).  The
+ * region is an external object: THE BIAS FORCES DO NOT SUM TO ZERO, and that is correct.
+ * Virial (only with a virial pointer): positions and box strained together, the centre following; then ds/d eps_ab = sum_i a_i
+ * dh/dd_a d_b, and  virial_i[ab] = -bias a_i (d_a h d_b + d_b h d_a) / 2,  so that sum_i virial_i = -bias (symmetrised ds/d eps).
+ * Layout, scalar type and pitch rule of mtd_ql_local_forces_virial (virial[c * pitch + i], c = xx, xy, xz, yy, yz, zz); every row
+ * [0, n_particles) is written, [n_particles, virial_pitch) is left alone.  The force array is the same, bit for bit, with and without.
+ * Arithmetic: everything behind the load is fp64 for both array types (fp32 positions are promoted exactly), so a term is the same bits
+ * on whichever rank its particle sits; sums in a fixed order, no atomics: two identical calls give identical bits.  Only lanes with
+ * |u| < r_c on some face evaluate erf and exp.
+ * A step is _accumulate, (mtd_comm_allreduce_small of *d_sums in a domain-decomposed run: any split of the particles over the ranks will
+ * do, ghosts are not handed over), _finalize, _forces with the same parameters, call block and scratch.  Arguments are checked before a
+ * device is touched: MTD_ERR_INVALID_ARGUMENT for null pointers, an unknown shape, axis, dtype; sigma_s or r_c not positive and finite;
+ * a half-width that is not positive (NaN included) or a box without a bounded axis; R not finite or not above r_c; a non-finite centre
+ * or weight; n_types == 0 or above MTD_MAX_TYPES; a d_scratch that is not 16-byte aligned; n_global == 0; a box without volume; a region
+ * that does not fit; a virial pitch below n_particles.
+ * ============================================================================================== */
+
+enum mtd_probe_shape { MTD_PROBE_BOX = 0, MTD_PROBE_SPHERE = 1, MTD_PROBE_CYLINDER = 2 };
+
+typedef struct
+    {
+    int shape;                                 /* enum mtd_probe_shape */
+    int axis;                                  /* cylinder: 0, 1, 2 for x, y, z; ignored otherwise */
+    double centre[3];                          /* FRACTIONAL coordinates of the centre in the global box */
+    double half_width[3];                      /* box: w_x, w_y, w_z; cylinder: half_width[axis] is the half-length; +inf: unbounded */
+    double radius;                             /* sphere, cylinder: R */
+    double sigma_s;
+    double r_c;
+    unsigned int n_types;
+    double coeff[MTD_MAX_TYPES];               /* a(t) */
+    } mtd_probe_params;
+
+/* What the calls of a step share beside the parameters.  n_global, the particles of all ranks, enters no formula; it tells an empty
+ * system, which is refused, from a rank that happens to hold no particle (n_particles == 0), which is not. */
+typedef struct
+    {
+    unsigned int n_particles;                  /* local particles only: ghosts are not counted */
+    const void *d_postype;
+    int dtype;
+    const mtd_box *global_box;
+    unsigned int n_global;
+    double *d_scratch;
+    mtd_stream_t stream;
+    } mtd_probe_call;
+
+/* device doubles the calls share: the two sums and the rows of block sums; the same for every particle count */
+size_t mtd_probe_scratch_doubles(unsigned int n_particles);
+
+/* This rank's sums: on return *d_sums points at *n_sums = 2 doubles inside c->d_scratch, (N~_v, N_v), ready for
+ * mtd_comm_allreduce_small. */
+int mtd_probe_accumulate(const mtd_probe_params *p, const mtd_probe_call *c, double **d_sums, unsigned int *n_sums);
+
+/* *d_value points at s = N~_v, one device double (consume with mtd_metad_set_cv_source(engine, slot, *d_value, 1, 1, 0, 1.0, 0.0)),
+ * *d_count (may be NULL) at N_v, both inside c->d_scratch.  The (reduced) sums ARE the results: this call launches nothing. */
+int mtd_probe_finalize(const mtd_probe_params *p, const mtd_probe_call *c, const double **d_value, const double **d_count);
+
+/* Writes d_force[0..n_particles) from the positions alone (nothing of _accumulate is read); bias = *d_bias when d_bias != NULL, else
+ * bias_host.  d_virial == NULL: no virial, and the kernel is the one without it.  n_particles == 0 is success. */
+int mtd_probe_forces(const mtd_probe_params *p, const mtd_probe_call *c, void *d_force, const double *d_bias, double bias_host,
+                     void *d_virial, unsigned int virial_pitch);
+
+/* Off the step path: d_out[0..n_particles) = h(d_i), one device double per particle, WITHOUT the weight of its type. */
+int mtd_probe_local(const mtd_probe_params *p, const mtd_probe_call *c, double *d_out);
+
+/* ================================================================================================
  * Neighbour list of the stand-alone path (cell list, built on the device)
  * no reference counterpart: HOOMD's md::NeighborList is HOOMD core.  Produces the three arrays SteinhardtQl.cc:80-85 reads, in
  * HOOMD's layout: the neighbours of particle i are d_nlist[d_head_list[i] .. d_head_list[i] + d_n_neigh[i]).

@@ -1869,6 +1869,138 @@ void BraggIntensity::computeBiasForces(unsigned int timestep)
     }
 
 // ------------------------------------------------------------------------------------------------
+// ProbeVolume
+// ------------------------------------------------------------------------------------------------
+
+ProbeVolume::ProbeVolume(std::shared_ptr<SystemDefinition> sysdef, int shape, const std::vector<double> &centre,
+                         const std::vector<double> &half_widths, double radius, int axis, double sigma_s, double r_c,
+                         const std::vector<double> &weights, const std::string &suffix)
+    : CollectiveVariable(sysdef, "cv_probe_volume" + suffix), m_par(), m_d_value(nullptr), m_d_count(nullptr), m_cv_last_updated(0),
+      m_have_computed(false)
+    {
+    if (weights.size() != m_pdata->getNTypes()) throw std::runtime_error("cv.probe_volume: one weight per particle type is required");
+    if (weights.size() > MTD_MAX_TYPES) throw std::runtime_error("cv.probe_volume: too many particle types");
+    m_scratch.resize(sizeof(double) * mtd_probe_scratch_doubles(m_pdata->getN()));
+    m_par.n_types = (unsigned int)weights.size();
+    setWeights(weights);
+    setRegion(shape, centre, half_widths, radius, axis, sigma_s, r_c);
+    }
+
+void ProbeVolume::setWeights(const std::vector<double> &weights)
+    {
+    if (weights.size() != m_par.n_types) throw std::runtime_error("cv.probe_volume: one weight per particle type is required");
+    for (double w : weights)
+        if (!std::isfinite(w)) throw std::runtime_error("cv.probe_volume: finite weights are required");
+    for (unsigned int t = 0; t < m_par.n_types; ++t) m_par.coeff[t] = weights[t];
+    m_have_computed = false;
+    }
+
+void ProbeVolume::setRegion(int shape, const std::vector<double> &centre, const std::vector<double> &half_widths, double radius, int axis,
+                            double sigma_s, double r_c)
+    {
+    if (centre.size() != 3 || half_widths.size() != 3) throw std::runtime_error("cv.probe_volume: centre and half-widths have three components");
+    mtd_probe_params par = m_par;
+    par.shape = shape;
+    par.axis = axis;
+    par.radius = radius;
+    par.sigma_s = sigma_s;
+    par.r_c = r_c;
+    const mtd_box box = m_pdata->getGlobalBox().toMtd();
+    // fractional coordinates in the box of this moment, c = lo + f_0 a_1 + f_1 a_2 + f_2 a_3: the centre follows the box from here on
+    const double z = centre[2] - box.lo[2], y = centre[1] - box.lo[1], x = centre[0] - box.lo[0];
+    par.centre[2] = z / box.L[2];
+    par.centre[1] = (y - par.centre[2] * box.yz * box.L[2]) / box.L[1];
+    par.centre[0] = (x - par.centre[1] * box.xy * box.L[1] - par.centre[2] * box.xz * box.L[2]) / box.L[0];
+    for (int d = 0; d < 3; ++d) par.half_width[d] = half_widths[d];
+    // the library's own checks, fit rule included (mtd_probe_finalize launches nothing)
+    mtd_probe_params keep = m_par;
+    m_par = par;
+    const mtd_probe_call c = call(&box);
+    const double *value = nullptr;
+    const int rc = mtd_probe_finalize(&m_par, &c, &value, nullptr);
+    if (rc != MTD_SUCCESS)
+        {
+        m_par = keep;
+        throw std::runtime_error("cv.probe_volume: the region is refused (sigma_s, r_c > 0; half-widths > 0, one of them finite; radius > r_c; "
+                                 "region and shell inside the minimum-image cell of the box)");
+        }
+    m_have_computed = false;
+    }
+
+mtd_probe_call ProbeVolume::call(const mtd_box *box)
+    {
+    mtd_probe_call c;
+    c.n_particles = m_pdata->getN();
+    c.d_postype = m_pdata->positionsPtr();
+    c.dtype = m_pdata->getDtype();
+    c.global_box = box;
+    c.n_global = m_pdata->getNGlobal();
+    c.d_scratch = (double *)m_scratch.data();
+    c.stream = m_exec_conf->getStream();
+    return c;
+    }
+
+void ProbeVolume::computeCV(unsigned int timestep)
+    {
+    ProfRange prof_range("CV");
+    if (m_have_computed && m_cv_last_updated == timestep) return;
+    const mtd_box box = m_pdata->getGlobalBox().toMtd();
+    const mtd_probe_call c = call(&box);
+    double *d_sums = nullptr;
+    unsigned int n_sums = 0;
+    mtd_check(mtd_probe_accumulate(&m_par, &c, &d_sums, &n_sums), "mtd_probe_accumulate");
+    // the smoothed and the sharp count of all ranks: any split of the particles will do, the same bits everywhere afterwards
+    if (distributed()) m_exec_conf->allreduceSmall(d_sums, n_sums, m_exec_conf->getStream());
+    mtd_check(mtd_probe_finalize(&m_par, &c, &m_d_value, &m_d_count), "mtd_probe_finalize");
+    m_have_computed = true;
+    m_cv_last_updated = timestep;
+    }
+
+double ProbeVolume::readOne(const double *const *d_src, const char *what, unsigned int timestep)
+    {
+    computeCV(timestep);                                             // (sets the pointer: before it is read)
+    m_exec_conf->sync();
+    double out = 0.0;
+    hip_check(hipMemcpy(&out, *d_src, sizeof(double), hipMemcpyDeviceToHost), what);
+    return out;
+    }
+
+double ProbeVolume::getCurrentValue(unsigned int timestep) { return readOne(&m_d_value, "cv read-back", timestep); }
+
+double ProbeVolume::getCount(unsigned int timestep) { return readOne(&m_d_count, "N_v read-back", timestep); }
+
+void ProbeVolume::enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot)
+    {
+    computeCV(timestep);
+    mtd_check(mtd_metad_set_cv_source(engine, slot, m_d_value, 1, 1, 0, 1.0, 0.0), "mtd_metad_set_cv_source");
+    }
+
+std::vector<double> ProbeVolume::getLocal(unsigned int timestep)
+    {
+    (void)timestep;                                                  // h_i follows from the positions of this moment alone
+    const unsigned int N = m_pdata->getN();
+    std::vector<double> out(N);
+    if (N == 0) return out;
+    if (m_local.bytes() < sizeof(double) * N) m_local.resize(sizeof(double) * N);
+    const mtd_box box = m_pdata->getGlobalBox().toMtd();
+    const mtd_probe_call c = call(&box);
+    mtd_check(mtd_probe_local(&m_par, &c, (double *)m_local.data()), "mtd_probe_local");
+    m_exec_conf->sync();
+    hip_check(hipMemcpy(out.data(), m_local.data(), sizeof(double) * N, hipMemcpyDeviceToHost), "h_i read-back");
+    return out;
+    }
+
+void ProbeVolume::computeBiasForces(unsigned int timestep)
+    {
+    ProfRange prof_range("Force");
+    (void)timestep;                                                  // the force pass recomputes grad h from the positions: no sums are read
+    const mtd_box box = m_pdata->getGlobalBox().toMtd();
+    const mtd_probe_call c = call(&box);
+    void *virial = virialTarget();                                   // the array while the pressure flag is set, else NULL
+    mtd_check(mtd_probe_forces(&m_par, &c, m_force.data(), m_bias_device, m_bias, virial, getVirialPitch()), "mtd_probe_forces");
+    }
+
+// ------------------------------------------------------------------------------------------------
 // AspectRatio, Density
 // ------------------------------------------------------------------------------------------------
 

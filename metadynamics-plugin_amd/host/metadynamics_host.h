@@ -671,6 +671,55 @@ class BraggIntensity : public CollectiveVariable
         bool m_have_computed;
     };
 
+//! Probe volume (no reference counterpart; include/mtd_abi.h "Probe volume"): the smoothed number of particles in a box, slab, sphere or
+//! cylinder fixed in space, s = sum_i a(type_i) h(min_image(r_i - c)) — the variable of the INDUS method.  A plain CollectiveVariable like
+//! BraggIntensity: one device double for the integrator, the bias factor back on the device, computed once per time step, any split of
+//! the particles over ranks (one allreduceSmall of two sums; ghosts are not counted).  Unlike every other variable here the bias forces do
+//! NOT sum to zero (the region is an external object), and there is a virial: written per particle while the pressure flag is set, for
+//! positions, box and centre strained together.  The centre is kept in fractional coordinates of the global box it was given in (at
+//! construction or setRegion) and follows the box; widths, radius, sigma_s and r_c are lengths.  The region is checked against the box at
+//! every step (the fit rule of the header): a box that has shrunk below it throws.
+class ProbeVolume : public CollectiveVariable
+    {
+    public:
+        //! shape: mtd_probe_shape; centre: Cartesian, in the current global box; half_widths: three numbers (box; +inf: unbounded) —
+        //! a cylinder reads half_widths[axis] as its half-length; weights: one per particle type
+        ProbeVolume(std::shared_ptr<SystemDefinition> sysdef, int shape, const std::vector<double> &centre, const std::vector<double> &half_widths,
+                    double radius, int axis, double sigma_s, double r_c, const std::vector<double> &weights, const std::string &suffix = "");
+        double getCurrentValue(unsigned int timestep) override;
+        void enqueueCurrentValue(unsigned int timestep, mtd_metad *engine, unsigned int slot) override;
+        void computeBiasForces(unsigned int timestep) override;
+        std::vector<std::string> getProvidedLogQuantities() override
+            {
+            auto l = CollectiveVariable::getProvidedLogQuantities();
+            l.push_back(m_cv_name);
+            return l;
+            }
+        double getLogValue(const std::string &quantity, unsigned int timestep) override
+            {
+            if (quantity == m_cv_name) return getCurrentValue(timestep);
+            return CollectiveVariable::getLogValue(quantity, timestep);
+            }
+        //! between runs (a probe volume is commonly moved or grown in stages); both throw and leave the variable as it was when refused
+        void setRegion(int shape, const std::vector<double> &centre, const std::vector<double> &half_widths, double radius, int axis,
+                       double sigma_s, double r_c);
+        void setWeights(const std::vector<double> &weights);
+        std::vector<double> getWeights() const { return std::vector<double>(m_par.coeff, m_par.coeff + m_par.n_types); }
+        std::vector<double> getFractionalCentre() const { return std::vector<double>(m_par.centre, m_par.centre + 3); }
+        double getCount(unsigned int timestep);                            //!< N_v: the weighted count inside the sharp region
+        std::vector<double> getLocal(unsigned int timestep);               //!< h_i of every local particle, without the weight of its type
+
+    private:
+        void computeCV(unsigned int timestep);
+        mtd_probe_call call(const mtd_box *box);
+        double readOne(const double *const *d_src, const char *what, unsigned int timestep);
+        mtd_probe_params m_par;
+        DeviceBuffer m_scratch, m_local;
+        const double *m_d_value, *m_d_count;
+        unsigned int m_cv_last_updated;
+        bool m_have_computed;
+    };
+
 //! AspectRatio.h / AspectRatio.cc:5-130 — box-shape CV, external virial only
 class AspectRatio : public CollectiveVariable
     {

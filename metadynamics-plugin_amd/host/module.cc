@@ -279,6 +279,20 @@ PYBIND11_MODULE(_metadynamics, m)
         .def("setTrigMode", &BraggIntensity::setTrigMode)
         .def("getTrigMode", &BraggIntensity::getTrigMode);
 
+    // no reference counterpart: the smoothed particle count in a region fixed in space (INDUS)
+    py::class_<ProbeVolume, CollectiveVariable, std::shared_ptr<ProbeVolume>>(m, "ProbeVolume")
+        .def(py::init<std::shared_ptr<SystemDefinition>, int, const std::vector<double> &, const std::vector<double> &, double, int, double, double,
+                      const std::vector<double> &, const std::string &>())
+        .def("setRegion", &ProbeVolume::setRegion)
+        .def("setWeights", &ProbeVolume::setWeights)
+        .def("getWeights", &ProbeVolume::getWeights)
+        .def("getFractionalCentre", &ProbeVolume::getFractionalCentre)
+        .def("getCount", &ProbeVolume::getCount)
+        .def("getLocal", [](ProbeVolume &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getLocal(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        });
+
     // OrderParameterMesh.cc:1181-1193 / OrderParameterMeshGPU.cc:571-584
     py::class_<OrderParameterMeshGPU, CollectiveVariable, std::shared_ptr<OrderParameterMeshGPU>>(m, "OrderParameterMeshGPU")
         .def(py::init<std::shared_ptr<SystemDefinition>, unsigned int, unsigned int, unsigned int, std::vector<double>, std::vector<int3>>())

@@ -288,6 +288,52 @@ class BraggCall(C.Structure):
                 ("d_scratch", C.c_void_p), ("stream", C.c_void_p)]
 
 
+MTD_PROBE_BOX, MTD_PROBE_SPHERE, MTD_PROBE_CYLINDER = 0, 1, 2
+
+
+class ProbeParams(C.Structure):
+    """mtd_probe_params: the shape, its FRACTIONAL centre and sizes, the smoothing and the weight of every particle type"""
+    _fields_ = [("shape", C.c_int), ("axis", C.c_int), ("centre", C.c_double * 3), ("half_width", C.c_double * 3), ("radius", C.c_double),
+                ("sigma_s", C.c_double), ("r_c", C.c_double), ("n_types", C.c_uint), ("coeff", C.c_double * MTD_MAX_TYPES)]
+
+    @staticmethod
+    def fractional(centre, box):
+        """f with centre = lo + f_0 a_1 + f_1 a_2 + f_2 a_3 in a Box (back-substitution: the lattice matrix is triangular)"""
+        x, y, z = (float(centre[d]) - box.lo[d] for d in range(3))
+        f2 = z / box.L[2]
+        f1 = (y - f2 * box.yz * box.L[2]) / box.L[1]
+        f0 = (x - f1 * box.xy * box.L[1] - f2 * box.xz * box.L[2]) / box.L[0]
+        return [f0, f1, f2]
+
+    @classmethod
+    def make(cls, shape, centre_frac, sigma_s, r_c=None, half_width=None, radius=0.0, axis=0, coeff=(1.0,), n_types=None):
+        """shape: "box" | "sphere" | "cylinder" or the enum value; centre_frac: fractional coordinates (see `fractional`); r_c defaults to
+        2 sigma_s; half_width: three numbers for a box, one for a cylinder (its half-length), inf for unbounded.  Nothing is checked here:
+        the entry points refuse what they do not take"""
+        o = cls()
+        o.shape = {"box": MTD_PROBE_BOX, "sphere": MTD_PROBE_SPHERE, "cylinder": MTD_PROBE_CYLINDER}.get(shape, shape)
+        o.axis = int(axis)
+        o.centre[:] = [float(x) for x in centre_frac]
+        if half_width is None:
+            half_width = [float("inf")] * 3
+        elif not hasattr(half_width, "__len__"):
+            half_width = [float(half_width) if d == o.axis else float("inf") for d in range(3)]
+        o.half_width[:] = [float(x) for x in half_width]
+        o.radius = float(radius)
+        o.sigma_s = float(sigma_s)
+        o.r_c = 2.0 * float(sigma_s) if r_c is None else float(r_c)
+        o.n_types = len(coeff) if n_types is None else int(n_types)
+        for t in range(min(len(coeff), MTD_MAX_TYPES)):
+            o.coeff[t] = float(coeff[t])
+        return o
+
+
+class ProbeCall(C.Structure):
+    """mtd_probe_call: particles, the GLOBAL box, the particle count of all ranks, scratch and stream of one step"""
+    _fields_ = [("n_particles", C.c_uint), ("d_postype", C.c_void_p), ("dtype", C.c_int), ("global_box", C.POINTER(Box)), ("n_global", C.c_uint),
+                ("d_scratch", C.c_void_p), ("stream", C.c_void_p)]
+
+
 _vp = C.c_void_p
 _dp = C.POINTER(C.c_double)
 _up = C.POINTER(C.c_uint)
@@ -472,6 +518,11 @@ _SIGNATURES = {
     "mtd_bragg_accumulate": (C.c_int, [C.POINTER(BraggParams), C.POINTER(BraggCall), C.POINTER(_vp), _up]),
     "mtd_bragg_finalize": (C.c_int, [C.POINTER(BraggParams), C.POINTER(BraggCall), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "mtd_bragg_forces": (C.c_int, [C.POINTER(BraggParams), C.POINTER(BraggCall), _vp, _vp, C.c_double]),
+    "mtd_probe_scratch_doubles": (C.c_size_t, [C.c_uint]),
+    "mtd_probe_accumulate": (C.c_int, [C.POINTER(ProbeParams), C.POINTER(ProbeCall), C.POINTER(_vp), _up]),
+    "mtd_probe_finalize": (C.c_int, [C.POINTER(ProbeParams), C.POINTER(ProbeCall), C.POINTER(_vp), C.POINTER(_vp)]),
+    "mtd_probe_forces": (C.c_int, [C.POINTER(ProbeParams), C.POINTER(ProbeCall), _vp, _vp, C.c_double, _vp, C.c_uint]),
+    "mtd_probe_local": (C.c_int, [C.POINTER(ProbeParams), C.POINTER(ProbeCall), _vp]),
     "mtd_nlist_create": (C.c_int, [C.POINTER(_vp)]),
     "mtd_nlist_destroy": (C.c_int, [_vp]),
     "mtd_nlist_build": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp, C.c_int, C.POINTER(Box), C.c_double, C.c_int, C.c_int,

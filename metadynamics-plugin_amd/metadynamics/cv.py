@@ -195,6 +195,124 @@ class bragg(_collective_variable):
         return self.cpp_force.getAmplitudes(context.current.system.getCurrentTimeStep())
 
 
+class probe_volume(_collective_variable):
+    """this build (no reference counterpart; include/mtd_abi.h "Probe volume"): the coarse-grained number of particles in a region fixed
+    in space, CV = sum_i a(type_i) h(min_image(r_i - centre)), the variable of the INDUS method (Patel, Varilly, Chandler, Garde,
+    J. Stat. Phys. 145, 265 (2011)).  Every other variable here is a property of the whole box; this one says where: it is biased to empty
+    a cavity next to a surface, to fill or drain a pore, to drive cavitation at a chosen place, to hold a slab at a given filling.
+
+    ``shape`` is "box" (``half_widths``: three numbers along the lab axes, ``float("inf")`` for an unbounded one: a slab, a channel),
+    "sphere" (``radius``) or "cylinder" (``axis`` "x" | "y" | "z", ``radius``, ``half_length``, by default unbounded).  h is the sharp
+    indicator smoothed with a truncated, shifted Gaussian of width ``sigma_s`` and cut-off ``r_c`` (default 2 sigma_s, the paper's
+    choice); the box uses the paper's product form, sphere and cylinder are smoothed RADIALLY, which is not the paper's three-dimensional
+    convolution (the two agree for sigma_s << radius).  ``weights`` maps type names to a(t); the default is 1 for every type, the usual
+    use 1 for one type and 0 for the rest.  Arguments that do not belong to the shape raise.
+
+    The region with its shell must fit the minimum-image cell of the box (orthorhombic: half-width + r_c <= L / 2 on every bounded axis;
+    see the header for tilted boxes); this is checked at every step.  ``centre`` is taken in the box of the moment it is given and
+    follows the box affinely afterwards; the sizes stay lengths.
+
+    The bias force is the exact gradient, -bias a_i grad h, zero outside region and shell.  The region is an external object: THE BIAS
+    FORCES DO NOT SUM TO ZERO.  Virial (``get_virial``, while the pressure flag is set): -bias a_i (d_a h d_b + d_b h d_a) / 2 per
+    particle, the derivative for positions, box and centre strained together.  Works in domain-decomposed runs with any split of the
+    particles; ghosts are not counted."""
+
+    _cv = "cv.probe_volume"
+    _SHAPES = {"box": 0, "sphere": 1, "cylinder": 2}
+    _AXES = {"x": 0, "y": 1, "z": 2, 0: 0, 1: 1, 2: 2}
+
+    def __init__(self, shape, centre, sigma_s, r_c=None, half_widths=None, radius=None, axis=None, half_length=None, weights=None,
+                 name=None, sigma=1.0):
+        if name is not None:
+            name = "_" + name
+            suffix = name
+        else:
+            suffix = ""
+        _collective_variable.__init__(self, sigma, name)
+        try:
+            region = self._region(shape, centre, sigma_s, r_c, half_widths, radius, axis, half_length)
+            cpp_weights = self._weights(weights)
+            self.cpp_force = _metadynamics.ProbeVolume(context.current.system_definition, *region, cpp_weights, suffix)
+        except (TypeError, ValueError, AttributeError, KeyError, RuntimeError):
+            context.current.forces.remove(self)                      # refused: the run must not find a half-made variable
+            raise RuntimeError("Error creating collective variable.")
+        self.weights = cpp_weights
+
+    @classmethod
+    def _region(cls, shape, centre, sigma_s, r_c, half_widths, radius, axis, half_length):
+        """the arguments of ProbeVolume / setRegion: (shape, centre, half_widths[3], radius, axis, sigma_s, r_c); ValueError for arguments
+        that are missing or do not belong to the shape"""
+        inf = float("inf")
+        code = cls._SHAPES[shape]
+        centre = [float(x) for x in centre]
+        if len(centre) != 3:
+            raise ValueError
+        sigma_s = float(sigma_s)
+        r_c = 2.0 * sigma_s if r_c is None else float(r_c)
+        if shape == "box":
+            if half_widths is None or radius is not None or axis is not None or half_length is not None:
+                raise ValueError
+            w = [float(x) for x in half_widths]
+            if len(w) != 3:
+                raise ValueError
+            return code, centre, w, 0.0, 0, sigma_s, r_c
+        if half_widths is not None or radius is None:
+            raise ValueError
+        if shape == "sphere":
+            if axis is not None or half_length is not None:
+                raise ValueError
+            return code, centre, [inf] * 3, float(radius), 0, sigma_s, r_c
+        if axis is None:
+            raise ValueError
+        ax = cls._AXES[axis]
+        w = [inf] * 3
+        w[ax] = inf if half_length is None else float(half_length)
+        return code, centre, w, float(radius), ax, sigma_s, r_c
+
+    @staticmethod
+    def _weights(weights):
+        """None: 1 for every type; else a mapping that names every particle type (nothing is assumed for a type left out: ValueError)"""
+        pdata = context.current.system_definition.getParticleData()
+        names = [pdata.getNameByType(i) for i in range(pdata.getNTypes())]
+        if weights is None:
+            return [1.0] * len(names)
+        if set(weights.keys()) != set(names):
+            raise ValueError
+        return [float(weights[t]) for t in names]
+
+    def set_region(self, shape, centre, sigma_s, r_c=None, half_widths=None, radius=None, axis=None, half_length=None):
+        """another region, between runs (a probe volume is commonly moved or grown in stages); the arguments of the constructor.  A
+        region that is refused leaves the variable as it was"""
+        try:
+            region = self._region(shape, centre, sigma_s, r_c, half_widths, radius, axis, half_length)
+            self.cpp_force.setRegion(*region)
+        except (TypeError, ValueError, KeyError, RuntimeError):
+            raise RuntimeError("Error setting parameters of collective variable.")
+
+    def set_weights(self, weights):
+        """a(t) for every type name (None: 1 for all)"""
+        try:
+            cpp_weights = self._weights(weights)
+            self.cpp_force.setWeights(cpp_weights)
+        except (TypeError, ValueError, AttributeError, RuntimeError):
+            raise RuntimeError("Error setting parameters of collective variable.")
+        self.weights = cpp_weights
+
+    def get_count(self):
+        """N_v = sum_i a(type_i) [particle i inside the sharp region] at the current time step (a diagnostic: it is not biased)"""
+        return self.cpp_force.getCount(context.current.system.getCurrentTimeStep())
+
+    def get_local(self):
+        """h_i of every local particle at the current positions, without the weight of its type: 1 inside, 0 outside, between in the shell"""
+        return self.cpp_force.getLocal(context.current.system.getCurrentTimeStep())
+
+    def get_virial(self, per_particle=False):
+        """the virial of the bias force the last step wrote, with the return convention of the neighbour-row variables: the six sums
+        xx, xy, xz, yy, yz, zz as float64, or with ``per_particle=True`` the (6, N) array.  The sums are -bias times the symmetrised
+        derivative of the variable under a strain of positions, box and centre.  Only while the pressure flag is set; else this raises."""
+        return _neighbour_variable.get_virial(self, per_particle)
+
+
 class aspect_ratio(_collective_variable):
     """cv.py:275-305"""
 
