@@ -1350,6 +1350,100 @@ int mtd_tet_forces(const mtd_tet_params *p, const mtd_tet_call *c, void *d_force
                    void *d_virial, unsigned int virial_pitch);
 
 /* ================================================================================================
+ * Bond-orientational order (cv.hexatic) — no reference counterpart.  The k-fold bond-orientational order psi_k about a lab axis: the
+ * order WITHIN a layer of two-dimensional and layered matter (2-d melting through the hexatic phase, monolayers at interfaces, confined
+ * films, the in-layer order of smectic-B and lamellar phases).  Not rotation invariant: psi_k is the single m = +-k component in the
+ * frame of the layer normal, and it carries a phase whose coherence over the box tells a hexatic or a solid from a polycrystal, which
+ * q_6 of "Local Steinhardt bond order" cannot.  The conventions of "Debye structure factor" above hold wherever nothing else is said.
+ * Parameters: a particle type t; an integer k, 1 <= k <= MTD_HEX_MAX_K; an axis a in {0, 1, 2} = {x, y, z}, the layer normal, with
+ * the in-plane components (u, v) the two that follow it cyclically (z -> (x, y), x -> (y, z), y -> (z, x)); 0 <= r_on < r_cut;
+ * `global_order`; with global_order = 0 only an optional switch (c0 > 0, integer p >= 1) and an optional gate (0 <= n_lo < n_hi), the
+ * functions of mtd_ql_local_options.
+ * Entries (i, j) of a FULL list take part when i and j are both of type t, j != i, j is a local particle and 0 < r = |d| <= r_cut,
+ * with d = minImage(r_j - r_i) (an entry with r = 0 has no direction and takes no part).  f(r) is the cosine window of the Steinhardt
+ * passes between r_on and r_cut.  SINGLE-DOMAIN ONLY: every per-particle array ends at n_particles, an entry j >= n_particles is
+ * skipped, and n_ghost > 0 is MTD_ERR_UNSUPPORTED.
+ * THIS IS THE DEFINITION:
+ *     z_ij  = (u_ij + i v_ij) / r_ij             B_ij = z_ij^k      ( = sin^k(theta) e^{i k phi}: the sectoral harmonic )
+ *     n_i   = sum_j f(r_ij)                      S_i  = sum_j f(r_ij) B_ij
+ *     psi_i = S_i / n_i     (n_i < MTD_HEX_N_MIN: psi_i = 0 with zero gradient)                  c_i = |psi_i|^2
+ *     local  (global_order = 0):   v_i = g(n_i) h(c_i),  s = (1 / N_t) sum_i v_i      (h(c) = c, g = 1 without options)
+ *     global (global_order = 1):   Psi = (1 / N_t) sum_i psi_i,  s = |Psi|^2          (v_i = c_i is still stored)
+ * with h(c) = x^p / (1 + x^p), x = max(c, 0) / c0, and g the smoothstep of n from n_lo to n_hi.  N_t is the number of centres of the
+ * type; N_t = 0: s = 0, no forces.  For a bond in the plane B is exactly the textbook e^{i k phi}; a bond out of the plane is
+ * de-weighted by sin^k theta.  B is a polynomial in d / r, so a bond ALONG the axis is an ordinary point (the form (x + i y) / rho has a
+ * 1 / rho singularity there).  |psi_i| < 1 on a rippled but perfect layer is therefore INTENDED, not an error of the implementation.
+ * c_i is used, not |psi_i|, because it is smooth at 0.  Lattice values: c_i = 1 and |Psi|^2 = 1 on a perfect triangular monolayer with
+ * k = 6, for any in-plane rotation, and 0 with k = 3; psi_i = -1/6, s = 1/36 in both modes on perfect fcc with the window over the first
+ * shell only, k = 4 and any of the three axes (in the plane 4 (-1), out of it 8 (1/4) (+1), over n = 12).
+ * Gradient.  With G(d) = grad_d [ f(|d|) B(d) ] = f' B d/r + f [ (k z^(k-1) / r) (e_u + i e_v) - (k B / r^2) d ] every centre has an
+ * adjoint (alpha_i complex, beta_i real) with d(N_t s) = sum_i [ Re(conj(alpha_i) dS_i) + beta_i dn_i ]:
+ *     local:    alpha_i = 2 g h' psi_i / n_i       beta_i = g' h - 2 g h' c_i / n_i
+ *     global:   alpha_i = 2 Psi / n_i              beta_i = -2 Re(conj(Psi) psi_i) / n_i
+ * both 0 where n_i < MTD_HEX_N_MIN.  An entry has g_ij = Re(conj(alpha_i) G(d_ij)) + beta_i grad f(d_ij) and gives +g_ij to
+ * d(N_t s)/dr_j and -g_ij to d(N_t s)/dr_i.  B has parity (-1)^k, so as a gather over row k of a symmetric list
+ *     N_t ds/dr_k = - sum_{j in row k} [ Re( conj(alpha_k + (-1)^k alpha_j) G(d_kj) ) + (beta_k + beta_j) grad f(d_kj) ],   F = -bias ds/dr
+ * The second terms read the adjoint of the neighbour.  sum_k F_k = 0 on a single domain.  The pair term is NOT parallel to d, and the
+ * variable is NOT invariant under a rotation that tilts the axis: there is a net torque about every direction but the axis.
+ * Virial (only with a virial pointer), in the convention of mtd_es_forces: the six stored components (a, b), a <= b, are derivatives
+ * under x_a -> x_a + eps x_b of positions and box, sum_k virial_k[ab] = -(bias / N_t) sum_entries g_ij,a d_ij,b; the tensor is not
+ * symmetric; half of every entry goes to each of its ends; no explicit volume term.  Layout, scalar type and pitch rule of
+ * mtd_tet_forces.
+ * KNOWN PROPERTY.  Without a gate a particle whose shell is nearly empty (one neighbour just entering the window) has |psi_i| = 1 and a
+ * jump-free but steep gradient of order 1 / f: inherent to a weighted mean.  The gate removes it; dilute systems should use one.
+ * A step is _accumulate, _finalize, _forces with the same parameters, call block and scratch.  _accumulate walks the rows once and
+ * stores n_i, c_i, v_i, psi_i and, in local mode, the adjoint row of every particle — ROW-major, four doubles (alpha_re, alpha_im, beta
+ * and a pad); _finalize forms s and Psi and, in global mode, writes the adjoint rows, which need Psi; _forces walks the rows a second time
+ * and reads the rows of the neighbours.  Every sum has a fixed order and there are no atomics: two identical calls give identical bits,
+ * and a row gives the same bits wherever it lies in the list.  Arguments are checked before a device is touched:
+ * MTD_ERR_INVALID_ARGUMENT for null pointers, a non-finite or out-of-range window, k = 0, axis > 2, a bad switch (c0, p) or gate
+ * (n_lo, n_hi), an unknown dtype, a d_scratch that is not 16-byte aligned, a virial pitch below n_particles; MTD_ERR_UNSUPPORTED for
+ * k > MTD_HEX_MAX_K, a switch or a gate together with global_order, and n_ghost > 0 (the force reads a neighbour's adjoint row, which a
+ * ghost does not have).
+ * ============================================================================================== */
+
+#define MTD_HEX_MAX_K 12
+#define MTD_HEX_N_MIN 1e-12
+
+typedef struct
+    {
+    unsigned int type;
+    unsigned int k;
+    unsigned int axis;                   /* 0, 1, 2: x, y, z — the layer normal */
+    double r_cut, r_on;
+    int global_order;
+    int switch_on;
+    double c0;
+    unsigned int p;
+    int gate_on;
+    double n_lo, n_hi;
+    } mtd_hex_params;
+
+typedef mtd_row_call mtd_hex_call;       /* "Debye structure factor" */
+
+/* device doubles the calls share: sums, value, block sums, the per-particle arrays and the adjoint table */
+size_t mtd_hex_scratch_doubles(unsigned int n_particles);
+
+/* This rank's sums: on return *d_sums points at *n_sums = 4 doubles inside c->d_scratch, in both modes: sum_i v_i, N_t, sum_i Re psi_i,
+ * sum_i Im psi_i — ready for mtd_comm_allreduce_small. */
+int mtd_hex_accumulate(const mtd_hex_params *p, const mtd_hex_call *c, double **d_sums, unsigned int *n_sums);
+
+/* The sums -> s.  *d_value points at s, one device double (consume with
+ * mtd_metad_set_cv_source(engine, slot, *d_value, 1, 1, 0, 1.0, 0.0)) followed by N_t, Re Psi and Im Psi (Psi in both modes);
+ * *d_local (may be NULL) at c_i[n_particles], *d_switched (may be NULL) at v_i[n_particles], *d_coordination (may be NULL) at
+ * n_i[n_particles] and *d_psi (may be NULL) at psi_i as n_particles interleaved (Re, Im) pairs of the last mtd_hex_accumulate, all inside
+ * c->d_scratch.  In global mode this is the launch that completes the adjoint rows. */
+int mtd_hex_finalize(const mtd_hex_params *p, const mtd_hex_call *c, const double **d_value, const double **d_local,
+                     const double **d_switched, const double **d_coordination, const double **d_psi);
+
+/* Writes d_force[0..n_particles) (w component 0; 0 for particles of another type) with what the last mtd_hex_accumulate and
+ * mtd_hex_finalize (same p and c) left in c->d_scratch; bias = *d_bias when d_bias != NULL, else bias_host.  d_virial == NULL: no
+ * virial; the force array is the same, bit for bit, either way.  Every row [0, n_particles) of the virial is written,
+ * [n_particles, virial_pitch) is left alone.  n_particles == 0 is success. */
+int mtd_hex_forces(const mtd_hex_params *p, const mtd_hex_call *c, void *d_force, const double *d_bias, double bias_host,
+                   void *d_virial, unsigned int virial_pitch);
+
+/* ================================================================================================
  * Bragg intensity (cv.bragg) — no reference counterpart.  The intensity of chosen Bragg peaks, i.e. the structure factor at chosen
  * reciprocal-lattice vectors: the phase-free companion of "Lamellar order parameter" above.  That variable takes Re rho_k and so depends
  * on where the density wave sits in the box (a shift by a quarter period takes it from its maximum to zero); |rho_k| does not.  It is

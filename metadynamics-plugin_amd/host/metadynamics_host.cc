@@ -1756,6 +1756,125 @@ void TetrahedralOrder::computeBiasForces(unsigned int timestep)
     }
 
 // ------------------------------------------------------------------------------------------------
+// HexaticOrder
+// ------------------------------------------------------------------------------------------------
+
+HexaticOrder::HexaticOrder(std::shared_ptr<SystemDefinition> sysdef, unsigned int k, unsigned int axis, double r_cut, double r_on,
+                           bool global_order, std::shared_ptr<NeighborList> nlist, unsigned int type, const std::string &log_suffix)
+    : NeighbourVariable(sysdef, "hexatic", log_suffix, nlist, type), m_par(), m_d_local(nullptr), m_d_switched(nullptr),
+      m_d_coordination(nullptr), m_d_psi(nullptr)
+    {
+    if (!nlist) throw std::runtime_error("cv.hexatic: a neighbour list is required");
+    if (!(r_on >= 0.0) || !(r_on < r_cut) || !std::isfinite(r_cut)) throw std::runtime_error("cv.hexatic: 0 <= r_on < r_cut is required");
+    if (k < 1 || k > MTD_HEX_MAX_K) throw std::runtime_error("cv.hexatic: 1 <= k <= " + std::to_string(MTD_HEX_MAX_K) + " is required");
+    if (axis > 2) throw std::runtime_error("cv.hexatic: the axis is 0, 1 or 2 (x, y or z)");
+    m_par.type = type;
+    m_par.k = k;
+    m_par.axis = axis;
+    m_par.r_cut = r_cut;
+    m_par.r_on = r_on;
+    m_par.global_order = global_order ? 1 : 0;
+    m_scratch.resize(sizeof(double) * mtd_hex_scratch_doubles(m_pdata->getN()));
+    }
+
+void HexaticOrder::setSwitch(double c0, unsigned int p)
+    {
+    if (m_par.global_order) throw std::runtime_error("cv.hexatic: a switch acts on |psi_i|^2, which global_order does not sum");
+    if (!(c0 > 0.0) || !std::isfinite(c0) || p == 0) throw std::runtime_error("cv.hexatic: a switch needs c0 > 0 and an integer p >= 1");
+    m_par.switch_on = 1;
+    m_par.c0 = c0;
+    m_par.p = p;
+    invalidate();                                                    // v_i and the adjoint rows in the scratch belong to the old switch
+    }
+
+void HexaticOrder::clearSwitch()
+    {
+    m_par.switch_on = 0;
+    m_par.c0 = 0.0;
+    m_par.p = 0;
+    invalidate();
+    }
+
+void HexaticOrder::setGate(double n_lo, double n_hi)
+    {
+    if (m_par.global_order) throw std::runtime_error("cv.hexatic: a gate acts on the per-particle values, which global_order does not sum");
+    if (!(n_lo >= 0.0) || !(n_lo < n_hi) || !std::isfinite(n_hi)) throw std::runtime_error("cv.hexatic: a gate needs 0 <= n_lo < n_hi");
+    m_par.gate_on = 1;
+    m_par.n_lo = n_lo;
+    m_par.n_hi = n_hi;
+    invalidate();
+    }
+
+void HexaticOrder::clearGate()
+    {
+    m_par.gate_on = 0;
+    m_par.n_lo = m_par.n_hi = 0.0;
+    invalidate();
+    }
+
+mtd_hex_call HexaticOrder::call(const mtd_box *box)
+    {
+    growScratch(sizeof(double) * mtd_hex_scratch_doubles(m_pdata->getN()));   // (more particles than at the last call)
+    return rowCall(box);
+    }
+
+void HexaticOrder::computeCV(unsigned int timestep)
+    {
+    ProfRange prof_range("CV");
+    if (fresh(timestep)) return;
+    requireFullList();
+    if (distributed())
+        throw std::runtime_error("cv.hexatic: domain-decomposed runs are not supported (the adjoint row of a ghost neighbour would have "
+                                 "to be exchanged)");
+    requireReach(getRCut(), "r_cut");
+    m_nlist->compute(timestep);
+    const mtd_box box = m_pdata->getBox().toMtd();
+    const mtd_hex_call c = call(&box);
+    double *d_sums = nullptr;
+    unsigned int n_sums = 0;
+    mtd_check(mtd_hex_accumulate(&m_par, &c, &d_sums, &n_sums), "mtd_hex_accumulate");
+    mtd_check(mtd_hex_finalize(&m_par, &c, &m_d_value, &m_d_local, &m_d_switched, &m_d_coordination, &m_d_psi), "mtd_hex_finalize");
+    computed(timestep);
+    }
+
+std::vector<double> HexaticOrder::getLocalValues(unsigned int timestep)
+    {
+    computeCV(timestep);
+    return readBack(m_d_local, m_pdata->getN(), "c_i read-back", timestep);
+    }
+
+std::vector<double> HexaticOrder::getSwitchedValues(unsigned int timestep)
+    {
+    computeCV(timestep);
+    return readBack(m_d_switched, m_pdata->getN(), "v_i read-back", timestep);
+    }
+
+std::vector<double> HexaticOrder::getCoordination(unsigned int timestep)
+    {
+    computeCV(timestep);
+    return readBack(m_d_coordination, m_pdata->getN(), "n_i read-back", timestep);
+    }
+
+std::vector<double> HexaticOrder::getPsi(unsigned int timestep)
+    {
+    computeCV(timestep);
+    return readBack(m_d_psi, 2 * (size_t)m_pdata->getN(), "psi_i read-back", timestep);
+    }
+
+std::vector<double> HexaticOrder::getGlobalPsi(unsigned int timestep)
+    {
+    computeCV(timestep);
+    return readBack(m_d_value + 2, 2, "Psi read-back", timestep);     // (s, N_t, Re Psi, Im Psi: mtd_hex_finalize)
+    }
+
+void HexaticOrder::computeBiasForces(unsigned int timestep)
+    {
+    const ForcePass f(*this, timestep);                              // (the adjoint rows of THIS step's positions)
+    const mtd_hex_call c = call(&f.box);
+    mtd_check(mtd_hex_forces(&m_par, &c, m_force.data(), m_bias_device, m_bias, f.virial, getVirialPitch()), "mtd_hex_forces");
+    }
+
+// ------------------------------------------------------------------------------------------------
 // BraggIntensity
 // ------------------------------------------------------------------------------------------------
 

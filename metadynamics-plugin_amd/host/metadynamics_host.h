@@ -318,7 +318,7 @@ class SteinhardtQl : public CollectiveVariable
     };
 
 //! What the variables that walk the rows of a FULL neighbour list share (SteinhardtLocal, PairEntropy, EnvironmentSimilarity,
-//! PairEntropyLocal, DebyeStructureFactor, CoordinationNumber, TetrahedralOrder): the list, the particle type, the scratch the passes leave their results
+//! PairEntropyLocal, DebyeStructureFactor, CoordinationNumber, TetrahedralOrder, HexaticOrder): the list, the particle type, the scratch the passes leave their results
 //! in and its growth, "this step is computed already", the refusals of a list that does not fit, the call block of a step, the
 //! all-reduce of a step's sums, the opening of a force pass, the value as one device double, the synchronising read-backs and the
 //! cv_<name> log quantity.  A subclass supplies computeCV (its checks in its own order: full list, distributed, reach, then the list's
@@ -624,6 +624,36 @@ class TetrahedralOrder : public NeighbourVariable
         mtd_tet_params m_par;
         const double *m_d_local, *m_d_switched, *m_d_coordination;
         LargestCluster m_cluster;
+    };
+
+//! Bond-orientational order (no reference counterpart; include/mtd_abi.h "Bond-orientational order"): the k-fold order psi_i of every
+//! particle about a lab axis, the layer normal, from the sectoral harmonics of its neighbour row; s = (1/N_t) sum_i g(n_i) h(|psi_i|^2),
+//! or with `global_order` s = |(1/N_t) sum_i psi_i|^2.  Single-domain runs only: the force on a particle reads the adjoint row of its
+//! neighbours, which a ghost does not have.
+class HexaticOrder : public NeighbourVariable
+    {
+    public:
+        HexaticOrder(std::shared_ptr<SystemDefinition> sysdef, unsigned int k, unsigned int axis, double r_cut, double r_on, bool global_order,
+                     std::shared_ptr<NeighborList> nlist, unsigned int type, const std::string &log_suffix = "");
+        void computeBiasForces(unsigned int timestep) override;
+        std::vector<double> getLocalValues(unsigned int timestep);     //!< c_i = |psi_i|^2 of every local particle (0 for other types)
+        std::vector<double> getSwitchedValues(unsigned int timestep);  //!< v_i = g(n_i) h(c_i) (c_i without options and with global_order)
+        std::vector<double> getCoordination(unsigned int timestep);    //!< n_i = sum_j f(r_ij)
+        std::vector<double> getPsi(unsigned int timestep);             //!< psi_i as N interleaved (Re, Im) pairs
+        std::vector<double> getGlobalPsi(unsigned int timestep);       //!< (Re, Im) of Psi = (1/N_t) sum_i psi_i, in both modes
+        //! the switch and the gate of mtd_ql_local_options, with n_lo >= 0; neither with `global_order`; every change invalidates the
+        //! cached step
+        void setSwitch(double c0, unsigned int p);                     //!< h(c) = x^p / (1 + x^p), x = max(c, 0) / c0
+        void clearSwitch();
+        void setGate(double n_lo, double n_hi);                        //!< g(n) = smoothstep from n_lo to n_hi
+        void clearGate();
+        double getRCut() const { return m_par.r_cut; }                 //!< what the neighbour list must reach
+
+    private:
+        void computeCV(unsigned int timestep) override;
+        mtd_hex_call call(const mtd_box *box);                         //!< rowCall behind a scratch grown to this step's particle count
+        mtd_hex_params m_par;
+        const double *m_d_local, *m_d_switched, *m_d_coordination, *m_d_psi;
     };
 
 //! Bragg intensity (no reference counterpart; include/mtd_abi.h "Bragg intensity"): s = sum_k w_k |rho_k|^2 / A1^2 (or sum_k w_k |rho_k| / A1)

@@ -537,6 +537,36 @@ PYBIND11_MODULE(_metadynamics, m)
             return py::array_t<double>((ssize_t)v.size(), v.data());
         });
 
+    // no reference counterpart: the k-fold bond-orientational order of one particle type about a lab axis, the layer normal
+    py::class_<HexaticOrder, CollectiveVariable, std::shared_ptr<HexaticOrder>>(m, "HexaticOrder")
+        .def(py::init<std::shared_ptr<SystemDefinition>, unsigned int, unsigned int, double, double, bool, std::shared_ptr<NeighborList>,
+                      unsigned int, const std::string &>())
+        .def("getRCut", &HexaticOrder::getRCut)
+        .def("setSwitch", &HexaticOrder::setSwitch)
+        .def("clearSwitch", &HexaticOrder::clearSwitch)
+        .def("setGate", &HexaticOrder::setGate)
+        .def("clearGate", &HexaticOrder::clearGate)
+        .def("getLocalValues", [](HexaticOrder &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getLocalValues(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        })
+        .def("getSwitchedValues", [](HexaticOrder &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getSwitchedValues(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        })
+        .def("getCoordination", [](HexaticOrder &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getCoordination(timestep);
+            return py::array_t<double>((ssize_t)v.size(), v.data());
+        })
+        .def("getPsi", [](HexaticOrder &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getPsi(timestep);
+            return py::array_t<double>({(ssize_t)(v.size() / 2), (ssize_t)2}, v.data());
+        })
+        .def("getGlobalPsi", [](HexaticOrder &cv, unsigned int timestep) {
+            const std::vector<double> v = cv.getGlobalPsi(timestep);
+            return py::make_tuple(v[0], v[1]);
+        });
+
     py::class_<WellTemperedEnsemble, CollectiveVariable, std::shared_ptr<WellTemperedEnsemble>>(m, "WellTemperedEnsemble")
         .def(py::init<std::shared_ptr<SystemDefinition>, const std::string &>());
 

@@ -256,6 +256,31 @@ class TetParams(C.Structure):
         return o
 
 
+HexCall = RowCall
+
+MTD_HEX_MAX_K = 12
+MTD_HEX_N_MIN = 1e-12
+
+
+class HexParams(C.Structure):
+    """mtd_hex_params: the particle type, the fold k, the axis (0, 1, 2: the layer normal), the window, the mode and the optional
+    switch and gate on c_i and n_i"""
+    _fields_ = [("type", C.c_uint), ("k", C.c_uint), ("axis", C.c_uint), ("r_cut", C.c_double), ("r_on", C.c_double),
+                ("global_order", C.c_int), ("switch_on", C.c_int), ("c0", C.c_double), ("p", C.c_uint), ("gate_on", C.c_int),
+                ("n_lo", C.c_double), ("n_hi", C.c_double)]
+
+    @classmethod
+    def make(cls, type_id, r_cut, r_on, k=6, axis=2, global_order=False, switch=None, gate=None):
+        """switch: None or (c0, p); gate: None or (n_lo, n_hi).  Nothing is checked here: the entry points refuse what they do not take"""
+        o = cls()
+        o.type, o.k, o.axis, o.r_cut, o.r_on, o.global_order = int(type_id), int(k), int(axis), float(r_cut), float(r_on), int(bool(global_order))
+        if switch is not None:
+            o.switch_on, o.c0, o.p = 1, float(switch[0]), int(switch[1])
+        if gate is not None:
+            o.gate_on, o.n_lo, o.n_hi = 1, float(gate[0]), float(gate[1])
+        return o
+
+
 MTD_BRAGG_MAX_MODES = 16
 MTD_TRIG_DEFAULT, MTD_TRIG_HARDWARE, MTD_TRIG_ACCURATE = 0, 1, 2
 
@@ -514,6 +539,11 @@ _SIGNATURES = {
                                                      _up, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "mtd_tet_finalize": (C.c_int, [C.POINTER(TetParams), C.POINTER(TetCall), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "mtd_tet_forces": (C.c_int, [C.POINTER(TetParams), C.POINTER(TetCall), _vp, _vp, C.c_double, _vp, C.c_uint]),
+    "mtd_hex_scratch_doubles": (C.c_size_t, [C.c_uint]),
+    "mtd_hex_accumulate": (C.c_int, [C.POINTER(HexParams), C.POINTER(HexCall), C.POINTER(_vp), _up]),
+    "mtd_hex_finalize": (C.c_int, [C.POINTER(HexParams), C.POINTER(HexCall), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
+                                   C.POINTER(_vp)]),
+    "mtd_hex_forces": (C.c_int, [C.POINTER(HexParams), C.POINTER(HexCall), _vp, _vp, C.c_double, _vp, C.c_uint]),
     "mtd_bragg_scratch_doubles": (C.c_size_t, [C.c_uint]),
     "mtd_bragg_accumulate": (C.c_int, [C.POINTER(BraggParams), C.POINTER(BraggCall), C.POINTER(_vp), _up]),
     "mtd_bragg_finalize": (C.c_int, [C.POINTER(BraggParams), C.POINTER(BraggCall), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),

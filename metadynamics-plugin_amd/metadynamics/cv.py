@@ -1003,6 +1003,117 @@ class tetrahedral(_neighbour_variable, _largest_cluster):
             raise RuntimeError("Error creating collective variable.")
 
 
+class hexatic(_neighbour_variable):
+    """this build (no reference counterpart; include/mtd_abi.h "Bond-orientational order"): the k-fold bond-orientational order psi_k of
+    the particles of ``type`` about the lab axis ``axis`` ("x", "y" or "z"), the order WITHIN a layer: 2-d melting and freezing (liquid,
+    hexatic, solid), monolayers at interfaces, confined films, the in-layer order of smectic-B and lamellar phases.  With f the cosine
+    window between ``r_on`` and ``r_cut``, d_ij the vector from i to its neighbour j and (u, v) its two components that follow the axis
+    cyclically (z: (x, y); x: (y, z); y: (z, x)),
+    z_ij = (u_ij + i v_ij) / r_ij,  psi_i = sum_j f_ij z_ij^k / sum_j f_ij,  c_i = |psi_i|^2.
+    z^k = sin^k(theta) e^{i k phi} is the SECTORAL harmonic: for a bond in the plane it is the textbook e^{i k phi}, a bond out of the
+    plane is de-weighted by sin^k(theta), and a bond along the axis is an ordinary point (the unweighted form has a 1 / rho singularity
+    there).  This is the definition: |psi_i| < 1 on a rippled but perfect layer is intended.
+    CV = (1 / N_type) sum_i g(n_i) h(c_i); ``switch=dict(c0=..., p=...)``: h(c) = x^p / (1 + x^p), x = max(c, 0) / c0 — CV * N_type is
+    then the smooth number of ordered particles; ``gate=dict(n_lo=..., n_hi=...)`` (0 <= n_lo < n_hi): a smoothstep in the coordination
+    n_i = sum_j f_ij.  ``global_order=True``: CV = |Psi|^2, Psi = (1 / N_type) sum_i psi_i — the phase coherence over the box that tells
+    a hexatic or a solid from a polycrystal; switch and gate are refused then.  k = 6 on a perfect triangular monolayer: 1, whatever its
+    in-plane orientation; k = 4 on perfect fcc about a cube axis: 1/36.
+
+    The variable SELECTS THE LAYER NORMAL: unlike ``cv.steinhardt_local`` it is not rotation invariant, and the bias exerts a torque
+    that turns the layers' normal towards ``axis``.
+
+    Needs a full list that reaches ``r_cut``; single-domain runs only (the force on a particle reads a table row of its neighbours,
+    which a ghost does not have).  A particle without neighbours has psi_i = 0.
+
+    Known property: without a gate a particle whose shell is nearly empty (its coordination n_i tiny but not zero) has a bounded psi_i
+    and a jump-free but steep gradient of order 1 / f, inherent to a weighted mean.  The gate removes it; dilute systems should use the
+    gate.
+
+    Virial (``get_virial``; mtd_hex_forces): half of every entry at each of its ends, no explicit volume term.  The pair term is not
+    parallel to the pair vector and the variable is not rotation invariant, so neither one particle's six components nor their sum are
+    those of a symmetric matrix: the stored (a, b), a <= b, are -bias * dCV/d(strain) under x_a -> x_a + eps x_b."""
+
+    _cv = "cv.hexatic"
+    _axes = {"x": 0, "y": 1, "z": 2}
+    _max_k = 12                                                      # MTD_HEX_MAX_K
+
+    def __init__(self, r_cut, r_on, nlist, type, k=6, axis="z", global_order=False, switch=None, gate=None, name=None, sigma=1.0):
+        suffix = self._begin(sigma, name)
+        try:
+            type_list = context.current.type_names
+            r_cut, r_on = float(r_cut), float(r_on)
+            if type not in type_list or not 0.0 <= r_on < r_cut < float("inf") or float(nlist.r_cut) < r_cut:
+                raise ValueError
+            if int(k) != k or not 1 <= int(k) <= self._max_k or axis not in self._axes:
+                raise ValueError
+            global_order = bool(global_order)
+            sw, gt = self._options(switch, gate, global_order)
+            self.type = type
+            self.nlist = nlist
+            self.r_cut, self.r_on, self.k, self.axis, self.global_order = r_cut, r_on, int(k), axis, global_order
+            self._full_list()
+            self.cpp_force = _metadynamics.HexaticOrder(context.current.system_definition, int(k), self._axes[axis], r_cut, r_on, global_order,
+                                                        nlist.cpp_nlist, type_list.index(type), suffix)
+            self._apply(sw, gt)
+        except (TypeError, ValueError, KeyError, AttributeError, RuntimeError):
+            context.current.forces.remove(self)                      # refused: the run must not find a half-made variable
+            raise RuntimeError("Error creating collective variable.")
+        self._attach(type_list.index(type))
+
+    @staticmethod
+    def _options(switch, gate, global_order):
+        """the checks of cv.steinhardt_local.set_options, with n_lo >= 0; neither option with ``global_order``"""
+        sw = None if switch is None else (float(switch["c0"]), int(switch["p"]))
+        gt = None if gate is None else (float(gate["n_lo"]), float(gate["n_hi"]))
+        if sw is not None and (set(switch.keys()) != {"c0", "p"} or int(switch["p"]) != switch["p"] or not 0.0 < sw[0] < float("inf")
+                               or sw[1] < 1):
+            raise ValueError
+        if gt is not None and (set(gate.keys()) != {"n_lo", "n_hi"} or not 0.0 <= gt[0] < gt[1] < float("inf")):
+            raise ValueError
+        if global_order and (sw is not None or gt is not None):
+            raise ValueError
+        return sw, gt
+
+    def _apply(self, sw, gt):
+        if sw is None:
+            self.cpp_force.clearSwitch()
+        else:
+            self.cpp_force.setSwitch(*sw)
+        if gt is None:
+            self.cpp_force.clearGate()
+        else:
+            self.cpp_force.setGate(*gt)
+
+    def get_local(self):
+        """c_i = |psi_i|^2 of every particle at the current time step (0 for particles of another type)"""
+        return self.cpp_force.getLocalValues(context.current.system.getCurrentTimeStep())
+
+    def get_switched(self):
+        """v_i = g(n_i) h(c_i) of every particle at the current time step: what the CV averages (c_i with ``global_order``)"""
+        return self.cpp_force.getSwitchedValues(context.current.system.getCurrentTimeStep())
+
+    def get_coordination(self):
+        """n_i = sum_j f(r_ij): the smoothed number of neighbours of every particle at the current time step"""
+        return self.cpp_force.getCoordination(context.current.system.getCurrentTimeStep())
+
+    def get_psi(self):
+        """psi_i of every particle at the current time step as an (N, 2) array of (Re, Im)"""
+        return self.cpp_force.getPsi(context.current.system.getCurrentTimeStep())
+
+    def get_global_psi(self):
+        """(Re, Im) of Psi = (1 / N_type) sum_i psi_i at the current time step, with and without ``global_order``"""
+        return self.cpp_force.getGlobalPsi(context.current.system.getCurrentTimeStep())
+
+    def set_options(self, switch=None, gate=None):
+        """replaces switch and gate (the defaults switch them off); takes effect with the next step.  Refused with ``global_order``; a
+        refused call leaves both as they were"""
+        try:
+            sw, gt = self._options(switch, gate, self.global_order)  # everything is checked before anything is changed
+            self._apply(sw, gt)
+        except (TypeError, KeyError, ValueError, AttributeError, RuntimeError):
+            raise RuntimeError("Error creating collective variable.")
+
+
 def environment_templates(structure, a):
     """the template environments of a cubic lattice with the conventional lattice constant ``a``, for ``cv.environment_similarity``:
     ``"fcc"`` 12 vectors of length a / sqrt(2), ``"bcc"`` 14 vectors (the 8 nearest of length a sqrt(3) / 2 and the 6 second neighbours of
